@@ -16,15 +16,23 @@ reference's FatBeagleParallelize deals a tree collection to its FatBeagles; a we
 figure (1000 trees per GPU) rides along in "weak".
 
 Output.  The LAST line of stdout is ONE compact JSON object (< 4 KB, asserted: final_line) with
-the contract's fields, the dominant kernel's `roofline`, `cpu_baseline`, the parity of the timed
-outputs, `small_batch_ms` (the 125-tree step one GPU of eight runs, from a hipGraph), the
-host-pointer / C++ adapter / fused-reduction legs, and one short entry per other configuration
-in `also` (GTR+4G full and branch-only, log-likelihoods, the 1949-pattern shape, a 36-taxon arena shape, fluA rooted,
-the 20-state 512 x 50 000 case).  Everything behind those numbers -- second rooflines, phase
-tables, notes, samples -- is written to bench_also.json and printed before the last line as
-`BENCH_ALSO <name> <json>` lines.
+the contract's fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...)
+and the dominant kernel's `roofline`.  A plain run does only that: set-up, `--warmup` steps,
+exactly `--steps` timed steps, the line.  With --full it also carries `cpu_baseline`, the parity
+of the timed outputs against the CPU oracle, the per-step spread (a second pass of the steps),
+`small_batch_ms` (the 125-tree step one GPU of eight runs, from a hipGraph), the host-pointer /
+C++ adapter / fused-reduction legs, the weak-scaled figure, and one short entry per other
+configuration in `also` (GTR+4G full and branch-only, log-likelihoods, the 1949-pattern shape, a
+36-taxon arena shape, fluA rooted, the 20-state 512 x 50 000 case).  Everything behind those
+numbers -- second rooflines, phase tables, notes, samples -- is written to bench_also.json and
+printed before the last line as `BENCH_ALSO <name> <json>` lines.
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned to its caller is
+written as DIR/<name>.npy (float64; the inputs are seeded, so two builds can be compared
+output for output).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--trees T_total] [--mode gradient|loglik]
+                  [--full] [--dump-outputs DIR]
 
 --gpus N > 1: one rank per GPU over RCCL.  Under a launcher (torch.distributed.run: WORLD_SIZE
 set) N must equal WORLD_SIZE; without one, bench.py starts the N ranks itself as a child
@@ -538,6 +546,26 @@ def emit(full):
     print(final_line(full), flush=True)  # the ONE JSON line, last thing on stdout
 
 
+DUMP_LIMIT = 64 << 20  # bytes: all files of one --dump-outputs together
+
+
+def dump_outputs(directory, arrays, seed=0):
+    """--dump-outputs: every array (first axis = trees) as <directory>/<name>.npy, float64.
+    Above DUMP_LIMIT bytes in all, every array keeps the same fixed, seeded sample of trees,
+    whose row numbers are written as tree_index.npy."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    rows = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes for a in arrays.values()) // rows
+    if rows * row_bytes > DUMP_LIMIT:
+        keep = DUMP_LIMIT // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(seed).choice(rows, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["tree_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 class Timed:
     """Times `steps` calls of fn() after `warmup` calls; kernel time from the engine's HIP
     events around its dominant kernel(s); optionally a second, separate pass with the call cut
@@ -997,6 +1025,12 @@ def swag_pattern_sharded(args, torch, dist, L, sharding, dev, rank, world, distr
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     assert bool(torch.isfinite(blk.buffer).all())
+    if args.dump_outputs is not None and rank == 0:  # (summed over the ranks' pattern blocks)
+        kept = {"log_likelihoods": blk.log_likelihoods.cpu().numpy()}
+        if grad:
+            kept["branch_length_gradients"] = blk.branch_gradients.cpu().numpy()
+            kept["site_model_gradients"] = blk.extras[0].cpu().numpy()
+        dump_outputs(args.dump_outputs, kept)
     # a separate pass with the call cut into phases (never inside the timed region)
     eng.profile_begin_phases(2)
     for _ in range(2):
@@ -1207,7 +1241,8 @@ def main():
                          "site patterns dealt to the GPUs, one all-reduce per step")
     ap.add_argument("--swag-trees", type=int, default=8)
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed headline steps (+ parity): no CPU baseline, other "
+                    help="with --full: only the timed headline steps (+ parity and the per-step "
+                         "spread): no CPU baseline, other "
                          "configurations, small batch, host legs or reduced leg -- for "
                          "rocprofv3 runs, whose --stats line of the dominant kernel would "
                          "otherwise average those legs' launches in")
@@ -1224,10 +1259,21 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="start the ranks, form the process group, deal the trees, print the "
                          "line -- no GPU work, value null (tests/test_bench_launcher.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: parity against the CPU oracle, "
+                         "the per-step spread, the weak-scaled, reduced, small-batch and host legs, "
+                         "the other configurations and the CPU baseline (each --no-* / "
+                         "--headline-only option still drops its part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (per-tree log-likelihoods and, "
+                         "in gradient mode, branch-length and site-model gradients) as "
+                         "DIR/<name>.npy, float64")
     args = ap.parse_args()
     if args.backend is None:
         args.backend = "gloo" if args.dry_run else "nccl"
-    if args.headline_only:
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("--steps must be >= 1 and --warmup >= 0")
+    if args.headline_only or not args.full:
         args.no_cpu_baseline = args.no_also = args.no_small_batch = True
         args.no_host_legs = args.no_reduced = True
 
@@ -1348,11 +1394,12 @@ def main():
             elapsed = float(tmax.item())
         return elapsed, kernel_ms
 
-    def run_config(T_local_max, lo, hi, steps, warmup, spread=False):
+    def run_config(T_local_max, lo, hi, steps, warmup, spread=False, keep=False):
         """Times `steps` steps of this rank's trees [lo, hi); all ranks gather blocks of
         T_local_max trees (shorter blocks are padded).  spread: afterwards, and OUTSIDE the
         timed region, the same steps once more with a HIP event after every step (the
-        per-step min / median / max of the line)."""
+        per-step min / median / max of the line).  keep: also returns, as host arrays, what
+        the last TIMED step handed its caller (every rank's trees, tree order; rank 0 only)."""
         T = hi - lo
         d_pid = torch.from_numpy(pids_all[lo:hi]).to(dev)
         d_bl = torch.from_numpy(bls_all[lo:hi]).to(dev)
@@ -1403,6 +1450,20 @@ def main():
                 state["gathered"], _ = sharding.all_gather_result_blocks(blk, out=outs[i])
 
         elapsed, kernel_ms = timed_region(step, steps, warmup, drain)
+        kept = None
+        if keep and rank == 0:
+            last = sets[(state["k"] - 1) & 1]
+            if distributed:  # every rank's gathered rows, its padding dropped
+                ll_all, ex_all, g_all = sharding.gathered_views(state["gathered"], last)
+                sizes = sharding.shard_sizes(T_total, world)
+                ll, site, g = (torch.cat([x[r][:c] for r, c in enumerate(sizes)])
+                               for x in (ll_all, ex_all[0], g_all))
+            else:
+                ll, site, g = last.log_likelihoods[:T], last.extras[0][:T], last.branch_gradients[:T]
+            kept = {"log_likelihoods": ll.cpu().numpy()}
+            if grad:
+                kept["branch_length_gradients"] = g.cpu().numpy()
+                kept["site_model_gradients"] = site.cpu().numpy()
         step_ms = None
         if spread:
             marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
@@ -1424,13 +1485,16 @@ def main():
             assert bool(torch.equal(ll_all[rank][:T], d_ll)), "gathered slice mismatch"
             if grad:
                 assert bool(torch.equal(g_all[rank][:T], d_g)), "gathered gradient slice mismatch"
-        return elapsed, kernel_ms, last, T, step_ms
+        return elapsed, kernel_ms, last, T, step_ms, kept
 
     # ---- strong scaling (the headline): T_total trees over all ranks
     lo, hi = sharding.tree_shard(T_total, rank, world)
     T_max = sharding.tree_shard(T_total, 0, world)[1]
-    elapsed, kernel_ms, last, T_local, step_ms = run_config(T_max, lo, hi, args.steps,
-                                                            args.warmup, spread=True)
+    elapsed, kernel_ms, last, T_local, step_ms, kept = run_config(
+        T_max, lo, hi, args.steps, args.warmup, spread=args.full,
+        keep=args.dump_outputs is not None)
+    if kept is not None:
+        dump_outputs(args.dump_outputs, kept)
     ms_per_step = 1e3 * elapsed / args.steps
     value = T_total / (elapsed / args.steps)
     kname, evals, gevals = eng.last_call_info()
@@ -1441,7 +1505,7 @@ def main():
 
     # ---- parity of the timed outputs: a sample of the last step against the CPU oracle
     parity_n, parity_err = 0, None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         O = oracle()
         parity_n = min(16, T_local)
         ospec = O.make_spec(n, P, "JC69", "weibull+4")
@@ -1463,7 +1527,7 @@ def main():
 
     # ---- weak scaling beside it (1000 trees per GPU), N > 1 only
     weak = None
-    if world > 1:
+    if world > 1 and args.full:
         wl, wh = rank * T_total, (rank + 1) * T_total
         w_elapsed = run_config(T_total, wl, wh, args.steps, args.warmup)[0]
         weak = {"value": world * T_total / (w_elapsed / args.steps), "unit": "trees/s",
@@ -1530,7 +1594,7 @@ def main():
     small = None
     if rank == 0 and world == 1 and not args.no_small_batch:
         Ts = max(1, T_total // 8)
-        s_elapsed, s_kernel, _, _, s_steps = run_config(Ts, 0, Ts, 50, 5, spread=True)
+        s_elapsed, s_kernel, _, _, s_steps, _ = run_config(Ts, 0, Ts, 50, 5, spread=True)
         small = {"trees": Ts, "ms_per_step": 1e3 * s_elapsed / 50,
                  "step_ms_device": {"min": float(np.min(s_steps)),
                                     "median": float(np.median(s_steps)),
@@ -1724,15 +1788,11 @@ def main():
                                - sharding.tree_shard(T_total, r, world)[0] for r in range(world)],
             "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "step_ms_device": {"min": float(np.min(step_ms)), "median": float(np.median(step_ms)),
-                               "max": float(np.max(step_ms)),
-                               "kernel_min": float(np.min(kernel_ms)) if kernel_ms else None,
+            "step_ms_device": {"kernel_min": float(np.min(kernel_ms)) if kernel_ms else None,
                                "kernel_median": float(np.median(kernel_ms)) if kernel_ms else None,
                                "kernel_max": float(np.max(kernel_ms)) if kernel_ms else None,
-                               "note": "rank 0, a second pass of the same steps AFTER the timed "
-                                       "region: HIP events on the calls' stream after every step "
-                                       "(device time between consecutive steps' ends); kernel_* "
-                                       "= the dominant kernel's launches of the timed region"},
+                               "note": "kernel_* = the dominant kernel's launches of the timed "
+                                       "region"},
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
             "data": "reference DS1 alignment + DS1.100_topologies; synthetic branch lengths "
                     "Exp(mean 0.1), seed 43",
@@ -1755,8 +1815,18 @@ def main():
             "parity_note": "first trees of the last timed step vs the CPU oracle, tolerance 1e-10",
             "rank_devices": rank_devices,
         }
+        if step_ms:
+            out["step_ms_device"].update(
+                {"min": float(np.min(step_ms)), "median": float(np.median(step_ms)),
+                 "max": float(np.max(step_ms)),
+                 "note": "rank 0, a second pass of the same steps AFTER the timed region: HIP "
+                         "events on the calls' stream after every step (device time between "
+                         "consecutive steps' ends); kernel_* = the dominant kernel's launches "
+                         "of the timed region"})
         if args.no_parity:
             out["parity"] = "skipped"
+        elif not args.full:
+            out["parity"] = "not checked (--full compares the timed outputs with the CPU oracle)"
         if weak:
             out["weak"] = weak
         if reduced:

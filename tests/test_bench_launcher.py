@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -156,3 +157,29 @@ def test_one_roofline_convention_on_every_leg():
     assert shard["pipe_busy"] is None  # (another instantiation than the profiled one)
     if shard["traffic"]:
         assert "share of the profiled alignment" in shard["traffic_source"]
+
+
+def test_dump_outputs_keeps_one_seeded_sample_under_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files; above the size limit every array keeps the SAME rows
+    (trees), the same ones from run to run, and their numbers are written beside them."""
+    bench = _bench_module()
+    rng = np.random.default_rng(1)
+    arrays = {"log_likelihoods": rng.normal(size=100),
+              "branch_length_gradients": rng.normal(size=(100, 7)).astype(np.float32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "all" / (name + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    assert not (tmp_path / "all" / "tree_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 64 * 30)  # room for 30 rows of 8 doubles (+ index)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    idx = np.load(tmp_path / "a" / "tree_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "tree_index.npy"))
+    assert 0 < len(idx) <= 30 and np.all(np.diff(idx) > 0)
+    total = 0
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "a" / (name + ".npy"))
+        assert np.array_equal(got, a[idx.astype(int)].astype(np.float64))
+        total += got.nbytes
+    assert total + idx.nbytes <= bench.DUMP_LIMIT

@@ -11,7 +11,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/prof_$tag
 S=$O/summary
 mkdir -p $S
-H="--steps 20 --warmup 3 --headline-only"
+H="--steps 20 --warmup 3 --headline-only --full"
 
 stats() {  # name, command...
   local name=$1; shift
@@ -29,7 +29,7 @@ pmc() {  # name, counter, command...
 
 stats gradient python3 bench.py $H
 stats loglik python3 bench.py --mode loglik $H
-stats small_batch_125 python3 bench.py --trees 125 --steps 50 --warmup 5 --headline-only
+stats small_batch_125 python3 bench.py --trees 125 --steps 50 --warmup 5 --headline-only --full
 stats gtr_full python3 tools/bench_gtr.py 1000 10
 stats flua_1 python3 tools/bench_flua.py 1
 stats flua_1000 python3 tools/bench_flua.py 1000
