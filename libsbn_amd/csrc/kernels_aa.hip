@@ -2039,9 +2039,8 @@ __global__ __launch_bounds__(256) void aa_reduce_kernel(AaWalkArgs a, int ll_blo
 // Launch wrappers
 // ------------------------------------------------------------------------
 void launch_aa_model_setup(const double* exch, const double* freqs, AaModel* model,
-                           int32_t* status, hipStream_t s) {
-  const bool seq = getenv("MI_PHYLO_AA_JACOBI") && std::string(getenv("MI_PHYLO_AA_JACOBI")) == "seq";  // (read per engine)
-  if (seq) hipLaunchKernelGGL(aa_model_setup_kernel, dim3(1), dim3(64), 0, s, exch, freqs, model, status);
+                           int32_t* status, const Switches& sw, hipStream_t s) {
+  if (sw.aa_jacobi_seq) hipLaunchKernelGGL(aa_model_setup_kernel, dim3(1), dim3(64), 0, s, exch, freqs, model, status);
   else hipLaunchKernelGGL(aa_model_setup_wave_kernel, dim3(1), dim3(64), 0, s, exch, freqs, model, status);
 }
 void launch_aa_transition(const AaTransitionArgs& a, hipStream_t s) {
@@ -2057,12 +2056,6 @@ static unsigned aa_grid(int blocks, int units) {
   const long W = (long)blocks * units;
   return (unsigned)(8 * ((W + 7) / 8));
 }
-// MI_PHYLO_AA_LDS_PAD=<bytes>: extra dynamic LDS per wave, to study the walk kernels at lower
-// occupancy (results are unaffected)
-static size_t aa_lds_pad() {
-  static const size_t pad = getenv("MI_PHYLO_AA_LDS_PAD") ? strtoul(getenv("MI_PHYLO_AA_LDS_PAD"), nullptr, 10) : 0;
-  return pad;
-}
 // tiles a wave of the post-order kernel takes: two (measured, workgroup form, log-likelihoods
 // of 8 trees: 17.1-17.3 ms against 17.7-17.8 with four at three waves per SIMD; gradients 20.8
 // against 24.5 in round 3) -- or ONE when the launch would otherwise leave the chip short of
@@ -2072,18 +2065,11 @@ static size_t aa_lds_pad() {
 // per wave is twice the workgroups with half the matrix instructions per visit each.
 // aa_post_tiles_threshold: workgroups (at two tiles) below which a launch takes one tile.
 // MI_PHYLO_AA_POST_TILES=1|2|4 overrides (workgroup form only: the wave form has 2 and 4).
-static int aa_post_tiles(const AaWalkArgs& a) {
-  static const int forced = getenv("MI_PHYLO_AA_POST_TILES") ? atoi(getenv("MI_PHYLO_AA_POST_TILES")) : 0;
-  if (forced == 4 || forced == 2 || forced == 1) return forced;
-  static const long threshold =
-      getenv("MI_PHYLO_AA_POST_ONE_TILE_BELOW") ? atol(getenv("MI_PHYLO_AA_POST_ONE_TILE_BELOW")) : 2L * device_compute_units();
+static int aa_post_tiles(const AaWalkArgs& a, const Switches& sw) {
+  if (sw.aa_post_tiles) return sw.aa_post_tiles;
+  const long threshold = sw.aa_post_one_tile_below >= 0 ? sw.aa_post_one_tile_below : 2L * device_compute_units();
   const long wgs2 = (long)((a.tiles / 2 + 4 - 1) / 4) * a.evals * a.K;
   return wgs2 < threshold ? 1 : 2;
-}
-// MI_PHYLO_AA_POST=wave selects the wave-per-block form of the post-order kernel
-static bool aa_post_wg() {
-  static const bool wg = !(getenv("MI_PHYLO_AA_POST") && std::string(getenv("MI_PHYLO_AA_POST")) == "wave");
-  return wg;
 }
 // Entries of the LDS ring a log-likelihood wave keeps the top of its vector stack in
 // (aa_post_wg_kernel); MI_PHYLO_AA_RING=0|1|2|4 overrides (0: every kept vector through the
@@ -2093,9 +2079,8 @@ static bool aa_post_wg() {
 // is the default for every launch: less than a third of the arena's HBM traffic (67 % of the
 // kept vectors never have another pushed on top of them) and 2-3 % less time; two entries
 // cost a workgroup per CU and lose.
-static int aa_ring_slots(size_t workgroups) {
-  static const int forced = getenv("MI_PHYLO_AA_RING") ? atoi(getenv("MI_PHYLO_AA_RING")) : -1;
-  if (forced == 0 || forced == 1 || forced == 2 || forced == 4) return forced;  // (powers of two)
+static int aa_ring_slots(size_t workgroups, int forced) {
+  if (forced >= 0) return forced;  // (0, 1, 2 or 4: powers of two)
   // (round 6: a launch that leaves the chip short of work -- fewer than two workgroups per CU: a
   // rank's pattern block of one tree -- is bound by its visits' latencies, not by workgroups per
   // CU: four entries keep 97 % of the kept vectors out of the arena; 512 x 6 250 x 4, one tree:
@@ -2103,13 +2088,15 @@ static int aa_ring_slots(size_t workgroups) {
   return workgroups < 2 * (size_t)device_compute_units() ? 4 : 1;
 }
 // (what launch_aa_post / launch_aa_pre will choose: for the engine's description of a call)
-int aa_post_tiles_per_wave(const AaWalkArgs& a) { return aa_post_wg() ? aa_post_tiles(a) : std::max(2, aa_post_tiles(a)); }
-int aa_post_ring_entries(const AaWalkArgs& a) {
-  if (!aa_post_wg()) return 0;
-  const int m = aa_post_tiles(a), blocks = a.tiles / m;
-  int entries = aa_ring_slots(aa_grid((blocks + kPostWaves - 1) / kPostWaves, a.evals * a.K));
+int aa_post_tiles_per_wave(const AaWalkArgs& a, const Switches& sw) {
+  return sw.aa_post_wave ? std::max(2, aa_post_tiles(a, sw)) : aa_post_tiles(a, sw);
+}
+int aa_post_ring_entries(const AaWalkArgs& a, const Switches& sw) {
+  if (sw.aa_post_wave) return 0;
+  const int m = aa_post_tiles(a, sw), blocks = a.tiles / m;
+  int entries = aa_ring_slots(aa_grid((blocks + kPostWaves - 1) / kPostWaves, a.evals * a.K), sw.aa_ring);
   // (a forced size must still fit a CU beside the 24.5 KB of operand buffers and schedule)
-  while (entries > 0 && sizeof(double) * (size_t)kPostWaves * entries * m * (kAaTileDoubles + 8) + aa_lds_pad() >
+  while (entries > 0 && sizeof(double) * (size_t)kPostWaves * entries * m * (kAaTileDoubles + 8) + sw.aa_lds_pad >
                             160 * 1024 - 25 * 1024)
     entries >>= 1;
   return entries;
@@ -2121,15 +2108,16 @@ static void launch_aa_post_wg(const AaWalkArgs& a, dim3 grid, dim3 block, size_t
   allow_large_lds(reinterpret_cast<const void*>(aa_post_wg_kernel<M, GRAD>), lds + 32 * 1024);
   hipLaunchKernelGGL((aa_post_wg_kernel<M, GRAD>), grid, block, lds, s, a);
 }
-void launch_aa_post(const AaWalkArgs& a_in, hipStream_t s) {
+void launch_aa_post(const AaWalkArgs& a_in, const Switches& sw, hipStream_t s) {
   AaWalkArgs a = a_in;
-  int m = aa_post_tiles(a);
-  if (aa_post_wg()) {
+  int m = aa_post_tiles(a, sw);
+  const size_t pad = sw.aa_lds_pad;
+  if (!sw.aa_post_wave) {
     const int blocks = a.tiles / m;
     const dim3 grid(aa_grid((blocks + kPostWaves - 1) / kPostWaves, a.evals * a.K)), block(kPostThreads);
-    a.ring_slots = aa_post_ring_entries(a);
+    a.ring_slots = aa_post_ring_entries(a, sw);
     const size_t ring = sizeof(double) * (size_t)kPostWaves * a.ring_slots * m * (kAaTileDoubles + 8);
-    const size_t lds = ring + aa_lds_pad();
+    const size_t lds = ring + pad;
     if (m == 4) {
       if (a.gradient) launch_aa_post_wg<4, true>(a, grid, block, lds, s);
       else launch_aa_post_wg<4, false>(a, grid, block, lds, s);
@@ -2146,52 +2134,48 @@ void launch_aa_post(const AaWalkArgs& a_in, hipStream_t s) {
   const dim3 grid(aa_grid(a.tiles / m, a.evals * a.K));
   if (m == 4) {
     if (a.gradient)
-      hipLaunchKernelGGL((aa_post_kernel<4, true>), grid, dim3(64), aa_lds_pad(), s, a);
+      hipLaunchKernelGGL((aa_post_kernel<4, true>), grid, dim3(64), pad, s, a);
     else
-      hipLaunchKernelGGL((aa_post_kernel<4, false>), grid, dim3(64), aa_lds_pad(), s, a);
+      hipLaunchKernelGGL((aa_post_kernel<4, false>), grid, dim3(64), pad, s, a);
     return;
   }
   if (a.gradient)
-    hipLaunchKernelGGL((aa_post_kernel<2, true>), grid, dim3(64), aa_lds_pad(), s, a);
+    hipLaunchKernelGGL((aa_post_kernel<2, true>), grid, dim3(64), pad, s, a);
   else
-    hipLaunchKernelGGL((aa_post_kernel<2, false>), grid, dim3(64), aa_lds_pad(), s, a);
+    hipLaunchKernelGGL((aa_post_kernel<2, false>), grid, dim3(64), pad, s, a);
 }
 void launch_aa_root(const AaWalkArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(aa_root_kernel, dim3(aa_ll_blocks(a.P), a.evals), dim3(256), 0, s, a);
 }
-static bool aa_pre_wg() {
-  static const bool wg = !(getenv("MI_PHYLO_AA_PRE") && std::string(getenv("MI_PHYLO_AA_PRE")) == "wave");
-  return wg;
-}
 // entries of the LDS ring of parked pre-order vectors (aa_pre_wg_kernel): one -- 20 KB per
 // workgroup beside 49 KB of operand buffers, two workgroups per CU by registers either way;
 // MI_PHYLO_AA_PRE_RING=0|1|2 overrides (2 costs a workgroup per CU)
-int aa_pre_ring_entries() {
-  static const int forced = getenv("MI_PHYLO_AA_PRE_RING") ? atoi(getenv("MI_PHYLO_AA_PRE_RING")) : -1;
-  if (!aa_pre_wg()) return 0;
-  return forced == 0 || forced == 1 || forced == 2 ? forced : 1;
+int aa_pre_ring_entries(const Switches& sw) {
+  if (sw.aa_pre_wave) return 0;
+  return sw.aa_pre_ring >= 0 ? sw.aa_pre_ring : 1;
 }
-void launch_aa_pre(const AaWalkArgs& a, hipStream_t s) {
-  if (aa_pre_wg()) {
+void launch_aa_pre(const AaWalkArgs& a, const Switches& sw, hipStream_t s) {
+  const size_t pad = sw.aa_lds_pad;
+  if (!sw.aa_pre_wave) {
     const int blocks = a.tiles / kAaPreTiles;
     const dim3 grid(aa_grid((blocks + kPreWaves - 1) / kPreWaves, a.evals * a.K)), block(kPreThreads);
     AaWalkArgs b = a;
-    b.pre_ring_slots = aa_pre_ring_entries();
+    b.pre_ring_slots = aa_pre_ring_entries(sw);
     const size_t lds = sizeof(double) * (2 * 2 * kPreOps + kAaPack) + sizeof(SchedEntry) * kSchedWindow +
-                       sizeof(double) * (size_t)kPreWaves * b.pre_ring_slots * kAaPreTiles * kAaTileDoubles + aa_lds_pad();
+                       sizeof(double) * (size_t)kPreWaves * b.pre_ring_slots * kAaPreTiles * kAaTileDoubles + pad;
     allow_large_lds(reinterpret_cast<const void*>(aa_pre_wg_kernel<kAaPreTiles>), lds);
     hipLaunchKernelGGL((aa_pre_wg_kernel<kAaPreTiles>), grid, block, lds, s, b);
     return;
   }
   const dim3 grid(aa_grid(a.tiles / kAaPreTiles, a.evals * a.K));
-  hipLaunchKernelGGL((aa_pre_kernel<kAaPreTiles>), grid, dim3(64), aa_lds_pad(), s, a);
+  hipLaunchKernelGGL((aa_pre_kernel<kAaPreTiles>), grid, dim3(64), pad, s, a);
 }
 void launch_aa_reduce(const AaWalkArgs& a, hipStream_t s) {
   const int gx = a.gradient ? 1 + (a.N + 63) / 64 : 1;
   hipLaunchKernelGGL(aa_reduce_kernel, dim3(gx, a.evals), dim3(256), 0, s, a, aa_ll_blocks(a.P));
 }
 // (the names rocprofv3 prints: the workgroup forms unless MI_PHYLO_AA_POST / _PRE = wave)
-const char* aa_post_kernel_name() { return aa_post_wg() ? "aa_post_wg_kernel" : "aa_post_kernel"; }
-const char* aa_pre_kernel_name() { return aa_pre_wg() ? "aa_pre_wg_kernel" : "aa_pre_kernel"; }
+const char* aa_post_kernel_name(const Switches& sw) { return sw.aa_post_wave ? "aa_post_kernel" : "aa_post_wg_kernel"; }
+const char* aa_pre_kernel_name(const Switches& sw) { return sw.aa_pre_wave ? "aa_pre_kernel" : "aa_pre_wg_kernel"; }
 
 }  // namespace miphylo

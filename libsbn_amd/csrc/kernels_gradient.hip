@@ -194,13 +194,10 @@ int gradient_mfma_tiles(int P, int K, int regs) {
 // tiles against four: 0.245 -> 0.260).  So: wide where tiles x cost falls, cost 1.16 or 1.33, and
 // never below five default tiles.  The width is the ENGINE's (all its look-up calls take it):
 // sums over patterns are formed tile by tile, and a tree's outputs must not depend on the size
-// of the batch it came in.  MI_PHYLO_WALK_TILE_REGS=3|4 forces a width (read at engine creation).
-int gradient_walk_tile_regs(int n, int P, int K) {
+// of the batch it came in.  MI_PHYLO_WALK_TILE_REGS=3|4 forces a width (`forced`).
+int gradient_walk_tile_regs(int n, int P, int K, int forced) {
   if (kLlR >= 4) return kLlR;
-  if (const char* env = getenv("MI_PHYLO_WALK_TILE_REGS")) {
-    const int r = atoi(env);
-    if (r == 4 || r == kLlR) return r;
-  }
+  if (forced == 4 || forced == kLlR) return forced;
   const int t3 = gradient_mfma_tiles(P, K, kLlR), t4 = gradient_mfma_tiles(P, K, 4);
   auto waves = [&](int regs) {
     const size_t lds = gradient_walk_lds_bytes_for(n, K, false, false, gradient_arena_slots_usual(n), regs);
@@ -364,8 +361,8 @@ __global__ __launch_bounds__(1024) void macro_slots_wg_kernel(const MacroEntry* 
 }
 void launch_macro_slots(const MacroEntry* macros_in, MacroEntry* macros_out,
                         const int32_t* macro_count, int n, int T, int32_t* need, int32_t* status,
-                        hipStream_t s) {
-  static const bool seq = getenv("MI_PHYLO_MACRO_SLOTS") && std::string(getenv("MI_PHYLO_MACRO_SLOTS")) == "seq";
+                        const Switches& sw, hipStream_t s) {
+  const bool seq = sw.macro_slots == 2;
   const size_t Mmax = max_macros(n), S = max_stored(n);
   const size_t wg_lds = macro_slots_wg_lds_bytes(n);
   (void)S;

@@ -679,26 +679,22 @@ int loglik_mfma_tiles(int P, int K) {
   const int per_wave = kLogR * (16 / kp);
   return (P + per_wave - 1) / per_wave;
 }
-bool loglik_mfma_supported(const LikArgs& a, bool rescale) {
+// forced: MI_PHYLO_LOGLIK_PATH (Switches::loglik_path)
+bool loglik_mfma_supported(const LikArgs& a, bool rescale, int forced) {
   // The matrix-core log-likelihood kernel needs tips in state-mask form (K > 4: the
   // categories are walked four at a time).  MI_PHYLO_LOGLIK_PATH=valu|mfma forces one of the two kernels.
-  const int forced = [] {  // (read per call: tools/audit_paths.py switches it between engines)
-    const char* env = getenv("MI_PHYLO_LOGLIK_PATH");
-    if (!env) return 0;
-    return std::string(env) == "mfma" ? 2 : (std::string(env) == "valu" ? 1 : 0);
-  }();
   (void)rescale;
   const bool possible = a.K <= kMaxCategories && a.tip_masks != nullptr;
   if (forced == 1) return false;
   if (forced == 2) return possible;
   return possible && kLoglikMfmaDefault;
 }
-static bool use_loglik_mfma(const LikArgs& a, bool rescale, int max_slots) {
-  return loglik_mfma_supported(a, rescale) &&
+static bool use_loglik_mfma(const LikArgs& a, bool rescale, int max_slots, const Switches& sw) {
+  return loglik_mfma_supported(a, rescale, sw.loglik_path) &&
          loglik_mfma_lds_bytes(a.n, a.K, max_slots) <= 160 * 1024;
 }
 static void launch_loglik_mfma(const LikArgs& a_in, int count, bool rescale, int max_slots,
-                               hipStream_t s) {
+                               int forced_epw, hipStream_t s) {
   LikArgs a = a_in;
   a.lds_slots = loglik_mfma_slots(max_slots);
   a.kp = a.K == 1 ? 1 : (a.K == 2 ? 2 : 4);
@@ -710,9 +706,8 @@ static void launch_loglik_mfma(const LikArgs& a_in, int count, bool rescale, int
   int epw = 1;
   if (a.eval_offset >= a.map.T && a.eval_offset + count <= 17 * a.map.T &&
       (a.eval_offset - a.map.T) % 16 == 0 && count % 16 == 0) {
-    static const int forced = getenv("MI_PHYLO_LOGLIK_EVALS_PER_WAVE") ? atoi(getenv("MI_PHYLO_LOGLIK_EVALS_PER_WAVE")) : 0;
     for (epw = 8; epw > 1; epw >>= 1)
-      if (forced ? epw <= forced : (long)(count / epw) * tiles >= 3L * 256 * 16) break;
+      if (forced_epw ? epw <= forced_epw : (long)(count / epw) * tiles >= 3L * 256 * 16) break;
   }
   a.evals_per_wave = epw;
   const dim3 grid(tiles, count / epw), block(kTile);
@@ -730,10 +725,11 @@ static void launch_loglik_mfma(const LikArgs& a_in, int count, bool rescale, int
     else go(loglik_mfma_kernel<kLogR, false, false>);
   }
 }
-void launch_loglik(const LikArgs& a_in, int count, bool rescale, int max_slots, hipStream_t s) {
+void launch_loglik(const LikArgs& a_in, int count, bool rescale, int max_slots, const Switches& sw,
+                   hipStream_t s) {
   if (count <= 0) return;
-  if (use_loglik_mfma(a_in, rescale, max_slots)) {
-    launch_loglik_mfma(a_in, count, rescale, max_slots, s);
+  if (use_loglik_mfma(a_in, rescale, max_slots, sw)) {
+    launch_loglik_mfma(a_in, count, rescale, max_slots, sw.loglik_evals_per_wave, s);
     return;
   }
   LikArgs a = a_in;
@@ -749,8 +745,8 @@ void launch_loglik(const LikArgs& a_in, int count, bool rescale, int max_slots, 
     else hipLaunchKernelGGL((loglik_onchip_kernel<false, false>), grid, block, lds, s, a);
   }
 }
-const char* loglik_kernel_name(const LikArgs& a, bool rescale, int max_slots) {
-  return use_loglik_mfma(a, rescale, max_slots) ? "loglik_mfma_kernel" : "loglik_onchip_kernel";
+const char* loglik_kernel_name(const LikArgs& a, bool rescale, int max_slots, const Switches& sw) {
+  return use_loglik_mfma(a, rescale, max_slots, sw) ? "loglik_mfma_kernel" : "loglik_onchip_kernel";
 }
 
 }  // namespace miphylo

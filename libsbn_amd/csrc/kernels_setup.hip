@@ -638,10 +638,10 @@ __global__ __launch_bounds__(kTransitionBlock) void transition_kernel(Transition
 // ------------------------------------------------------------------------
 // Launch wrappers
 // ------------------------------------------------------------------------
-bool launch_setup(const TreeSetupArgs& a_in, const ModelSetupArgs& ms, hipStream_t s) {
+bool launch_setup(const TreeSetupArgs& a_in, const ModelSetupArgs& ms, const Switches& sw, hipStream_t s) {
   TreeSetupArgs a = a_in;
   // MI_PHYLO_MACRO_SLOTS=own|seq: the arena's slot assignment stays a launch of its own (A/B, tests)
-  const bool fold_slots = getenv("MI_PHYLO_MACRO_SLOTS") == nullptr;  // (read per call)
+  const bool fold_slots = sw.macro_slots == 0;
   a.arena_sure = gradient_arena_slots_sure(a.n);
   const size_t lds = sizeof(int32_t) * 13 * (size_t)(2 * a.n - 1);
   a.use_lds = lds <= 64 * 1024;
@@ -651,12 +651,12 @@ bool launch_setup(const TreeSetupArgs& a_in, const ModelSetupArgs& ms, hipStream
   // 840 us / workgroup 38 us.  So: register arrays up to 64 nodes, a workgroup per tree above,
   // the sequential kernel only for trees whose arrays exceed the LDS.
   // MI_PHYLO_TREE_SETUP=small|wg|lds forces one of them where it applies (testing).
-  static const std::string forced = getenv("MI_PHYLO_TREE_SETUP") ? getenv("MI_PHYLO_TREE_SETUP") : "";
+  const int forced = sw.tree_setup;  // 0 by size, 1 small, 2 wg, 3 lds
   const int N = 2 * a.n - 1;
   const size_t wg_lds = sizeof(int32_t) * kSetupArrays * (size_t)N;
   const bool small_ok = a.n >= 3 && N <= 256, wg_ok = a.n >= 3 && wg_lds <= 160 * 1024 - 1024;
-  const bool use_small = small_ok && (forced == "small" || (forced.empty() && N <= 64));
-  const bool use_wg = !use_small && wg_ok && forced != "lds" && !(forced == "small" && small_ok);
+  const bool use_small = small_ok && (forced == 1 || (forced == 0 && N <= 64));
+  const bool use_wg = !use_small && wg_ok && forced != 3 && !(forced == 1 && small_ok);
   if (use_small) {
     // T workgroups of trees, then the model instances, 64 per workgroup
     const dim3 grid(a.T + (ms.T * ms.models_per_tree + 63) / 64), block(64);
@@ -700,9 +700,9 @@ __global__ void weibull_table_kernel(int K, double* table) {
 void launch_weibull_table(int K, double* table, hipStream_t s) {
   hipLaunchKernelGGL(weibull_table_kernel, dim3(1), dim3(64), 0, s, K, table);
 }
-bool launch_tree_setup(const TreeSetupArgs& a, hipStream_t s) {  // trees only
+bool launch_tree_setup(const TreeSetupArgs& a, const Switches& sw, hipStream_t s) {  // trees only
   ModelSetupArgs none{};
-  return launch_setup(a, none, s);
+  return launch_setup(a, none, sw, s);
 }
 void launch_transition(const TransitionArgs& a, hipStream_t s) {
   const long total = (long)a.E * (a.N - 1) * a.K;

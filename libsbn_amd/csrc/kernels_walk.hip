@@ -984,7 +984,8 @@ static void launch_walk_store(const LikArgs& a, dim3 grid, size_t lds, bool resc
   else if (compact) launch_walk_variant<false, false, ARENA, true>(a, grid, lds, s);
   else launch_walk_variant<false, false, ARENA, false>(a, grid, lds, s);
 }
-void launch_gradient_walk(const LikArgs& a_in, int count, bool rescale, bool subst, hipStream_t s) {
+void launch_gradient_walk(const LikArgs& a_in, int count, bool rescale, bool subst, const Switches& sw,
+                          hipStream_t s) {
   if (count <= 0) return;
   LikArgs a = a_in;
   a.kp = a.K == 1 ? 1 : (a.K == 2 ? 2 : 4);
@@ -999,17 +1000,14 @@ void launch_gradient_walk(const LikArgs& a_in, int count, bool rescale, bool sub
   // work that runs as the second or later tile of a wave.  (A wave stays in one category
   // group; the arena and analytic variants take one tile per wave: kernel comment.)
   // MI_PHYLO_WALK_TILES_PER_WAVE=k forces k (1: every tile its own wave, as until round 3).
-  static const int forced_tpw = [] {
-    const char* env = getenv("MI_PHYLO_WALK_TILES_PER_WAVE");
-    return env ? std::max(1, atoi(env)) : 0;
-  }();
+  const int forced_tpw = sw.walk_tiles_per_wave;
   const int gtiles = gradient_mfma_tiles(a.P, a.K) * a.cat_groups;
   const bool arena_variant =
       a.store ? a.store == 2
-              : gradient_walk_use_arena(a.n, a.K, rescale, subst, (size_t)gtiles * (size_t)count);
+              : gradient_walk_use_arena(sw.gradient_store, a.n, a.K, rescale, subst, (size_t)gtiles * (size_t)count);
   int tpw = 1, big = 0;
   if (a.cat_groups == 1 && !arena_variant && !subst) {
-    const double slots = (double)device_compute_units() * gradient_walk_waves_per_cu(a.n, a.K);
+    const double slots = (double)device_compute_units() * gradient_walk_waves_per_cu(sw.gradient_store, a.n, a.K);
     double best = 0;
     for (int k = forced_tpw ? forced_tpw : 2; k <= (forced_tpw ? forced_tpw : 8); k++) {
       // (measured, 1000 and 125 DS1 trees: fewer small jobs -- k / 4 + 1, k / 8 + 1/2 rounds --
@@ -1054,13 +1052,8 @@ void launch_gradient_walk(const LikArgs& a_in, int count, bool rescale, bool sub
                            subst, s);
 }
 
-bool gradient_walk_use_arena(int n, int K, bool rescale, bool subst, size_t waves, bool lut, int regs) {
-  // (read at every call: tools/audit_paths.py switches it between engines of one process)
-  const int forced = [] {
-    const char* env = getenv("MI_PHYLO_GRADIENT_STORE");
-    if (!env) return 0;
-    return std::string(env) == "arena" ? 2 : (std::string(env) == "lds" ? 1 : 0);
-  }();
+bool gradient_walk_use_arena(int store, int n, int K, bool rescale, bool subst, size_t waves, bool lut, int regs) {
+  const int forced = store;  // MI_PHYLO_GRADIENT_STORE: 0 unset, 1 lds, 2 arena
   if (regs > kLlR) {
     // A wide-tile engine (look-up walk, kernels_walk3.hip): wide tiles pay in the arena; the form
     // with every vector in LDS runs at one wave per SIMD (registers) and takes the calls whose
@@ -1094,15 +1087,15 @@ bool gradient_walk_batches_take_arena(int n, int K, bool lut) {
   const size_t lds_all = gradient_walk_lds_bytes(n, K, false, false);
   return lds_all > 160 * 1024 || (160 * 1024) / lds_all < (size_t)(lut ? 6 : 5);
 }
-int gradient_walk_waves_per_cu(int n, int K);
+int gradient_walk_waves_per_cu(int store, int n, int K);
 bool gradient_walk_fits(int n, int K, bool rescale) {
   if (n < 3 || K > kMaxCategories) return false;
   if (gradient_walk_lds_bytes(n, K, rescale, true) <= 160 * 1024) return true;
   return gradient_walk_lds_bytes_for(n, K, rescale, true, gradient_arena_slots_sure(n)) <= 160 * 1024;
 }
 // waves per CU the kernel's LDS footprint allows (the registers allow 8)
-int gradient_walk_waves_per_cu(int n, int K) {
-  const size_t lds = gradient_walk_use_arena(n, K, false, false, (size_t)-1, false)
+int gradient_walk_waves_per_cu(int store, int n, int K) {
+  const size_t lds = gradient_walk_use_arena(store, n, K, false, false, (size_t)-1, false)
                          ? gradient_walk_lds_bytes_for(n, K, false, false, gradient_arena_slots_usual(n))
                          : gradient_walk_lds_bytes(n, K, false, false);
   return (int)std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1));

@@ -31,9 +31,11 @@
 // -- everything the reference produces), one to four rate categories (one category group; KP =
 // categories per matrix instruction), stored vectors in LDS or -- batches of trees of 36 taxa and
 // more -- in a per-wave HBM arena (ARENA), no analytic substitution gradient.  The second
-// generation keeps: more than four categories, the analytic gradient, 0/1 tip vectors that are
-// not one-hot, and one-category engines whose vectors fit LDS (its waves take several tiles in a
-// row there).  The first generation (gradient_mfma_kernel) was retired in round 6.
+// generation keeps: more than four categories, the analytic gradient and 0/1 tip vectors that are
+// not one-hot.  (One-category calls with their vectors in LDS take this walk too since round 6,
+// when the tip codes were pre-tiled; MI_PHYLO_WALK3_K1=0 keeps the old rule: this walk only where
+// the one-launch call applies.)  The first generation (gradient_mfma_kernel) was retired in
+// round 6.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1445,14 +1447,12 @@ void launch_transition_lut(const TransitionMacroArgs& a, hipStream_t s) {
 bool gradient_walk_lut_applies(int K) { return K >= 1 && K <= 4 && kRegs >= 2; }
 
 template <bool RESCALE, bool ARENA, int KP, int RR>
-static void launch_lut_variant(const LikArgs& a, dim3 grid, size_t lds, hipStream_t s, bool resident) {
+static void launch_lut_variant(const LikArgs& a, dim3 grid, size_t lds, hipStream_t s, bool resident,
+                               int forced) {
   // (non-temporal arena accesses up to 48 default-width pattern tiles per tree, and for a call
   // whose waves are all resident at once -- 64 taxa x 1000 x 4 categories, 16 trees: 0.0990
   // against 0.1025 ms, tools/audit_paths.py: walk_lut_body; MI_PHYLO_ARENA_NT=0|1 forces plain /
-  // non-temporal)
-  // (read per launch: tests switch it between calls of one process)
-  const char* nt_env = getenv("MI_PHYLO_ARENA_NT");
-  const int forced = nt_env ? atoi(nt_env) : -1;
+  // non-temporal: `forced`, -1 if unset)
   if (ARENA && (forced < 0 ? (a.g_tiles * RR <= 48 * kRegs || resident) : forced != 0)) {
     allow_large_lds(reinterpret_cast<const void*>(gradient_walk_lut_kernel<RESCALE, ARENA, KP, ARENA, RR>), lds);
     hipLaunchKernelGGL((gradient_walk_lut_kernel<RESCALE, ARENA, KP, ARENA, RR>), grid, dim3(kTile), lds, s, a);
@@ -1463,18 +1463,18 @@ static void launch_lut_variant(const LikArgs& a, dim3 grid, size_t lds, hipStrea
 }
 template <bool ARENA, int RR = kRegs>
 static void launch_lut_store(const LikArgs& a, dim3 grid, size_t lds, bool rescale, hipStream_t s,
-                             bool resident = false) {
+                             int arena_nt, bool resident = false) {
   switch ((rescale ? 8 : 0) | a.kp) {
-    case 1: launch_lut_variant<false, ARENA, 1, RR>(a, grid, lds, s, resident); break;
-    case 2: launch_lut_variant<false, ARENA, 2, RR>(a, grid, lds, s, resident); break;
-    case 4: launch_lut_variant<false, ARENA, 4, RR>(a, grid, lds, s, resident); break;
-    case 9: launch_lut_variant<true, ARENA, 1, RR>(a, grid, lds, s, resident); break;
-    case 10: launch_lut_variant<true, ARENA, 2, RR>(a, grid, lds, s, resident); break;
-    default: launch_lut_variant<true, ARENA, 4, RR>(a, grid, lds, s, resident); break;
+    case 1: launch_lut_variant<false, ARENA, 1, RR>(a, grid, lds, s, resident, arena_nt); break;
+    case 2: launch_lut_variant<false, ARENA, 2, RR>(a, grid, lds, s, resident, arena_nt); break;
+    case 4: launch_lut_variant<false, ARENA, 4, RR>(a, grid, lds, s, resident, arena_nt); break;
+    case 9: launch_lut_variant<true, ARENA, 1, RR>(a, grid, lds, s, resident, arena_nt); break;
+    case 10: launch_lut_variant<true, ARENA, 2, RR>(a, grid, lds, s, resident, arena_nt); break;
+    default: launch_lut_variant<true, ARENA, 4, RR>(a, grid, lds, s, resident, arena_nt); break;
   }
 }
 
-void launch_gradient_walk_lut(const LikArgs& a_in, int count, bool rescale, hipStream_t s) {
+void launch_gradient_walk_lut(const LikArgs& a_in, int count, bool rescale, const Switches& sw, hipStream_t s) {
   if (count <= 0) return;
   LikArgs a = a_in;
   a.kp = lut_kp(a.K);
@@ -1486,7 +1486,7 @@ void launch_gradient_walk_lut(const LikArgs& a_in, int count, bool rescale, hipS
   const int gtiles = gradient_mfma_tiles(a.P, a.K, regs);
   const bool arena_variant =
       a.store ? a.store == 2
-              : gradient_walk_use_arena(a.n, a.K, rescale, false, (size_t)gtiles * (size_t)count, true, regs);
+              : gradient_walk_use_arena(sw.gradient_store, a.n, a.K, rescale, false, (size_t)gtiles * (size_t)count, true, regs);
   const dim3 grid((unsigned)((size_t)count * gtiles));
   if (arena_variant) {
     // two launches over one grid, as the second generation's arena variant: the trees whose
@@ -1494,8 +1494,8 @@ void launch_gradient_walk_lut(const LikArgs& a_in, int count, bool rescale, hipS
     const int usual = gradient_arena_slots_usual(a.n), sure = gradient_arena_slots_sure(a.n);
     auto lds_for = [&](int slots) { return gradient_walk_lds_bytes_for(a.n, a.K, rescale, false, slots, regs); };
     auto launch = [&](int slots, bool resident) {
-      if (wide) launch_lut_store<true, kRegsWide>(a, grid, lds_for(slots), rescale, s, resident);
-      else launch_lut_store<true>(a, grid, lds_for(slots), rescale, s, resident);
+      if (wide) launch_lut_store<true, kRegsWide>(a, grid, lds_for(slots), rescale, s, sw.arena_nt, resident);
+      else launch_lut_store<true>(a, grid, lds_for(slots), rescale, s, sw.arena_nt, resident);
     };
     a.lds_lo = -1;
     // (ONE launch with the larger footprint only when all waves are resident at once anyway -- a
@@ -1534,7 +1534,7 @@ void launch_gradient_walk_lut(const LikArgs& a_in, int count, bool rescale, hipS
     }
     return;
   }
-  launch_lut_store<false>(a, grid, gradient_walk_lds_bytes(a.n, a.K, rescale, false), rescale, s);
+  launch_lut_store<false>(a, grid, gradient_walk_lds_bytes(a.n, a.K, rescale, false), rescale, s, sw.arena_nt);
 }
 // The look-up walk's tip codes per pattern tile, in the form its LDS holds them (walk_lut_body,
 // TileCodes): per (tile, taxon) one word per column (byte r: the code of register r's pattern) for

@@ -71,8 +71,8 @@ CallShape call_shape(const mi_engine* e, int T, bool gradient, bool analytic = f
 bool walk3_possible(const mi_engine* e);
 bool use_arena(const mi_engine* e, bool rescale, bool subst, size_t waves = (size_t)-1, int regs = 0) {
   // (the look-up walk's arena variant starts one step earlier: gradient_walk_use_arena)
-  const bool lut = walk3_possible(e) && e->walk3_arena && !subst && gradient_mfma_groups(e->K) == 1;
-  return gradient_walk_use_arena(e->n, e->K, rescale, subst, waves, lut, regs);
+  const bool lut = walk3_possible(e) && e->sw.walk3_arena && !subst && gradient_mfma_groups(e->K) == 1;
+  return gradient_walk_use_arena(e->sw.gradient_store, e->n, e->K, rescale, subst, waves, lut, regs);
 }
 bool walk_fits(const mi_engine* e, bool rescale) { return gradient_walk_fits(e->n, e->K, rescale); }
 // (engine creation, tips in mask form on the device: the log-likelihood kernel's pre-tiled copy)
@@ -97,9 +97,9 @@ int build_tip_tiles(mi_engine* e) {
 // gradient_walk_use_arena.)
 int engine_tile_regs(mi_engine* e) {
   if (e->tile_regs < 0) {
-    const bool lut = walk3_possible(e) && e->walk3_arena && gradient_mfma_groups(e->K) == 1;
-    const bool forced = getenv("MI_PHYLO_WALK_TILE_REGS") != nullptr;
-    const int r = lut && (forced || gradient_walk_batches_take_arena(e->n, e->K, true)) ? gradient_walk_tile_regs(e->n, e->P, e->K) : 0;
+    const bool lut = walk3_possible(e) && e->sw.walk3_arena && gradient_mfma_groups(e->K) == 1;
+    const int forced = e->sw.walk_tile_regs;
+    const int r = lut && (forced || gradient_walk_batches_take_arena(e->n, e->K, true)) ? gradient_walk_tile_regs(e->n, e->P, e->K, forced) : 0;
     e->tile_regs = r > kLlR ? r : 0;
   }
   return e->tile_regs;
@@ -111,7 +111,7 @@ bool loglik_kernel_is_valu(const mi_engine* e, bool rescaling) {
   probe.n = e->n;
   probe.K = e->K;
   probe.tip_masks = e->have_tip_masks ? e->tip_masks.as<uint8_t>() : nullptr;
-  return std::string(loglik_kernel_name(probe, rescaling, e->max_slots)) == "loglik_onchip_kernel";
+  return std::string(loglik_kernel_name(probe, rescaling, e->max_slots, e->sw)) == "loglik_onchip_kernel";
 }
 // Does a gradient call run on the matrix-core walk kernel?  ONE predicate for run_device and
 // mi_engine_reserve (a reserve that guesses differently leaves a later *_device call to
@@ -119,15 +119,23 @@ bool loglik_kernel_is_valu(const mi_engine* e, bool rescaling) {
 // likelihoods from a pass of the matrix-core log-likelihood kernel; if that one cannot run,
 // neither can it.)
 bool matrix_core_gradient(const mi_engine* e, bool rescaling) {
-  return e->allow_onchip_gradient && e->have_tip_masks && walk_fits(e, rescaling) &&
+  return !e->sw.hbm_gradient && e->have_tip_masks && walk_fits(e, rescaling) &&
          reduce_tiles_fits(e->N) &&
          (gradient_mfma_groups(e->K) == 1 || !loglik_kernel_is_valu(e, rescaling));
 }
 
 // Can calls of this engine take the third-generation walk (kernels_walk3.hip)?  (Per call it
-// also needs the stored vectors in LDS and no analytic substitution gradient.)
+// also needs no analytic substitution gradient.)  Which generation of the matrix-core gradient
+// walk a call takes: the third (kernels_walk3.hip: tip children looked up; one-hot / all-ones
+// tips, at most four rate categories, no analytic substitution gradient -- everything the
+// reference produces) wherever it applies, else the second (kernels_walk.hip: mask tips, any
+// category count, analytic gradient).  MI_PHYLO_GRADIENT_WALK=v2 keeps every call on the second.
+// (The first generation, gradient_mfma_kernel, was retired in round 6: the second had been ahead
+// of it on every shape but the arena shapes with fewer than three categories and a handful of
+// tiles -- fluA: 0.321 against 0.335 ms per 1000 trees -- and those now take the third: 0.305 ->
+// 0.29.)
 bool walk3_possible(const mi_engine* e) {
-  return e->walk3 && e->have_tip_codes && gradient_walk_lut_applies(e->K);
+  return e->sw.walk3 && e->have_tip_codes && gradient_walk_lut_applies(e->K);
 }
 
 size_t plv_bytes_per_eval(const mi_engine* e) {
@@ -205,7 +213,7 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   const bool mfma = d.gradient && matrix_core_gradient(e, d.rescaling);
   const bool onchip = mfma;  // the only on-chip gradient kernel; everything else streams PLVs
   const int groups = mfma ? gradient_mfma_groups(e->K) : 1;
-  const bool analytic = e->analytic_subst && mfma && e->spec.subst_model == MI_SUBST_GTR;
+  const bool analytic = e->sw.analytic_subst && mfma && e->spec.subst_model == MI_SUBST_GTR;
   // (a wide-tile engine: every call the look-up walk can take runs it, with wide tiles)
   const int tile_regs = mfma && !analytic && groups == 1 ? engine_tile_regs(e) : 0;
   const int g_tiles = mfma ? gradient_mfma_tiles(e->P, e->K, tile_regs) * groups : e->tiles;
@@ -266,19 +274,15 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   // The one-launch call (kernels_walk3.hip): tree set-up, model instances and operand records
   // ride in the walk's launch.  One evaluation and one model instance per tree (JC69-type
   // calls), trees of at most 64 nodes, one walk launch, nobody else reads the schedule's LDS
-  // slots.
-  static const bool fuse_allowed =
-      !(getenv("MI_PHYLO_FUSE_FINALIZE") && std::string(getenv("MI_PHYLO_FUSE_FINALIZE")) == "0");
+  // slots.  (MI_PHYLO_FUSE_FINALIZE=0: neither this nor the fused reduction, below.)
   // Up to 512 trees: the set-up waves take wave slots the walk would use (four waves of ~10
   // microseconds per tree, a GTR eigensystem on one lane of each) -- measured, DS1
   // (tools/bench_fused_scan.py): one launch / four launches 0.91 at 1-8 trees,
   // 0.98 at 250-500, 0.99 at 1000 (JC69; GTR 1.00), 1.01 beyond.  MI_PHYLO_FUSED_MAX_TREES
   // moves the cross-over (testing).
-  static const int fuse_max_trees =
-      getenv("MI_PHYLO_FUSED_MAX_TREES") ? atoi(getenv("MI_PHYLO_FUSED_MAX_TREES")) : 512;
   const bool fuse_possible = mfma && walk3_possible(e) && !analytic && groups == 1 && !arena && !tile_regs && e->fused_setup &&
-                             fuse_allowed && c.E == T && c.models_per_tree == 1 && !ts.need_slots &&
-                             T <= fuse_max_trees && e->ready.ptr && gradient_walk_lut_fused_applies(n, e->K);
+                             e->sw.fuse_finalize && c.E == T && c.models_per_tree == 1 && !ts.need_slots &&
+                             T <= e->sw.fused_max_trees && e->ready.ptr && gradient_walk_lut_fused_applies(n, e->K);
   // One rate category with the stored vectors in LDS.  The second generation, whose waves take
   // several tiles of a tree in a row, was 5-7 % ahead on a large batch (DS1 x 1000 with the
   // constant site model 0.281 against 0.297 ms) and the look-up walk, with its one-launch call,
@@ -292,7 +296,7 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   // (MI_PHYLO_WALK3_K1=0: the old rule).  (Two and three categories: look-up walk 0.462 / 0.490
   // and 0.831 / 0.868 ms per 1000 DS1 trees.)
   const bool walk3 = walk2 && walk3_possible(e) && !analytic && groups == 1 &&
-                     (tile_regs || (arena ? e->walk3_arena : (e->K > 1 || e->walk3_k1_lds || fuse_possible)));
+                     (tile_regs || (arena ? e->sw.walk3_arena : (e->K > 1 || e->sw.walk3_k1_lds || fuse_possible)));
   const bool fuse_setup = walk3 && fuse_possible;
   // Beyond the one-launch call's size the same set-up waves CAN run as one launch in front of the
   // walk's (round 6, MI_PHYLO_SETUP_RECORDS=1): trees, model instances and operand records --
@@ -302,8 +306,7 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   // 0.7826 against 0.7823 ms (tools/ab_kernels.py, four rounds), direct launches -1 %.
   const bool setup_records = walk3 && !fuse_setup && !arena && !tile_regs && !analytic && groups == 1 && e->fused_setup &&
                              c.E == T && c.models_per_tree == 1 && !ts.need_slots && T <= kMaxEvals &&
-                             gradient_walk_lut_fused_applies(n, e->K) &&
-                             getenv("MI_PHYLO_SETUP_RECORDS") && getenv("MI_PHYLO_SETUP_RECORDS")[0] == '1';
+                             gradient_walk_lut_fused_applies(n, e->K) && e->sw.setup_records;
   // (arena calls: the slot assignment rides in the set-up launch where a workgroup builds the tree)
   ts.arena_macros = arena ? e->arena_macros.as<MacroEntry>() : nullptr;
   ts.slot_need = e->slot_need.as<int32_t>();
@@ -312,14 +315,14 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
     fs.ts = ts;
     fs.ms = ms;
     fs.mmats = e->mmats.as<double>();
-    fs.colocate = e->fused_colocate;
+    fs.colocate = e->sw.fused_colocate;
     launch_setup_records(fs, T, s);
   }
-  const bool slots_done = !fuse_setup && !setup_records && launch_setup(ts, ms, s);  // tree schedules and model instances, one launch
+  const bool slots_done = !fuse_setup && !setup_records && launch_setup(ts, ms, e->sw, s);  // tree schedules and model instances, one launch
   if (arena && !slots_done)
     launch_macro_slots(e->macros.as<MacroEntry>(), e->arena_macros.as<MacroEntry>(),
                        e->macro_count.as<int32_t>(), n, T, e->slot_need.as<int32_t>(),
-                       e->status.as<int32_t>(), s);
+                       e->status.as<int32_t>(), e->sw, s);
 
   const EvalMap map{T, c.models_per_tree};
   TransitionArgs tr{};
@@ -410,16 +413,11 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   la.mphi = e->mphi.as<double>();
   la.tip_states = e->tip_states.as<int8_t>();
   la.tip_masks = e->have_tip_masks ? e->tip_masks.as<uint8_t>() : nullptr;
-  {  // (the look-up walk's pre-tiled codes were made for the engine's tile width)
-    const char* off = getenv("MI_PHYLO_TIP_TILES");
-    la.tip_code_tiles = e->have_tip_codes && e->tip_code_tiles.ptr && !(off && off[0] == '0') &&
-                                engine_tile_regs(e) == tile_regs
-                            ? e->tip_code_tiles.as<uint8_t>()
-                            : nullptr;
-  }
-  // (MI_PHYLO_TIP_TILES=0: the kernels stage their tip bytes from tip_masks / tip_codes themselves -- A/B, tests)
-  la.tip_tiles = e->have_tip_masks && e->tip_tiles.ptr && !(getenv("MI_PHYLO_TIP_TILES") && getenv("MI_PHYLO_TIP_TILES")[0] == '0')
-                     ? e->tip_tiles.as<uint8_t>() : nullptr;
+  // (MI_PHYLO_TIP_TILES=0: the kernels stage their tip bytes from tip_masks / tip_codes themselves
+  // -- A/B, tests; the look-up walk's pre-tiled codes were made for the engine's tile width)
+  la.tip_code_tiles = e->have_tip_codes && e->tip_code_tiles.ptr && e->sw.tip_tiles && engine_tile_regs(e) == tile_regs
+                          ? e->tip_code_tiles.as<uint8_t>() : nullptr;
+  la.tip_tiles = e->have_tip_masks && e->tip_tiles.ptr && e->sw.tip_tiles ? e->tip_tiles.as<uint8_t>() : nullptr;
   la.tip_codes = e->have_tip_codes ? e->tip_codes.as<uint8_t>() : nullptr;
   la.tip_partials = e->spec.use_tip_states ? nullptr : e->tip_partials.as<double>();
   la.weights = e->weights.as<double>();
@@ -440,7 +438,7 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
       walk_launches++;
       LikArgs l = la;
       l.eval_offset = eval_begin + done;
-      launch_loglik(l, std::min(kMaxEvals, count - done), d.rescaling, e->max_slots, s);
+      launch_loglik(l, std::min(kMaxEvals, count - done), d.rescaling, e->max_slots, e->sw, s);
     }
   };
   auto grad_range = [&](int eval_begin, int grad_begin, int count) {
@@ -461,7 +459,7 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
           // K > 4: the site likelihoods (and logL) come from a log-likelihood pass
           g.site_lik = e->site_lik.as<double>();
           g.site_exp = e->site_exp.as<int32_t>();
-          launch_loglik(g, part, d.rescaling, e->max_slots, s);
+          launch_loglik(g, part, d.rescaling, e->max_slots, e->sw, s);
         }
         if (fuse_setup) {
           FusedSetupArgs fs{};
@@ -469,13 +467,13 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
           fs.ms = ms;
           fs.mmats = e->mmats.as<double>();
           fs.ready = e->ready.as<int32_t>();
-          fs.debug_skip = e->fused_debug_skip;
-          fs.spin_ticks = e->fused_spin_ticks;
-          fs.fence = e->fused_fence;
-          fs.colocate = e->fused_colocate;
+          fs.debug_skip = e->sw.fused_debug_skip;
+          fs.spin_ticks = e->sw.fused_spin_ticks;
+          fs.fence = e->sw.fused_fence;
+          fs.colocate = e->sw.fused_colocate;
           launch_gradient_walk_lut_fused(g, fs, part, d.rescaling, s);
-        } else if (walk3) launch_gradient_walk_lut(g, part, d.rescaling, s);
-        else launch_gradient_walk(g, part, d.rescaling, analytic, s);
+        } else if (walk3) launch_gradient_walk_lut(g, part, d.rescaling, e->sw, s);
+        else launch_gradient_walk(g, part, d.rescaling, analytic, e->sw, s);
       }
       return;
     }
@@ -496,7 +494,7 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   PROF_MARK(e, marks, 2, s);
   if (!d.gradient) {
     loglik_range(0, T);
-    e->dominant = loglik_kernel_name(la, d.rescaling, e->max_slots);
+    e->dominant = loglik_kernel_name(la, d.rescaling, e->max_slots, e->sw);
     if (prof) HIP_TRY(hipEventRecord(prof_event(e, 1), s));
     PROF_MARK(e, marks, 3, s);
   } else {
@@ -577,7 +575,7 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
     ra.macro_count = e->macro_count.as<int32_t>();
     // one evaluation per tree (JC69-type models, the analytic GTR gradient; log-likelihood
     // calls too): tile reduction and finalize step in ONE launch, a workgroup per tree
-    fused = fuse_allowed && c.E == T;
+    fused = e->sw.fuse_finalize && c.E == T;
     if (!fused) launch_reduce_tiles(ra, s);
     fused_ra = ra;
     fa.ll_tiles = 1;
@@ -718,17 +716,25 @@ int32_t mi_device_count(void) {
 }
 
 // (device_tips / device_weights: the tips already on the device, mi_engine_create_device_tips)
-static int32_t create_engine(const mi_engine_spec* spec, const double* exchangeabilities,
-                             const double* frequencies, const int32_t* tip_states,
-                             const double* tip_partials, const double* pattern_weights,
-                             mi_engine** out_engine, const int32_t* device_tips = nullptr,
+static int32_t create_engine(const mi_engine_spec* spec, const Switches& sw,
+                             const double* exchangeabilities, const double* frequencies,
+                             const int32_t* tip_states, const double* tip_partials,
+                             const double* pattern_weights, mi_engine** out_engine,
+                             const int32_t* device_tips = nullptr,
                              const double* device_weights = nullptr);
+// The switches of a new engine (or sharded handle), read before anything else is done.
+static int32_t read_switches(Switches& sw) {
+  std::string error;
+  return parse_switches(sw, error) ? 0 : fail(error);
+}
 
 int32_t mi_engine_create_device_tips(const mi_engine_spec* spec, const int32_t* device_tip_states,
                                      const double* device_pattern_weights,
                                      mi_engine** out_engine) {
+  Switches sw;
+  if (read_switches(sw)) return 1;
   if (!device_tip_states || !device_pattern_weights) return fail("null device pointer");
-  return create_engine(spec, nullptr, nullptr, nullptr, nullptr, nullptr, out_engine,
+  return create_engine(spec, sw, nullptr, nullptr, nullptr, nullptr, nullptr, out_engine,
                        device_tip_states, device_pattern_weights);
 }
 
@@ -759,7 +765,9 @@ __global__ __launch_bounds__(256) void tips_prepare_kernel(const int32_t* in, in
 int32_t mi_engine_create(const mi_engine_spec* spec, const int32_t* tip_states,
                          const double* tip_partials, const double* pattern_weights,
                          mi_engine** out_engine) {
-  return create_engine(spec, nullptr, nullptr, tip_states, tip_partials, pattern_weights,
+  Switches sw;
+  if (read_switches(sw)) return 1;
+  return create_engine(spec, sw, nullptr, nullptr, tip_states, tip_partials, pattern_weights,
                        out_engine);
 }
 
@@ -767,19 +775,21 @@ int32_t mi_engine_create_reversible(const mi_engine_spec* spec, const double* ex
                                     const double* frequencies, const int32_t* tip_states,
                                     const double* tip_partials, const double* pattern_weights,
                                     mi_engine** out_engine) {
+  Switches sw;
+  if (read_switches(sw)) return 1;
   if (spec && spec->subst_model != MI_SUBST_REVERSIBLE)
     return fail("mi_engine_create_reversible needs subst_model == MI_SUBST_REVERSIBLE");
   if ((exchangeabilities == nullptr) != (frequencies == nullptr))
     return fail("pass both exchangeabilities and frequencies, or neither (built-in WAG)");
-  return create_engine(spec, exchangeabilities, frequencies, tip_states, tip_partials,
+  return create_engine(spec, sw, exchangeabilities, frequencies, tip_states, tip_partials,
                        pattern_weights, out_engine);
 }
 
-static int32_t create_engine(const mi_engine_spec* spec, const double* exchangeabilities,
-                             const double* frequencies, const int32_t* tip_states,
-                             const double* tip_partials, const double* pattern_weights,
-                             mi_engine** out_engine, const int32_t* device_tips,
-                             const double* device_weights) {
+static int32_t create_engine(const mi_engine_spec* spec, const Switches& sw,
+                             const double* exchangeabilities, const double* frequencies,
+                             const int32_t* tip_states, const double* tip_partials,
+                             const double* pattern_weights, mi_engine** out_engine,
+                             const int32_t* device_tips, const double* device_weights) {
   if (!spec || !out_engine) return fail("null spec / out_engine");
   *out_engine = nullptr;
   if (spec->taxon_count < 3) return fail("need at least 3 taxa");
@@ -836,36 +846,9 @@ static int32_t create_engine(const mi_engine_spec* spec, const double* exchangea
   int lg = 0;
   while ((2 << lg) <= e->n) lg++;
   e->max_slots = lg + 1;
-  if (const char* env = getenv("MI_PHYLO_PLV_BYTES")) e->plv_budget = strtoull(env, nullptr, 10);
-  if (const char* env = getenv("MI_PHYLO_SUBST_GRADIENT"))
-    e->analytic_subst = std::string(env) == "analytic";
-  // Which generation of the matrix-core gradient walk a call takes: the third (kernels_walk3.hip:
-  // tip children looked up; one-hot / all-ones tips, at most four rate categories, no analytic
-  // substitution gradient -- everything the reference produces) wherever it applies, else the
-  // second (kernels_walk.hip: mask tips, any category count, analytic gradient).
-  // MI_PHYLO_GRADIENT_WALK=v2 keeps every call on the second.  (The first generation,
-  // gradient_mfma_kernel, was retired in round 6: the second had been ahead of it on every shape
-  // but the arena shapes with fewer than three categories and a handful of tiles -- fluA: 0.321
-  // against 0.335 ms per 1000 trees -- and those now take the third: 0.305 -> 0.29.)
-  if (const char* env = getenv("MI_PHYLO_GRADIENT_WALK")) e->walk3 = std::string(env) != "v2";
-  if (const char* env = getenv("MI_PHYLO_FUSED_SETUP")) e->fused_setup = std::string(env) != "0";
-  if (const char* env = getenv("MI_PHYLO_DEBUG_FUSED_SKIP")) e->fused_debug_skip = atoi(env);
-  // the one-launch call's hand-off (kernels_walk3.hip, walk_lut_body): none | l1 (default) | agent
-  if (const char* env = getenv("MI_PHYLO_FUSED_FENCE"))
-    e->fused_fence = std::string(env) == "none" ? 0 : (std::string(env) == "agent" ? 2 : 1);
-  if (const char* env = getenv("MI_PHYLO_FUSED_COLOCATE")) e->fused_colocate = std::string(env) != "0";
-  // how long a walk wave of the one-launch call polls before it gives up (testing; default 1 s)
-  if (const char* env = getenv("MI_PHYLO_FUSED_SPIN_MS"))
-    e->fused_spin_ticks = (int)std::min(2.0e9, std::max(0.01, atof(env)) * 1.0e5);
-  // MI_PHYLO_WALK3_ARENA=0: arena-variant calls stay with the second / first generation (A/B)
-  if (const char* env = getenv("MI_PHYLO_WALK3_ARENA")) e->walk3_arena = std::string(env) != "0";
-  // MI_PHYLO_WALK3_K1=0: one-category calls with the vectors in LDS take the third generation only where the one-launch call applies (A/B)
-  if (const char* env = getenv("MI_PHYLO_WALK3_K1")) e->walk3_k1_lds = std::string(env) != "0";
-  if (const char* env = getenv("MI_PHYLO_GRADIENT_PATH")) {  // force one gradient kernel
-    const std::string v(env);
-    e->gradient_path = v == "hbm" ? 2 : v == "mfma" ? 3 : 0;
-    e->allow_onchip_gradient = v != "hbm";
-  }
+  e->sw = sw;
+  e->fused_setup = sw.fused_setup;
+  if (sw.plv_bytes >= 0) e->plv_budget = (size_t)sw.plv_bytes;
 
   // BlockSpecification (block_specification.cpp:11-50, phylo_model.cpp:13-15)
   std::map<std::string, std::pair<int, int>> bm;
@@ -1135,7 +1118,7 @@ int32_t mi_engine_reserve(mi_engine* e, int32_t tree_count, int32_t for_gradient
     if (e->red_g.ensure(sizeof(double) * (size_t)tree_count * e->N)) return 1;
     if (e->red_site.ensure(sizeof(double) * tree_count)) return 1;
   }
-  const bool analytic = e->analytic_subst && e->spec.subst_model == MI_SUBST_GTR;
+  const bool analytic = e->sw.analytic_subst && e->spec.subst_model == MI_SUBST_GTR;
   if (reserve(e, tree_count, grad, !onchip_plain, analytic && onchip_plain)) return 1;
   if (grad && onchip_plain != onchip_rescaled &&
       reserve(e, tree_count, grad, !onchip_rescaled, analytic && onchip_rescaled))
@@ -1433,6 +1416,8 @@ int32_t mi_engine_create_sharded(const mi_engine_spec* spec, int32_t shard_count
                                  const double* exchangeabilities, const double* frequencies,
                                  const int32_t* tip_states, const double* tip_partials,
                                  const double* pattern_weights, mi_engine** out_engine) {
+  Switches sw;  // (one snapshot for every shard)
+  if (read_switches(sw)) return 1;
   if (!spec || !out_engine) return fail("null spec / out_engine");
   *out_engine = nullptr;
   if (shard_count <= 0) return fail("Thread count needs to be strictly positive.");  // engine.cpp:14-16
@@ -1447,6 +1432,7 @@ int32_t mi_engine_create_sharded(const mi_engine_spec* spec, int32_t shard_count
   if (hipGetDevice(&current) != hipSuccess) current = 0;
   mi_engine* front = new mi_engine();
   front->spec = *spec;
+  front->sw = sw;
   front->shard_mode = shard_mode;
   front->n = spec->taxon_count;
   front->N = 2 * front->n - 1;
@@ -1483,7 +1469,7 @@ int32_t mi_engine_create_sharded(const mi_engine_spec* spec, int32_t shard_count
     }
     mi_engine* shard = nullptr;
     const int rc = create_engine(
-        &sub, exchangeabilities, frequencies,
+        &sub, sw, exchangeabilities, frequencies,
         shard_mode == MI_SHARD_PATTERNS ? (tip_states ? tips.data() : nullptr) : tip_states,
         shard_mode == MI_SHARD_PATTERNS ? (tip_partials ? parts.data() : nullptr) : tip_partials,
         pattern_weights + b, &shard);

@@ -143,24 +143,15 @@ struct mi_engine {
       ll_sum, g_sum, status;
   Buffer weibull_x;  // [K][2] {x_k, log x_k} of the Weibull quantiles (once per engine)
   Buffer ready;  // [T] hand-off words of the one-launch small call (zero between calls)
-  bool fused_setup = true;  // MI_PHYLO_FUSED_SETUP=0: always the four-launch sequence
+  bool fused_setup = true;  // sw.fused_setup, turned off for good by a time-out (check_status)
   bool fused_timed_out = false;  // check_status found the one-launch call's time-out word set
   int fused_fallbacks = 0;       // host-pointer calls that were run again through four launches
-  int fused_fence = 1;           // MI_PHYLO_FUSED_FENCE=none|l1|agent: 0 | 1 | 2 (FusedSetupArgs::fence)
-  bool fused_colocate = true;    // MI_PHYLO_FUSED_COLOCATE=0: set-up waves in id order (round 5)
-  int fused_spin_ticks = 0;      // MI_PHYLO_FUSED_SPIN_MS (testing): the walk waves' poll budget, 100 MHz ticks
-  int fused_debug_skip = 0;      // MI_PHYLO_DEBUG_FUSED_SKIP=t+1: tree t's set-up never reports (testing)
   // 20-state path: the engine's eigensystem and the streamed workspace (the arena is `plv`)
   Buffer aa_model, aa_matP, aa_matPT, aa_tipP, aa_tipPQ, aa_exp_cum, aa_exp_loc,
       aa_root_val, aa_root_exp, aa_root_scale;
   bool aa_reserved_gradient = false;
   PinnedArena pinned;
-  bool allow_onchip_gradient = true;
-  bool analytic_subst = false;       // MI_PHYLO_SUBST_GRADIENT=analytic (opt-in)
-  int gradient_path = 0;  // 0 auto, 2 hbm, 3 mfma (MI_PHYLO_GRADIENT_PATH)
-  bool walk3 = true;      // third generation where it applies (tip children looked up; MI_PHYLO_GRADIENT_WALK=v2: off)
-  bool walk3_k1_lds = true;  // one category, vectors in LDS: third generation for every batch size (MI_PHYLO_WALK3_K1=0: only where the one-launch call applies, the second generation beyond -- the rule until the tip codes were pre-tiled)
-  bool walk3_arena = true;  // ... for arena-variant calls too (MI_PHYLO_WALK3_ARENA=0: off)
+  Switches sw;  // the MI_PHYLO_* switches as they were when the engine was created
   int tile_regs = -1;  // look-up walk: the engine's tile width (0: default, 4: wide; -1: not decided yet -- engine_tile_regs)
   // a sharded handle (mi_engine_create_sharded): the per-device / per-shard engines it
   // drives; such a handle owns no device memory itself
@@ -176,7 +167,7 @@ struct mi_engine {
   Buffer in_parent, in_bl, in_params, in_rates, in_rate_counts, in_heights, in_bounds,
       in_ratios, out_ll, out_a, out_b, out_site, out_subst;
   Buffer in_pack, out_pack;  // one block each way per host-pointer call (begin_host_call)
-  size_t plv_budget = (size_t)8 << 30;
+  size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)
   std::vector<hipEvent_t> prof_events;  // kProfEvents per call: [begin, end, mark 0..4]
   int prof_capacity = 0, prof_used = 0;

@@ -48,7 +48,7 @@ int aa_engine_init(mi_engine* e, const double* exchangeabilities, const double* 
                          e->stream));
   HIP_TRY(hipMemsetAsync(e->status.ptr, 0, sizeof(int32_t) * 2, e->stream));
   launch_aa_model_setup(dex.as<double>(), dfr.as<double>(), e->aa_model.as<AaModel>(),
-                        e->status.as<int32_t>(), e->stream);
+                        e->status.as<int32_t>(), e->sw, e->stream);
   int32_t st[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(st, e->status.ptr, sizeof st, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -163,7 +163,7 @@ int aa_run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   const bool prof = e->prof_used < e->prof_capacity;
   const bool marks = prof && e->prof_phases;
   PROF_MARK(e, marks, 0, s);
-  launch_setup(ts, ms, s);
+  launch_setup(ts, ms, e->sw, s);
 
   if (prof) HIP_TRY(hipEventRecord(prof_event(e, 0), s));
   const int chunk = aa_chunk(e, T, d.gradient);
@@ -220,23 +220,23 @@ int aa_run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
     w.g_sum = e->g_sum.as<double>();
     PROF_MARK(e, marks && off == 0, 1, s);
     if (first_chunk) {  // (the path string describes the first -- largest -- launch of the call)
-      post_ring = aa_post_ring_entries(w);
-      post_tiles = aa_post_tiles_per_wave(w);
+      post_ring = aa_post_ring_entries(w, e->sw);
+      post_tiles = aa_post_tiles_per_wave(w, e->sw);
       first_chunk = false;
     }
-    launch_aa_post(w, s);
+    launch_aa_post(w, e->sw, s);
     launch_aa_root(w, s);
     PROF_MARK(e, marks && off == 0, 2, s);
-    if (d.gradient) launch_aa_pre(w, s);
+    if (d.gradient) launch_aa_pre(w, e->sw, s);
     PROF_MARK(e, marks && off == 0, 3, s);
     launch_aa_reduce(w, s);
   }
   if (prof) HIP_TRY(hipEventRecord(prof_event(e, 1), s));
-  e->dominant = d.gradient ? aa_pre_kernel_name() : aa_post_kernel_name();
+  e->dominant = d.gradient ? aa_pre_kernel_name(e->sw) : aa_post_kernel_name(e->sw);
   // (the stack tops of the walks live in LDS rings: kernels_aa.hip)
   e->last_path = std::string(e->dominant) + " store=hbm-arena" +
                  " post-tiles=" + std::to_string(post_tiles) + " post-ring=" + std::to_string(post_ring) +
-                 (d.gradient ? " pre-ring=" + std::to_string(aa_pre_ring_entries()) : std::string()) +
+                 (d.gradient ? " pre-ring=" + std::to_string(aa_pre_ring_entries(e->sw)) : std::string()) +
                  " states=20 K=" + std::to_string(e->K);
   e->last_evals = T;
   e->last_grad_evals = d.gradient ? T : 0;

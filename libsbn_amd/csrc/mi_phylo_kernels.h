@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mi_phylo_device.h"
+#include "mi_phylo_switches.h"
 
 namespace miphylo {
 
@@ -169,12 +170,14 @@ struct FinalizeArgs {
 
 // tree schedules (one wave per tree) and model instances (one thread each) in one launch
 // (returns true when the arena's slot assignment was done in the same launch: a.arena_macros)
-bool launch_setup(const TreeSetupArgs& a, const ModelSetupArgs& ms, hipStream_t s);
-bool launch_tree_setup(const TreeSetupArgs& a, hipStream_t s);  // (as launch_setup)  // trees only
+// (sw: MI_PHYLO_TREE_SETUP, MI_PHYLO_MACRO_SLOTS)
+bool launch_setup(const TreeSetupArgs& a, const ModelSetupArgs& ms, const Switches& sw, hipStream_t s);
+bool launch_tree_setup(const TreeSetupArgs& a, const Switches& sw, hipStream_t s);  // (as launch_setup)  // trees only
 void launch_weibull_table(int K, double* table, hipStream_t s);  // once per engine: ModelSetupArgs::weibull_x
 void launch_transition(const TransitionArgs& a, hipStream_t s);
 // On-chip (LDS-resident) log-likelihood: evaluations [eval_offset, eval_offset+count)
-void launch_loglik(const LikArgs& a, int count, bool rescale, int max_slots, hipStream_t s);
+// (sw: MI_PHYLO_LOGLIK_PATH, MI_PHYLO_LOGLIK_EVALS_PER_WAVE)
+void launch_loglik(const LikArgs& a, int count, bool rescale, int max_slots, const Switches& sw, hipStream_t s);
 int loglik_mfma_tiles(int P, int K);
 // the matrix-core log-likelihood kernel's tip bytes, pre-tiled once per engine (LikArgs::tip_tiles)
 size_t loglik_tip_tiles_bytes(int n, int P, int K);
@@ -184,8 +187,8 @@ int gradient_mfma_tiles(int P, int K, int regs = 0);  // regs: registers per vec
 size_t tip_code_tiles_bytes(int n, int P, int K, int regs);
 void launch_tip_code_tiles(const uint8_t* codes, uint8_t* out, int n, int P, int K, int regs, hipStream_t s);
 // tile width of the look-up walk for an engine whose batches take the arena (kLlR or 4:
-// kernels_walk3.hip, RR)
-int gradient_walk_tile_regs(int n, int P, int K);
+// kernels_walk3.hip, RR; forced: MI_PHYLO_WALK_TILE_REGS, 0 if unset)
+int gradient_walk_tile_regs(int n, int P, int K, int forced);
 // Gradient, partial-likelihood vectors streamed through HBM (any tree size, rescaling)
 void launch_gradient_hbm(const LikArgs& a, int count, bool rescale, hipStream_t s);
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
@@ -199,7 +202,7 @@ int gradient_mfma_width(int n, bool subst = false);  // doubles per (gradient ev
 // assignment pass, and its HBM need per evaluation
 void launch_macro_slots(const MacroEntry* macros_in, MacroEntry* macros_out,
                         const int32_t* macro_count, int n, int T, int32_t* need, int32_t* status,
-                        hipStream_t s);
+                        const Switches& sw, hipStream_t s);
 size_t gradient_arena_bytes_per_eval(int n, int P, int K);
 int device_compute_units();  // of the current device
 bool arena_single_launch(size_t lds_bytes, size_t waves);  // all waves resident at once?
@@ -207,12 +210,14 @@ int gradient_arena_slots_sure(int n);
 int gradient_arena_slots_usual(int n);
 // second generation of the same walk (kernels_walk.hip): macro-ordered operand streams
 void launch_transition_macro(const TransitionMacroArgs& a, hipStream_t s);
-void launch_gradient_walk(const LikArgs& a, int count, bool rescale, bool subst, hipStream_t s);
+// (sw: MI_PHYLO_WALK_TILES_PER_WAVE, MI_PHYLO_GRADIENT_STORE)
+void launch_gradient_walk(const LikArgs& a, int count, bool rescale, bool subst, const Switches& sw, hipStream_t s);
 bool gradient_walk_fits(int n, int K, bool rescale);
-// lut: the call runs the third-generation (look-up) walk, whose arena variant pays one step earlier
-bool gradient_walk_use_arena(int n, int K, bool rescale, bool subst, size_t waves = (size_t)-1, bool lut = false,
-                             int regs = 0);  // regs: the engine's tile width (0: default)
-bool gradient_walk_batches_take_arena(int n, int K, bool lut);  // (large batch, no rescaling, whatever MI_PHYLO_GRADIENT_STORE says)
+// lut: the call runs the third-generation (look-up) walk, whose arena variant pays one step earlier;
+// store: MI_PHYLO_GRADIENT_STORE (Switches::gradient_store)
+bool gradient_walk_use_arena(int store, int n, int K, bool rescale, bool subst, size_t waves = (size_t)-1,
+                             bool lut = false, int regs = 0);  // regs: the engine's tile width (0: default)
+bool gradient_walk_batches_take_arena(int n, int K, bool lut);  // (large batch, no rescaling, no store forced)
 size_t gradient_walk_lds_bytes(int n, int K, bool rescale, bool subst, int regs = 0);
 size_t gradient_walk_lds_bytes_for(int n, int K, bool rescale, bool subst, int slots, int regs = 0);
 size_t gradient_walk_mats_bytes_per_eval(int n, int K);
@@ -221,7 +226,8 @@ const char* gradient_walk_kernel_name();
 size_t gradient_walk_lut_mats_bytes_per_eval(int n);
 void launch_transition_lut(const TransitionMacroArgs& a, hipStream_t s);
 bool gradient_walk_lut_applies(int K);
-void launch_gradient_walk_lut(const LikArgs& a, int count, bool rescale, hipStream_t s);
+// (sw: MI_PHYLO_ARENA_NT, MI_PHYLO_GRADIENT_STORE)
+void launch_gradient_walk_lut(const LikArgs& a, int count, bool rescale, const Switches& sw, hipStream_t s);
 // The one-launch small call (round 5): tree set-up, model instances and operand records as the
 // FIRST workgroups of the walk's launch (four waves per tree), the walk waves wait for their
 // tree's hand-off word `ready[t]` (zero before the launch; reduce_finalize clears it again).
@@ -252,7 +258,7 @@ void launch_setup_records(const FusedSetupArgs& f, int count, hipStream_t s);
 const char* gradient_walk_lut_kernel_name();
 const char* gradient_walk_lut_fused_kernel_name();
 // waves per CU the walks' LDS footprint allows for this tree size and category count
-int gradient_walk_waves_per_cu(int n, int K);
+int gradient_walk_waves_per_cu(int store, int n, int K);
 // Sum of the per-tile partials: ll_sum[e] = sum_i ll_part[e][i] for e < E,
 // g_sum[gi][2N] = sum_i g_part[gi][i][2N] for gi < Eg (fixed order: deterministic).
 struct ReduceArgs {
@@ -384,22 +390,23 @@ struct AaWalkArgs {
 };
 
 void launch_aa_model_setup(const double* exchangeabilities, const double* freqs, AaModel* model,
-                           int32_t* status, hipStream_t s);
+                           int32_t* status, const Switches& sw, hipStream_t s);
 void launch_aa_transition(const AaTransitionArgs& a, hipStream_t s);
 int aa_tiles(int P);                 // padded tile count
 int aa_ll_blocks(int P);             // partial log-likelihood sums per evaluation
-void launch_aa_post(const AaWalkArgs& a, hipStream_t s);
+// (sw: the MI_PHYLO_AA_* launch switches)
+void launch_aa_post(const AaWalkArgs& a, const Switches& sw, hipStream_t s);
 void launch_aa_root(const AaWalkArgs& a, hipStream_t s);
-void launch_aa_pre(const AaWalkArgs& a, hipStream_t s);
+void launch_aa_pre(const AaWalkArgs& a, const Switches& sw, hipStream_t s);
 // entries of the LDS rings the two launchers above will use for these arguments
-int aa_post_ring_entries(const AaWalkArgs& a);
-int aa_post_tiles_per_wave(const AaWalkArgs& a);  // 16-pattern tiles a wave of the post-order kernel takes (1, 2 or 4)
-int aa_pre_ring_entries();
+int aa_post_ring_entries(const AaWalkArgs& a, const Switches& sw);
+int aa_post_tiles_per_wave(const AaWalkArgs& a, const Switches& sw);  // 16-pattern tiles a wave of the post-order kernel takes (1, 2 or 4)
+int aa_pre_ring_entries(const Switches& sw);
 void launch_aa_reduce(const AaWalkArgs& a, hipStream_t s);
-const char* aa_post_kernel_name();
-const char* aa_pre_kernel_name();
+const char* aa_post_kernel_name(const Switches& sw);
+const char* aa_pre_kernel_name(const Switches& sw);
 
-const char* loglik_kernel_name(const LikArgs& a, bool rescale, int max_slots);
+const char* loglik_kernel_name(const LikArgs& a, bool rescale, int max_slots, const Switches& sw);
 const char* gradient_kernel_name();
 
 }  // namespace miphylo

@@ -29,11 +29,14 @@ int main(int argc, char** argv) {
   TreeSetupArgs a{}; a.n = n; a.T = T; a.rooted = rooted; a.parent_ids = d_pid; a.bl = d_bl; a.rates = nullptr; a.scratch = d_scratch;
   a.sched = d_sched; a.macros = d_mac; a.macro_count = d_mc; a.bl_eff = d_ble; a.status = d_status; a.max_slots = 32; a.need_slots = 1;
   const int fold = argc > 6 ? atoi(argv[6]) : 0;
+  Switches sw;  // MI_PHYLO_TREE_SETUP / MI_PHYLO_MACRO_SLOTS, as an engine reads them
+  std::string error;
+  if (!parse_switches(sw, error)) { fprintf(stderr, "%s\n", error.c_str()); return 1; }
   MacroEntry* d_mac2; int32_t* d_need;
   hipMalloc(&d_mac2, sizeof(MacroEntry) * (size_t)T * macro_stride(n)); hipMalloc(&d_need, T * 4);
   hipMemset(d_mac2, 0, sizeof(MacroEntry) * (size_t)T * macro_stride(n)); hipMemset(d_need, 0, T * 4);
   if (fold) { a.arena_macros = d_mac2; a.slot_need = d_need; }
-  const bool folded = launch_tree_setup(a, nullptr); hipDeviceSynchronize();
+  const bool folded = launch_tree_setup(a, sw, nullptr); hipDeviceSynchronize();
   std::vector<SchedEntry> sc((size_t)T * (n - 1)); std::vector<MacroEntry> mac((size_t)T * macro_stride(n)); std::vector<int32_t> mc(T); int32_t st[2];
   hipMemcpy(sc.data(), d_sched, sc.size() * sizeof(SchedEntry), hipMemcpyDeviceToHost);
   hipMemcpy(mac.data(), d_mac, mac.size() * sizeof(MacroEntry), hipMemcpyDeviceToHost);
@@ -41,7 +44,7 @@ int main(int argc, char** argv) {
   // the arena variant's macro order / LDS slots / arena indices (macro_slots kernels)
   std::vector<MacroEntry> mac2((size_t)T * macro_stride(n)); std::vector<int32_t> need(T);
   if (st[0] == 0) {
-    if (!folded) launch_macro_slots(d_mac, d_mac2, d_mc, n, T, d_need, d_status, nullptr);
+    if (!folded) launch_macro_slots(d_mac, d_mac2, d_mc, n, T, d_need, d_status, sw, nullptr);
     hipDeviceSynchronize();
     hipMemcpy(mac2.data(), d_mac2, mac2.size() * sizeof(MacroEntry), hipMemcpyDeviceToHost);
     hipMemcpy(need.data(), d_need, T * 4, hipMemcpyDeviceToHost);

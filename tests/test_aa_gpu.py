@@ -268,8 +268,8 @@ def test_builtin_wag_equals_explicit_table_and_errors():
 def test_kernel_forms_agree_bitwise(tmp_path):
     """The wave-per-block walk kernels (MI_PHYLO_AA_POST=wave / MI_PHYLO_AA_PRE=wave, kept
     selectable) and the workgroup kernels with LDS-DMA staging are the same arithmetic in the
-    same order: identical log-likelihoods and gradients.  (The switches are read once per
-    process: each form runs in its own interpreter.)"""
+    same order: identical log-likelihoods and gradients.  (Each form runs in its own
+    interpreter.)"""
     import os
     import subprocess
     import sys

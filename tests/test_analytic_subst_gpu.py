@@ -22,7 +22,7 @@ WALK_KERNEL = ("gradient_walk_kernel",)
 
 @pytest.fixture
 def analytic(monkeypatch):
-    monkeypatch.setenv("MI_PHYLO_SUBST_GRADIENT", "analytic")  # read at engine creation
+    monkeypatch.setenv("MI_PHYLO_SUBST_GRADIENT", "analytic")
 
 
 def _params(spec, T, **blocks):

@@ -21,7 +21,7 @@ def test_cpp_engine_adapter(tmp_path):
     assert "all checks passed" in out.stdout
 
 
-def test_tree_setup_kernels_agree(tmp_path):
+def test_tree_setup_kernels_agree_with_parsed_switches(tmp_path):
     """The register-array tree-setup kernel (N <= 256, branch-free) and the workgroup-per-tree
     kernel (larger trees) must produce exactly what the sequential LDS kernel produces:
     status, macro counts, the Sethi-Ullman schedule with its LDS slots, and the half-storage

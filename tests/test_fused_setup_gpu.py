@@ -24,7 +24,7 @@ PLAIN = "gradient_walk_lut_kernel"
 
 
 def _engines(subst, site, tips, w, **kw):
-    """(one-launch engine, four-launch engine): the switch is read at engine creation."""
+    """(one-launch engine, four-launch engine)"""
     import libsbn_amd as L
     old = os.environ.get("MI_PHYLO_FUSED_SETUP")
     try:
@@ -116,8 +116,8 @@ def _site_params(spec, T, site, rng):
 @pytest.mark.parametrize("site", ["constant", "weibull+2", "weibull+3", "weibull+4"])
 def test_small_and_rooted_trees(site):
     """(round 6: two rate categories take the look-up walk, and with it the one-launch call, as
-    well; one category with the vectors in LDS stays with the second generation, whose waves take
-    several tiles in a row -- MI_PHYLO_WALK3_K1=1 sends it through the look-up walk too)"""
+    well; so does one category with the vectors in LDS since MI_PHYLO_WALK3_K1=1 became the
+    default -- set here all the same, so that the constant site model keeps this path)"""
     if site == "constant":
         os.environ["MI_PHYLO_WALK3_K1"] = "1"
     try:
@@ -252,7 +252,7 @@ def test_a_time_out_does_not_reach_a_host_pointer_caller(monkeypatch):
     pr = _params(spec, T, **{"Weibull shape": rng.uniform(0.3, 2.0, size=(T, 1))})
     _, plain = _engines("JC69", "weibull+4", tips, w)
     ref = _flat(plain.gradients(pids, bls, pr))
-    monkeypatch.setenv("MI_PHYLO_FUSED_SPIN_MS", "20")  # (read at engine creation)
+    monkeypatch.setenv("MI_PHYLO_FUSED_SPIN_MS", "20")
     monkeypatch.setenv("MI_PHYLO_DEBUG_FUSED_SKIP", "3")
     monkeypatch.setenv("MI_PHYLO_FUSED_SETUP", "1")
     broken = L.Engine(L.PhyloModelSpecification("JC69", "weibull+4", "strict"), tips, w)
@@ -335,14 +335,14 @@ def test_hand_off_modes_and_arena_access_forms_are_bit_identical(monkeypatch):
     for regs in ("3", "4"):
         monkeypatch.setenv("MI_PHYLO_WALK_TILE_REGS", regs)
         monkeypatch.setenv("MI_PHYLO_GRADIENT_STORE", "arena")
-        eng = L.Engine(L.PhyloModelSpecification("JC69", "weibull+4", "strict"), tips, w)
         for nt in ("0", "1"):
-            monkeypatch.setenv("MI_PHYLO_ARENA_NT", nt)  # (read by the launcher at every launch)
+            monkeypatch.setenv("MI_PHYLO_ARENA_NT", nt)
+            eng = L.Engine(L.PhyloModelSpecification("JC69", "weibull+4", "strict"), tips, w)
             got[regs, nt] = _flat(eng.gradients(pids, bls, pr))
             assert "store=arena" in eng.last_call_path()
             assert ("tile=wide" in eng.last_call_path()) == (regs == "4")
+            eng.close()
         monkeypatch.delenv("MI_PHYLO_ARENA_NT")
-        eng.close()
     monkeypatch.setenv("MI_PHYLO_WALK_TILE_REGS", "3")
     monkeypatch.setenv("MI_PHYLO_GRADIENT_STORE", "lds")
     eng = L.Engine(L.PhyloModelSpecification("JC69", "weibull+4", "strict"), tips, w)
@@ -354,10 +354,10 @@ def test_hand_off_modes_and_arena_access_forms_are_bit_identical(monkeypatch):
     assert np.allclose(got["4", "0"], lds, rtol=1e-11, atol=1e-12 * np.max(np.abs(lds)))
 
 
-def test_setup_and_records_in_one_launch_for_large_batches(monkeypatch):
+def test_setup_and_records_in_one_launch_engine_per_setting(monkeypatch):
     """Beyond the one-launch call's 512 trees the same set-up waves can run as ONE launch in front
-    of the walk's (round 6: launch_setup_records, MI_PHYLO_SETUP_RECORDS=1, read per call; measured
-    level with the two launches it replaces and not the default) instead of the tree set-up and
+    of the walk's (round 6: launch_setup_records, MI_PHYLO_SETUP_RECORDS=1; measured level with
+    the two launches it replaces and not the default) instead of the tree set-up and
     the record launches.  Same trees, model instances and operand records: results bit-identical
     to the four-launch sequence -- two to four categories,
     rescaling, GTR with the branch-length gradient only, an input error reported with its tree."""
@@ -372,11 +372,11 @@ def test_setup_and_records_in_one_launch_for_large_batches(monkeypatch):
             blocks["GTR rates"] = r
             blocks["frequencies"] = f
         pr = _params(spec, T, **blocks)
-        eng = L.Engine(L.PhyloModelSpecification(subst, site, "strict"), tips, w)
         only = ("branch_lengths",) if subst == "GTR" else None
-        got = {}
+        got, engs = {}, {}
         for mode in ("1", "0"):
             monkeypatch.setenv("MI_PHYLO_SETUP_RECORDS", mode)
+            eng = engs[mode] = L.Engine(L.PhyloModelSpecification(subst, site, "strict"), tips, w)
             res = []
             for resc in (False, True):
                 res.append(_flat(eng.gradients(pids, bls, pr, resc, gradient_blocks=only)))
@@ -386,12 +386,12 @@ def test_setup_and_records_in_one_launch_for_large_batches(monkeypatch):
         monkeypatch.delenv("MI_PHYLO_SETUP_RECORDS")
         assert np.isfinite(got["1"]).all() and np.array_equal(got["1"], got["0"]), (subst, site)
         if subst == "JC69" and site == "weibull+4":
-            monkeypatch.setenv("MI_PHYLO_SETUP_RECORDS", "1")
+            eng = engs["1"]
             bad = pids.copy()
             bad[640, 5] = 2
             with pytest.raises(RuntimeError) as err:
                 eng.gradients(bad, bls, pr)
             assert "(tree 640)" in str(err.value)
             assert np.array_equal(_flat(eng.gradients(pids, bls, pr)), got["1"][:len(got["1"]) // 2])
-            monkeypatch.delenv("MI_PHYLO_SETUP_RECORDS")
-        eng.close()
+        for eng in engs.values():
+            eng.close()

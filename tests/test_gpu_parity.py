@@ -474,8 +474,8 @@ def test_rescaled_gradients_stay_on_the_matrix_core_kernel():
 def test_both_loglik_kernels_match_oracle(path, kernel):
     """The matrix-core log-likelihood kernel (default for K <= 4 without rescaling) and
     the VALU kernel (rescaling, K > 4, real-valued tip partials) can each be forced with
-    MI_PHYLO_LOGLIK_PATH: same parity bar for both.  The path is chosen once per
-    process, hence the subprocess."""
+    MI_PHYLO_LOGLIK_PATH: same parity bar for both.  (Each path runs in a subprocess of its
+    own.)"""
     import subprocess
     import sys
     code = r"""
@@ -519,7 +519,7 @@ print('path-ok')
 def test_both_gradient_stores_match_oracle(store):
     """The matrix-core gradient kernel keeps the stored post-order vectors either all in LDS
     (small trees) or in an HBM arena with a few reusable LDS slots (MI_PHYLO_GRADIENT_STORE
-    forces one; chosen once per process, hence the subprocess): same parity bar, on DS1
+    forces one; each in a subprocess of its own): same parity bar, on DS1
     (27 taxa) and on 40- and 70-taxon random / ladder / balanced trees, with and without
     rescaling, constant rate and four categories, FD and analytic GTR gradients."""
     import subprocess
@@ -924,8 +924,7 @@ def test_walk_kernels_agree():
     order: log-likelihoods and gradients BIT-IDENTICAL wherever both apply, over rate-category
     counts 1 / 2 / 3 / 4 / 8, with and without rescaling, finite-difference GTR, stored vectors
     in LDS and in the arena, unrooted and rooted; the second generation's analytic-GTR form agrees
-    between the two stores to the last bits.  (The switches are read at engine creation / once per
-    process: each form runs in its own interpreter.)"""
+    between the two stores to the last bits.  (Each form runs in its own interpreter.)"""
     import subprocess
     import sys
     import tempfile
@@ -1040,8 +1039,8 @@ def test_waves_taking_several_tiles_are_bit_identical_and_match_oracle():
     """gradient_walk_kernel gives the first evaluations of a large launch to waves that take
     several pattern tiles in turn and the last ones a wave per tile.  The
     arithmetic of a tile does not depend on who walks it: results with 2, 3 and 8 tiles per
-    wave are bit-identical to a wave per tile (MI_PHYLO_WALK_TILES_PER_WAVE, read once per
-    process), with and without rescaling, with a partial last tile (130 patterns = 10 tiles of
+    wave are bit-identical to a wave per tile (MI_PHYLO_WALK_TILES_PER_WAVE), with and without
+    rescaling, with a partial last tile (130 patterns = 10 tiles of
     12 + 10) -- and trees of both sections agree with the oracle."""
     import subprocess
     import sys
@@ -1098,7 +1097,7 @@ def test_stored_vectors_in_lds_or_arena_are_bit_identical():
     (batches) -- is decided per call; the walk generation is fixed per engine.  With the
     generation held (v2, v3) the two stores give bit-identical results: unrooted and rooted,
     with and without rescaling, 1 / 3 / 4 rate categories -- so a tree's outputs do not
-    depend on the size of the batch it came in.  (The switches are read once per process.)"""
+    depend on the size of the batch it came in."""
     import subprocess
     import sys
     import tempfile
@@ -1187,7 +1186,7 @@ def test_limits_are_refused_at_the_c_abi_with_a_message():
 def test_pretiled_tip_bytes_are_what_the_kernel_stages_itself(monkeypatch):
     """loglik_mfma_kernel takes its tile's tip bytes from a copy laid out per tile at engine
     creation (round 6: launch_tip_tiles) instead of gathering them from the [taxon][pattern]
-    masks in every wave; MI_PHYLO_TIP_TILES=0 (read per call) keeps the gather.  Same bytes, same
+    masks in every wave; an engine made with MI_PHYLO_TIP_TILES=0 keeps the gather.  Same bytes, same
     arithmetic: bit-identical log-likelihoods -- 1 / 2 / 4 / 8 categories, a partial last tile,
     gaps, rescaling, tips handed over as states or as 0/1 partial vectors -- and the GTR
     finite-difference gradient, whose sixteen passes run the same kernel."""
@@ -1198,7 +1197,6 @@ def test_pretiled_tip_bytes_are_what_the_kernel_stages_itself(monkeypatch):
         T = 6
         tips, w = TU.random_alignment(n, P, rng, gap_fraction=0.1)
         pids, bls = TU.random_trees(n, T, rng, mean_bl=0.08)
-        eng = _engine(subst, site, "strict", tips, w, use_tip_states=not as_partials)
         spec = O.make_spec(n, P, subst, site, "strict", use_tip_states=0 if as_partials else 1)
         blocks = {}
         if subst == "GTR":
@@ -1211,6 +1209,7 @@ def test_pretiled_tip_bytes_are_what_the_kernel_stages_itself(monkeypatch):
         got = {}
         for tiles in ("1", "0"):
             monkeypatch.setenv("MI_PHYLO_TIP_TILES", tiles)
+            eng = _engine(subst, site, "strict", tips, w, use_tip_states=not as_partials)
             res = []
             for resc in (False, True):
                 res.append(np.asarray(eng.log_likelihoods(pids, bls, pr, resc)))
@@ -1218,8 +1217,8 @@ def test_pretiled_tip_bytes_are_what_the_kernel_stages_itself(monkeypatch):
             if subst == "GTR":
                 res.append(np.stack([x.gradient["substitution_model"] for x in eng.gradients(pids, bls, pr)]).ravel())
             got[tiles] = np.concatenate(res)
+            eng.close()
         monkeypatch.delenv("MI_PHYLO_TIP_TILES")
-        eng.close()
         assert np.isfinite(got["1"]).all()
         assert np.array_equal(got["1"], got["0"]), (n, P, site, np.max(np.abs(got["1"] - got["0"])))
 
@@ -1228,7 +1227,7 @@ def test_pretiled_tip_codes_are_what_the_walk_stages_itself(monkeypatch):
     """The look-up gradient walk copies a tip's codes of its tile from a per-tile layout made at
     engine creation (launch_tip_code_tiles: one word per column for three / four categories, one
     16-bit field for one / two) instead of regrouping the tile's bytes in every wave;
-    MI_PHYLO_TIP_TILES=0 (read per call) keeps the regrouping.  Same LDS contents: bit-identical
+    an engine made with MI_PHYLO_TIP_TILES=0 keeps the regrouping.  Same LDS contents: bit-identical
     gradients -- one to four categories, the one-launch call (small trees), every vector in LDS,
     the arena with default and wide tiles, a partial last tile, gaps, rescaling, rooted."""
     rng = np.random.default_rng(78)
@@ -1240,13 +1239,13 @@ def test_pretiled_tip_codes_are_what_the_walk_stages_itself(monkeypatch):
             monkeypatch.setenv("MI_PHYLO_WALK_TILE_REGS", regs)
         tips, w = TU.random_alignment(n, P, rng, gap_fraction=0.1)
         pids, bls = TU.random_trees(n, T, rng, mean_bl=0.08)
-        eng = _engine("JC69", site, "strict", tips, w)
         spec = O.make_spec(n, P, "JC69", site, "strict")
         blocks = {} if site == "constant" else {"Weibull shape": rng.uniform(0.4, 1.5, size=(T, 1))}
         pr = _params(spec, T, **blocks)
         got, paths = {}, set()
         for tiles in ("1", "0"):
             monkeypatch.setenv("MI_PHYLO_TIP_TILES", tiles)
+            eng = _engine("JC69", site, "strict", tips, w)
             res = []
             for resc in (False, True):
                 for x in eng.gradients(pids, bls, pr, resc):
@@ -1254,10 +1253,10 @@ def test_pretiled_tip_codes_are_what_the_walk_stages_itself(monkeypatch):
                     res += [np.atleast_1d(x.gradient[k]).ravel() for k in sorted(x.gradient)]
                 paths.add(eng.last_call_path())
             got[tiles] = np.concatenate(res)
+            eng.close()
         monkeypatch.delenv("MI_PHYLO_TIP_TILES")
         if regs:
             monkeypatch.delenv("MI_PHYLO_WALK_TILE_REGS")
-        eng.close()
         assert np.isfinite(got["1"]).all()
         assert np.array_equal(got["1"], got["0"]), (n, P, site, T, paths, np.max(np.abs(got["1"] - got["0"])))
     # rooted (fluA-like: one category, arena)
@@ -1271,17 +1270,17 @@ def test_pretiled_tip_codes_are_what_the_walk_stages_itself(monkeypatch):
     bd = np.stack([s[1] for s in state])
     ra = np.stack([s[2] for s in state])
     rates = np.full((T, 2 * n - 2), 0.7)
-    eng = _engine("JC69", "constant", "strict", tips, w)
     spec = O.make_spec(n, P, "JC69", "constant", "strict")
     pr = _params(spec, T)
     got = {}
     for tiles in ("1", "0"):
         monkeypatch.setenv("MI_PHYLO_TIP_TILES", tiles)
+        eng = _engine("JC69", "constant", "strict", tips, w)
         res = []
         for x in eng.rooted_gradients(pids, bls, pr, rates, np.ones(T, np.int32), h, bd, ra):
             res.append([x.log_likelihood])
             res += [np.atleast_1d(x.gradient[k]).ravel() for k in sorted(x.gradient)]
         got[tiles] = np.concatenate(res)
+        eng.close()
     monkeypatch.delenv("MI_PHYLO_TIP_TILES")
-    eng.close()
     assert np.isfinite(got["1"]).all() and np.array_equal(got["1"], got["0"])

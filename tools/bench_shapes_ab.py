@@ -1,6 +1,6 @@
 """A/B over the standard alignment shapes (DS1-DS8, 100 x 500, fluA-sized one-category trees):
 ms per `phylo_gradients` call of T random trees with the engine's default path against forced
-alternatives (environment switches read at engine creation), interleaved in one process on one
+alternatives (environment switches: an engine per variant), interleaved in one process on one
 box.  Prints, per shape and variant, ms per call, 1e9 taxa x patterns x trees / s, the fraction
 of the measured FP64 matrix peak (71.1 TFLOP/s) that the SURVEY 8(d) flop count amounts to, and
 the path the call took.  Every variant's log-likelihoods and gradients are compared with the

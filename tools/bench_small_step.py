@@ -1,6 +1,6 @@
 """The small (strong-scaling) step under switches: DS1 trees, `phylo_gradients` with the site
 gradient (JC69 + weibull+4), replayed from a hipGraph -- 200 replays between two events, best of
-five -- for every variant given (environment switches read at engine creation), interleaved in
+five -- for every variant given (environment switches: an engine per variant), interleaved in
 one process on one box; outputs compared with the first variant's.
   python tools/bench_small_step.py [--trees 125] name[=ENV=val[,ENV=val]] ...
 (the hand-off fences of the one-launch call, round 6.)"""
