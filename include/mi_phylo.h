@@ -184,6 +184,30 @@ int32_t mi_engine_gradients_unrooted_reduced(mi_engine* engine, int32_t tree_cou
                                              double* out_index_gradient /* [index_count] */,
                                              double* out_log_likelihoods /* [T] or NULL */);
 
+/* The diagonal of the branch-length Hessian of unrooted trees, per tree (an extension: no
+ * counterpart in the reference's Engine).  For branch j of length t_j, with q the pre-order
+ * vector at the bottom of the branch, L the post-order vector below it, Q the rate matrix and
+ * category rates r_k, weights c_k: per pattern L_p = sum_k c_k q.L, D1_p = sum_k c_k r_k q.(Q L),
+ * D2_p = sum_k c_k r_k^2 q.(Q^2 L), and
+ *   out_branch_gradient[t][j]    = sum_p w_p D1_p / L_p                       (the gradient)
+ *   out_branch_hessian[t][j]     = d^2 logL / d t_j^2 = sum_p w_p D2_p / L_p - S_j
+ *   out_branch_gradient_sq[t][j] = S_j = sum_p w_p (D1_p / L_p)^2   (squared-derivative sum)
+ * all [T][2n-1] in node-id order, the root and the fixed node (the last two entries) 0.  One
+ * evaluation per tree with the tree's own model (a GTR engine: no finite-difference passes);
+ * out_log_likelihoods, out_branch_gradient and out_branch_gradient_sq may be NULL.  The
+ * log-likelihood and the gradient delivered are the gradient call's to 1e-12 relative.
+ * 4-state engines only: a 20-state engine returns nonzero.  Sharded handles: MI_SHARD_TREES
+ * deals the trees as the other calls do, results in tree order; MI_SHARD_PATTERNS adds all
+ * four outputs (sums over patterns) in shard order. */
+int32_t mi_engine_branch_hessian_unrooted(mi_engine* engine, int32_t tree_count,
+                                          const int32_t* parent_ids,     /* [T][2n-3] */
+                                          const double* branch_lengths,  /* [T][2n-2] */
+                                          const double* params, int32_t rescaling,
+                                          double* out_log_likelihoods /* [T] or NULL */,
+                                          double* out_branch_gradient /* [T][2n-1] or NULL */,
+                                          double* out_branch_hessian /* [T][2n-1] */,
+                                          double* out_branch_gradient_sq /* [T][2n-1] or NULL */);
+
 /* Engine::LogLikelihoods(const RootedTreeCollection&) when with_jacobian != 0
  * (branch lengths x rates, + log-det-Jacobian, fat_beagle.cpp:82-104), or
  * Engine::UnrootedLogLikelihoods(const RootedTreeCollection&) when 0
@@ -269,6 +293,15 @@ int32_t mi_engine_gradients_unrooted_reduced_device(
     const int32_t* branch_index, const double* tree_weights, int32_t index_count,
     double* out_sums, double* out_index_gradient, double* out_log_likelihoods);
 
+int32_t mi_engine_branch_hessian_unrooted_device(mi_engine* engine, void* stream,
+                                                 int32_t tree_count, const int32_t* parent_ids,
+                                                 const double* branch_lengths,
+                                                 const double* params, int32_t rescaling,
+                                                 double* out_log_likelihoods,
+                                                 double* out_branch_gradient,
+                                                 double* out_branch_hessian,
+                                                 double* out_branch_gradient_sq);
+
 /* Make sure the workspace for `tree_count` trees exists (so that a following
  * *_device call allocates nothing and can be captured in a hipGraph).  20-state engines: if
  * the device cannot give the partial-vector arena its budget (MI_PHYLO_PLV_BYTES), the budget
@@ -283,6 +316,10 @@ int32_t mi_engine_reserve(mi_engine* engine, int32_t tree_count, int32_t for_gra
  * *_device call of at most that size then allocates nothing either (it used to
  * size and allocate its sort workspace inside the call). */
 int32_t mi_engine_reserve_reduced(mi_engine* engine, int32_t tree_count, int32_t index_count);
+/* The workspace of mi_engine_branch_hessian_unrooted[_device] for `tree_count` trees: a
+ * *_device call of at most that size then allocates nothing (hipGraph capture).  4-state
+ * engines only. */
+int32_t mi_engine_reserve_hessian(mi_engine* engine, int32_t tree_count);
 /* Synchronise `stream` and report the first per-tree error since the last check (the status
  * word is sticky and cleared when an error is reported: calls themselves never clear it). */
 int32_t mi_engine_check_status(mi_engine* engine, void* stream);

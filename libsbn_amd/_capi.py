@@ -61,8 +61,13 @@ SYMBOLS = {
     "mi_engine_gradients_rooted_device":
         (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, C.c_int32, _V, _V, _V,
                      _V, _V]),
+    "mi_engine_branch_hessian_unrooted":
+        (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V]),
+    "mi_engine_branch_hessian_unrooted_device":
+        (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V]),
     "mi_engine_reserve": (C.c_int32, [_V, C.c_int32, C.c_int32]),
     "mi_engine_reserve_reduced": (C.c_int32, [_V, C.c_int32, C.c_int32]),
+    "mi_engine_reserve_hessian": (C.c_int32, [_V, C.c_int32]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),
     "mi_engine_profile_begin": (C.c_int32, [_V, C.c_int32]),
     "mi_engine_profile_collect": (C.c_int32, [_V, F64P, C.c_int32, I32P]),

@@ -43,6 +43,11 @@ struct PhyloGradient {
   double log_likelihood_ = 0.;
   GradientMap gradient_;
 };
+// Engine::BranchHessians, per tree: [2n-1] each (an extension, include/mi_phylo.h)
+struct BranchHessian {
+  double log_likelihood_ = 0.;
+  std::vector<double> gradient_, hessian_, gradient_sq_;
+};
 
 struct ParamMatrix {  // row-major [rows x cols]
   size_t rows = 0, cols = 0;
@@ -181,6 +186,29 @@ class Engine {
       m.emplace_hint(m.end(), std::piecewise_construct, std::forward_as_tuple("branch_lengths"),
                      std::forward_as_tuple(g + t * N, g + (t + 1) * N));
       AddModelGradients(&out[t], site[t], subst + 8 * t);
+    }
+    return out;
+  }
+
+  // Diagonal of the branch-length Hessian per tree (an extension; 4-state engines):
+  // mi_engine_branch_hessian_unrooted.  Vectors in node-id order, root and fixed node 0.
+  std::vector<BranchHessian> BranchHessians(const UnrootedTreeCollection& trees,
+                                            const ParamMatrix& params, const bool rescaling) const {
+    const size_t T = trees.size(), N = 2 * site_pattern_.SequenceCount() - 1;
+    std::vector<int32_t> parents;
+    std::vector<double> bl;
+    Flatten(trees, params, false, &parents, &bl);
+    if (trees.empty()) return {};
+    std::vector<double> ll(T), g(T * N), h(T * N), s(T * N);
+    Check(mi_engine_branch_hessian_unrooted(handle_, static_cast<int32_t>(T), parents.data(),
+                                            bl.data(), params.data.data(), rescaling, ll.data(),
+                                            g.data(), h.data(), s.data()));
+    std::vector<BranchHessian> out(T);
+    for (size_t t = 0; t < T; t++) {
+      out[t].log_likelihood_ = ll[t];
+      out[t].gradient_.assign(g.begin() + t * N, g.begin() + (t + 1) * N);
+      out[t].hessian_.assign(h.begin() + t * N, h.begin() + (t + 1) * N);
+      out[t].gradient_sq_.assign(s.begin() + t * N, s.begin() + (t + 1) * N);
     }
     return out;
   }

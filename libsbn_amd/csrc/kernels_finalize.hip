@@ -647,11 +647,116 @@ __global__ __launch_bounds__(256) void reduce_finalize_kernel(ReduceArgs ra, Fin
   finalize_body(fa, blockIdx.x, rf_lds, keep);
 }
 
+// ------------------------------------------------------------------------
+// Branch-length Hessian call: tile reduction and finalize in one launch, a workgroup per tree.
+// g_part [T][g_tiles][3][N] by node id (gradient_hbm_hess_kernel).  Every column is summed in
+// the order reduce_tiles_body sums it -- wave w's share (tiles w, w + 8, ... and w + 4, w + 12,
+// ...), then (w0 + w1) + (w2 + w3) -- here by one thread per column, so that the
+// log-likelihood and the gradient are bit for bit those of a gradient call on the HBM path.
+// Root and fixed node (the last two entries) are 0, as in the gradient.
+// ------------------------------------------------------------------------
+__device__ __forceinline__ double hess_wave_share(const double* src, int W, int g_tiles, int col, int wv) {
+  double s0 = 0, s1 = 0;
+  int i = wv;
+  for (; i + 4 < g_tiles; i += 8) {
+    s0 += src[(size_t)i * W + col];
+    s1 += src[(size_t)(i + 4) * W + col];
+  }
+  if (i < g_tiles) s0 += src[(size_t)i * W + col];
+  return s0 + s1;
+}
+__global__ __launch_bounds__(256) void hessian_finalize_kernel(HessFinalizeArgs a) {
+  __shared__ double llw[4];
+  const int t = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int N = a.N, W = 3 * N;
+  double llp = 0;
+  for (int i = threadIdx.x; i < a.ll_used; i += 256) llp += a.ll_part[(size_t)t * a.ll_tiles + i];
+  llp = wave_sum(llp);
+  if (lane == 0) llw[wv] = llp;
+  const double* src = a.g_part + (size_t)t * a.g_tiles * W;
+  for (int v = threadIdx.x; v < N; v += 256) {
+    double r[3];
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      const int c = q * N + v;
+      r[q] = (hess_wave_share(src, W, a.g_tiles, c, 0) + hess_wave_share(src, W, a.g_tiles, c, 1)) +
+             (hess_wave_share(src, W, a.g_tiles, c, 2) + hess_wave_share(src, W, a.g_tiles, c, 3));
+    }
+    const bool edge = v < N - 2;
+    const size_t o = (size_t)t * N + v;
+    if (a.out_branch) a.out_branch[o] = edge ? r[0] : 0.0;
+    a.out_hess[o] = edge ? r[1] - r[2] : 0.0;
+    if (a.out_gsq) a.out_gsq[o] = edge ? r[2] : 0.0;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && a.out_ll) a.out_ll[t] = (llw[0] + llw[1]) + (llw[2] + llw[3]);
+}
+// The same for the walk form (gradient_walk_hess_kernel): positional sums, g_part
+// [T][g_tiles][g_width] = [Mmax][6][2] {D1, D2} then [Mmax][6] S, mapped to node ids through the
+// macros the walk used (a column of a position the macro does not have is never read); every
+// column in the same tile order as above.  LDS: [3][N] by node id.
+__global__ __launch_bounds__(256) void hessian_walk_finalize_kernel(HessFinalizeArgs a) {
+  extern __shared__ double hf[];
+  __shared__ double llw[4];
+  const int t = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int N = a.N, W = a.g_width, Mmax = max_macros(a.n);
+  for (int v = threadIdx.x; v < 3 * N; v += 256) hf[v] = 0.0;
+  double llp = 0;
+  for (int i = threadIdx.x; i < a.ll_used; i += 256) llp += a.ll_part[(size_t)t * a.ll_tiles + i];
+  llp = wave_sum(llp);
+  if (lane == 0) llw[wv] = llp;
+  __syncthreads();
+  const int M = a.macro_count[t];
+  const MacroEntry* mac = a.macros + (size_t)t * macro_stride(a.n);
+  const double* src = a.g_part + (size_t)t * a.g_tiles * W;
+  for (int c = threadIdx.x; c < M * kMacroPositions * 3; c += 256) {
+    int m, pos, q, col;
+    if (c < M * kMacroPositions * 2) {
+      m = c / (kMacroPositions * 2);
+      const int r = c - m * (kMacroPositions * 2);
+      pos = r >> 1;
+      q = r & 1;
+      col = c;
+    } else {
+      const int k = c - M * kMacroPositions * 2;
+      m = k / kMacroPositions;
+      pos = k - m * kMacroPositions;
+      q = 2;
+      col = Mmax * kMacroPositions * 2 + k;
+    }
+    const MacroEntry& me = mac[m];
+    const bool exists = pos < 2 || ((me.shape >> (2 * ((pos - 2) >> 1))) & 3) == 2;
+    if (!exists) continue;
+    const int node = pos < 2 ? me.child[pos] : me.grand[pos - 2];
+    hf[q * N + node] = (hess_wave_share(src, W, a.g_tiles, col, 0) + hess_wave_share(src, W, a.g_tiles, col, 1)) +
+                       (hess_wave_share(src, W, a.g_tiles, col, 2) + hess_wave_share(src, W, a.g_tiles, col, 3));
+  }
+  __syncthreads();
+  for (int v = threadIdx.x; v < N; v += 256) {
+    const bool edge = v < N - 2;
+    const size_t o = (size_t)t * N + v;
+    if (a.out_branch) a.out_branch[o] = edge ? hf[v] : 0.0;
+    a.out_hess[o] = edge ? hf[N + v] - hf[2 * N + v] : 0.0;
+    if (a.out_gsq) a.out_gsq[o] = edge ? hf[2 * N + v] : 0.0;
+  }
+  if (threadIdx.x == 0 && a.out_ll) a.out_ll[t] = (llw[0] + llw[1]) + (llw[2] + llw[3]);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------
 // Launch wrappers
 // ------------------------------------------------------------------------
+void launch_hessian_finalize(const HessFinalizeArgs& a, hipStream_t s) {
+  if (a.T <= 0) return;
+  if (a.macros) {
+    const size_t lds = sizeof(double) * 3 * (size_t)a.N;
+    allow_large_lds(reinterpret_cast<const void*>(hessian_walk_finalize_kernel), lds);
+    hipLaunchKernelGGL(hessian_walk_finalize_kernel, dim3(a.T), dim3(256), lds, s, a);
+    return;
+  }
+  hipLaunchKernelGGL(hessian_finalize_kernel, dim3(a.T), dim3(256), 0, s, a);
+}
 void launch_subst_gradient(const SubstGradArgs& a, hipStream_t s) {
   if (a.T <= 0) return;
   hipLaunchKernelGGL(subst_gradient_kernel, dim3((a.T + 63) / 64), dim3(64), 0, s, a);

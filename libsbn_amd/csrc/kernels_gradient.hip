@@ -159,6 +159,150 @@ __global__ __launch_bounds__(kTile) void gradient_hbm_kernel(LikArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------
+// The branch-length Hessian call: the kernel above with, per edge, the second
+// derivative D2_p = sum_k c_k r_k^2 q.(Q^2 L), Q^2 L = Q (Q L), and the squared per-pattern
+// first derivative instead of the site-model sum.  g_part is [Eg][tiles][3][N] by node id:
+// {sum w D1/L, sum w D2/L, sum w (D1/L)^2}.  (A kernel of its own rather than a template flag
+// on the one above: that kernel's code stays exactly as it was.)  One evaluation per tree.
+// ------------------------------------------------------------------------
+template <bool RESCALE, bool TIP_PARTIALS>
+__global__ __launch_bounds__(kTile) void gradient_hbm_hess_kernel(LikArgs a) {
+  const int lane = threadIdx.x;
+  const TileEval te = xcd_tile_eval();
+  const int tile = te.tile;
+  const int e = a.eval_offset + te.eval;
+  const int gi = a.grad_offset + te.eval;
+  int t, mi;
+  a.map.decode(e, t, mi);
+  const DevModel* __restrict__ model = a.models + mi;
+  const SchedEntry* __restrict__ sched = a.sched + (size_t)t * (a.n - 1);
+  const int p = tile * kTile + lane;
+  const int pc = p < a.P ? p : a.P - 1;
+  const double w = p < a.P ? a.weights[pc] : 0.0;
+  const int K = a.K, n = a.n, N = a.N;
+  const size_t ppad = (size_t)a.tiles * kTile;
+  const double* __restrict__ mats_e = a.mats + (size_t)e * (N - 1) * K * 16;
+  double* plv_e = a.plv + (size_t)te.eval * (n - 1) * K * ppad * 4 + (size_t)p * 4;
+  double* gout = a.g_part + ((size_t)gi * a.g_tiles + tile) * 3 * N;
+
+  auto plv_at = [&](int node, int k) { return plv_e + ((size_t)(node - n) * K + k) * ppad * 4; };
+  auto tip_L = [&](int node) {
+    if (TIP_PARTIALS) return load4(a.tip_partials + ((size_t)node * a.P + pc) * 4);
+    return tip_vector(a.tip_states[(size_t)node * a.P + pc]);
+  };
+
+  // ---- post-order (as gradient_hbm_kernel) ----
+  int cum_exp = 0;
+  double site = 0.0;
+  for (int i = 0; i < n - 1; i++) {
+    const SchedEntry s = sched[i];
+    const bool is_root = i == n - 2;
+    double mx = 0.0;
+    for (int k = 0; k < K; k++) {
+      const double* __restrict__ M0 = mats_e + ((size_t)s.child0 * K + k) * 16;
+      const double* __restrict__ M1 = mats_e + ((size_t)s.child1 * K + k) * 16;
+      const D4 L0 = s.child0 < n ? tip_L(s.child0) : load4(plv_at(s.child0, k));
+      const D4 L1 = s.child1 < n ? tip_L(s.child1) : load4(plv_at(s.child1, k));
+      const D4 L = mul4(matvec(M0, L0), matvec(M1, L1));
+      if (RESCALE) mx = fmax(mx, max4(L));
+      if (is_root && !RESCALE) {
+        site += model->cat_weight[k] * (model->pi[0] * L.x0 + model->pi[1] * L.x1 +
+                                        model->pi[2] * L.x2 + model->pi[3] * L.x3);
+      } else {
+        store4(plv_at(s.node, k), L);
+      }
+    }
+    if (RESCALE) {
+      const int ex = max_exponent(mx);
+      cum_exp += ex;
+      for (int k = 0; k < K; k++) {
+        const D4 L = scale4(load4(plv_at(s.node, k)), -ex);
+        if (is_root)
+          site += model->cat_weight[k] * (model->pi[0] * L.x0 + model->pi[1] * L.x1 +
+                                          model->pi[2] * L.x2 + model->pi[3] * L.x3);
+        else
+          store4(plv_at(s.node, k), L);
+      }
+    }
+  }
+  {
+    double ll = log(site);
+    if (RESCALE) ll += cum_exp * 0.6931471805599453;
+    ll = p < a.P ? w * ll : 0.0;
+    ll = wave_sum(ll);
+    if (lane == 0) a.ll_part[(size_t)e * a.ll_tiles + tile] = ll;
+  }
+
+  // ---- pre-order + first and second edge derivatives, parents before children ----
+  for (int i = n - 2; i >= 0; i--) {
+    const SchedEntry s = sched[i];
+    const bool is_root = i == n - 2;
+    double nb0 = 0, hb0 = 0, den0 = 0, nb1 = 0, hb1 = 0, den1 = 0;
+    double mx0 = 0, mx1 = 0;
+    for (int k = 0; k < K; k++) {
+      const double* __restrict__ M0 = mats_e + ((size_t)s.child0 * K + k) * 16;
+      const double* __restrict__ M1 = mats_e + ((size_t)s.child1 * K + k) * 16;
+      const D4 qv = is_root ? D4{model->pi[0], model->pi[1], model->pi[2], model->pi[3]}
+                            : load4(plv_at(s.node, k));
+      const D4 L0 = s.child0 < n ? tip_L(s.child0) : load4(plv_at(s.child0, k));
+      const D4 L1 = s.child1 < n ? tip_L(s.child1) : load4(plv_at(s.child1, k));
+      const D4 A = matvec(M0, L0), B = matvec(M1, L1);
+      const D4 q0 = matTvec(M0, mul4(qv, B));
+      const D4 q1 = matTvec(M1, mul4(qv, A));
+      const double cw = model->cat_weight[k], r = model->cat_rate[k];
+      const D4 QL0 = matvec(model->Q, L0), QL1 = matvec(model->Q, L1);
+      nb0 += r * (cw * dot4(q0, QL0));
+      hb0 += r * r * (cw * dot4(q0, matvec(model->Q, QL0)));
+      den0 += cw * dot4(q0, L0);
+      nb1 += r * (cw * dot4(q1, QL1));
+      hb1 += r * r * (cw * dot4(q1, matvec(model->Q, QL1)));
+      den1 += cw * dot4(q1, L1);
+      if (s.child0 >= n) {
+        store4(plv_at(s.child0, k), q0);
+        if (RESCALE) mx0 = fmax(mx0, max4(q0));
+      }
+      if (s.child1 >= n) {
+        store4(plv_at(s.child1, k), q1);
+        if (RESCALE) mx1 = fmax(mx1, max4(q1));
+      }
+    }
+    if (RESCALE) {
+      if (s.child0 >= n) {
+        const int ex = max_exponent(mx0);
+        for (int k = 0; k < K; k++)
+          store4(plv_at(s.child0, k), scale4(load4(plv_at(s.child0, k)), -ex));
+      }
+      if (s.child1 >= n) {
+        const int ex = max_exponent(mx1);
+        for (int k = 0; k < K; k++)
+          store4(plv_at(s.child1, k), scale4(load4(plv_at(s.child1, k)), -ex));
+      }
+    }
+    // D1/L per pattern before it is squared: w (D1/L)^2 carries w once; padding lanes add 0
+    const double d0 = nb0 / den0, d1 = nb1 / den1;
+    const double g0 = wave_sum(p < a.P ? w * d0 : 0.0);
+    const double h0 = wave_sum(p < a.P ? w * (hb0 / den0) : 0.0);
+    const double s0 = wave_sum(p < a.P ? w * (d0 * d0) : 0.0);
+    const double g1 = wave_sum(p < a.P ? w * d1 : 0.0);
+    const double h1 = wave_sum(p < a.P ? w * (hb1 / den1) : 0.0);
+    const double s1 = wave_sum(p < a.P ? w * (d1 * d1) : 0.0);
+    if (lane == 0) {
+      gout[s.child0] = g0;
+      gout[N + s.child0] = h0;
+      gout[2 * N + s.child0] = s0;
+      gout[s.child1] = g1;
+      gout[N + s.child1] = h1;
+      gout[2 * N + s.child1] = s1;
+    }
+  }
+  if (lane == 0) {
+    gout[N - 1] = 0.0;
+    gout[2 * N - 1] = 0.0;
+    gout[3 * N - 1] = 0.0;
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------
@@ -174,6 +318,18 @@ void launch_gradient_hbm(const LikArgs& a, int count, bool rescale, hipStream_t 
   } else {
     if (tp) hipLaunchKernelGGL((gradient_hbm_kernel<false, true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((gradient_hbm_kernel<false, false>), grid, block, 0, s, a);
+  }
+}
+void launch_gradient_hbm_hessian(const LikArgs& a, int count, bool rescale, hipStream_t s) {
+  if (count <= 0) return;
+  const dim3 grid(a.tiles, count), block(kTile);
+  const bool tp = a.tip_partials != nullptr;
+  if (rescale) {
+    if (tp) hipLaunchKernelGGL((gradient_hbm_hess_kernel<true, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((gradient_hbm_hess_kernel<true, false>), grid, block, 0, s, a);
+  } else {
+    if (tp) hipLaunchKernelGGL((gradient_hbm_hess_kernel<false, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((gradient_hbm_hess_kernel<false, false>), grid, block, 0, s, a);
   }
 }
 int gradient_mfma_width(int n, bool subst) {
@@ -401,5 +557,6 @@ bool arena_single_launch(size_t lds, size_t waves) {
   return waves <= (size_t)cus * per_cu;
 }
 const char* gradient_kernel_name() { return "gradient_hbm_kernel"; }
+const char* gradient_hessian_kernel_name() { return "gradient_hbm_hess_kernel"; }
 
 }  // namespace miphylo

@@ -628,6 +628,212 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   return 0;
 }
 
+// ---- the branch-length Hessian call (mi_engine_branch_hessian_unrooted*) ----
+// One evaluation per tree with the tree's own model, as the `light` GTR call: no
+// finite-difference passes, no site pass.  Tree set-up and model instances, then either the
+// Hessian form of the second-generation matrix-core walk (K <= 4, tip masks, the tree fits
+// the walk) with its macro-ordered matrices, or the Hessian form of the HBM-streamed gradient
+// kernel (everything else, and MI_PHYLO_GRADIENT_PATH=hbm) with node-ordered ones; one launch
+// reduces the tiles and writes the outputs.
+const char kHessian4State[] = "the branch-length Hessian call is 4-state only";
+
+bool hessian_walk(const mi_engine* e, bool rescale) {
+  return !e->sw.hbm_gradient && e->have_tip_masks && e->K <= 4 && walk_fits(e, rescale);
+}
+// the walk form's store: the plain walk's rule for a batch of this many waves (one per tile)
+bool hessian_arena(const mi_engine* e, bool rescale, int T) {
+  const size_t waves = (size_t)T * gradient_mfma_tiles(e->P, e->K);
+  return gradient_walk_use_arena(e->sw.gradient_store, e->n, e->K, rescale, false, waves, false, 0);
+}
+
+int reserve_hessian(mi_engine* e, int T) {
+  const int n = e->n, N = e->N;
+  // (both rescaling settings: a later *_device call of either allocates nothing)
+  for (int rs = 0; rs < 2; rs++) {
+    if (!hessian_walk(e, rs)) continue;
+    const size_t gt = gradient_mfma_tiles(e->P, e->K);
+    if (e->macros.ensure(sizeof(MacroEntry) * (size_t)T * macro_stride(n))) return 1;
+    if (e->mmats.ensure(gradient_walk_mats_bytes_per_eval(n, e->K) * (size_t)T)) return 1;
+    if (e->g_part.ensure(sizeof(double) * (size_t)T * gt * max_macros(n) * kMacroPositions * 3)) return 1;
+    if (hessian_arena(e, rs, T)) {
+      const size_t aper = gradient_arena_bytes_per_eval(n, e->P, e->K);
+      const size_t achunk = std::max<size_t>(1, std::min<size_t>(T, e->plv_budget / aper));
+      if (e->plv.ensure(aper * achunk)) return 1;
+      if (e->arena_macros.ensure(sizeof(MacroEntry) * (size_t)T * macro_stride(n))) return 1;
+      if (e->slot_need.ensure(sizeof(int32_t) * (size_t)T)) return 1;
+    }
+  }
+  if (e->tree_scratch.ensure(sizeof(int32_t) * (size_t)T * 13 * N)) return 1;
+  if (e->sched.ensure(sizeof(SchedEntry) * (size_t)T * (n - 1))) return 1;
+  if (e->macro_count.ensure(sizeof(int32_t) * (size_t)T)) return 1;
+  if (e->bl_eff.ensure(sizeof(double) * (size_t)T * N)) return 1;
+  if (e->models.ensure(sizeof(DevModel) * (size_t)T)) return 1;
+  if (e->mats.ensure(sizeof(double) * (size_t)T * (N - 1) * e->K * 16)) return 1;
+  if (e->ll_part.ensure(sizeof(double) * (size_t)T * e->ll_stride)) return 1;
+  if (e->status.ensure(sizeof(int32_t) * kStatusWords)) return 1;
+  if (!hessian_walk(e, false) || !hessian_walk(e, true)) {
+    const size_t per = plv_bytes_per_eval(e);
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(T, e->plv_budget / per));
+    if (e->plv.ensure(per * chunk)) return 1;
+    if (e->g_part.ensure(sizeof(double) * (size_t)T * e->tiles * 3 * N)) return 1;
+  }
+  return 0;
+}
+
+int run_hessian_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
+  HIP_TRY(hipSetDevice(e->spec.device));
+  if (e->s == kAa) return fail(kHessian4State);
+  if (d.T <= 0) return fail("tree_count must be positive");
+  if (!d.parent_ids || !d.bl || !d.out_hess) return fail("null tree / output pointer");
+  if (e->param_count > 0 && !d.params) return fail("null parameter matrix");
+  if (reserve_hessian(e, d.T)) return 1;
+  const int n = e->n, N = e->N, T = d.T;
+  const bool walk = hessian_walk(e, d.rescaling);
+  const bool arena = walk && hessian_arena(e, d.rescaling, T);
+  const int g_tiles = walk ? gradient_mfma_tiles(e->P, e->K) : e->tiles;
+  TreeSetupArgs ts{};
+  ts.n = n;
+  ts.T = T;
+  ts.parent_ids = d.parent_ids;
+  ts.bl = d.bl;
+  ts.scratch = e->tree_scratch.as<int32_t>();
+  ts.sched = e->sched.as<SchedEntry>();
+  ts.macro_count = e->macro_count.as<int32_t>();
+  ts.bl_eff = e->bl_eff.as<double>();
+  ts.status = e->status.as<int32_t>();
+  ts.max_slots = e->max_slots;
+  ts.macros = walk ? e->macros.as<MacroEntry>() : nullptr;
+  ts.need_slots = !walk;  // (the HBM kernel walks the node-level schedule)
+  ts.arena_macros = arena ? e->arena_macros.as<MacroEntry>() : nullptr;
+  ts.slot_need = e->slot_need.as<int32_t>();
+  ModelSetupArgs ms{};
+  ms.T = T;
+  ms.models_per_tree = 1;
+  ms.subst = e->spec.subst_model;
+  ms.site = e->spec.site_model;
+  ms.K = e->K;
+  ms.param_count = e->param_count;
+  ms.rates_off = e->rates_off;
+  ms.freqs_off = e->freqs_off;
+  ms.shape_off = e->shape_off;
+  ms.params = d.params;
+  ms.models = e->models.as<DevModel>();
+  ms.status = e->status.as<int32_t>();
+  ms.weibull_x = e->weibull_x.as<double>();
+  const bool prof = e->prof_used < e->prof_capacity;
+  const bool marks = prof && e->prof_phases;
+  PROF_MARK(e, marks, 0, s);
+  const bool slots_done = launch_setup(ts, ms, e->sw, s);
+  if (arena && !slots_done)
+    launch_macro_slots(e->macros.as<MacroEntry>(), e->arena_macros.as<MacroEntry>(),
+                       e->macro_count.as<int32_t>(), n, T, e->slot_need.as<int32_t>(),
+                       e->status.as<int32_t>(), e->sw, s);
+  const EvalMap map{T, 1};
+  const MacroEntry* walk_macros = arena ? e->arena_macros.as<MacroEntry>() : e->macros.as<MacroEntry>();
+  if (walk) {
+    TransitionMacroArgs tm{};
+    tm.n = n;
+    tm.N = N;
+    tm.K = e->K;
+    tm.count = T;
+    tm.eval_begin = 0;
+    tm.map = map;
+    tm.models = e->models.as<DevModel>();
+    tm.bl_eff = e->bl_eff.as<double>();
+    tm.macros = walk_macros;
+    tm.macro_count = e->macro_count.as<int32_t>();
+    tm.mmats = e->mmats.as<double>();
+    tm.mphi = nullptr;
+    launch_transition_macro(tm, s);
+  } else {
+    TransitionArgs tr{};
+    tr.E = T;
+    tr.N = N;
+    tr.K = e->K;
+    tr.map = map;
+    tr.models = e->models.as<DevModel>();
+    tr.bl_eff = e->bl_eff.as<double>();
+    tr.mats = e->mats.as<double>();
+    tr.tip_tables = nullptr;
+    tr.n = n;
+    launch_transition(tr, s);
+  }
+
+  LikArgs la{};
+  la.n = n;
+  la.N = N;
+  la.P = e->P;
+  la.K = e->K;
+  la.tiles = e->tiles;
+  la.ll_tiles = e->ll_stride;
+  la.g_tiles = g_tiles;
+  la.map = map;
+  la.models = e->models.as<DevModel>();
+  la.sched = e->sched.as<SchedEntry>();
+  la.macros = walk_macros;
+  la.macro_count = e->macro_count.as<int32_t>();
+  la.mmats = e->mmats.as<double>();
+  la.tip_masks = e->have_tip_masks ? e->tip_masks.as<uint8_t>() : nullptr;
+  la.slot_need = e->slot_need.as<int32_t>();
+  la.store = walk ? (arena ? 2 : 1) : 0;
+  la.mats = e->mats.as<double>();
+  la.tip_states = e->tip_states.as<int8_t>();
+  la.tip_partials = e->spec.use_tip_states ? nullptr : e->tip_partials.as<double>();
+  la.weights = e->weights.as<double>();
+  la.ll_part = e->ll_part.as<double>();
+  la.plv = e->plv.as<double>();
+  la.g_part = e->g_part.as<double>();
+  la.status = e->status.as<int32_t>();
+  if (prof) HIP_TRY(hipEventRecord(prof_event(e, 0), s));
+  PROF_MARK(e, marks, 1, s);
+  PROF_MARK(e, marks, 2, s);
+  constexpr int kMaxEvals = 32768;  // (grid y dimension, as run_device)
+  // (a launch covers what the vector arena holds: the HBM kernel's, or the walk's arena)
+  const size_t per = !walk ? plv_bytes_per_eval(e) : arena ? gradient_arena_bytes_per_eval(n, e->P, e->K) : 0;
+  const int chunk = per ? (int)std::max<size_t>(1, std::min<size_t>(std::min(T, kMaxEvals), e->plv.bytes / per))
+                        : std::min(T, kMaxEvals);
+  int walk_launches = 0;
+  for (int done = 0; done < T; done += chunk) {
+    walk_launches++;
+    LikArgs g = la;
+    g.eval_offset = done;
+    g.grad_offset = done;
+    if (walk) launch_gradient_walk_hessian(g, std::min(chunk, T - done), d.rescaling, s);
+    else launch_gradient_hbm_hessian(g, std::min(chunk, T - done), d.rescaling, s);
+  }
+  if (prof) HIP_TRY(hipEventRecord(prof_event(e, 1), s));
+  PROF_MARK(e, marks, 3, s);
+  HessFinalizeArgs fa{};
+  fa.N = N;
+  fa.T = T;
+  fa.g_tiles = g_tiles;
+  fa.ll_tiles = e->ll_stride;
+  fa.ll_used = g_tiles;
+  fa.n = n;
+  fa.g_width = walk ? max_macros(n) * kMacroPositions * 3 : 3 * N;
+  fa.macros = walk ? walk_macros : nullptr;
+  fa.macro_count = e->macro_count.as<int32_t>();
+  fa.ll_part = e->ll_part.as<double>();
+  fa.g_part = e->g_part.as<double>();
+  fa.out_ll = d.out_ll;
+  fa.out_branch = d.out_branch;
+  fa.out_hess = d.out_hess;
+  fa.out_gsq = d.out_gsq;
+  launch_hessian_finalize(fa, s);
+  PROF_MARK(e, marks, 4, s);
+  if (prof) e->prof_used++;
+  e->dominant = walk ? gradient_walk_hess_kernel_name() : gradient_hessian_kernel_name();
+  e->last_path = std::string(e->dominant) + (!walk ? " store=hbm" : arena ? " store=arena" : " store=lds") +
+                 " setup=own-launch hess" +
+                 (d.rescaling ? " rescaled" : "") + " K=" + std::to_string(e->K);
+  e->prof_first_launch_evals = std::min(chunk, T);
+  e->last_evals = T;
+  e->last_grad_evals = T;
+  e->last_walk_launches = walk_launches;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 int check_status(mi_engine* e, hipStream_t s) {
   HIP_TRY(hipSetDevice(e->spec.device));
   int32_t st[kStatusWords] = {};
@@ -1269,6 +1475,45 @@ int32_t mi_engine_gradients_unrooted_device(mi_engine* e, void* stream, int32_t 
   return run_device(e, pick_stream(e, stream), d);
 }
 
+int32_t mi_engine_branch_hessian_unrooted_device(mi_engine* e, void* stream, int32_t T,
+                                                 const int32_t* parent_ids, const double* bl,
+                                                 const double* params, int32_t rescaling,
+                                                 double* out_ll, double* out_branch,
+                                                 double* out_hess, double* out_gsq) {
+  if (!e) return fail("null engine");
+  if (e->s == kAa) return fail(kHessian4State);
+  if (!e->shards.empty()) return fail(kShardedDeviceCall);
+  if (!out_hess) return fail("null branch-Hessian output");
+  DeviceCall d;
+  d.T = T;
+  d.rescaling = rescaling != 0;
+  d.parent_ids = parent_ids;
+  d.bl = bl;
+  d.params = params;
+  d.out_ll = out_ll;
+  d.out_branch = out_branch;
+  d.out_hess = out_hess;
+  d.out_gsq = out_gsq;
+  return run_hessian_device(e, pick_stream(e, stream), d);
+}
+
+int32_t mi_engine_reserve_hessian(mi_engine* e, int32_t tree_count) {
+  if (!e) return fail("null engine");
+  if (tree_count <= 0) return fail("tree_count must be positive");
+  if (e->s == kAa) return fail(kHessian4State);
+  if (!e->shards.empty()) {
+    const int D = (int)e->shards.size();
+    for (int i = 0; i < D; i++) {
+      int32_t b = 0, c = tree_count;
+      if (e->shard_mode == MI_SHARD_TREES) mi_shard_range(tree_count, D, i, &b, &c);
+      if (c > 0 && mi_engine_reserve_hessian(e->shards[i], c)) return 1;
+    }
+    return 0;
+  }
+  HIP_TRY(hipSetDevice(e->spec.device));
+  return reserve_hessian(e, tree_count);
+}
+
 int32_t mi_engine_log_likelihoods_rooted_device(mi_engine* e, void* stream, int32_t T,
                                                 const int32_t* parent_ids, const double* bl,
                                                 const double* params, const double* rates,
@@ -1524,6 +1769,11 @@ struct HostCall {
   double* out_b = nullptr;  // clock gradient [T][N-1] (rooted)
   double* out_site = nullptr;
   double* out_subst = nullptr;
+  // branch-length Hessian call (mi_engine_branch_hessian_unrooted): out_ll and out_a
+  // (gradient) may be null there
+  bool hessian = false;
+  double* out_h = nullptr;  // [T][N]
+  double* out_s = nullptr;  // [T][N] or null
   // fused reductions of a variational-inference step (mi_engine_gradients_unrooted_reduced)
   bool reduced = false;
   const int32_t* branch_index = nullptr;  // [T][N]
@@ -1638,6 +1888,19 @@ int begin_host_call(mi_engine* e, const HostCall& h) {
   auto P32 = [](const void* p) { return static_cast<const int32_t*>(p); };
   auto F64 = [](const void* p) { return static_cast<const double*>(p); };
   double *o_ll, *o_a, *o_b, *o_site, *o_subst, *o_sum, *o_index;
+  if (h.hessian) {
+    double *o_h, *o_s;
+    const std::initializer_list<OutPiece> outs = {{h.out_ll, h.out_ll ? (size_t)T : 0, &o_ll},
+                                                  {h.out_a, h.out_a ? (size_t)T * N : 0, &o_a},
+                                                  {h.out_h, (size_t)T * N, &o_h},
+                                                  {h.out_s, h.out_s ? (size_t)T * N : 0, &o_s}};
+    if (place_out_pack(e, outs)) return 1;
+    if (mi_engine_branch_hessian_unrooted_device(e, e->stream, T, P32(d_parent), F64(d_bl), F64(d_params),
+                                                 h.rescaling, h.out_ll ? o_ll : nullptr,
+                                                 h.out_a ? o_a : nullptr, o_h, h.out_s ? o_s : nullptr))
+      return 1;
+    return download_pack(e, outs);
+  }
   if (!h.gradient) {
     const std::initializer_list<OutPiece> outs = {{h.out_ll, (size_t)T, &o_ll}};
     if (place_out_pack(e, outs)) return 1;
@@ -1740,6 +2003,8 @@ int run_sharded(mi_engine* e, const HostCall& h) {
       if (h.out_b) s.out_b = h.out_b + (size_t)b * (N - 1);
       if (h.out_site) s.out_site = h.out_site + b;
       if (h.out_subst) s.out_subst = h.out_subst + (size_t)b * 8;
+      if (h.out_h) s.out_h = h.out_h + (size_t)b * N;
+      if (h.out_s) s.out_s = h.out_s + (size_t)b * N;
       if (h.reduced) {
         s.branch_index = h.branch_index + (size_t)b * N;
         if (h.tree_weights) s.tree_weights = h.tree_weights + b;
@@ -1770,7 +2035,9 @@ int run_sharded(mi_engine* e, const HostCall& h) {
   if (h.rooted)
     return fail("pattern-sharded engines evaluate unrooted calls only (the log-det-Jacobian "
                 "and the rooted chain rule are not sums over site patterns)");
-  const size_t per = (size_t)T * (1 + (h.gradient ? N + 1 + 8 : 0)) + 2 + h.index_count;
+  // (a Hessian call: per shard logL, gradient, H and S, [T] + 3 [T][N]; H = D2 term - S adds
+  // up shard by shard like the rest)
+  const size_t per = (size_t)T * (1 + (h.gradient ? N + 1 + 8 : 0) + (h.hessian ? 3 * N : 0)) + 2 + h.index_count;
   e->shard_sums.assign((size_t)D * per, 0.0);
   int rc = 0, started = 0;
   std::vector<HostCall> calls(D);
@@ -1778,6 +2045,11 @@ int run_sharded(mi_engine* e, const HostCall& h) {
     double* base = e->shard_sums.data() + (size_t)i * per;
     HostCall s = h;
     s.out_ll = base;
+    if (h.hessian) {
+      s.out_a = h.out_a ? base + T : nullptr;
+      s.out_h = base + (size_t)T * (1 + N);
+      s.out_s = h.out_s ? base + (size_t)T * (1 + 2 * N) : nullptr;
+    }
     if (h.gradient) {
       s.out_a = base + T;
       s.out_site = h.out_site ? base + (size_t)T * (1 + N) : nullptr;
@@ -1801,6 +2073,11 @@ int run_sharded(mi_engine* e, const HostCall& h) {
     }
   };
   add(h.out_ll, 0, T);
+  if (h.hessian) {
+    add(h.out_a, T, (size_t)T * N);
+    add(h.out_h, (size_t)T * (1 + N), (size_t)T * N);
+    add(h.out_s, (size_t)T * (1 + 2 * N), (size_t)T * N);
+  }
   if (h.gradient) {
     add(h.out_a, T, (size_t)T * N);
     if (e->K > 1) add(h.out_site, (size_t)T * (1 + N), T);
@@ -1869,6 +2146,26 @@ int32_t mi_engine_gradients_unrooted(mi_engine* e, int32_t T, const int32_t* par
   h.out_a = out_branch;
   h.out_site = out_site;
   h.out_subst = out_subst;
+  return run_host(e, h);
+}
+
+int32_t mi_engine_branch_hessian_unrooted(mi_engine* e, int32_t T, const int32_t* parent_ids,
+                                          const double* bl, const double* params, int32_t rescaling,
+                                          double* out_ll, double* out_branch, double* out_hess,
+                                          double* out_gsq) {
+  if (!out_hess) return fail("null branch-Hessian output");
+  if (e && e->s == kAa) return fail(kHessian4State);
+  HostCall h;
+  h.hessian = true;
+  h.T = T;
+  h.rescaling = rescaling;
+  h.parent_ids = parent_ids;
+  h.bl = bl;
+  h.params = params;
+  h.out_ll = out_ll;
+  h.out_a = out_branch;
+  h.out_h = out_hess;
+  h.out_s = out_gsq;
   return run_host(e, h);
 }
 

@@ -213,6 +213,9 @@ struct DeviceCall {
   double* out_clock = nullptr;
   double* out_site = nullptr;
   double* out_subst = nullptr;
+  // branch-length Hessian call (run_hessian_device): out_ll / out_branch may be nullptr there
+  double* out_hess = nullptr;
+  double* out_gsq = nullptr;
 };
 
 // mi_phylo_engine_aa.cpp

@@ -191,6 +191,30 @@ void launch_tip_code_tiles(const uint8_t* codes, uint8_t* out, int n, int P, int
 int gradient_walk_tile_regs(int n, int P, int K, int forced);
 // Gradient, partial-likelihood vectors streamed through HBM (any tree size, rescaling)
 void launch_gradient_hbm(const LikArgs& a, int count, bool rescale, hipStream_t s);
+// ... its branch-length Hessian form (one evaluation per tree; g_part [Eg][tiles][3][N]:
+// sums of w D1/L, w D2/L and w (D1/L)^2 by node id -- DESIGN.md 4.8)
+void launch_gradient_hbm_hessian(const LikArgs& a, int count, bool rescale, hipStream_t s);
+const char* gradient_hessian_kernel_name();
+// ... and the Hessian form of the second-generation walk (kernels_walk.hip; K <= 4, tip masks):
+// g_part [Eg][tiles][Mmax][6][2] = {sum w D1/L, sum w D2/L} by (macro, position), then
+// [Mmax][6] sums of w (D1/L)^2; a wave per pattern tile; a.store: 1 LDS, 2 arena
+void launch_gradient_walk_hessian(const LikArgs& a, int count, bool rescale, hipStream_t s);
+const char* gradient_walk_hess_kernel_name();
+// The Hessian call's tile reduction and finalize, a workgroup per tree (kernels_finalize.hip)
+struct HessFinalizeArgs {
+  int N, T, g_tiles, ll_tiles, ll_used;
+  // walk form (positional sums; macros == nullptr: the HBM kernel's [3][N] by node id)
+  int n, g_width;
+  const MacroEntry* macros;    // [T][macro_stride(n)], the order the walk used
+  const int32_t* macro_count;  // [T]
+  const double* ll_part;  // [T][ll_tiles]
+  const double* g_part;   // [T][g_tiles][3][N]
+  double* out_ll;         // [T] or nullptr
+  double* out_branch;     // [T][N] or nullptr
+  double* out_hess;       // [T][N]: sum w D2/L - sum w (D1/L)^2
+  double* out_gsq;        // [T][N] or nullptr: sum w (D1/L)^2
+};
+void launch_hessian_finalize(const HessFinalizeArgs& a, hipStream_t s);
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
 // the first, gradient_mfma_kernel, was retired in round 6): all categories of a group of four
 // per instruction; they also write the log-likelihood partial sums, so no separate logL pass is

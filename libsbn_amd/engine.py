@@ -271,6 +271,27 @@ class Engine:
             int(index_count), _ptr(sums), _ptr(ig), _ptr(ll)))
         return sums[0], sums[1], ig[:index_count], ll
 
+    def branch_hessian(self, parent_ids, branch_lengths, params=None, rescaling=False,
+                       squared_gradient=False):
+        """Diagonal of the branch-length Hessian per tree (mi_engine_branch_hessian_unrooted;
+        an extension, 4-state engines): returns (log-likelihoods [T], branch gradient [T][2n-1],
+        d^2 logL / d t_j^2 [T][2n-1]) and, with squared_gradient=True, also
+        S [T][2n-1] = sum_p w_p (d log L_p / d t_j)^2.  Root and fixed node entries are 0."""
+        n, N = self.taxon_count, self.node_count
+        pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
+        T = pid.shape[0]
+        if T == 0:
+            empty = (np.empty(0), np.empty((0, N)), np.empty((0, N)))
+            return empty + ((np.empty((0, N)),) if squared_gradient else ())
+        bl = _np(branch_lengths, np.float64).reshape(T, 2 * n - 2)
+        pr = self._params(params, T)
+        ll, g, h = np.empty(T), np.empty((T, N)), np.empty((T, N))
+        s = np.empty((T, N)) if squared_gradient else None
+        self._check(self._lib.mi_engine_branch_hessian_unrooted(
+            self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), _ptr(ll), _ptr(g),
+            _ptr(h), _ptr(s)))
+        return (ll, g, h, s) if squared_gradient else (ll, g, h)
+
     def _phylo_gradients(self, ll, blocks, site, subst):
         """Per-tree PhyloGradient objects over row views of the freshly allocated result
         arrays of one call (no per-tree copies: 1000 trees cost ~0.3 ms instead of ~1.1)."""
@@ -355,6 +376,17 @@ class Engine:
         self._check(self._lib.mi_engine_gradients_unrooted_device(
             self._h, stream, T, parent_ids, branch_lengths, params, int(rescaling), out_ll,
             out_branch, out_site, out_subst))
+
+    def branch_hessian_device(self, stream, T, parent_ids, branch_lengths, params, out_hess,
+                              out_ll=None, out_branch=None, out_gsq=None, rescaling=False):
+        """mi_engine_branch_hessian_unrooted_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_branch_hessian_unrooted_device(
+            self._h, stream, T, parent_ids, branch_lengths, params, int(rescaling), out_ll,
+            out_branch, out_hess, out_gsq))
+
+    def reserve_hessian(self, tree_count):
+        """mi_engine_reserve_hessian: workspace of a Hessian call (graph capture)."""
+        self._check(self._lib.mi_engine_reserve_hessian(self._h, int(tree_count)))
 
     def reserve_reduced(self, tree_count, index_count):
         """mi_engine_reserve_reduced: workspace of a fused-reduction call (graph capture)."""
