@@ -208,6 +208,45 @@ int32_t mi_engine_branch_hessian_unrooted(mi_engine* engine, int32_t tree_count,
                                           double* out_branch_hessian /* [T][2n-1] */,
                                           double* out_branch_gradient_sq /* [T][2n-1] or NULL */);
 
+/* Maximum-likelihood branch lengths of unrooted trees under box bounds (an extension: the
+ * consumer of the Hessian call's outputs).  Every tree of the batch is
+ * iterated on the device: an evaluation is one Hessian pass at a trial point, a step is a
+ * safeguarded diagonal Newton step from g, H and S, accepted when the log-likelihood does
+ * not fall by more than its rounding error (2^-48 |logL|).  A tree stops when max_j |pg_j| max(t_j, 1e-3) <= tolerance at its accepted point
+ * (pg: the gradient, 0 where t_j sits on a bound and the gradient points outward), when its
+ * step scale has fallen below 2^-20, or after max_iterations evaluations.
+ *   out_branch_lengths  [T][2n-2]  the last accepted point (the entry of the fixed node, 2n-3,
+ *                                  is the caller's, unchanged)
+ *   out_log_likelihoods [T], out_branch_gradient / out_branch_hessian [T][2n-1] or NULL:
+ *                                  the Hessian call's outputs at that point
+ *   out_iterations      [T] or NULL: evaluations the tree used, the first one included
+ *   out_status          [T]        MI_BRANCH_OPT_*
+ * Returns 0 when it ran, whatever the per-tree statuses; nonzero for bad arguments and
+ * per-tree input errors.  4-state engines only.  Sharded handles: MI_SHARD_TREES deals the
+ * trees as the other calls do (each shard optimises its block; results in tree order);
+ * MI_SHARD_PATTERNS is refused (every iteration would need a sum across the shards).
+ * mi_engine_last_call_path names the Hessian kernel that ran and adds
+ * "opt iters=<passes> evals=<tree evaluations> batches=<trees>x<passes>,..."; the evaluation
+ * count of mi_engine_last_call_info is the number of tree evaluations done. */
+enum { MI_BRANCH_OPT_CONVERGED = 0, MI_BRANCH_OPT_ITERATION_LIMIT = 1, MI_BRANCH_OPT_STALLED = 2 };
+typedef struct {
+  int32_t max_iterations; /* evaluations per tree, 1..1000 (default 100) */
+  int32_t check_interval; /* passes between two reads of the active count (default 4) */
+  int32_t pack_active;    /* 1: passes run on the active trees only (default); 0: on all T */
+  double tolerance;       /* default 1e-6 */
+  double min_length;      /* default 1e-8 */
+  double max_length;      /* default 10 */
+  int32_t reserved[4];    /* 0 */
+} mi_branch_opt_options;
+int32_t mi_engine_optimize_branch_lengths_unrooted(
+    mi_engine* engine, int32_t tree_count, const int32_t* parent_ids /* [T][2n-3] */,
+    const double* start_branch_lengths /* [T][2n-2] */, const double* params, int32_t rescaling,
+    const mi_branch_opt_options* options /* NULL: the defaults */,
+    double* out_branch_lengths /* [T][2n-2] */, double* out_log_likelihoods /* [T] */,
+    double* out_branch_gradient /* [T][2n-1] or NULL */,
+    double* out_branch_hessian /* [T][2n-1] or NULL */, int32_t* out_iterations /* [T] or NULL */,
+    int32_t* out_status /* [T] */);
+
 /* Engine::LogLikelihoods(const RootedTreeCollection&) when with_jacobian != 0
  * (branch lengths x rates, + log-det-Jacobian, fat_beagle.cpp:82-104), or
  * Engine::UnrootedLogLikelihoods(const RootedTreeCollection&) when 0
@@ -302,6 +341,17 @@ int32_t mi_engine_branch_hessian_unrooted_device(mi_engine* engine, void* stream
                                                  double* out_branch_hessian,
                                                  double* out_branch_gradient_sq);
 
+/* The device form of mi_engine_optimize_branch_lengths_unrooted.  Unlike the other *_device
+ * calls it SYNCHRONISES `stream` at its check points (it reads the number of active trees to
+ * decide whether to go on), so it cannot be captured in a hipGraph; when it returns, every
+ * kernel it needed has been enqueued, and the outputs are complete once the stream is. */
+int32_t mi_engine_optimize_branch_lengths_unrooted_device(
+    mi_engine* engine, void* stream, int32_t tree_count, const int32_t* parent_ids,
+    const double* start_branch_lengths, const double* params, int32_t rescaling,
+    const mi_branch_opt_options* options, double* out_branch_lengths, double* out_log_likelihoods,
+    double* out_branch_gradient, double* out_branch_hessian, int32_t* out_iterations,
+    int32_t* out_status);
+
 /* Make sure the workspace for `tree_count` trees exists (so that a following
  * *_device call allocates nothing and can be captured in a hipGraph).  20-state engines: if
  * the device cannot give the partial-vector arena its budget (MI_PHYLO_PLV_BYTES), the budget
@@ -320,6 +370,10 @@ int32_t mi_engine_reserve_reduced(mi_engine* engine, int32_t tree_count, int32_t
  * *_device call of at most that size then allocates nothing (hipGraph capture).  4-state
  * engines only. */
 int32_t mi_engine_reserve_hessian(mi_engine* engine, int32_t tree_count);
+/* The workspace of mi_engine_optimize_branch_lengths_unrooted[_device] for `tree_count` trees
+ * (the Hessian call's included): a *_device call of at most that size then allocates
+ * nothing.  4-state engines only. */
+int32_t mi_engine_reserve_branch_opt(mi_engine* engine, int32_t tree_count);
 /* Synchronise `stream` and report the first per-tree error since the last check (the status
  * word is sticky and cleared when an error is reported: calls themselves never clear it). */
 int32_t mi_engine_check_status(mi_engine* engine, void* stream);

@@ -20,6 +20,13 @@ class EngineSpec(C.Structure):
         "site_model", "clock_model", "use_tip_states", "device", "reserved")]
 
 
+class BranchOptOptions(C.Structure):
+    """mi_branch_opt_options (include/mi_phylo.h)."""
+    _fields_ = [("max_iterations", C.c_int32), ("check_interval", C.c_int32),
+                ("pack_active", C.c_int32), ("tolerance", C.c_double), ("min_length", C.c_double),
+                ("max_length", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
 # Every symbol include/mi_phylo.h declares: (restype, argtypes)
 _V = C.c_void_p
 SYMBOLS = {
@@ -68,6 +75,11 @@ SYMBOLS = {
     "mi_engine_reserve": (C.c_int32, [_V, C.c_int32, C.c_int32]),
     "mi_engine_reserve_reduced": (C.c_int32, [_V, C.c_int32, C.c_int32]),
     "mi_engine_reserve_hessian": (C.c_int32, [_V, C.c_int32]),
+    "mi_engine_optimize_branch_lengths_unrooted":
+        (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_optimize_branch_lengths_unrooted_device":
+        (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_reserve_branch_opt": (C.c_int32, [_V, C.c_int32]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),
     "mi_engine_profile_begin": (C.c_int32, [_V, C.c_int32]),
     "mi_engine_profile_collect": (C.c_int32, [_V, F64P, C.c_int32, I32P]),

@@ -49,6 +49,16 @@ struct BranchHessian {
   std::vector<double> gradient_, hessian_, gradient_sq_;
 };
 
+// Engine::OptimizeBranchLengths, per tree (an extension, include/mi_phylo.h): the
+// maximum-likelihood branch lengths [2n-2] and the Hessian call's outputs at them [2n-1]
+struct BranchOptimum {
+  std::vector<double> branch_lengths_;
+  double log_likelihood_ = 0.;
+  std::vector<double> gradient_, hessian_;
+  int32_t iterations_ = 0;
+  int32_t status_ = 0;  // MI_BRANCH_OPT_*
+};
+
 struct ParamMatrix {  // row-major [rows x cols]
   size_t rows = 0, cols = 0;
   std::vector<double> data;
@@ -209,6 +219,34 @@ class Engine {
       out[t].gradient_.assign(g.begin() + t * N, g.begin() + (t + 1) * N);
       out[t].hessian_.assign(h.begin() + t * N, h.begin() + (t + 1) * N);
       out[t].gradient_sq_.assign(s.begin() + t * N, s.begin() + (t + 1) * N);
+    }
+    return out;
+  }
+
+  // Maximum-likelihood branch lengths per tree, started from the trees' own lengths
+  // (an extension; 4-state engines): mi_engine_optimize_branch_lengths_unrooted.
+  // options == nullptr: the defaults of include/mi_phylo.h.
+  std::vector<BranchOptimum> OptimizeBranchLengths(const UnrootedTreeCollection& trees,
+                                                   const ParamMatrix& params, const bool rescaling,
+                                                   const mi_branch_opt_options* options = nullptr) const {
+    const size_t T = trees.size(), N = 2 * site_pattern_.SequenceCount() - 1;
+    std::vector<int32_t> parents;
+    std::vector<double> bl;
+    Flatten(trees, params, false, &parents, &bl);
+    if (trees.empty()) return {};
+    std::vector<double> t(T * (N - 1)), ll(T), g(T * N), h(T * N);
+    std::vector<int32_t> iters(T), status(T);
+    Check(mi_engine_optimize_branch_lengths_unrooted(
+        handle_, static_cast<int32_t>(T), parents.data(), bl.data(), params.data.data(), rescaling,
+        options, t.data(), ll.data(), g.data(), h.data(), iters.data(), status.data()));
+    std::vector<BranchOptimum> out(T);
+    for (size_t i = 0; i < T; i++) {
+      out[i].branch_lengths_.assign(t.begin() + i * (N - 1), t.begin() + (i + 1) * (N - 1));
+      out[i].log_likelihood_ = ll[i];
+      out[i].gradient_.assign(g.begin() + i * N, g.begin() + (i + 1) * N);
+      out[i].hessian_.assign(h.begin() + i * N, h.begin() + (i + 1) * N);
+      out[i].iterations_ = iters[i];
+      out[i].status_ = status[i];
     }
     return out;
   }

@@ -167,6 +167,9 @@ struct mi_engine {
   Buffer in_parent, in_bl, in_params, in_rates, in_rate_counts, in_heights, in_bounds,
       in_ratios, out_ll, out_a, out_b, out_site, out_subst;
   Buffer in_pack, out_pack;  // one block each way per host-pointer call (begin_host_call)
+  // branch-length optimisation (mi_engine_optimize_branch_lengths_unrooted*)
+  Buffer opt_ws;                // trial points, kept derivatives, packed inputs, maps, counters
+  int32_t* opt_word = nullptr;  // pinned: the active count read at a check point
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)
   std::vector<hipEvent_t> prof_events;  // kProfEvents per call: [begin, end, mark 0..4]
@@ -216,6 +219,10 @@ struct DeviceCall {
   // branch-length Hessian call (run_hessian_device): out_ll / out_branch may be nullptr there
   double* out_hess = nullptr;
   double* out_gsq = nullptr;
+  // ... as one pass of the branch-length optimisation: the batch size the kernel and its store
+  // are chosen for (the whole batch's, so that a tree's results do not depend on how many
+  // trees are still active); 0: T
+  int route_T = 0;
 };
 
 // mi_phylo_engine_aa.cpp

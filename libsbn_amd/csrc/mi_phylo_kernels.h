@@ -215,6 +215,41 @@ struct HessFinalizeArgs {
   double* out_gsq;        // [T][N] or nullptr: sum w (D1/L)^2
 };
 void launch_hessian_finalize(const HessFinalizeArgs& a, hipStream_t s);
+// Branch-length optimisation (kernels_branch_opt.hip): the step between two
+// Hessian passes and the packing of the active trees.  "Packed" arrays hold the trees that
+// are still being evaluated, in `map` order (map == nullptr: all trees, in their own order).
+constexpr int kBranchOptActive = -1;  // internal; the rest are mi_phylo.h's MI_BRANCH_OPT_*
+constexpr int kBranchOptConverged = 0, kBranchOptIterationLimit = 1, kBranchOptStalled = 2;
+struct BranchOptArgs {
+  int N, T;        // nodes per tree (2n-1), trees of the batch
+  int count;       // trees of the packed set
+  int evals_max;   // evaluations a tree may use
+  int pass;        // index of this pass: its word of `active`
+  double tol, tmin, tmax;
+  const int32_t* map;  // [count] packed position -> tree, or nullptr
+  // what the Hessian pass returned for the trial points, by packed position
+  const double *tr_ll, *tr_g, *tr_h, *tr_s;  // [count], [count][N] each
+  double* trial;       // [count][N-1] trial lengths: evaluated ones in, next ones out
+  double* trial_full;  // [T][N-1] the same by tree (what a later packing reads), or nullptr
+  // the accepted point, by tree: these are the call's outputs
+  double *bl, *ll, *g, *h, *s, *alpha;  // [T][N-1], [T], [T][N] x 3, [T]
+  int32_t *evals, *status;              // [T]
+  int32_t* active;  // [passes] trees still active after each pass (zeroed by the host)
+};
+struct BranchOptPackArgs {
+  int N, count, param_count;  // count: trees of the NEW packed set
+  int32_t* map;               // [count] new map (written by the scan, read by the gather)
+  const int32_t* parent_ids;  // [T][N-2] the caller's
+  const double* params;       // [T][param_count] the caller's
+  const double* trial_full;   // [T][N-1]
+  int32_t* pk_parent;         // [count][N-2]
+  double* pk_trial;           // [count][N-1]
+  double* pk_params;          // [count][param_count]
+};
+void launch_branch_opt_init(const BranchOptArgs& a, const double* start, hipStream_t s);
+void launch_branch_opt_step(const BranchOptArgs& a, hipStream_t s);
+void launch_branch_opt_pack(const BranchOptPackArgs& a, int old_count, const int32_t* map_old,
+                            const int32_t* status, hipStream_t s);
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
 // the first, gradient_mfma_kernel, was retired in round 6): all categories of a group of four
 // per instruction; they also write the log-likelihood partial sums, so no separate logL pass is

@@ -49,6 +49,25 @@ class PhyloGradient:
         return f"PhyloGradient(log_likelihood={self.log_likelihood!r}, gradient={self.gradient!r})"
 
 
+@dataclass
+class BranchOptResult:
+    """What Engine.optimize_branch_lengths returns: per tree the maximum-likelihood branch
+    lengths [T][2n-2], the log-likelihood, branch gradient and Hessian diagonal [T][2n-1] at
+    them, the evaluations used and the status (0 converged, 1 iteration limit, 2 stalled)."""
+    branch_lengths: np.ndarray
+    log_likelihood: np.ndarray
+    gradient: np.ndarray
+    hessian: np.ndarray
+    iterations: np.ndarray
+    status: np.ndarray
+
+
+def _branch_opt_options(max_iterations, check_interval, pack_active, tolerance, min_length,
+                        max_length):
+    return _capi.BranchOptOptions(int(max_iterations), int(check_interval), int(bool(pack_active)),
+                                  float(tolerance), float(min_length), float(max_length))
+
+
 def _parse_site(site):
     # src/site_model.cpp:10-25
     if site == "constant":
@@ -292,6 +311,31 @@ class Engine:
             _ptr(h), _ptr(s)))
         return (ll, g, h, s) if squared_gradient else (ll, g, h)
 
+    def optimize_branch_lengths(self, parent_ids, start_branch_lengths, params=None,
+                                rescaling=False, max_iterations=100, check_interval=4,
+                                pack_active=True, tolerance=1e-6, min_length=1e-8,
+                                max_length=10.0):
+        """Maximum-likelihood branch lengths of unrooted trees within [min_length, max_length]
+        (mi_engine_optimize_branch_lengths_unrooted; an extension, 4-state engines): iterated
+        on the device from the Hessian call's g, H and S.  Returns a BranchOptResult."""
+        n, N = self.taxon_count, self.node_count
+        pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
+        T = pid.shape[0]
+        opts = _branch_opt_options(max_iterations, check_interval, pack_active, tolerance,
+                                   min_length, max_length)
+        if T == 0:
+            return BranchOptResult(np.empty((0, 2 * n - 2)), np.empty(0), np.empty((0, N)),
+                                   np.empty((0, N)), np.empty(0, np.int32), np.empty(0, np.int32))
+        bl = _np(start_branch_lengths, np.float64).reshape(T, 2 * n - 2)
+        pr = self._params(params, T)
+        out = BranchOptResult(np.empty((T, 2 * n - 2)), np.empty(T), np.empty((T, N)),
+                              np.empty((T, N)), np.empty(T, np.int32), np.empty(T, np.int32))
+        self._check(self._lib.mi_engine_optimize_branch_lengths_unrooted(
+            self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), C.addressof(opts),
+            _ptr(out.branch_lengths), _ptr(out.log_likelihood), _ptr(out.gradient),
+            _ptr(out.hessian), _ptr(out.iterations), _ptr(out.status)))
+        return out
+
     def _phylo_gradients(self, ll, blocks, site, subst):
         """Per-tree PhyloGradient objects over row views of the freshly allocated result
         arrays of one call (no per-tree copies: 1000 trees cost ~0.3 ms instead of ~1.1)."""
@@ -387,6 +431,24 @@ class Engine:
     def reserve_hessian(self, tree_count):
         """mi_engine_reserve_hessian: workspace of a Hessian call (graph capture)."""
         self._check(self._lib.mi_engine_reserve_hessian(self._h, int(tree_count)))
+
+    def optimize_branch_lengths_device(self, stream, T, parent_ids, start_branch_lengths, params,
+                                       out_branch_lengths, out_ll, out_status, out_branch=None,
+                                       out_hess=None, out_iterations=None, rescaling=False,
+                                       max_iterations=100, check_interval=4, pack_active=True,
+                                       tolerance=1e-6, min_length=1e-8, max_length=10.0):
+        """mi_engine_optimize_branch_lengths_unrooted_device: device pointers.  The call
+        synchronises `stream` at its check points, so it cannot be captured in a graph."""
+        opts = _branch_opt_options(max_iterations, check_interval, pack_active, tolerance,
+                                   min_length, max_length)
+        self._check(self._lib.mi_engine_optimize_branch_lengths_unrooted_device(
+            self._h, stream, T, parent_ids, start_branch_lengths, params, int(rescaling),
+            C.addressof(opts), out_branch_lengths, out_ll, out_branch, out_hess, out_iterations,
+            out_status))
+
+    def reserve_branch_opt(self, tree_count):
+        """mi_engine_reserve_branch_opt: workspace of an optimisation call of that size."""
+        self._check(self._lib.mi_engine_reserve_branch_opt(self._h, int(tree_count)))
 
     def reserve_reduced(self, tree_count, index_count):
         """mi_engine_reserve_reduced: workspace of a fused-reduction call (graph capture)."""
