@@ -1,0 +1,341 @@
+// Maximum-likelihood branch lengths (mi_engine_optimize_branch_lengths_unrooted*).
+// A host-driven loop of Hessian passes (run_hessian_device on the packed trial points) and
+// step kernels.  Every check_interval passes the host reads one word: the trees still active.
+// It stops at 0, and packs the active trees to the front when fewer than half of the packed
+// set are left.  Nothing else is synchronised, downloaded or allocated inside the loop.
+#include <cmath>
+
+#include "mi_phylo_engine.h"
+
+namespace {
+
+constexpr int kBranchOptMaxIterations = 1000;
+const mi_branch_opt_options kBranchOptDefaults = {100, 4, 1, 1e-6, 1e-8, 10.0, {0, 0, 0, 0}};
+
+struct BranchOptCall {
+  int T = 0;
+  bool rescaling = false;
+  const int32_t* parent_ids = nullptr;
+  const double* start = nullptr;
+  const double* params = nullptr;
+  const mi_branch_opt_options* options = nullptr;
+  double* out_bl = nullptr;
+  double* out_ll = nullptr;
+  double* out_g = nullptr;      // may be null
+  double* out_h = nullptr;      // may be null
+  int32_t* out_iters = nullptr;  // may be null
+  int32_t* out_status = nullptr;
+};
+
+// the pieces of e->opt_ws for a batch of T trees, 256-byte aligned
+struct BranchOptWorkspace {
+  double *trial, *trial_full, *tr_ll, *tr_g, *tr_h, *tr_s, *g, *h, *s, *alpha, *pk_params;
+  int32_t *map[2], *pk_parent, *evals, *active;
+  size_t bytes;
+  BranchOptWorkspace(const mi_engine* e, int T, char* base) {
+    const size_t N = e->N, t = (size_t)T;
+    size_t off = 0;
+    auto take = [&](size_t b) {
+      char* p = base + off;
+      off += (b + 255) & ~(size_t)255;
+      return p;
+    };
+    auto f64 = [&](size_t count) { return reinterpret_cast<double*>(take(sizeof(double) * count)); };
+    auto i32 = [&](size_t count) { return reinterpret_cast<int32_t*>(take(sizeof(int32_t) * count)); };
+    trial = f64(t * (N - 1));
+    trial_full = f64(t * (N - 1));
+    tr_ll = f64(t);
+    tr_g = f64(t * N);
+    tr_h = f64(t * N);
+    tr_s = f64(t * N);
+    g = f64(t * N);
+    h = f64(t * N);
+    s = f64(t * N);
+    alpha = f64(t);
+    pk_params = f64(t * std::max(e->param_count, 1));
+    map[0] = i32(t);
+    map[1] = i32(t);
+    pk_parent = i32(t * (N - 2));
+    evals = i32(t);
+    active = i32(kBranchOptMaxIterations);
+    bytes = off;
+  }
+};
+
+int reserve_branch_opt(mi_engine* e, int T) {
+  if (reserve_hessian_calls(e, T)) return 1;
+  if (e->opt_ws.ensure(BranchOptWorkspace(e, T, nullptr).bytes)) return 1;
+  if (!e->opt_word) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->opt_word), 256, hipHostMallocDefault));
+  return 0;
+}
+
+int check_branch_opt_options(const mi_branch_opt_options& o) {
+  if (o.max_iterations < 1 || o.max_iterations > kBranchOptMaxIterations)
+    return fail("branch-length optimisation: max_iterations must be in 1.." +
+                std::to_string(kBranchOptMaxIterations));
+  if (o.check_interval < 1) return fail("branch-length optimisation: check_interval must be positive");
+  if (!(o.tolerance >= 0.0)) return fail("branch-length optimisation: tolerance must be >= 0");
+  if (!(o.min_length >= 0.0) || !(o.max_length >= o.min_length) || !(o.max_length < INFINITY))
+    return fail("branch-length optimisation: need 0 <= min_length <= max_length < inf");
+  return 0;
+}
+
+int run_branch_opt_device(mi_engine* e, hipStream_t s, const BranchOptCall& c) {
+  HIP_TRY(hipSetDevice(e->spec.device));
+  if (e->s == kAa) return fail(kHessian4State);
+  if (c.T <= 0) return fail("tree_count must be positive");
+  if (!c.parent_ids || !c.start) return fail("null tree arrays");
+  if (!c.out_bl || !c.out_ll || !c.out_status) return fail("null output pointer");
+  if (e->param_count > 0 && !c.params) return fail("null parameter matrix");
+  const mi_branch_opt_options o = c.options ? *c.options : kBranchOptDefaults;
+  if (check_branch_opt_options(o)) return 1;
+  const int T = c.T, N = e->N;
+  if (reserve_branch_opt(e, T)) return 1;
+  const BranchOptWorkspace w(e, T, e->opt_ws.as<char>());
+  const bool pack = o.pack_active != 0;
+  HIP_TRY(hipMemsetAsync(w.active, 0, sizeof(int32_t) * o.max_iterations, s));
+  // (the maps are written before they are read; zeroed so that no index is ever out of range)
+  if (pack) {
+    HIP_TRY(hipMemsetAsync(w.map[0], 0, sizeof(int32_t) * (size_t)T, s));
+    HIP_TRY(hipMemsetAsync(w.map[1], 0, sizeof(int32_t) * (size_t)T, s));
+  }
+  BranchOptArgs st{};
+  st.N = N;
+  st.T = T;
+  st.count = T;
+  st.evals_max = o.max_iterations;
+  st.tol = o.tolerance;
+  st.tmin = o.min_length;
+  st.tmax = o.max_length;
+  st.map = nullptr;
+  st.tr_ll = w.tr_ll;
+  st.tr_g = w.tr_g;
+  st.tr_h = w.tr_h;
+  st.tr_s = w.tr_s;
+  st.trial = w.trial;
+  st.trial_full = pack ? w.trial_full : nullptr;
+  st.bl = c.out_bl;
+  st.ll = c.out_ll;
+  st.g = c.out_g ? c.out_g : w.g;
+  st.h = c.out_h ? c.out_h : w.h;
+  st.s = w.s;
+  st.alpha = w.alpha;
+  st.evals = c.out_iters ? c.out_iters : w.evals;
+  st.status = c.out_status;
+  st.active = w.active;
+  launch_branch_opt_init(st, c.start, s);
+  DeviceCall d;
+  d.T = T;
+  d.route_T = T;
+  d.rescaling = c.rescaling;
+  d.parent_ids = c.parent_ids;
+  d.bl = w.trial;
+  d.params = c.params;
+  d.out_ll = w.tr_ll;
+  d.out_branch = w.tr_g;
+  d.out_hess = w.tr_h;
+  d.out_gsq = w.tr_s;
+  int64_t evals = 0;
+  int passes = 0, launches = 0, which = 0;
+  std::string batches;  // "<trees>x<passes>,..."
+  int run_trees = 0, run_len = 0;
+  auto note = [&](int trees) {
+    if (trees == run_trees) {
+      run_len++;
+      return;
+    }
+    if (run_len) batches += (batches.empty() ? "" : ",") + std::to_string(run_trees) + "x" + std::to_string(run_len);
+    run_trees = trees;
+    run_len = trees ? 1 : 0;
+  };
+  for (int it = 0; it < o.max_iterations; it++) {
+    if (run_hessian_device(e, s, d)) return 1;
+    launches += e->last_walk_launches;
+    st.pass = it;
+    launch_branch_opt_step(st, s);
+    passes++;
+    evals += d.T;
+    note(d.T);
+    if (it + 1 == o.max_iterations) break;  // (every tree has stopped by now)
+    if ((it + 1) % o.check_interval) continue;
+    HIP_TRY(hipMemcpyAsync(e->opt_word, w.active + it, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int active = *e->opt_word;
+    if (active <= 0) break;
+    if (pack && 2 * active < d.T) {
+      BranchOptPackArgs pa{};
+      pa.N = N;
+      pa.count = active;
+      pa.param_count = e->param_count;
+      pa.map = w.map[which];
+      pa.parent_ids = c.parent_ids;
+      pa.params = c.params;
+      pa.trial_full = w.trial_full;
+      pa.pk_parent = w.pk_parent;
+      pa.pk_trial = w.trial;
+      pa.pk_params = w.pk_params;
+      launch_branch_opt_pack(pa, d.T, st.map, c.out_status, s);
+      st.map = pa.map;
+      st.count = active;
+      which ^= 1;
+      d.T = active;
+      d.parent_ids = w.pk_parent;
+      if (e->param_count > 0) d.params = w.pk_params;
+    }
+  }
+  note(0);
+  e->last_path += " opt iters=" + std::to_string(passes) + " evals=" + std::to_string(evals) +
+                  " batches=" + batches + (pack ? "" : " pack=off");
+  e->last_evals = evals;
+  e->last_grad_evals = evals;
+  e->last_walk_launches = launches;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The host-pointer form of the branch-length optimisation on one engine: inputs up in one
+// copy, the loop (which synchronises at its check points), outputs back in one copy and the
+// call's one error check.
+int run_branch_opt_host(mi_engine* e, const BranchOptCall& h) {
+  const int T = h.T, n = e->n, N = e->N;
+  if (T <= 0) return fail("tree_count must be positive");
+  if (!h.parent_ids || !h.start) return fail("null tree arrays");
+  if (!h.out_bl || !h.out_ll || !h.out_status) return fail("null output pointer");
+  if (e->param_count > 0 && !h.params) return fail("null parameter matrix");
+  HIP_TRY(hipSetDevice(e->spec.device));
+  e->fused_timed_out = false;
+  e->pinned.reset();
+  HIP_TRY(hipMemsetAsync(e->status.ptr, 0, sizeof(int32_t) * kStatusWords, e->stream));
+  const void *d_parent, *d_bl, *d_params;
+  if (upload_pack(e, {{h.parent_ids, sizeof(int32_t) * (size_t)T * (2 * n - 3), &d_parent},
+                      {h.start, sizeof(double) * (size_t)T * (2 * n - 2), &d_bl},
+                      {e->param_count > 0 ? h.params : nullptr, sizeof(double) * (size_t)T * e->param_count, &d_params}}))
+    return 1;
+  if (!d_params) d_params = e->in_pack.ptr;
+  double *o_bl, *o_ll, *o_g, *o_h, *o_iters, *o_status;  // (the last two: [T] int32)
+  const std::initializer_list<OutPiece> outs = {{h.out_bl, (size_t)T * (N - 1), &o_bl},
+                                                {h.out_ll, (size_t)T, &o_ll},
+                                                {h.out_g, h.out_g ? (size_t)T * N : 0, &o_g},
+                                                {h.out_h, h.out_h ? (size_t)T * N : 0, &o_h},
+                                                {h.out_iters, (size_t)T, &o_iters, sizeof(int32_t)},
+                                                {h.out_status, (size_t)T, &o_status, sizeof(int32_t)}};
+  if (place_out_pack(e, outs)) return 1;
+  BranchOptCall c = h;
+  c.parent_ids = static_cast<const int32_t*>(d_parent);
+  c.start = static_cast<const double*>(d_bl);
+  c.params = static_cast<const double*>(d_params);
+  c.out_bl = o_bl;
+  c.out_ll = o_ll;
+  c.out_g = h.out_g ? o_g : nullptr;
+  c.out_h = h.out_h ? o_h : nullptr;
+  c.out_iters = reinterpret_cast<int32_t*>(o_iters);
+  c.out_status = reinterpret_cast<int32_t*>(o_status);
+  if (run_branch_opt_device(e, e->stream, c)) return 1;
+  // one copy back; the pieces are handed over after the error check below
+  if (download_pack(e, outs)) return 1;
+  int rc = check_status(e, e->stream);
+  e->fused_timed_out = false;
+  if (rc == 0) e->pinned.flush();
+  e->pinned.reset();
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t mi_engine_optimize_branch_lengths_unrooted(
+    mi_engine* e, int32_t T, const int32_t* parent_ids, const double* start, const double* params,
+    int32_t rescaling, const mi_branch_opt_options* options, double* out_bl, double* out_ll,
+    double* out_g, double* out_h, int32_t* out_iters, int32_t* out_status) {
+  if (!e) return fail("null engine");
+  if (e->s == kAa) return fail(kHessian4State);
+  if (T <= 0) return fail("tree_count must be positive");
+  if (check_branch_opt_options(options ? *options : kBranchOptDefaults)) return 1;
+  BranchOptCall c;
+  c.T = T;
+  c.rescaling = rescaling != 0;
+  c.parent_ids = parent_ids;
+  c.start = start;
+  c.params = params;
+  c.options = options;
+  c.out_bl = out_bl;
+  c.out_ll = out_ll;
+  c.out_g = out_g;
+  c.out_h = out_h;
+  c.out_iters = out_iters;
+  c.out_status = out_status;
+  if (e->shards.empty()) {
+    if (run_branch_opt_host(e, c)) {
+      e->pinned.reset();
+      return 1;
+    }
+    return 0;
+  }
+  if (e->shard_mode != MI_SHARD_TREES)
+    return fail("pattern-sharded engines do not optimise branch lengths (every iteration would "
+                "need a sum across the shards): use MI_SHARD_TREES or a single engine");
+  if (!parent_ids || !start || !out_bl || !out_ll || !out_status) return fail("null tree / output pointer");
+  // Each shard optimises its block of trees independently, one shard after the other (the
+  // loop synchronises its device at every check point).
+  const int D = (int)e->shards.size(), n = e->n, N = e->N;
+  for (int i = 0; i < D; i++) {
+    int32_t b = 0, cnt = 0;
+    mi_shard_range(T, D, i, &b, &cnt);
+    if (cnt == 0) continue;
+    BranchOptCall sc = c;
+    sc.T = cnt;
+    sc.parent_ids = parent_ids + (size_t)b * (2 * n - 3);
+    sc.start = start + (size_t)b * (2 * n - 2);
+    if (params) sc.params = params + (size_t)b * e->param_count;
+    sc.out_bl = out_bl + (size_t)b * (N - 1);
+    sc.out_ll = out_ll + b;
+    if (out_g) sc.out_g = out_g + (size_t)b * N;
+    if (out_h) sc.out_h = out_h + (size_t)b * N;
+    if (out_iters) sc.out_iters = out_iters + b;
+    sc.out_status = out_status + b;
+    e->shards[i]->status_tree_offset = b;
+    if (run_branch_opt_host(e->shards[i], sc)) {
+      e->shards[i]->pinned.reset();
+      return 1;
+    }
+  }
+  return 0;
+}
+
+int32_t mi_engine_optimize_branch_lengths_unrooted_device(
+    mi_engine* e, void* stream, int32_t T, const int32_t* parent_ids, const double* start,
+    const double* params, int32_t rescaling, const mi_branch_opt_options* options, double* out_bl,
+    double* out_ll, double* out_g, double* out_h, int32_t* out_iters, int32_t* out_status) {
+  if (!e) return fail("null engine");
+  if (e->s == kAa) return fail(kHessian4State);
+  if (!e->shards.empty()) return fail(kShardedDeviceCall);
+  BranchOptCall c;
+  c.T = T;
+  c.rescaling = rescaling != 0;
+  c.parent_ids = parent_ids;
+  c.start = start;
+  c.params = params;
+  c.options = options;
+  c.out_bl = out_bl;
+  c.out_ll = out_ll;
+  c.out_g = out_g;
+  c.out_h = out_h;
+  c.out_iters = out_iters;
+  c.out_status = out_status;
+  return run_branch_opt_device(e, pick_stream(e, stream), c);
+}
+
+int32_t mi_engine_reserve_branch_opt(mi_engine* e, int32_t tree_count) {
+  if (!e) return fail("null engine");
+  if (tree_count <= 0) return fail("tree_count must be positive");
+  if (e->s == kAa) return fail(kHessian4State);
+  if (!e->shards.empty()) {
+    if (e->shard_mode != MI_SHARD_TREES) return fail("pattern-sharded engines do not optimise branch lengths");
+    return for_each_shard(e, tree_count, mi_engine_reserve_branch_opt);
+  }
+  HIP_TRY(hipSetDevice(e->spec.device));
+  return reserve_branch_opt(e, tree_count);
+}
+
+}  // extern "C"

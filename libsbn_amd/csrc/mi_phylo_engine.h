@@ -1,11 +1,18 @@
-// Private to libmi_phylo.so: the engine object behind include/mi_phylo.h and the helpers
-// its translation units share (mi_phylo_engine.cpp: 4-state call sequence and the C ABI;
-// mi_phylo_engine_aa.cpp: 20-state call sequence).
+// Private to libmi_phylo.so: the engine object behind include/mi_phylo.h and what its
+// translation units share:
+//   mi_phylo_engine.cpp       engine creation / destruction, status, profiling, the thin
+//                             device-pointer entry points of the C ABI
+//   mi_phylo_call.cpp         the call plan (which route a call takes: plan_call), reservation,
+//                             the argument-block builders, the 4-state and Hessian call sequences
+//   mi_phylo_branch_opt.cpp   branch-length optimisation
+//   mi_phylo_host_calls.cpp   host-pointer entry points, sharded handles
+//   mi_phylo_engine_aa.cpp    20-state call sequence
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -152,21 +159,19 @@ struct mi_engine {
   bool aa_reserved_gradient = false;
   PinnedArena pinned;
   Switches sw;  // the MI_PHYLO_* switches as they were when the engine was created
-  int tile_regs = -1;  // look-up walk: the engine's tile width (0: default, 4: wide; -1: not decided yet -- engine_tile_regs)
+  int tile_regs = 0;  // look-up walk: the engine's tile width (0: default, 4: wide -- engine_tile_regs, at creation)
   // a sharded handle (mi_engine_create_sharded): the per-device / per-shard engines it
   // drives; such a handle owns no device memory itself
   std::vector<mi_engine*> shards;
   int shard_mode = 0;
   std::vector<double> shard_sums;  // per-shard partial results (pattern shards, fused sums)
   // fused reductions (mi_engine_gradients_unrooted_reduced*)
-  Buffer in_index, in_weights, out_reduced, red_ll, red_g, red_site, red_sort;
+  Buffer red_ll, red_g, red_site, red_sort;
   long red_ws_entries = -1;  // what red_ws_bytes (the sort's workspace size) was computed for
   int red_ws_bits = 0;
   size_t red_ws_bytes = 0;
-  // staging for the host-pointer entry points
-  Buffer in_parent, in_bl, in_params, in_rates, in_rate_counts, in_heights, in_bounds,
-      in_ratios, out_ll, out_a, out_b, out_site, out_subst;
-  Buffer in_pack, out_pack;  // one block each way per host-pointer call (begin_host_call)
+  // staging for the host-pointer entry points: one block each way per call (begin_host_call)
+  Buffer in_pack, out_pack;
   // branch-length optimisation (mi_engine_optimize_branch_lengths_unrooted*)
   Buffer opt_ws;                // trial points, kept derivatives, packed inputs, maps, counters
   int32_t* opt_word = nullptr;  // pinned: the active count read at a check point
@@ -198,6 +203,44 @@ inline hipEvent_t prof_event(mi_engine* e, int which) {
     if (on) HIP_TRY(hipEventRecord(prof_event(e, 2 + (which)), s)); \
   } while (0)
 
+// ---- the call plan (mi_phylo_call.cpp) ----
+// Everything the engine decides about ONE call before it enqueues anything: the evaluation
+// shape, the kernel family and its store, which set-up form runs, which passes run and who
+// fills the tip tables.  plan_call is the only place these are decided; reservation
+// (reserve, reserve_hessian), the argument-block builders, the call sequences and the path
+// string (plan_path) read the plan -- so a reserve cannot guess differently from the call it
+// reserves for (and leave that call to allocate inside a hipGraph capture).
+enum CallKind { kLogLikCall, kGradientCall, kHessianCall };
+enum WalkStore { kStoreHbm = 0, kStoreLds = 1, kStoreArena = 2 };  // (LikArgs::store: 0 = not a matrix-core walk)
+struct CallPlan {
+  CallKind kind;
+  int T;
+  bool rescaling, rooted;
+  // evaluation shape (EvalMap, mi_phylo_kernels.h): evaluations, gradient evaluations, model instances
+  int E, Eg, M, models_per_tree;
+  bool gtr, site_fused, site_separate;
+  // the gradient / Hessian kernel family and its store
+  bool mfma;        // a matrix-core walk (else, for gradient and Hessian calls: the HBM-streamed kernel)
+  bool walk3;       // ... of the third generation (look-up walk, kernels_walk3.hip)
+  WalkStore store;  // where a walk keeps its stored vectors (kStoreHbm: no walk runs)
+  int groups;       // waves per pattern tile (category groups of four)
+  int tile_regs;    // look-up walk: tile width of this call (0: the default)
+  int g_tiles;      // gradient partial sums per gradient evaluation
+  bool analytic;    // analytic substitution gradient (opt-in) instead of finite differences
+  bool light;       // GTR gradient call nobody reads the substitution / site gradient of
+  bool fuse_setup;     // set-up rides in the walk's launch (the one-launch call)
+  bool setup_records;  // set-up and operand records in one launch in front of the walk's
+  bool need_slots;     // the schedule gets LDS slots: a log-likelihood (or HBM Hessian) kernel walks it
+  bool fd_pass, site_pass;  // the 16 finite-difference passes / the perturbed-model site pass run
+  bool loglik_runs;         // a log-likelihood kernel runs at all
+  bool loglik_is_valu;      // ... the VALU one (else the matrix-core one)
+  bool need_tip_tables;     // the transition launch fills the per-state tip tables (VALU log-likelihood kernel)
+  // reservation only: what does not follow from this call alone
+  size_t mmats_bytes_per_eval;  // macro-ordered matrices of either walk generation this engine can take
+  bool reserve_arena;           // some call of this engine (other rescaling / batch size) takes the arena
+  bool hand_off_words;          // the one-launch call may run on this engine: `ready` is kept
+  const char* dominant;  // the dominant kernel's name
+};
 // One engine call with every pointer a device pointer (what the *_device entry points build).
 struct DeviceCall {
   bool gradient = false, rooted = false, with_jacobian = false, rescaling = false;
@@ -224,6 +267,59 @@ struct DeviceCall {
   // trees are still active); 0: T
   int route_T = 0;
 };
+// (the defaults: what reservation plans for -- every optional output wanted)
+CallPlan plan_call(const mi_engine* e, CallKind kind, int T, bool rescaling, int route_T = 0,
+                   bool rooted = false, bool want_site = true, bool want_subst = true);
+inline CallPlan plan_call(const mi_engine* e, CallKind kind, const DeviceCall& d) {
+  return plan_call(e, kind, d.T, d.rescaling, d.route_T, d.rooted, d.out_site != nullptr, d.out_subst != nullptr);
+}
+std::string plan_path(const mi_engine* e, const CallPlan& p);  // mi_engine_last_call_path
+bool walk3_possible(const mi_engine* e);  // (engine creation: the look-up walk's pre-tiled tip codes)
+int engine_tile_regs(const mi_engine* e);  // (engine creation: decided once, kept in e->tile_regs)
+int reserve(mi_engine* e, const CallPlan& p);
+int reserve_hessian(mi_engine* e, const CallPlan& p);
+int reserve_hessian_calls(mi_engine* e, int T);  // of either rescaling setting (mi_engine_reserve_hessian)
+// set-up blocks every call sequence fills the same way (20 states: with a plan that only says need_slots)
+TreeSetupArgs tree_setup_args(const mi_engine* e, const DeviceCall& d, const CallPlan& p);
+ModelSetupArgs model_setup_args(const mi_engine* e, const DeviceCall& d, const CallPlan& p);
+FinalizeArgs finalize_args(const mi_engine* e, const DeviceCall& d);  // what comes from the engine and the call
+int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
+int run_hessian_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
+
+// ---- mi_phylo_engine.cpp ----
+extern const char kShardedDeviceCall[], kHessian4State[];
+int check_status(mi_engine* e, hipStream_t s);
+inline hipStream_t pick_stream(mi_engine* e, void* stream) {
+  return stream ? static_cast<hipStream_t>(stream) : e->stream;
+}
+// A sharded handle: one(shard, its share of `tree_count` trees) for every shard that has trees
+// (pattern shards: every shard gets all of them).
+template <typename F>
+int for_each_shard(mi_engine* e, int tree_count, F one) {
+  const int D = (int)e->shards.size();
+  for (int i = 0; i < D; i++) {
+    int32_t b = 0, c = tree_count;
+    if (e->shard_mode == MI_SHARD_TREES) mi_shard_range(tree_count, D, i, &b, &c);
+    if (c > 0 && one(e->shards[i], c)) return 1;
+  }
+  return 0;
+}
+
+// ---- mi_phylo_host_calls.cpp: one DMA each way per host-pointer call ----
+struct InPiece {
+  const void* host;
+  size_t bytes;
+  const void** dev;
+};
+struct OutPiece {
+  void* host;    // may be null: not wanted
+  size_t count;  // elements
+  double** dev;
+  size_t elem = sizeof(double);  // bytes per element
+};
+int upload_pack(mi_engine* e, std::initializer_list<InPiece> pieces);
+int place_out_pack(mi_engine* e, std::initializer_list<OutPiece> pieces);
+int download_pack(mi_engine* e, std::initializer_list<OutPiece> pieces);
 
 // mi_phylo_engine_aa.cpp
 int aa_engine_init(mi_engine* e, const double* exchangeabilities, const double* frequencies);

@@ -131,35 +131,13 @@ int aa_run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   const int n = e->n, N = e->N, T = d.T;
   if (aa_reserve(e, T, d.gradient)) return 1;
 
-  TreeSetupArgs ts{};
-  ts.n = n;
-  ts.T = T;
-  ts.rooted = d.rooted;
-  ts.parent_ids = d.parent_ids;
-  ts.bl = d.bl;
-  ts.rates = (d.rooted && (d.gradient || d.with_jacobian)) ? d.rates : nullptr;
-  ts.scratch = e->tree_scratch.as<int32_t>();
-  ts.sched = e->sched.as<SchedEntry>();
-  ts.macros = nullptr;
-  ts.macro_count = e->macro_count.as<int32_t>();
-  ts.bl_eff = e->bl_eff.as<double>();
-  ts.status = e->status.as<int32_t>();
-  ts.max_slots = e->max_slots;
-  ts.need_slots = 1;
-  ModelSetupArgs ms{};
-  ms.T = T;
-  ms.models_per_tree = 1;
-  ms.subst = 0;  // the 4-state part of DevModel is unused here; only the site model is read
-  ms.site = e->spec.site_model;
-  ms.K = e->K;
-  ms.param_count = e->param_count;
-  ms.rates_off = e->rates_off;
-  ms.freqs_off = e->freqs_off;
-  ms.shape_off = e->shape_off;
-  ms.params = d.params;
-  ms.models = e->models.as<DevModel>();
-  ms.status = e->status.as<int32_t>();
-  ms.weibull_x = e->weibull_x.as<double>();
+  // (tree schedules with LDS slots, no gradient schedule; only the site model of DevModel is read)
+  CallPlan p{};
+  p.need_slots = true;
+  p.models_per_tree = 1;
+  const TreeSetupArgs ts = tree_setup_args(e, d, p);
+  ModelSetupArgs ms = model_setup_args(e, d, p);
+  ms.subst = 0;  // the 4-state part of DevModel is unused here
   const bool prof = e->prof_used < e->prof_capacity;
   const bool marks = prof && e->prof_phases;
   PROF_MARK(e, marks, 0, s);
@@ -242,39 +220,13 @@ int aa_run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   e->last_grad_evals = d.gradient ? T : 0;
   e->last_walk_launches = (T + chunk - 1) / chunk;
 
-  FinalizeArgs fa{};
-  fa.n = n;
-  fa.N = N;
-  fa.T = T;
-  fa.K = e->K;
-  fa.tiles = e->tiles;
+  FinalizeArgs fa = finalize_args(e, d);
   fa.ll_tiles = 1;
   fa.ll_used = LlCounts{1, 1, 0, 0};
   fa.g_tiles = 1;
   fa.ll_part = e->ll_sum.as<double>();
   fa.g_part = e->g_sum.as<double>();
-  fa.gradient = d.gradient;
-  fa.rooted = d.rooted;
-  fa.with_jacobian = d.with_jacobian;
-  fa.gtr = 0;
   fa.site_fused = d.gradient && e->K > 1;
-  fa.site_separate = 0;
-  fa.bl_eff = e->bl_eff.as<double>();
-  fa.bl_raw = d.bl;
-  fa.rates = d.rates;
-  fa.rate_counts = d.rate_counts;
-  fa.node_heights = d.heights;
-  fa.node_bounds = d.bounds;
-  fa.height_ratios = d.ratios;
-  fa.sched = e->sched.as<SchedEntry>();
-  fa.scratch = e->fin_scratch.as<double>();
-  fa.out_ll = d.out_ll;
-  fa.out_branch = d.out_branch;
-  fa.out_ratios = d.out_ratios;
-  fa.out_clock = d.out_clock;
-  fa.out_site = d.out_site;
-  fa.out_subst = nullptr;
-  fa.status = e->status.as<int32_t>();
   launch_finalize(fa, s);
   PROF_MARK(e, marks, 4, s);
   if (prof) e->prof_used++;

@@ -54,6 +54,8 @@ def main():
         if k:
             print(f"{name:24s} {res[name].get('name', ''):24s} kernel min {min(k):.4f} median {np.median(k):.4f} ms | "
                   f"step min {min(s):.4f} median {np.median(s):.4f} ms   ({len(k)} runs)")
+            # (each round's step median: their largest minus smallest is the day's noise)
+            print(f"{'':24s} step by round: " + " ".join(f"{x:.4f}" for x in s) + f"   spread {max(s) - min(s):.4f} ms")
 
 
 if __name__ == "__main__":
