@@ -208,6 +208,42 @@ int32_t mi_engine_branch_hessian_unrooted(mi_engine* engine, int32_t tree_count,
                                           double* out_branch_hessian /* [T][2n-1] */,
                                           double* out_branch_gradient_sq /* [T][2n-1] or NULL */);
 
+/* The NNI neighbourhood scan of unrooted trees (an extension: no counterpart in the reference's
+ * Engine): the log-likelihood change of every nearest-neighbour interchange,
+ * with the same model row and the same branch lengths, from one walk per tree.  In the
+ * caller's tree (leaves 0..n-1, internal nodes in post-order, the trifurcating root 2n-3,
+ * children ordered by largest leaf id) every internal node v with n <= v < 2n-3 is the lower
+ * end of one inner edge.  Let (a, b) be v's children in child order, u its parent and c the
+ * first, in child order, of u's children other than v (v's sibling; at the root the first of
+ * the other two root children).
+ *   neighbour 0 of v: v keeps a and takes c; b takes c's place under u
+ *   neighbour 1 of v: v keeps b and takes c; a takes c's place under u
+ * Every subtree carries the branch above it along, edge v keeps its length, nothing else
+ * changes (mi_nni_neighbour builds these trees).
+ *   out_nni_delta[t][v][i] = logL(neighbour i of v) - logL(tree t) = sum_p w_p log(L'_p / L_p)
+ * per pattern, not a difference of two totals; [T][2n-1][2] by node id, 0 for leaves, 2n-3 and
+ * 2n-2.  out_best_move[t] = 2 v + i of the largest delta, the lowest code among equals, -1 when
+ * n == 3.  out_log_likelihoods is that of a gradient call on the HBM path, bit for bit.  One
+ * evaluation per tree with the tree's own model (a GTR engine: no finite-difference passes).
+ * 4-state engines only: a 20-state engine returns nonzero.  Sharded handles: MI_SHARD_TREES
+ * deals the trees as the other calls do, results in tree order; MI_SHARD_PATTERNS adds logL
+ * and delta (sums over patterns) in shard order and takes the best move from the sums. */
+int32_t mi_engine_nni_scan_unrooted(mi_engine* engine, int32_t tree_count,
+                                    const int32_t* parent_ids,     /* [T][2n-3] */
+                                    const double* branch_lengths,  /* [T][2n-2] */
+                                    const double* params, int32_t rescaling,
+                                    double* out_log_likelihoods /* [T] or NULL */,
+                                    double* out_nni_delta /* [T][2n-1][2] */,
+                                    int32_t* out_best_move /* [T] or NULL */);
+/* Neighbour `which` (0 | 1) of inner edge `node` of ONE tree, as defined above, renumbered in
+ * the reference's convention, every branch length moved to its subtree's new id (the entry of
+ * the root, 2n-3, is copied).  Pure host arithmetic: no device is touched.  Nonzero when
+ * `node` is not the lower end of an inner edge, `which` is neither 0 nor 1, or the parent-id
+ * vector is not a tree in the reference's form. */
+int32_t mi_nni_neighbour(int32_t taxon_count, const int32_t* parent_ids /* [2n-3] */,
+                         const double* branch_lengths /* [2n-2] */, int32_t node, int32_t which,
+                         int32_t* out_parent_ids /* [2n-3] */, double* out_branch_lengths /* [2n-2] */);
+
 /* Maximum-likelihood branch lengths of unrooted trees under box bounds (an extension: the
  * consumer of the Hessian call's outputs).  Every tree of the batch is
  * iterated on the device: an evaluation is one Hessian pass at a trial point, a step is a
@@ -341,6 +377,12 @@ int32_t mi_engine_branch_hessian_unrooted_device(mi_engine* engine, void* stream
                                                  double* out_branch_hessian,
                                                  double* out_branch_gradient_sq);
 
+int32_t mi_engine_nni_scan_unrooted_device(mi_engine* engine, void* stream, int32_t tree_count,
+                                           const int32_t* parent_ids, const double* branch_lengths,
+                                           const double* params, int32_t rescaling,
+                                           double* out_log_likelihoods, double* out_nni_delta,
+                                           int32_t* out_best_move);
+
 /* The device form of mi_engine_optimize_branch_lengths_unrooted.  Unlike the other *_device
  * calls it SYNCHRONISES `stream` at its check points (it reads the number of active trees to
  * decide whether to go on), so it cannot be captured in a hipGraph; when it returns, every
@@ -370,6 +412,9 @@ int32_t mi_engine_reserve_reduced(mi_engine* engine, int32_t tree_count, int32_t
  * *_device call of at most that size then allocates nothing (hipGraph capture).  4-state
  * engines only. */
 int32_t mi_engine_reserve_hessian(mi_engine* engine, int32_t tree_count);
+/* The workspace of mi_engine_nni_scan_unrooted[_device] for `tree_count` trees: a *_device
+ * call of at most that size then allocates nothing (hipGraph capture).  4-state engines only. */
+int32_t mi_engine_reserve_nni_scan(mi_engine* engine, int32_t tree_count);
 /* The workspace of mi_engine_optimize_branch_lengths_unrooted[_device] for `tree_count` trees
  * (the Hessian call's included): a *_device call of at most that size then allocates
  * nothing.  4-state engines only. */

@@ -72,6 +72,12 @@ SYMBOLS = {
         (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V]),
     "mi_engine_branch_hessian_unrooted_device":
         (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V]),
+    "mi_engine_nni_scan_unrooted":
+        (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V]),
+    "mi_engine_nni_scan_unrooted_device":
+        (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V]),
+    "mi_engine_reserve_nni_scan": (C.c_int32, [_V, C.c_int32]),
+    "mi_nni_neighbour": (C.c_int32, [C.c_int32, _V, _V, C.c_int32, C.c_int32, _V, _V]),
     "mi_engine_reserve": (C.c_int32, [_V, C.c_int32, C.c_int32]),
     "mi_engine_reserve_reduced": (C.c_int32, [_V, C.c_int32, C.c_int32]),
     "mi_engine_reserve_hessian": (C.c_int32, [_V, C.c_int32]),

@@ -49,6 +49,15 @@ struct BranchHessian {
   std::vector<double> gradient_, hessian_, gradient_sq_;
 };
 
+// Engine::NniScan, per tree (an extension, include/mi_phylo.h): delta_[2 v + i] = logL(neighbour i
+// of inner edge v) - logL(tree), [2 (2n-1)] by node id, 0 where v is no inner edge; best_move_ =
+// 2 v + i of the largest delta (-1: no inner edge)
+struct NniNeighbourhood {
+  double log_likelihood_ = 0.;
+  std::vector<double> delta_;
+  int32_t best_move_ = -1;
+};
+
 // Engine::OptimizeBranchLengths, per tree (an extension, include/mi_phylo.h): the
 // maximum-likelihood branch lengths [2n-2] and the Hessian call's outputs at them [2n-1]
 struct BranchOptimum {
@@ -219,6 +228,28 @@ class Engine {
       out[t].gradient_.assign(g.begin() + t * N, g.begin() + (t + 1) * N);
       out[t].hessian_.assign(h.begin() + t * N, h.begin() + (t + 1) * N);
       out[t].gradient_sq_.assign(s.begin() + t * N, s.begin() + (t + 1) * N);
+    }
+    return out;
+  }
+
+  // Log-likelihood change of every nearest-neighbour interchange per tree (an extension;
+  // 4-state engines): mi_engine_nni_scan_unrooted.  mi_nni_neighbour builds the tree of a move.
+  std::vector<NniNeighbourhood> NniScan(const UnrootedTreeCollection& trees, const ParamMatrix& params,
+                                        const bool rescaling) const {
+    const size_t T = trees.size(), N = 2 * site_pattern_.SequenceCount() - 1;
+    std::vector<int32_t> parents;
+    std::vector<double> bl;
+    Flatten(trees, params, false, &parents, &bl);
+    if (trees.empty()) return {};
+    std::vector<double> ll(T), d(T * N * 2);
+    std::vector<int32_t> best(T);
+    Check(mi_engine_nni_scan_unrooted(handle_, static_cast<int32_t>(T), parents.data(), bl.data(),
+                                      params.data.data(), rescaling, ll.data(), d.data(), best.data()));
+    std::vector<NniNeighbourhood> out(T);
+    for (size_t t = 0; t < T; t++) {
+      out[t].log_likelihood_ = ll[t];
+      out[t].delta_.assign(d.begin() + t * N * 2, d.begin() + (t + 1) * N * 2);
+      out[t].best_move_ = best[t];
     }
     return out;
   }

@@ -84,6 +84,7 @@ const char kShardedDeviceCall[] =
     "device-pointer entry points need a single-device engine: one engine per device (one "
     "process per GPU), or the host-pointer entry points";
 const char kHessian4State[] = "the branch-length Hessian call is 4-state only";
+const char kNni4State[] = "the NNI neighbourhood scan is 4-state only";
 
 extern "C" {
 
@@ -663,6 +664,35 @@ int32_t mi_engine_reserve_hessian(mi_engine* e, int32_t tree_count) {
   if (!e->shards.empty()) return for_each_shard(e, tree_count, mi_engine_reserve_hessian);
   HIP_TRY(hipSetDevice(e->spec.device));
   return reserve_hessian_calls(e, tree_count);
+}
+
+int32_t mi_engine_nni_scan_unrooted_device(mi_engine* e, void* stream, int32_t T,
+                                           const int32_t* parent_ids, const double* bl,
+                                           const double* params, int32_t rescaling, double* out_ll,
+                                           double* out_delta, int32_t* out_best) {
+  if (!e) return fail("null engine");
+  if (e->s == kAa) return fail(kNni4State);
+  if (!e->shards.empty()) return fail(kShardedDeviceCall);
+  if (!out_delta) return fail("null NNI delta output");
+  DeviceCall d;
+  d.T = T;
+  d.rescaling = rescaling != 0;
+  d.parent_ids = parent_ids;
+  d.bl = bl;
+  d.params = params;
+  d.out_ll = out_ll;
+  d.out_nni = out_delta;
+  d.out_best = out_best;
+  return run_nni_device(e, pick_stream(e, stream), d);
+}
+
+int32_t mi_engine_reserve_nni_scan(mi_engine* e, int32_t tree_count) {
+  if (!e) return fail("null engine");
+  if (tree_count <= 0) return fail("tree_count must be positive");
+  if (e->s == kAa) return fail(kNni4State);
+  if (!e->shards.empty()) return for_each_shard(e, tree_count, mi_engine_reserve_nni_scan);
+  HIP_TRY(hipSetDevice(e->spec.device));
+  return reserve_nni_calls(e, tree_count);
 }
 
 int32_t mi_engine_log_likelihoods_rooted_device(mi_engine* e, void* stream, int32_t T,

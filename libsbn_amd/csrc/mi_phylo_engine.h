@@ -3,8 +3,9 @@
 //   mi_phylo_engine.cpp       engine creation / destruction, status, profiling, the thin
 //                             device-pointer entry points of the C ABI
 //   mi_phylo_call.cpp         the call plan (which route a call takes: plan_call), reservation,
-//                             the argument-block builders, the 4-state and Hessian call sequences
+//                             the argument-block builders, the 4-state, Hessian and NNI-scan call sequences
 //   mi_phylo_branch_opt.cpp   branch-length optimisation
+//   mi_phylo_nni.cpp          mi_nni_neighbour, the scan's best move on the host (no device code)
 //   mi_phylo_host_calls.cpp   host-pointer entry points, sharded handles
 //   mi_phylo_engine_aa.cpp    20-state call sequence
 #pragma once
@@ -210,7 +211,7 @@ inline hipEvent_t prof_event(mi_engine* e, int which) {
 // (reserve, reserve_hessian), the argument-block builders, the call sequences and the path
 // string (plan_path) read the plan -- so a reserve cannot guess differently from the call it
 // reserves for (and leave that call to allocate inside a hipGraph capture).
-enum CallKind { kLogLikCall, kGradientCall, kHessianCall };
+enum CallKind { kLogLikCall, kGradientCall, kHessianCall, kNniCall };
 enum WalkStore { kStoreHbm = 0, kStoreLds = 1, kStoreArena = 2 };  // (LikArgs::store: 0 = not a matrix-core walk)
 struct CallPlan {
   CallKind kind;
@@ -262,6 +263,9 @@ struct DeviceCall {
   // branch-length Hessian call (run_hessian_device): out_ll / out_branch may be nullptr there
   double* out_hess = nullptr;
   double* out_gsq = nullptr;
+  // NNI neighbourhood scan (run_nni_device): out_ll / out_best may be nullptr there
+  double* out_nni = nullptr;    // [T][N][2]
+  int32_t* out_best = nullptr;  // [T]
   // ... as one pass of the branch-length optimisation: the batch size the kernel and its store
   // are chosen for (the whole batch's, so that a tree's results do not depend on how many
   // trees are still active); 0: T
@@ -285,9 +289,14 @@ ModelSetupArgs model_setup_args(const mi_engine* e, const DeviceCall& d, const C
 FinalizeArgs finalize_args(const mi_engine* e, const DeviceCall& d);  // what comes from the engine and the call
 int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
 int run_hessian_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
+int reserve_nni(mi_engine* e, const CallPlan& p);
+int reserve_nni_calls(mi_engine* e, int T);  // of either rescaling setting (mi_engine_reserve_nni_scan)
+int run_nni_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
+// the scan's best move from a tree's delta [N][2] (what the finalize kernel does; pattern shards)
+int32_t nni_best_move(int n, const double* delta);
 
 // ---- mi_phylo_engine.cpp ----
-extern const char kShardedDeviceCall[], kHessian4State[];
+extern const char kShardedDeviceCall[], kHessian4State[], kNni4State[];
 int check_status(mi_engine* e, hipStream_t s);
 inline hipStream_t pick_stream(mi_engine* e, void* stream) {
   return stream ? static_cast<hipStream_t>(stream) : e->stream;

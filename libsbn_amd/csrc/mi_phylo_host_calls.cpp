@@ -29,6 +29,10 @@ struct HostCall {
   bool hessian = false;
   double* out_h = nullptr;  // [T][N]
   double* out_s = nullptr;  // [T][N] or null
+  // NNI neighbourhood scan (mi_engine_nni_scan_unrooted): out_ll and out_best may be null there
+  bool nni = false;
+  double* out_nni = nullptr;    // [T][N][2]
+  int32_t* out_best = nullptr;  // [T] or null
   // fused reductions of a variational-inference step (mi_engine_gradients_unrooted_reduced)
   bool reduced = false;
   const int32_t* branch_index = nullptr;  // [T][N]
@@ -151,6 +155,18 @@ int begin_host_call(mi_engine* e, const HostCall& h) {
       return 1;
     return download_pack(e, outs);
   }
+  if (h.nni) {
+    double *o_d, *o_best;
+    const std::initializer_list<OutPiece> outs = {{h.out_ll, h.out_ll ? (size_t)T : 0, &o_ll},
+                                                  {h.out_nni, (size_t)T * N * 2, &o_d},
+                                                  {h.out_best, h.out_best ? (size_t)T : 0, &o_best, sizeof(int32_t)}};
+    if (place_out_pack(e, outs)) return 1;
+    if (mi_engine_nni_scan_unrooted_device(e, e->stream, T, P32(d_parent), F64(d_bl), F64(d_params), h.rescaling,
+                                           h.out_ll ? o_ll : nullptr, o_d,
+                                           h.out_best ? reinterpret_cast<int32_t*>(o_best) : nullptr))
+      return 1;
+    return download_pack(e, outs);
+  }
   if (!h.gradient) {
     const std::initializer_list<OutPiece> outs = {{h.out_ll, (size_t)T, &o_ll}};
     if (place_out_pack(e, outs)) return 1;
@@ -255,6 +271,8 @@ int run_sharded(mi_engine* e, const HostCall& h) {
       if (h.out_subst) s.out_subst = h.out_subst + (size_t)b * 8;
       if (h.out_h) s.out_h = h.out_h + (size_t)b * N;
       if (h.out_s) s.out_s = h.out_s + (size_t)b * N;
+      if (h.out_nni) s.out_nni = h.out_nni + (size_t)b * N * 2;
+      if (h.out_best) s.out_best = h.out_best + b;
       if (h.reduced) {
         s.branch_index = h.branch_index + (size_t)b * N;
         if (h.tree_weights) s.tree_weights = h.tree_weights + b;
@@ -287,7 +305,8 @@ int run_sharded(mi_engine* e, const HostCall& h) {
                 "and the rooted chain rule are not sums over site patterns)");
   // (a Hessian call: per shard logL, gradient, H and S, [T] + 3 [T][N]; H = D2 term - S adds
   // up shard by shard like the rest)
-  const size_t per = (size_t)T * (1 + (h.gradient ? N + 1 + 8 : 0) + (h.hessian ? 3 * N : 0)) + 2 + h.index_count;
+  // (an NNI scan: per shard logL and delta, [T] + [T][N][2]; the best move is taken from the sums)
+  const size_t per = (size_t)T * (1 + (h.gradient ? N + 1 + 8 : 0) + (h.hessian ? 3 * N : 0) + (h.nni ? 2 * N : 0)) + 2 + h.index_count;
   e->shard_sums.assign((size_t)D * per, 0.0);
   int rc = 0, started = 0;
   std::vector<HostCall> calls(D);
@@ -299,6 +318,10 @@ int run_sharded(mi_engine* e, const HostCall& h) {
       s.out_a = h.out_a ? base + T : nullptr;
       s.out_h = base + (size_t)T * (1 + N);
       s.out_s = h.out_s ? base + (size_t)T * (1 + 2 * N) : nullptr;
+    }
+    if (h.nni) {
+      s.out_nni = base + T;
+      s.out_best = nullptr;
     }
     if (h.gradient) {
       s.out_a = base + T;
@@ -327,6 +350,11 @@ int run_sharded(mi_engine* e, const HostCall& h) {
     add(h.out_a, T, (size_t)T * N);
     add(h.out_h, (size_t)T * (1 + N), (size_t)T * N);
     add(h.out_s, (size_t)T * (1 + 2 * N), (size_t)T * N);
+  }
+  if (h.nni) {
+    add(h.out_nni, T, (size_t)T * N * 2);
+    if (h.out_best)
+      for (int t = 0; t < T; t++) h.out_best[t] = nni_best_move(n, h.out_nni + (size_t)t * N * 2);
   }
   if (h.gradient) {
     add(h.out_a, T, (size_t)T * N);
@@ -416,6 +444,24 @@ int32_t mi_engine_branch_hessian_unrooted(mi_engine* e, int32_t T, const int32_t
   h.out_a = out_branch;
   h.out_h = out_hess;
   h.out_s = out_gsq;
+  return run_host(e, h);
+}
+
+int32_t mi_engine_nni_scan_unrooted(mi_engine* e, int32_t T, const int32_t* parent_ids, const double* bl,
+                                    const double* params, int32_t rescaling, double* out_ll,
+                                    double* out_delta, int32_t* out_best) {
+  if (!out_delta) return fail("null NNI delta output");
+  if (e && e->s == kAa) return fail(kNni4State);
+  HostCall h;
+  h.nni = true;
+  h.T = T;
+  h.rescaling = rescaling;
+  h.parent_ids = parent_ids;
+  h.bl = bl;
+  h.params = params;
+  h.out_ll = out_ll;
+  h.out_nni = out_delta;
+  h.out_best = out_best;
   return run_host(e, h);
 }
 

@@ -215,6 +215,20 @@ struct HessFinalizeArgs {
   double* out_gsq;        // [T][N] or nullptr: sum w (D1/L)^2
 };
 void launch_hessian_finalize(const HessFinalizeArgs& a, hipStream_t s);
+// The NNI neighbourhood scan (kernels_nni.hip): the HBM-streamed walk with, per
+// inner edge, the log-likelihood change of its two interchanges; one evaluation per tree;
+// g_part [Eg][tiles][2][N] by node id.  Its tile reduction and outputs, a workgroup per tree.
+void launch_nni_scan_hbm(const LikArgs& a, int count, bool rescale, hipStream_t s);
+const char* nni_scan_kernel_name();
+struct NniFinalizeArgs {
+  int N, n, T, g_tiles, ll_tiles, ll_used;
+  const double* ll_part;  // [T][ll_tiles]
+  const double* g_part;   // [T][g_tiles][2][N]
+  double* out_ll;         // [T] or nullptr
+  double* out_delta;      // [T][N][2]
+  int32_t* out_best;      // [T] or nullptr: 2 v + i of the largest delta (-1: no inner edge)
+};
+void launch_nni_finalize(const NniFinalizeArgs& a, hipStream_t s);
 // Branch-length optimisation (kernels_branch_opt.hip): the step between two
 // Hessian passes and the packing of the active trees.  "Packed" arrays hold the trees that
 // are still being evaluated, in `map` order (map == nullptr: all trees, in their own order).

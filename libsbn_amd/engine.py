@@ -68,6 +68,20 @@ def _branch_opt_options(max_iterations, check_interval, pack_active, tolerance, 
                                   float(tolerance), float(min_length), float(max_length))
 
 
+def nni_neighbour(taxon_count, parent_ids, branch_lengths, node, which):
+    """Neighbour `which` (0 | 1) of inner edge `node` of one unrooted tree (mi_nni_neighbour:
+    the trees Engine.nni_scan scores): (parent ids [2n-3], branch lengths [2n-2]) renumbered
+    in the reference's convention.  Host arithmetic only."""
+    n = int(taxon_count)
+    pid = _np(parent_ids, np.int32).reshape(2 * n - 3)
+    bl = _np(branch_lengths, np.float64).reshape(2 * n - 2)
+    out_pid, out_bl = np.empty(2 * n - 3, np.int32), np.empty(2 * n - 2)
+    if _capi.load().mi_nni_neighbour(n, _ptr(pid), _ptr(bl), int(node), int(which), _ptr(out_pid),
+                                     _ptr(out_bl)):
+        raise RuntimeError(_capi.last_error())
+    return out_pid, out_bl
+
+
 def _parse_site(site):
     # src/site_model.cpp:10-25
     if site == "constant":
@@ -311,6 +325,25 @@ class Engine:
             _ptr(h), _ptr(s)))
         return (ll, g, h, s) if squared_gradient else (ll, g, h)
 
+    def nni_scan(self, parent_ids, branch_lengths, params=None, rescaling=False):
+        """Log-likelihood change of every nearest-neighbour interchange per tree
+        (mi_engine_nni_scan_unrooted; an extension, 4-state engines): returns (log-likelihoods
+        [T], delta [T][2n-1][2] by node id -- delta[t][v][i] = logL(neighbour i of inner edge v)
+        - logL(tree t), 0 where v is no inner edge --, best move [T] = 2 v + i of the largest
+        delta, -1 for three taxa).  nni_neighbour builds the tree a move leads to."""
+        n, N = self.taxon_count, self.node_count
+        pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
+        T = pid.shape[0]
+        if T == 0:
+            return np.empty(0), np.empty((0, N, 2)), np.empty(0, np.int32)
+        bl = _np(branch_lengths, np.float64).reshape(T, 2 * n - 2)
+        pr = self._params(params, T)
+        ll, delta, best = np.empty(T), np.empty((T, N, 2)), np.empty(T, np.int32)
+        self._check(self._lib.mi_engine_nni_scan_unrooted(
+            self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), _ptr(ll), _ptr(delta),
+            _ptr(best)))
+        return ll, delta, best
+
     def optimize_branch_lengths(self, parent_ids, start_branch_lengths, params=None,
                                 rescaling=False, max_iterations=100, check_interval=4,
                                 pack_active=True, tolerance=1e-6, min_length=1e-8,
@@ -431,6 +464,17 @@ class Engine:
     def reserve_hessian(self, tree_count):
         """mi_engine_reserve_hessian: workspace of a Hessian call (graph capture)."""
         self._check(self._lib.mi_engine_reserve_hessian(self._h, int(tree_count)))
+
+    def nni_scan_device(self, stream, T, parent_ids, branch_lengths, params, out_delta,
+                        out_ll=None, out_best=None, rescaling=False):
+        """mi_engine_nni_scan_unrooted_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_nni_scan_unrooted_device(
+            self._h, stream, T, parent_ids, branch_lengths, params, int(rescaling), out_ll,
+            out_delta, out_best))
+
+    def reserve_nni_scan(self, tree_count):
+        """mi_engine_reserve_nni_scan: workspace of an NNI scan (graph capture)."""
+        self._check(self._lib.mi_engine_reserve_nni_scan(self._h, int(tree_count)))
 
     def optimize_branch_lengths_device(self, stream, T, parent_ids, start_branch_lengths, params,
                                        out_branch_lengths, out_ll, out_status, out_branch=None,
