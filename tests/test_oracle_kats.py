@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import tree_utils as TU
 
 K = O.load_kats()
 
@@ -16,7 +17,7 @@ def _state_loops(request):
     the 20-state parity tests (tests/test_aa_gpu.py) rely on, which has no reference values
     of its own (the reference is DNA-only)."""
     O.set_generic_states(request.param == "generic_s")
-    yield
+    yield request.param == "generic_s"
     O.set_generic_states(False)
 
 
@@ -304,3 +305,86 @@ def test_reversible_model_at_four_states_is_gtr():
     # leaves perturbed by 1e-6 -- fat_beagle.cpp:433-436; a model
     # without free parameters has no such pass)
     assert np.max(np.abs(a["site_model"] - b["site_model"]) / np.abs(a["site_model"])) < 1e-6
+
+
+def test_clocklike_rooted_tree_seeded_draw_is_unchanged():
+    """clocklike_rooted_tree(n, rng) without its later arguments (topology, isochronous) draws
+    what it drew before they existed: the digest was recorded from the version without them.
+    Seeded inputs all over the suite, and the input hashes of golden/call_paths.json, rest on it."""
+    import hashlib
+    rng = np.random.default_rng(20261017)
+    m = hashlib.sha256()
+    for n in (5, 12, 33):
+        pid, bl, dates = TU.clocklike_rooted_tree(n, rng)
+        for a in (pid.astype(np.int32), bl, dates):
+            m.update(np.ascontiguousarray(a).tobytes())
+    m.update(rng.random(4).tobytes())  # the generator is left where it used to be left
+    assert m.hexdigest() == "f5c76f15e7bd1668f526aaaa4cd7e3663f025a9f31c3572ca5048bd079a7172d"
+
+
+def _fd_tree(kind, n, rng):
+    if kind == "random":
+        return TU.clocklike_rooted_tree(n, rng)
+    if kind == "random-isochronous":
+        return TU.clocklike_rooted_tree(n, rng, isochronous=True)
+    if kind == "ladder-isochronous":
+        return TU.clocklike_rooted_tree(n, rng, TU.ladder_topology(n, rooted=True), True)
+    assert kind == "balanced"
+    return TU.clocklike_rooted_tree(n, rng, TU.balanced_topology(n, rooted=True))
+
+
+@pytest.mark.parametrize("kind,n", [("random", 6), ("random", 40), ("random-isochronous", 12),
+                                    ("ladder-isochronous", 20), ("balanced", 16)])
+def test_oracle_ratio_gradient_matches_finite_differences(kind, n, _state_loops):
+    """The value every rooted GPU test is compared with: the oracle's height-ratio / root-height
+    gradient (rooted_gradient_transforms.cpp:17-170), otherwise pinned by one known answer
+    (fluA).  It is the gradient of logL + log|J| in the ratio coordinates (the last one is the
+    root height): central differences of the oracle's own rooted log-likelihood with the
+    Jacobian, every coordinate moved by 1e-5 and heights and branch lengths rebuilt from the
+    ratios in plain numpy.  Long-double build of the oracle, so that the rounding of the
+    differences (two ~1e3-sized numbers over 2e-5) stays under the truncation error.
+    Bound 1e-8 of max |g|: ten times the 9.9e-10 measured with this build on five trees of these
+    kinds when the test was specified (the seeded trees here: 1.3e-10 ... 2.3e-9, printed); a
+    wrong term of the transform shows at order 1."""
+    rng = np.random.default_rng(1000 + n)
+    P, N, eps = 25, 2 * n - 1, 1e-5
+    tips, w = TU.random_alignment(n, P, rng)
+    pid, bl, dates = _fd_tree(kind, n, rng)
+    rates = rng.uniform(0.01, 0.1, size=(1, N - 1))
+    spec = O.make_spec(n, P, "JC69", "weibull+4", "strict")
+    pr = _params(spec, 1, **{"Weibull shape": rng.uniform(0.3, 2)})
+    O.select("ld")
+    try:
+        O.set_generic_states(_state_loops)
+        h, bd, ra = O.time_tree_init(n, pid, bl, dates)
+        if "isochronous" in kind:
+            assert np.all(bd == 0)
+        assert np.allclose(TU.heights_from_ratios(n, pid, bd, ra), h, rtol=1e-13, atol=1e-13)
+        assert np.allclose(TU.branch_lengths_from_heights(pid, h), bl, rtol=1e-13, atol=1e-13)
+        out = O.rooted_gradients(spec, tips, w, pid[None], bl[None], pr, rates, [N - 1], h[None],
+                                 bd[None], ra[None])
+        g = out["ratios_root_height"][0]
+        assert np.all(np.isfinite(g)) and np.max(np.abs(g)) > 0
+        # the log-likelihood next to the gradient is the one WITHOUT the Jacobian (of the
+        # rate-scaled branch lengths: the call without the Jacobian takes them as they come)
+        plain = O.rooted_log_likelihoods(spec, tips, w, pid[None], bl[None] * np.append(rates[0], 0.),
+                                         pr, rates, h[None], bd[None], False)
+        assert abs(out["log_likelihood"][0] - plain[0]) <= 1e-12 * abs(plain[0])
+
+        def f(ratios):
+            hh = TU.heights_from_ratios(n, pid, bd, ratios)
+            bb = TU.branch_lengths_from_heights(pid, hh)
+            return O.rooted_log_likelihoods(spec, tips, w, pid[None], bb[None], pr, rates, hh[None],
+                                            bd[None], True)[0]
+        fd = np.zeros(n - 1)
+        for i in range(n - 1):
+            rp, rm = ra.copy(), ra.copy()
+            rp[i] += eps
+            rm[i] -= eps
+            fd[i] = (f(rp) - f(rm)) / (2 * eps)
+        err = np.max(np.abs(fd - g)) / np.max(np.abs(g))
+        print(f"ratio gradient vs finite differences, {kind} n={n}: {err:.3g} of max |g|")
+        assert err <= 1e-8, (kind, n, err, fd, g)
+    finally:
+        O.set_generic_states(False)
+        O.select("f64")

@@ -43,9 +43,14 @@ def random_topology(n, rng, rooted=False):
 def ladder_topology(n, rooted=False):
     t = 0
     if rooted:
-        for i in range(1, n):
-            t = (i, t)
-        return _polish(t, n)
+        # (n-1, (n-2, ... (1, 0))) as _polish numbers it, written out: the nesting is too deep
+        # for its recursion from about 330 taxa on.  Leaves 0 and 1 hang under node n, leaf
+        # i >= 2 and internal node n + i - 2 under node n + i - 1.
+        pid = np.empty(2 * n - 2, dtype=np.int32)
+        pid[:2] = n
+        pid[2:n] = n + np.arange(1, n - 1)
+        pid[n:] = n + np.arange(1, n - 1)
+        return pid
     for i in range(1, n - 2):
         t = (i, t)
     return _polish((t, n - 2, n - 1), n)
@@ -89,12 +94,22 @@ def random_gtr_params(T, rng):
     return rates, freqs
 
 
-def clocklike_rooted_tree(n, rng):
-    """Rooted topology + tip dates + branch lengths consistent with node heights."""
-    pid = random_topology(n, rng, rooted=True)
+def clocklike_rooted_tree(n, rng, topology=None, isochronous=False):
+    """Rooted topology + tip dates + branch lengths consistent with node heights.
+    topology: a rooted parent-id vector (ladder_topology(n, rooted=True), ...) instead of a
+    random one.  isochronous: every tip date 0 -- all bounds are then equal and every epoch
+    term of the ratio transform takes its bound[v] == bound[c] branch.  With both left out the
+    draws from rng are what they have always been (the seeded inputs of other tests, and the
+    input hashes of golden/call_paths.json, rest on that)."""
+    pid = random_topology(n, rng, rooted=True) if topology is None else \
+        np.asarray(topology, dtype=np.int32)
     N = 2 * n - 1
-    dates = np.round(rng.uniform(0, 3, size=n), 3)
-    dates[rng.integers(n)] = 0.0
+    assert pid.shape == (N - 1,)
+    if isochronous:
+        dates = np.zeros(n)
+    else:
+        dates = np.round(rng.uniform(0, 3, size=n), 3)
+        dates[rng.integers(n)] = 0.0
     h = np.zeros(N)
     h[:n] = dates
     kids = {}
@@ -106,3 +121,37 @@ def clocklike_rooted_tree(n, rng):
     for v, p in enumerate(pid):
         bl[v] = h[p] - h[v]
     return pid, bl, dates
+
+
+def heights_from_ratios(n, parent_ids, bounds, ratios):
+    """Node heights of a time tree from its height ratios (ratios[n-2] is the root height),
+    top-down: a parent has a larger id than its children, so descending ids do it."""
+    N = 2 * n - 1
+    h = np.zeros(N)
+    h[:n] = bounds[:n]
+    h[N - 1] = ratios[n - 2]
+    for v in range(N - 2, n - 1, -1):
+        h[v] = bounds[v] + ratios[v - n] * (h[parent_ids[v]] - bounds[v])
+    return h
+
+
+def branch_lengths_from_heights(parent_ids, h):
+    """bl[v] = h[parent[v]] - h[v]; the root's entry is 0."""
+    bl = np.zeros(len(h))
+    bl[:-1] = h[np.asarray(parent_ids)] - h[:-1]
+    return bl
+
+
+def rooted_batch(n, T, rng, topologies=None, isochronous=None):
+    """T clock-like rooted trees as the rooted calls take them: the stacked
+    parent ids, branch lengths, node heights, node bounds, height ratios.
+    topologies / isochronous: one entry per tree (None: random topology / random dates)."""
+    import oracle_lib as O
+    cols = [[] for _ in range(5)]
+    for t in range(T):
+        pid, bl, dates = clocklike_rooted_tree(
+            n, rng, None if topologies is None else topologies[t],
+            bool(isochronous is not None and isochronous[t]))
+        for col, x in zip(cols, (pid, bl) + tuple(O.time_tree_init(n, pid, bl, dates))):
+            col.append(x)
+    return tuple(np.stack(c) for c in cols)
