@@ -214,6 +214,36 @@ def test_arena_store_36_taxa_1812_patterns(monkeypatch):
     _check(eng, res, _evaluators(spec, tips, w, pids, start, pr), pids, start, pr)
 
 
+def test_gradient_and_hessian_at_the_optimum_match_the_analytic_reference():
+    """res.gradient and res.hessian per branch at the lengths where the optimiser stops, branches
+    ON the lower bound among them, against tests/dense_ref.py (long double, no pre-order pass)
+    under the bounds of tests/test_branch_hessian_edges_gpu.py.  (_check compares them with the
+    same engine's Hessian call only.)"""
+    import dense_ref as D
+    tips, w, pids, start, spec, pr = _evolved_case(8, 49, 2, "weibull+4", 41)
+    eng = _engine("JC69", "weibull+4", tips, w)
+    res = eng.optimize_branch_lengths(pids, start, pr)
+    _path(eng, WALK, "lds")
+    _check(eng, res, _evaluators(spec, tips, w, pids, start, pr), pids, start, pr)
+    Q, pi = D.gtr_q(np.ones(6), np.full(4, 0.25))
+    for t in range(len(pids)):
+        x = res.branch_lengths[t]
+        assert np.sum((x[:-1] == LO) | (x[:-1] == HI)) >= 1, x
+        m = O.model_set(spec, pr[t])
+        ref = D.branch_derivatives(pids[t], x, Q, pi, m.cat_rates[:4], m.cat_weights[:4],
+                                   D.tip_vectors(tips), w)
+        tol = D.tolerances(ref, 1e-10)
+        for got in (res.log_likelihood[t], res.gradient[t], res.hessian[t]):
+            assert np.all(np.isfinite(np.asarray(got))), got
+        rll = abs(res.log_likelihood[t] - ref.log_likelihood) / (1e-10 * abs(ref.log_likelihood))
+        rg = np.max(np.abs(res.gradient[t, :-2] - ref.g[:-2]) / tol.g[:-2])
+        rh = np.max(np.abs(res.hessian[t, :-2] - ref.H[:-2]) / tol.H[:-2])
+        print(f"ratio optimum tree {t}: logL={float(rll):.3e} g={float(rg):.3e} H={float(rh):.3e} "
+              f"on a bound: {np.flatnonzero((x[:-1] == LO) | (x[:-1] == HI))}")
+        assert np.all(np.array([rll, rg, rh], dtype=D.LD) <= 1.0)  # (a NaN is not)
+        assert np.all(res.gradient[t, -2:] == 0) and np.all(res.hessian[t, -2:] == 0)
+
+
 # ---- 6. the upper bound ----
 
 def test_small_max_length_ends_on_the_upper_bound():
