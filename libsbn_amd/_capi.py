@@ -27,6 +27,12 @@ class BranchOptOptions(C.Structure):
                 ("max_length", C.c_double), ("reserved", C.c_int32 * 4)]
 
 
+class NniSearchOptions(C.Structure):
+    """mi_nni_search_options (include/mi_phylo.h)."""
+    _fields_ = [("max_moves", C.c_int32), ("pack_active", C.c_int32), ("min_gain", C.c_double),
+                ("reserved", C.c_int32 * 4), ("branch_opt", BranchOptOptions)]
+
+
 # Every symbol include/mi_phylo.h declares: (restype, argtypes)
 _V = C.c_void_p
 SYMBOLS = {
@@ -86,6 +92,14 @@ SYMBOLS = {
     "mi_engine_optimize_branch_lengths_unrooted_device":
         (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V]),
     "mi_engine_reserve_branch_opt": (C.c_int32, [_V, C.c_int32]),
+    "mi_engine_nni_apply_unrooted": (C.c_int32, [_V, C.c_int32, _V, _V, _V, _V, _V]),
+    "mi_engine_nni_apply_unrooted_device": (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, _V, _V]),
+    "mi_engine_nni_search_unrooted":
+        (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_nni_search_unrooted_device":
+        (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V,
+                     _V]),
+    "mi_engine_reserve_nni_search": (C.c_int32, [_V, C.c_int32]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),
     "mi_engine_profile_begin": (C.c_int32, [_V, C.c_int32]),
     "mi_engine_profile_collect": (C.c_int32, [_V, F64P, C.c_int32, I32P]),

@@ -10,22 +10,6 @@
 namespace {
 
 constexpr int kBranchOptMaxIterations = 1000;
-const mi_branch_opt_options kBranchOptDefaults = {100, 4, 1, 1e-6, 1e-8, 10.0, {0, 0, 0, 0}};
-
-struct BranchOptCall {
-  int T = 0;
-  bool rescaling = false;
-  const int32_t* parent_ids = nullptr;
-  const double* start = nullptr;
-  const double* params = nullptr;
-  const mi_branch_opt_options* options = nullptr;
-  double* out_bl = nullptr;
-  double* out_ll = nullptr;
-  double* out_g = nullptr;      // may be null
-  double* out_h = nullptr;      // may be null
-  int32_t* out_iters = nullptr;  // may be null
-  int32_t* out_status = nullptr;
-};
 
 // the pieces of e->opt_ws for a batch of T trees, 256-byte aligned
 struct BranchOptWorkspace {
@@ -61,6 +45,10 @@ struct BranchOptWorkspace {
     bytes = off;
   }
 };
+
+}  // namespace
+
+const mi_branch_opt_options kBranchOptDefaults = {100, 4, 1, 1e-6, 1e-8, 10.0, {0, 0, 0, 0}};
 
 int reserve_branch_opt(mi_engine* e, int T) {
   if (reserve_hessian_calls(e, T)) return 1;
@@ -126,7 +114,7 @@ int run_branch_opt_device(mi_engine* e, hipStream_t s, const BranchOptCall& c) {
   launch_branch_opt_init(st, c.start, s);
   DeviceCall d;
   d.T = T;
-  d.route_T = T;
+  d.route_T = c.route_T ? c.route_T : T;
   d.rescaling = c.rescaling;
   d.parent_ids = c.parent_ids;
   d.bl = w.trial;
@@ -192,6 +180,8 @@ int run_branch_opt_device(mi_engine* e, hipStream_t s, const BranchOptCall& c) {
   HIP_TRY(hipGetLastError());
   return 0;
 }
+
+namespace {
 
 // The host-pointer form of the branch-length optimisation on one engine: inputs up in one
 // copy, the loop (which synchronises at its check points), outputs back in one copy and the

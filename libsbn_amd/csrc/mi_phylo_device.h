@@ -88,6 +88,7 @@ enum StatusCode : int32_t {
   kBadRateCount = 6,
   kTooManySlots = 7,
   kFusedTimeout = 8,
+  kBadNniMove = 9,
 };
 
 }  // namespace miphylo

@@ -436,7 +436,7 @@ void mi_engine_destroy(mi_engine* e) {
         &e->ll_sum, &e->g_sum, &e->status, &e->ready, &e->weibull_x, &e->aa_model, &e->aa_matP, &e->aa_matPT,
         &e->aa_tipP, &e->aa_tipPQ, &e->aa_exp_cum, &e->aa_exp_loc, &e->aa_root_val,
         &e->aa_root_exp, &e->aa_root_scale, &e->red_ll, &e->red_g, &e->red_site, &e->red_sort,
-        &e->in_pack, &e->out_pack, &e->opt_ws})
+        &e->in_pack, &e->out_pack, &e->opt_ws, &e->nni_apply_ws, &e->nni_search_ws})
     b->release();
   if (e->opt_word) (void)hipHostFree(e->opt_word);
   e->pinned.release();

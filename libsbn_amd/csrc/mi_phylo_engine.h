@@ -6,6 +6,7 @@
 //                             the argument-block builders, the 4-state, Hessian and NNI-scan call sequences
 //   mi_phylo_branch_opt.cpp   branch-length optimisation
 //   mi_phylo_nni.cpp          mi_nni_neighbour, the scan's best move on the host (no device code)
+//   mi_phylo_nni_search.cpp   NNI moves on the device, the NNI hill-climbing search
 //   mi_phylo_host_calls.cpp   host-pointer entry points, sharded handles
 //   mi_phylo_engine_aa.cpp    20-state call sequence
 #pragma once
@@ -127,6 +128,7 @@ inline const char* status_message(int code) {
     case kFusedTimeout:
       return "internal error: the walk waves of the one-launch call waited in vain for their "
              "tree's set-up waves (MI_PHYLO_FUSED_SETUP=0 selects the four-launch sequence)";
+    case kBadNniMove: return "NNI move is neither -1 nor the code 2 v + i of an inner edge";
     default: return "unknown device status";
   }
 }
@@ -176,6 +178,9 @@ struct mi_engine {
   // branch-length optimisation (mi_engine_optimize_branch_lengths_unrooted*)
   Buffer opt_ws;                // trial points, kept derivatives, packed inputs, maps, counters
   int32_t* opt_word = nullptr;  // pinned: the active count read at a check point
+  // NNI moves and the NNI search (mi_engine_nni_{apply,search}_unrooted*)
+  Buffer nni_apply_ws;   // the apply kernel's working arrays of trees too large for LDS
+  Buffer nni_search_ws;  // the pair of tree buffers, a round's results, packed inputs, maps, counters
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)
   std::vector<hipEvent_t> prof_events;  // kProfEvents per call: [begin, end, mark 0..4]
@@ -294,6 +299,28 @@ int reserve_nni_calls(mi_engine* e, int T);  // of either rescaling setting (mi_
 int run_nni_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
 // the scan's best move from a tree's delta [N][2] (what the finalize kernel does; pattern shards)
 int32_t nni_best_move(int n, const double* delta);
+
+// ---- mi_phylo_branch_opt.cpp ----
+struct BranchOptCall {
+  int T = 0;
+  bool rescaling = false;
+  const int32_t* parent_ids = nullptr;
+  const double* start = nullptr;
+  const double* params = nullptr;
+  const mi_branch_opt_options* options = nullptr;
+  double* out_bl = nullptr;
+  double* out_ll = nullptr;
+  double* out_g = nullptr;      // may be null
+  double* out_h = nullptr;      // may be null
+  int32_t* out_iters = nullptr;  // may be null
+  int32_t* out_status = nullptr;
+  // as one round of the NNI search: the batch size the Hessian passes' route is chosen for (0: T)
+  int route_T = 0;
+};
+extern const mi_branch_opt_options kBranchOptDefaults;
+int reserve_branch_opt(mi_engine* e, int T);
+int check_branch_opt_options(const mi_branch_opt_options& o);
+int run_branch_opt_device(mi_engine* e, hipStream_t s, const BranchOptCall& c);
 
 // ---- mi_phylo_engine.cpp ----
 extern const char kShardedDeviceCall[], kHessian4State[], kNni4State[];

@@ -264,6 +264,55 @@ void launch_branch_opt_init(const BranchOptArgs& a, const double* start, hipStre
 void launch_branch_opt_step(const BranchOptArgs& a, hipStream_t s);
 void launch_branch_opt_pack(const BranchOptPackArgs& a, int old_count, const int32_t* map_old,
                             const int32_t* status, hipStream_t s);
+// The NNI hill-climbing search (kernels_nni_search.hip): taking NNI moves on the
+// device in the reference's numbering, and the per-tree step between two rounds of the search.
+// A wave per tree; the working arrays of a tree (six of 2n-2 words and eight more) are in LDS
+// up to kNniApplyLdsNodes nodes, else in `ws`.
+constexpr int kNniApplyLdsNodes = 512, kNniApplyArrays = 6, kNniApplyExtra = 8;
+inline __host__ __device__ size_t nni_apply_ws_words(int n) {  // per tree; 0: the arrays are in LDS
+  const size_t R = 2 * (size_t)n - 2;
+  return R > kNniApplyLdsNodes ? kNniApplyArrays * R + kNniApplyExtra : 0;
+}
+struct NniApplyArgs {
+  int n, T;
+  const int32_t* parent_ids;  // [T][2n-3]
+  const double* bl;           // [T][2n-2]
+  const int32_t* moves;       // [T] 2 v + i, or -1: copy
+  int32_t* ws;                // [T][nni_apply_ws_words(n)]
+  int32_t* status;            // the engine's status word
+  int32_t* out_parent_ids;    // [T][2n-3]  (no output may overlap an input)
+  double* out_bl;             // [T][2n-2]
+};
+void launch_nni_apply(const NniApplyArgs& a, hipStream_t s);
+constexpr int kNniSearchActive = -1;  // internal; the rest are mi_phylo.h's MI_NNI_SEARCH_*
+struct NniSearchStepArgs {
+  int n, count, round, max_moves;  // count: trees of the packed set
+  double min_gain;
+  const int32_t* map;  // [count] packed position -> tree, or nullptr
+  // this round's results, by packed position
+  const double *opt_bl, *opt_ll;  // [count][2n-2], [count]
+  const int32_t* opt_status;      // [count]
+  const double* delta;            // [count][2n-1][2]
+  const int32_t* best;            // [count]
+  // the trees by tree index: this round's and the other half of the pair
+  const int32_t* cur_pid;  // [T][2n-3]
+  double* cur_bl;          // [T][2n-2]
+  int32_t* next_pid;
+  double* next_bl;
+  // the packed inputs of the next round (map != nullptr)
+  int32_t* pk_pid;  // [count][2n-3]
+  double* pk_bl;    // [count][2n-2]
+  int32_t* ws;      // [count][nni_apply_ws_words(n)]
+  int32_t* engine_status;
+  // the call's outputs, by tree
+  int32_t* out_pid;
+  double *out_bl, *out_ll, *out_best_delta;  // (out_best_delta may be nullptr)
+  int32_t *move_count, *move_log;            // [T], [T][max_moves] or nullptr
+  double* move_gain;                         // [T][max_moves] or nullptr
+  int32_t *status, *out_opt_status;          // [T] kNniSearchActive while searching; [T] or nullptr
+  int32_t* active;                           // this round's word: trees that moved
+};
+void launch_nni_search_step(const NniSearchStepArgs& a, hipStream_t s);
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
 // the first, gradient_mfma_kernel, was retired in round 6): all categories of a group of four
 // per instruction; they also write the log-likelihood partial sums, so no separate logL pass is

@@ -1,0 +1,497 @@
+// NNI moves on the device and the NNI hill-climbing search (mi_engine_nni_apply_unrooted*,
+// mi_engine_nni_search_unrooted*).  The search is a host-driven loop of rounds:
+// the branch-length optimisation (run_branch_opt_device) and the neighbourhood scan
+// (run_nni_device) on the packed set of trees that are still searching, then one step kernel
+// that moves or stops every tree.  Once per round the host reads one word: the trees that
+// moved.  It stops at 0, and packs the searching trees to the front when fewer than half of the
+// packed set are left.  Nothing else is downloaded, uploaded or allocated inside the loop.
+#include <cmath>
+
+#include "mi_phylo_engine.h"
+
+namespace {
+
+constexpr int kNniSearchMaxMoves = 10000;
+const char kSearch4State[] = "the NNI search is 4-state only";
+const char kSearchPatternShards[] =
+    "pattern-sharded engines do not run the NNI search (every optimiser iteration would need a sum "
+    "across the shards): use MI_SHARD_TREES or a single engine";
+
+// ---- taking moves ----
+
+int reserve_nni_apply(mi_engine* e, int T) {
+  if (e->nni_apply_ws.ensure(std::max<size_t>(sizeof(int32_t) * (size_t)T * nni_apply_ws_words(e->n), 256))) return 1;
+  return e->status.ensure(sizeof(int32_t) * kStatusWords);
+}
+
+int run_nni_apply_device(mi_engine* e, hipStream_t s, int T, const int32_t* parent_ids, const double* bl,
+                         const int32_t* moves, int32_t* out_parent_ids, double* out_bl) {
+  HIP_TRY(hipSetDevice(e->spec.device));
+  if (T <= 0) return fail("tree_count must be positive");
+  if (!parent_ids || !bl || !moves) return fail("null tree / move arrays");
+  if (!out_parent_ids || !out_bl) return fail("null output pointer");
+  if (reserve_nni_apply(e, T)) return 1;
+  NniApplyArgs a{};
+  a.n = e->n;
+  a.T = T;
+  a.parent_ids = parent_ids;
+  a.bl = bl;
+  a.moves = moves;
+  a.ws = e->nni_apply_ws.as<int32_t>();
+  a.status = e->status.as<int32_t>();
+  a.out_parent_ids = out_parent_ids;
+  a.out_bl = out_bl;
+  launch_nni_apply(a, s);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- the search ----
+
+struct NniSearchCall {
+  int T = 0;
+  bool rescaling = false;
+  const int32_t* parent_ids = nullptr;
+  const double* start = nullptr;
+  const double* params = nullptr;
+  const mi_nni_search_options* options = nullptr;
+  int32_t* out_pid = nullptr;
+  double* out_bl = nullptr;
+  double* out_ll = nullptr;
+  double* out_best_delta = nullptr;  // may be null
+  int32_t* out_move_count = nullptr;
+  int32_t* out_move_log = nullptr;  // may be null
+  double* out_move_gain = nullptr;  // may be null
+  int32_t* out_status = nullptr;
+  int32_t* out_opt_status = nullptr;  // may be null
+};
+
+mi_nni_search_options search_defaults() {
+  mi_nni_search_options o{};
+  o.max_moves = 100;
+  o.pack_active = 1;
+  o.min_gain = 1e-3;
+  o.branch_opt = kBranchOptDefaults;
+  return o;
+}
+
+bool all_zero(const mi_branch_opt_options& b) {
+  return b.max_iterations == 0 && b.check_interval == 0 && b.pack_active == 0 && b.tolerance == 0.0 &&
+         b.min_length == 0.0 && b.max_length == 0.0;
+}
+
+// the options a call runs with (branch_opt of zeros: the optimiser's defaults), checked
+int search_options(const mi_nni_search_options* given, mi_nni_search_options* out) {
+  mi_nni_search_options o = given ? *given : search_defaults();
+  if (all_zero(o.branch_opt)) o.branch_opt = kBranchOptDefaults;
+  if (o.max_moves < 0 || o.max_moves > kNniSearchMaxMoves)
+    return fail("NNI search: max_moves must be in 0.." + std::to_string(kNniSearchMaxMoves));
+  if (!(o.min_gain >= 0.0)) return fail("NNI search: min_gain must be >= 0");
+  if (check_branch_opt_options(o.branch_opt)) return 1;
+  *out = o;
+  return 0;
+}
+
+// the pieces of e->nni_search_ws for a batch of T trees, 256-byte aligned
+struct NniSearchWorkspace {
+  int32_t *pid[2], *pk_pid, *opt_status, *best, *map[2], *active, *apply_ws;
+  double *bl[2], *pk_bl, *pk_params, *opt_bl, *opt_ll, *delta;
+  size_t bytes;
+  NniSearchWorkspace(const mi_engine* e, int T, char* base) {
+    const size_t N = e->N, t = (size_t)T;
+    size_t off = 0;
+    auto take = [&](size_t b) {
+      char* p = base + off;
+      off += (b + 255) & ~(size_t)255;
+      return p;
+    };
+    auto f64 = [&](size_t count) { return reinterpret_cast<double*>(take(sizeof(double) * count)); };
+    auto i32 = [&](size_t count) { return reinterpret_cast<int32_t*>(take(sizeof(int32_t) * count)); };
+    for (int h = 0; h < 2; h++) {
+      pid[h] = i32(t * (N - 2));
+      bl[h] = f64(t * (N - 1));
+    }
+    pk_pid = i32(t * (N - 2));
+    pk_bl = f64(t * (N - 1));
+    pk_params = f64(t * std::max(e->param_count, 1));
+    opt_bl = f64(t * (N - 1));
+    opt_ll = f64(t);
+    opt_status = i32(t);
+    delta = f64(t * N * 2);
+    best = i32(t);
+    map[0] = i32(t);
+    map[1] = i32(t);
+    active = i32(kNniSearchMaxMoves + 1);
+    apply_ws = i32(std::max<size_t>(t * nni_apply_ws_words(e->n), 1));
+    bytes = off;
+  }
+};
+
+int reserve_nni_search(mi_engine* e, int T) {
+  if (reserve_branch_opt(e, T)) return 1;
+  if (reserve_nni_calls(e, T)) return 1;
+  return e->nni_search_ws.ensure(NniSearchWorkspace(e, T, nullptr).bytes);
+}
+
+int run_nni_search_device(mi_engine* e, hipStream_t s, const NniSearchCall& c) {
+  HIP_TRY(hipSetDevice(e->spec.device));
+  if (e->s == kAa) return fail(kSearch4State);
+  if (c.T <= 0) return fail("tree_count must be positive");
+  if (!c.parent_ids || !c.start) return fail("null tree arrays");
+  if (!c.out_pid || !c.out_bl || !c.out_ll || !c.out_move_count || !c.out_status) return fail("null output pointer");
+  if (e->param_count > 0 && !c.params) return fail("null parameter matrix");
+  mi_nni_search_options o;
+  if (search_options(c.options, &o)) return 1;
+  const int T = c.T, n = e->n, N = e->N;
+  if (reserve_nni_search(e, T)) return 1;
+  const NniSearchWorkspace w(e, T, e->nni_search_ws.as<char>());
+  const bool pack = o.pack_active != 0;
+  const size_t np = (size_t)N - 2, nl = (size_t)N - 1;
+  HIP_TRY(hipMemcpyAsync(w.pid[0], c.parent_ids, sizeof(int32_t) * T * np, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(w.bl[0], c.start, sizeof(double) * T * nl, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemsetAsync(w.active, 0, sizeof(int32_t) * ((size_t)o.max_moves + 1), s));
+  // (the maps are written before they are read; zeroed so that no index is ever out of range)
+  HIP_TRY(hipMemsetAsync(w.map[0], 0, sizeof(int32_t) * (size_t)T, s));
+  HIP_TRY(hipMemsetAsync(w.map[1], 0, sizeof(int32_t) * (size_t)T, s));
+  HIP_TRY(hipMemsetAsync(c.out_status, 0xff, sizeof(int32_t) * (size_t)T, s));  // kNniSearchActive
+  HIP_TRY(hipMemsetAsync(c.out_move_count, 0, sizeof(int32_t) * (size_t)T, s));
+  if (c.out_move_log && o.max_moves) HIP_TRY(hipMemsetAsync(c.out_move_log, 0xff, sizeof(int32_t) * (size_t)T * o.max_moves, s));
+  if (c.out_move_gain && o.max_moves) HIP_TRY(hipMemsetAsync(c.out_move_gain, 0, sizeof(double) * (size_t)T * o.max_moves, s));
+
+  NniSearchStepArgs st{};
+  st.n = n;
+  st.max_moves = o.max_moves;
+  st.min_gain = o.min_gain;
+  st.map = nullptr;
+  st.opt_bl = w.opt_bl;
+  st.opt_ll = w.opt_ll;
+  st.opt_status = w.opt_status;
+  st.delta = w.delta;
+  st.best = w.best;
+  st.pk_pid = w.pk_pid;
+  st.pk_bl = w.pk_bl;
+  st.ws = w.apply_ws;
+  st.engine_status = e->status.as<int32_t>();
+  st.out_pid = c.out_pid;
+  st.out_bl = c.out_bl;
+  st.out_ll = c.out_ll;
+  st.out_best_delta = c.out_best_delta;
+  st.move_count = c.out_move_count;
+  st.move_log = c.out_move_log;
+  st.move_gain = c.out_move_gain;
+  st.status = c.out_status;
+  st.out_opt_status = c.out_opt_status;
+
+  int count = T, half = 0, which = 0, rounds = 0;
+  int64_t evals = 0, moves = 0;
+  int launches = 0;
+  std::string hess_path, batches;  // "<trees>x<rounds>,..."
+  const char* hess_kernel = "";
+  int run_trees = 0, run_len = 0;
+  auto note = [&](int trees) {
+    if (trees == run_trees) {
+      run_len++;
+      return;
+    }
+    if (run_len) batches += (batches.empty() ? "" : ",") + std::to_string(run_trees) + "x" + std::to_string(run_len);
+    run_trees = trees;
+    run_len = trees ? 1 : 0;
+  };
+  for (int r = 0; r <= o.max_moves; r++) {  // (a searching tree has moved once per round)
+    const bool packed = st.map != nullptr;
+    const int32_t* pid_in = packed ? w.pk_pid : w.pid[half];
+    const double* params_in = packed && e->param_count > 0 ? w.pk_params : c.params;
+    BranchOptCall b;
+    b.T = count;
+    b.route_T = T;
+    b.rescaling = c.rescaling;
+    b.parent_ids = pid_in;
+    b.start = packed ? w.pk_bl : w.bl[half];
+    b.params = params_in;
+    b.options = &o.branch_opt;
+    b.out_bl = w.opt_bl;
+    b.out_ll = w.opt_ll;
+    b.out_status = w.opt_status;
+    if (run_branch_opt_device(e, s, b)) return 1;
+    evals += e->last_evals;
+    launches += e->last_walk_launches;
+    hess_path = e->last_path.substr(0, e->last_path.find(" opt iters="));
+    hess_kernel = e->dominant;
+    DeviceCall d;
+    d.T = count;
+    d.route_T = T;
+    d.rescaling = c.rescaling;
+    d.parent_ids = pid_in;
+    d.bl = w.opt_bl;
+    d.params = params_in;
+    d.out_nni = w.delta;
+    d.out_best = w.best;
+    if (run_nni_device(e, s, d)) return 1;
+    evals += count;
+    launches += e->last_walk_launches;
+    st.count = count;
+    st.round = r;
+    st.cur_pid = w.pid[half];
+    st.cur_bl = w.bl[half];
+    st.next_pid = w.pid[half ^ 1];
+    st.next_bl = w.bl[half ^ 1];
+    st.active = w.active + r;
+    launch_nni_search_step(st, s);
+    rounds++;
+    note(count);
+    HIP_TRY(hipMemcpyAsync(e->opt_word, w.active + r, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int active = *e->opt_word;
+    if (active <= 0) break;
+    moves += active;
+    if (pack && 2 * active < count) {
+      BranchOptPackArgs pa{};
+      pa.N = N;
+      pa.count = active;
+      pa.param_count = e->param_count;
+      pa.map = w.map[which];
+      pa.parent_ids = w.pid[half ^ 1];
+      pa.params = c.params;
+      pa.trial_full = w.bl[half ^ 1];
+      pa.pk_parent = w.pk_pid;
+      pa.pk_trial = w.pk_bl;
+      pa.pk_params = w.pk_params;
+      launch_branch_opt_pack(pa, count, st.map, c.out_status, s);
+      st.map = pa.map;
+      which ^= 1;
+      count = active;
+    }
+    half ^= 1;
+  }
+  note(0);
+  e->dominant = hess_kernel;
+  e->last_path = hess_path + " nni-search rounds=" + std::to_string(rounds) + " moves=" + std::to_string(moves) +
+                 " batches=" + batches + (pack ? "" : " pack=off");
+  e->last_evals = evals;
+  e->last_grad_evals = evals;
+  e->last_walk_launches = launches;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The host-pointer forms on one engine: inputs up in one copy, the work, outputs back in one
+// copy and the call's one error check.
+int begin_host(mi_engine* e) {
+  HIP_TRY(hipSetDevice(e->spec.device));
+  e->fused_timed_out = false;
+  e->pinned.reset();
+  if (e->status.ensure(sizeof(int32_t) * kStatusWords)) return 1;
+  HIP_TRY(hipMemsetAsync(e->status.ptr, 0, sizeof(int32_t) * kStatusWords, e->stream));
+  return 0;
+}
+int finish_host(mi_engine* e) {
+  int rc = check_status(e, e->stream);
+  e->fused_timed_out = false;
+  if (rc == 0) e->pinned.flush();
+  e->pinned.reset();
+  return rc;
+}
+
+int run_nni_apply_host(mi_engine* e, int T, const int32_t* parent_ids, const double* bl, const int32_t* moves,
+                       int32_t* out_pid, double* out_bl) {
+  const int n = e->n;
+  if (T <= 0) return fail("tree_count must be positive");
+  if (!parent_ids || !bl || !moves) return fail("null tree / move arrays");
+  if (!out_pid || !out_bl) return fail("null output pointer");
+  if (begin_host(e)) return 1;
+  const void *d_parent, *d_bl, *d_moves;
+  if (upload_pack(e, {{parent_ids, sizeof(int32_t) * (size_t)T * (2 * n - 3), &d_parent},
+                      {bl, sizeof(double) * (size_t)T * (2 * n - 2), &d_bl},
+                      {moves, sizeof(int32_t) * (size_t)T, &d_moves}}))
+    return 1;
+  double *o_pid, *o_bl;  // (the first: int32)
+  const std::initializer_list<OutPiece> outs = {{out_pid, (size_t)T * (2 * n - 3), &o_pid, sizeof(int32_t)},
+                                                {out_bl, (size_t)T * (2 * n - 2), &o_bl}};
+  if (place_out_pack(e, outs)) return 1;
+  if (run_nni_apply_device(e, e->stream, T, static_cast<const int32_t*>(d_parent), static_cast<const double*>(d_bl),
+                           static_cast<const int32_t*>(d_moves), reinterpret_cast<int32_t*>(o_pid), o_bl))
+    return 1;
+  if (download_pack(e, outs)) return 1;
+  return finish_host(e);
+}
+
+int run_nni_search_host(mi_engine* e, const NniSearchCall& h) {
+  const int T = h.T, n = e->n;
+  if (T <= 0) return fail("tree_count must be positive");
+  if (!h.parent_ids || !h.start) return fail("null tree arrays");
+  if (!h.out_pid || !h.out_bl || !h.out_ll || !h.out_move_count || !h.out_status) return fail("null output pointer");
+  if (e->param_count > 0 && !h.params) return fail("null parameter matrix");
+  mi_nni_search_options o;
+  if (search_options(h.options, &o)) return 1;
+  if (begin_host(e)) return 1;
+  const void *d_parent, *d_bl, *d_params;
+  if (upload_pack(e, {{h.parent_ids, sizeof(int32_t) * (size_t)T * (2 * n - 3), &d_parent},
+                      {h.start, sizeof(double) * (size_t)T * (2 * n - 2), &d_bl},
+                      {e->param_count > 0 ? h.params : nullptr, sizeof(double) * (size_t)T * e->param_count, &d_params}}))
+    return 1;
+  if (!d_params) d_params = e->in_pack.ptr;
+  const size_t log = (size_t)T * o.max_moves;
+  double *o_pid, *o_bl, *o_ll, *o_delta, *o_count, *o_log, *o_gain, *o_status, *o_opt;
+  const std::initializer_list<OutPiece> outs = {{h.out_pid, (size_t)T * (2 * n - 3), &o_pid, sizeof(int32_t)},
+                                                {h.out_bl, (size_t)T * (2 * n - 2), &o_bl},
+                                                {h.out_ll, (size_t)T, &o_ll},
+                                                {h.out_best_delta, h.out_best_delta ? (size_t)T : 0, &o_delta},
+                                                {h.out_move_count, (size_t)T, &o_count, sizeof(int32_t)},
+                                                {h.out_move_log, h.out_move_log ? log : 0, &o_log, sizeof(int32_t)},
+                                                {h.out_move_gain, h.out_move_gain ? log : 0, &o_gain},
+                                                {h.out_status, (size_t)T, &o_status, sizeof(int32_t)},
+                                                {h.out_opt_status, h.out_opt_status ? (size_t)T : 0, &o_opt, sizeof(int32_t)}};
+  if (place_out_pack(e, outs)) return 1;
+  NniSearchCall c = h;
+  c.parent_ids = static_cast<const int32_t*>(d_parent);
+  c.start = static_cast<const double*>(d_bl);
+  c.params = static_cast<const double*>(d_params);
+  c.out_pid = reinterpret_cast<int32_t*>(o_pid);
+  c.out_bl = o_bl;
+  c.out_ll = o_ll;
+  c.out_best_delta = h.out_best_delta ? o_delta : nullptr;
+  c.out_move_count = reinterpret_cast<int32_t*>(o_count);
+  c.out_move_log = h.out_move_log ? reinterpret_cast<int32_t*>(o_log) : nullptr;
+  c.out_move_gain = h.out_move_gain ? o_gain : nullptr;
+  c.out_status = reinterpret_cast<int32_t*>(o_status);
+  c.out_opt_status = h.out_opt_status ? reinterpret_cast<int32_t*>(o_opt) : nullptr;
+  if (run_nni_search_device(e, e->stream, c)) return 1;
+  if (download_pack(e, outs)) return 1;
+  return finish_host(e);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t mi_engine_nni_apply_unrooted(mi_engine* e, int32_t T, const int32_t* parent_ids, const double* bl,
+                                     const int32_t* moves, int32_t* out_parent_ids, double* out_bl) {
+  if (!e) return fail("null engine");
+  // (a move needs no alignment: a sharded handle of either kind lets its first shard take them all)
+  mi_engine* one = e->shards.empty() ? e : e->shards[0];
+  one->status_tree_offset = 0;
+  if (run_nni_apply_host(one, T, parent_ids, bl, moves, out_parent_ids, out_bl)) {
+    one->pinned.reset();
+    return 1;
+  }
+  return 0;
+}
+
+int32_t mi_engine_nni_apply_unrooted_device(mi_engine* e, void* stream, int32_t T, const int32_t* parent_ids,
+                                            const double* bl, const int32_t* moves, int32_t* out_parent_ids,
+                                            double* out_bl) {
+  if (!e) return fail("null engine");
+  if (!e->shards.empty()) return fail(kShardedDeviceCall);
+  return run_nni_apply_device(e, pick_stream(e, stream), T, parent_ids, bl, moves, out_parent_ids, out_bl);
+}
+
+int32_t mi_engine_nni_search_unrooted(mi_engine* e, int32_t T, const int32_t* parent_ids, const double* start,
+                                      const double* params, int32_t rescaling,
+                                      const mi_nni_search_options* options, int32_t* out_parent_ids,
+                                      double* out_bl, double* out_ll, double* out_best_delta,
+                                      int32_t* out_move_count, int32_t* out_move_log, double* out_move_gain,
+                                      int32_t* out_status, int32_t* out_opt_status) {
+  if (!e) return fail("null engine");
+  if (e->s == kAa) return fail(kSearch4State);
+  if (T <= 0) return fail("tree_count must be positive");
+  mi_nni_search_options o;
+  if (search_options(options, &o)) return 1;
+  NniSearchCall c;
+  c.T = T;
+  c.rescaling = rescaling != 0;
+  c.parent_ids = parent_ids;
+  c.start = start;
+  c.params = params;
+  c.options = options;
+  c.out_pid = out_parent_ids;
+  c.out_bl = out_bl;
+  c.out_ll = out_ll;
+  c.out_best_delta = out_best_delta;
+  c.out_move_count = out_move_count;
+  c.out_move_log = out_move_log;
+  c.out_move_gain = out_move_gain;
+  c.out_status = out_status;
+  c.out_opt_status = out_opt_status;
+  if (e->shards.empty()) {
+    if (run_nni_search_host(e, c)) {
+      e->pinned.reset();
+      return 1;
+    }
+    return 0;
+  }
+  if (e->shard_mode != MI_SHARD_TREES) return fail(kSearchPatternShards);
+  if (!parent_ids || !start || !out_parent_ids || !out_bl || !out_ll || !out_move_count || !out_status)
+    return fail("null tree / output pointer");
+  // Each shard searches from its block of trees, one shard after the other (the loop
+  // synchronises its device every round).
+  const int D = (int)e->shards.size(), n = e->n;
+  for (int i = 0; i < D; i++) {
+    int32_t b = 0, cnt = 0;
+    mi_shard_range(T, D, i, &b, &cnt);
+    if (cnt == 0) continue;
+    NniSearchCall sc = c;
+    sc.T = cnt;
+    sc.parent_ids = parent_ids + (size_t)b * (2 * n - 3);
+    sc.start = start + (size_t)b * (2 * n - 2);
+    if (params) sc.params = params + (size_t)b * e->param_count;
+    sc.out_pid = out_parent_ids + (size_t)b * (2 * n - 3);
+    sc.out_bl = out_bl + (size_t)b * (2 * n - 2);
+    sc.out_ll = out_ll + b;
+    if (out_best_delta) sc.out_best_delta = out_best_delta + b;
+    sc.out_move_count = out_move_count + b;
+    if (out_move_log) sc.out_move_log = out_move_log + (size_t)b * o.max_moves;
+    if (out_move_gain) sc.out_move_gain = out_move_gain + (size_t)b * o.max_moves;
+    sc.out_status = out_status + b;
+    if (out_opt_status) sc.out_opt_status = out_opt_status + b;
+    e->shards[i]->status_tree_offset = b;
+    if (run_nni_search_host(e->shards[i], sc)) {
+      e->shards[i]->pinned.reset();
+      return 1;
+    }
+  }
+  return 0;
+}
+
+int32_t mi_engine_nni_search_unrooted_device(mi_engine* e, void* stream, int32_t T, const int32_t* parent_ids,
+                                             const double* start, const double* params, int32_t rescaling,
+                                             const mi_nni_search_options* options, int32_t* out_parent_ids,
+                                             double* out_bl, double* out_ll, double* out_best_delta,
+                                             int32_t* out_move_count, int32_t* out_move_log,
+                                             double* out_move_gain, int32_t* out_status,
+                                             int32_t* out_opt_status) {
+  if (!e) return fail("null engine");
+  if (e->s == kAa) return fail(kSearch4State);
+  if (!e->shards.empty()) return fail(kShardedDeviceCall);
+  NniSearchCall c;
+  c.T = T;
+  c.rescaling = rescaling != 0;
+  c.parent_ids = parent_ids;
+  c.start = start;
+  c.params = params;
+  c.options = options;
+  c.out_pid = out_parent_ids;
+  c.out_bl = out_bl;
+  c.out_ll = out_ll;
+  c.out_best_delta = out_best_delta;
+  c.out_move_count = out_move_count;
+  c.out_move_log = out_move_log;
+  c.out_move_gain = out_move_gain;
+  c.out_status = out_status;
+  c.out_opt_status = out_opt_status;
+  return run_nni_search_device(e, pick_stream(e, stream), c);
+}
+
+int32_t mi_engine_reserve_nni_search(mi_engine* e, int32_t tree_count) {
+  if (!e) return fail("null engine");
+  if (tree_count <= 0) return fail("tree_count must be positive");
+  if (e->s == kAa) return fail(kSearch4State);
+  if (!e->shards.empty()) {
+    if (e->shard_mode != MI_SHARD_TREES) return fail(kSearchPatternShards);
+    return for_each_shard(e, tree_count, mi_engine_reserve_nni_search);
+  }
+  HIP_TRY(hipSetDevice(e->spec.device));
+  if (reserve_nni_apply(e, tree_count)) return 1;
+  return reserve_nni_search(e, tree_count);
+}
+
+}  // extern "C"

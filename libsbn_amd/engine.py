@@ -68,6 +68,38 @@ def _branch_opt_options(max_iterations, check_interval, pack_active, tolerance, 
                                   float(tolerance), float(min_length), float(max_length))
 
 
+@dataclass
+class NniSearchResult:
+    """What Engine.nni_search returns: per tree the topology [T][2n-3] and branch lengths
+    [T][2n-2] of its last optimisation, the log-likelihood and the largest NNI delta there, the
+    moves taken, their codes 2 v + i (in the ids of the tree at that round; -1: unused) and
+    deltas [T][max_moves], the status (0 local optimum, 1 move limit) and that optimisation's
+    status."""
+    parent_ids: np.ndarray
+    branch_lengths: np.ndarray
+    log_likelihood: np.ndarray
+    best_delta: np.ndarray
+    move_count: np.ndarray
+    move_log: np.ndarray
+    move_gain: np.ndarray
+    status: np.ndarray
+    branch_opt_status: np.ndarray
+
+
+def _nni_search_options(max_moves, pack_active, min_gain, branch_opt):
+    o = _capi.NniSearchOptions()
+    o.max_moves, o.pack_active, o.min_gain = int(max_moves), int(bool(pack_active)), float(min_gain)
+    if branch_opt:  # (left at zeros: the optimiser's defaults)
+        keys = dict(max_iterations=100, check_interval=4, pack_active=True, tolerance=1e-6,
+                    min_length=1e-8, max_length=10.0)
+        unknown = set(branch_opt) - set(keys)
+        if unknown:
+            raise RuntimeError(f"unknown branch_opt options: {sorted(unknown)}")
+        keys.update(branch_opt)
+        o.branch_opt = _branch_opt_options(**keys)
+    return o
+
+
 def nni_neighbour(taxon_count, parent_ids, branch_lengths, node, which):
     """Neighbour `which` (0 | 1) of inner edge `node` of one unrooted tree (mi_nni_neighbour:
     the trees Engine.nni_scan scores): (parent ids [2n-3], branch lengths [2n-2]) renumbered
@@ -369,6 +401,48 @@ class Engine:
             _ptr(out.hessian), _ptr(out.iterations), _ptr(out.status)))
         return out
 
+    def nni_apply(self, parent_ids, branch_lengths, moves):
+        """Take one NNI move per tree on the device (mi_engine_nni_apply_unrooted): moves [T] are
+        codes 2 v + i as nni_scan's best move gives them, or -1 for a copy.  Returns (parent ids
+        [T][2n-3], branch lengths [T][2n-2]): per tree what nni_neighbour returns, bit for bit."""
+        n = self.taxon_count
+        pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
+        T = pid.shape[0]
+        if T == 0:
+            return np.empty((0, 2 * n - 3), np.int32), np.empty((0, 2 * n - 2))
+        bl = _np(branch_lengths, np.float64).reshape(T, 2 * n - 2)
+        mv = _np(moves, np.int32).reshape(T)
+        out_pid, out_bl = np.empty((T, 2 * n - 3), np.int32), np.empty((T, 2 * n - 2))
+        self._check(self._lib.mi_engine_nni_apply_unrooted(
+            self._h, T, _ptr(pid), _ptr(bl), _ptr(mv), _ptr(out_pid), _ptr(out_bl)))
+        return out_pid, out_bl
+
+    def nni_search(self, parent_ids, start_branch_lengths, params=None, rescaling=False,
+                   max_moves=100, pack_active=True, min_gain=1e-3, branch_opt=None):
+        """NNI hill climbing per tree on the device (mi_engine_nni_search_unrooted; an extension,
+        4-state engines): optimise the branch lengths, scan the neighbourhood, take the best move
+        while its delta exceeds min_gain, at most max_moves times.  branch_opt: a dict of
+        optimize_branch_lengths' keyword options for every round.  Returns an NniSearchResult."""
+        n = self.taxon_count
+        pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
+        T = pid.shape[0]
+        opts = _nni_search_options(max_moves, pack_active, min_gain, branch_opt)
+        M = max(int(max_moves), 0)
+        out = NniSearchResult(np.empty((T, 2 * n - 3), np.int32), np.empty((T, 2 * n - 2)),
+                              np.empty(T), np.empty(T), np.empty(T, np.int32),
+                              np.empty((T, M), np.int32), np.empty((T, M)), np.empty(T, np.int32),
+                              np.empty(T, np.int32))
+        if T == 0:
+            return out
+        bl = _np(start_branch_lengths, np.float64).reshape(T, 2 * n - 2)
+        pr = self._params(params, T)
+        self._check(self._lib.mi_engine_nni_search_unrooted(
+            self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), C.addressof(opts),
+            _ptr(out.parent_ids), _ptr(out.branch_lengths), _ptr(out.log_likelihood),
+            _ptr(out.best_delta), _ptr(out.move_count), _ptr(out.move_log), _ptr(out.move_gain),
+            _ptr(out.status), _ptr(out.branch_opt_status)))
+        return out
+
     def _phylo_gradients(self, ll, blocks, site, subst):
         """Per-tree PhyloGradient objects over row views of the freshly allocated result
         arrays of one call (no per-tree copies: 1000 trees cost ~0.3 ms instead of ~1.1)."""
@@ -493,6 +567,30 @@ class Engine:
     def reserve_branch_opt(self, tree_count):
         """mi_engine_reserve_branch_opt: workspace of an optimisation call of that size."""
         self._check(self._lib.mi_engine_reserve_branch_opt(self._h, int(tree_count)))
+
+    def nni_apply_device(self, stream, T, parent_ids, branch_lengths, moves, out_parent_ids,
+                         out_branch_lengths):
+        """mi_engine_nni_apply_unrooted_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_nni_apply_unrooted_device(
+            self._h, stream, T, parent_ids, branch_lengths, moves, out_parent_ids,
+            out_branch_lengths))
+
+    def nni_search_device(self, stream, T, parent_ids, start_branch_lengths, params,
+                          out_parent_ids, out_branch_lengths, out_ll, out_move_count, out_status,
+                          out_best_delta=None, out_move_log=None, out_move_gain=None,
+                          out_branch_opt_status=None, rescaling=False, max_moves=100,
+                          pack_active=True, min_gain=1e-3, branch_opt=None):
+        """mi_engine_nni_search_unrooted_device: device pointers.  The call synchronises `stream`
+        every round, so it cannot be captured in a graph."""
+        opts = _nni_search_options(max_moves, pack_active, min_gain, branch_opt)
+        self._check(self._lib.mi_engine_nni_search_unrooted_device(
+            self._h, stream, T, parent_ids, start_branch_lengths, params, int(rescaling),
+            C.addressof(opts), out_parent_ids, out_branch_lengths, out_ll, out_best_delta,
+            out_move_count, out_move_log, out_move_gain, out_status, out_branch_opt_status))
+
+    def reserve_nni_search(self, tree_count):
+        """mi_engine_reserve_nni_search: workspace of a search or apply call of that size."""
+        self._check(self._lib.mi_engine_reserve_nni_search(self._h, int(tree_count)))
 
     def reserve_reduced(self, tree_count, index_count):
         """mi_engine_reserve_reduced: workspace of a fused-reduction call (graph capture)."""
