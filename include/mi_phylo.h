@@ -244,6 +244,77 @@ int32_t mi_nni_neighbour(int32_t taxon_count, const int32_t* parent_ids /* [2n-3
                          const double* branch_lengths /* [2n-2] */, int32_t node, int32_t which,
                          int32_t* out_parent_ids /* [2n-3] */, double* out_branch_lengths /* [2n-2] */);
 
+/* Per-pattern log-likelihoods of unrooted trees (an extension: what RELL bootstrap, expected-
+ * likelihood weights and the KH / SH / AU tests start from).
+ *   out_pattern_log_likelihoods[t][p] = log L_p(tree t), UNWEIGHTED: the pattern weight is not
+ * applied and patterns of weight 0 are reported like the others.  With rescaling it is
+ * log(mantissa) + exponent ln 2, the expression the log-likelihood kernels sum.  A pattern of
+ * likelihood 0 gives -inf (IEEE; not trapped).  A pattern in which every tip vector is all ones
+ * (an all-gap column) has likelihood 1 whatever the tree and is reported as exactly 0.0 (the
+ * log-likelihood call's arithmetic leaves it a few units of 2^-53 off, which the sums keep).  out_log_likelihoods is what
+ * mi_engine_log_likelihoods_unrooted returns for the same inputs, bit for bit: the call takes
+ * the log-likelihood call's route (MI_PHYLO_LOGLIK_PATH included) with the PATTERN_LL variant
+ * of its kernel, one evaluation per tree with the tree's own model row (a GTR engine: no
+ * finite-difference passes).  mi_engine_last_call_path is the log-likelihood call's line with
+ * the token " pattern_ll".  4-state engines only: a 20-state engine returns nonzero.  Sharded
+ * handles: MI_SHARD_TREES deals the trees as the other calls do, rows in tree order;
+ * MI_SHARD_PATTERNS is refused (each shard holds a block of columns). */
+int32_t mi_engine_pattern_log_likelihoods_unrooted(mi_engine* engine, int32_t tree_count,
+                                                   const int32_t* parent_ids,     /* [T][2n-3] */
+                                                   const double* branch_lengths,  /* [T][2n-2] */
+                                                   const double* params, int32_t rescaling,
+                                                   double* out_log_likelihoods /* [T] or NULL */,
+                                                   double* out_pattern_log_likelihoods /* [T][P] */);
+
+/* RELL re-summation (resampling of estimated log-likelihoods) and its reductions (an extension;
+ * DESIGN.md 4.12), for B replicates, T trees and P patterns -- P is an argument: any engine
+ * serves (the alignment plays no part), a sharded handle lets its first shard do it.
+ *   C[b][t]  = sum_p W[b][p] s[t][p]       (FP64 matrix cores)
+ *   best[b]  = the tree of the largest C[b][.], the lowest index among equals
+ *   bp[t]    = (double)#{b : best[b] = t} / B
+ *   elw[t]   = (1/B) sum_b exp(C[b][t] - m_b) / sum_t' exp(C[b][t'] - m_b),  m_b = max_t C[b][t]
+ * Determinism is part of the interface: every C[b][t] is accumulated over p in one fixed order
+ * (ascending, four patterns per step, one accumulator) that depends neither on B, T nor on
+ * where the pair falls in the launch -- equal rows of s give bit-identical columns of C --; the
+ * reductions use fixed trees and ordered sums; no floating-point atomics anywhere. */
+int32_t mi_engine_rell(mi_engine* engine, int32_t replicate_count, int32_t tree_count,
+                       int32_t pattern_count, const double* pattern_log_likelihoods /* [T][P] */,
+                       const double* replicate_weights /* [B][P] */,
+                       double* out_replicate_log_likelihoods /* [B][T] or NULL */,
+                       int32_t* out_best_tree /* [B] or NULL */,
+                       double* out_bootstrap_proportion /* [T] */,
+                       double* out_expected_likelihood_weight /* [T] or NULL */);
+
+/* The common case in one host call: upload, mi_engine_pattern_log_likelihoods_unrooted,
+ * mi_engine_rell with the engine's pattern count, download -- nothing returns to the host in
+ * between.  Sharded handles of more than one shard are refused (the product needs every
+ * tree's row on one device). */
+int32_t mi_engine_rell_bootstrap_unrooted(mi_engine* engine, int32_t tree_count,
+                                          const int32_t* parent_ids,     /* [T][2n-3] */
+                                          const double* branch_lengths,  /* [T][2n-2] */
+                                          const double* params, int32_t rescaling,
+                                          int32_t replicate_count,
+                                          const double* replicate_weights /* [B][P] */,
+                                          double* out_log_likelihoods /* [T] */,
+                                          double* out_pattern_log_likelihoods /* [T][P] or NULL */,
+                                          double* out_replicate_log_likelihoods /* [B][T] or NULL */,
+                                          int32_t* out_best_tree /* [B] or NULL */,
+                                          double* out_bootstrap_proportion /* [T] */,
+                                          double* out_expected_likelihood_weight /* [T] or NULL */);
+
+/* The marginal of a mixture of trees from their per-pattern log-likelihoods (an extension;
+ * DESIGN.md 4.12):
+ *   out_pattern_log_marginal[p] = logsumexp_t(s[t][p] + tree_log_weights[t])
+ *   out_log_marginal[0]         = sum_p pattern_weights[p] out_pattern_log_marginal[p]
+ * tree_log_weights NULL: log(1/T) each.  t in ascending order after a maximum pass, the final
+ * sum in a fixed order.  Any engine serves, as for mi_engine_rell. */
+int32_t mi_engine_pattern_mixture(mi_engine* engine, int32_t tree_count, int32_t pattern_count,
+                                  const double* pattern_log_likelihoods /* [T][P] */,
+                                  const double* tree_log_weights /* [T] or NULL */,
+                                  const double* pattern_weights /* [P] */,
+                                  double* out_pattern_log_marginal /* [P] */,
+                                  double* out_log_marginal /* [1] */);
+
 /* Maximum-likelihood branch lengths of unrooted trees under box bounds (an extension: the
  * consumer of the Hessian call's outputs).  Every tree of the batch is
  * iterated on the device: an evaluation is one Hessian pass at a trial point, a step is a
@@ -449,6 +520,25 @@ int32_t mi_engine_nni_scan_unrooted_device(mi_engine* engine, void* stream, int3
                                            double* out_log_likelihoods, double* out_nni_delta,
                                            int32_t* out_best_move);
 
+/* The device forms of mi_engine_pattern_log_likelihoods_unrooted, mi_engine_rell and
+ * mi_engine_pattern_mixture: they only enqueue -- no allocation and no synchronisation after
+ * mi_engine_reserve(tree_count, 0), mi_engine_reserve_rell and (the mixture) a first call of
+ * that pattern count. */
+int32_t mi_engine_pattern_log_likelihoods_unrooted_device(
+    mi_engine* engine, void* stream, int32_t tree_count, const int32_t* parent_ids,
+    const double* branch_lengths, const double* params, int32_t rescaling,
+    double* out_log_likelihoods, double* out_pattern_log_likelihoods);
+int32_t mi_engine_rell_device(mi_engine* engine, void* stream, int32_t replicate_count,
+                              int32_t tree_count, int32_t pattern_count,
+                              const double* pattern_log_likelihoods, const double* replicate_weights,
+                              double* out_replicate_log_likelihoods, int32_t* out_best_tree,
+                              double* out_bootstrap_proportion,
+                              double* out_expected_likelihood_weight);
+int32_t mi_engine_pattern_mixture_device(mi_engine* engine, void* stream, int32_t tree_count,
+                                         int32_t pattern_count, const double* pattern_log_likelihoods,
+                                         const double* tree_log_weights, const double* pattern_weights,
+                                         double* out_pattern_log_marginal, double* out_log_marginal);
+
 /* The device form of mi_engine_optimize_branch_lengths_unrooted.  Unlike the other *_device
  * calls it SYNCHRONISES `stream` at its check points (it reads the number of active trees to
  * decide whether to go on), so it cannot be captured in a hipGraph; when it returns, every
@@ -509,6 +599,11 @@ int32_t mi_engine_reserve_branch_opt(mi_engine* engine, int32_t tree_count);
  * included): a *_device call of at most that size then allocates nothing.  4-state engines
  * only. */
 int32_t mi_engine_reserve_nni_search(mi_engine* engine, int32_t tree_count);
+/* The workspace of mi_engine_rell[_device] for `replicate_count` replicates and `tree_count`
+ * trees (the [B][T] product when the caller wants none, the row statistics, the counts): a
+ * *_device call of at most that size then allocates nothing.  `pattern_count` needs none. */
+int32_t mi_engine_reserve_rell(mi_engine* engine, int32_t replicate_count, int32_t tree_count,
+                               int32_t pattern_count);
 /* Synchronise `stream` and report the first per-tree error since the last check (the status
  * word is sticky and cleared when an error is reported: calls themselves never clear it). */
 int32_t mi_engine_check_status(mi_engine* engine, void* stream);

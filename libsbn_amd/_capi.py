@@ -100,6 +100,19 @@ SYMBOLS = {
         (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V,
                      _V]),
     "mi_engine_reserve_nni_search": (C.c_int32, [_V, C.c_int32]),
+    "mi_engine_pattern_log_likelihoods_unrooted":
+        (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V]),
+    "mi_engine_pattern_log_likelihoods_unrooted_device":
+        (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V]),
+    "mi_engine_rell": (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_rell_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_reserve_rell": (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32]),
+    "mi_engine_rell_bootstrap_unrooted":
+        (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_pattern_mixture": (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),
+    "mi_engine_pattern_mixture_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),
     "mi_engine_profile_begin": (C.c_int32, [_V, C.c_int32]),
     "mi_engine_profile_collect": (C.c_int32, [_V, F64P, C.c_int32, I32P]),

@@ -58,6 +58,21 @@ struct NniNeighbourhood {
   int32_t best_move_ = -1;
 };
 
+// Engine::PatternLogLikelihoods (an extension, include/mi_phylo.h): log_likelihoods_ [T] and the
+// unweighted per-pattern values [T][P], row-major
+struct PatternLogLikelihood {
+  std::vector<double> log_likelihoods_, pattern_log_likelihoods_;
+};
+
+// Engine::RellBootstrap (an extension, include/mi_phylo.h): the per-pattern values [T][P], the
+// replicate log-likelihoods [B][T], the best tree per replicate [B] (lowest index among equals),
+// bootstrap proportions and expected-likelihood weights [T]
+struct RellBootstrapResult {
+  std::vector<double> log_likelihoods_, pattern_log_likelihoods_, replicate_log_likelihoods_;
+  std::vector<int32_t> best_tree_;
+  std::vector<double> bootstrap_proportion_, expected_likelihood_weight_;
+};
+
 // Engine::OptimizeBranchLengths, per tree (an extension, include/mi_phylo.h): the
 // maximum-likelihood branch lengths [2n-2] and the Hessian call's outputs at them [2n-1]
 struct BranchOptimum {
@@ -264,6 +279,50 @@ class Engine {
       out[t].delta_.assign(d.begin() + t * N * 2, d.begin() + (t + 1) * N * 2);
       out[t].best_move_ = best[t];
     }
+    return out;
+  }
+
+  // Unweighted per-pattern log-likelihoods log L_p per tree (an extension; 4-state engines):
+  // mi_engine_pattern_log_likelihoods_unrooted.
+  PatternLogLikelihood PatternLogLikelihoods(const UnrootedTreeCollection& trees, const ParamMatrix& params,
+                                             const bool rescaling) const {
+    const size_t T = trees.size(), P = site_pattern_.PatternCount();
+    std::vector<int32_t> parents;
+    std::vector<double> bl;
+    Flatten(trees, params, false, &parents, &bl);
+    PatternLogLikelihood out;
+    if (trees.empty()) return out;
+    out.log_likelihoods_.resize(T);
+    out.pattern_log_likelihoods_.resize(T * P);
+    Check(mi_engine_pattern_log_likelihoods_unrooted(handle_, static_cast<int32_t>(T), parents.data(), bl.data(),
+                                                     params.data.data(), rescaling, out.log_likelihoods_.data(),
+                                                     out.pattern_log_likelihoods_.data()));
+    return out;
+  }
+
+  // RELL bootstrap of the trees from `replicates` rows of replicate weights [B][P] (an extension;
+  // 4-state engines, one device): mi_engine_rell_bootstrap_unrooted.
+  RellBootstrapResult RellBootstrap(const UnrootedTreeCollection& trees, const ParamMatrix& params,
+                                    const bool rescaling, const size_t replicates,
+                                    const std::vector<double>& replicate_weights) const {
+    const size_t T = trees.size(), P = site_pattern_.PatternCount(), B = replicates;
+    if (replicate_weights.size() != B * P) Failwith("RellBootstrap: replicate weights must be [replicates][patterns].");
+    std::vector<int32_t> parents;
+    std::vector<double> bl;
+    Flatten(trees, params, false, &parents, &bl);
+    RellBootstrapResult out;
+    if (trees.empty()) return out;
+    out.log_likelihoods_.resize(T);
+    out.pattern_log_likelihoods_.resize(T * P);
+    out.replicate_log_likelihoods_.resize(B * T);
+    out.best_tree_.resize(B);
+    out.bootstrap_proportion_.resize(T);
+    out.expected_likelihood_weight_.resize(T);
+    Check(mi_engine_rell_bootstrap_unrooted(
+        handle_, static_cast<int32_t>(T), parents.data(), bl.data(), params.data.data(), rescaling,
+        static_cast<int32_t>(B), replicate_weights.data(), out.log_likelihoods_.data(),
+        out.pattern_log_likelihoods_.data(), out.replicate_log_likelihoods_.data(), out.best_tree_.data(),
+        out.bootstrap_proportion_.data(), out.expected_likelihood_weight_.data()));
     return out;
   }
 

@@ -39,7 +39,10 @@ __device__ __forceinline__ double ll_row_ror_add(double v) {
 // conflict-free ds_read_b64 / ds_write_b64).  HBM traffic: tip states, the
 // schedule and the transition matrices only.
 // ------------------------------------------------------------------------
-template <bool RESCALE, bool TIP_PARTIALS>
+// PATTERN_LL (both kernels): the variant that also hands out the per-pattern log-likelihoods
+// (LikArgs::pattern_ll; one evaluation per tree).  A compile-time variant: the plain
+// instantiations are what they were before it existed.
+template <bool RESCALE, bool TIP_PARTIALS, bool PATTERN_LL = false>
 __global__ __launch_bounds__(kTile) void loglik_onchip_kernel(LikArgs a) {
   extern __shared__ double lds[];
   const int lane = threadIdx.x;
@@ -166,6 +169,10 @@ __global__ __launch_bounds__(kTile) void loglik_onchip_kernel(LikArgs a) {
     a.site_lik[((size_t)a.grad_offset + te.eval) * a.tiles * kTile + p] = site;
   double ll = log(site);
   if (RESCALE) ll += site_exp * 0.6931471805599453;
+  if constexpr (PATTERN_LL) {
+    // (unweighted; a pattern without information has likelihood 1 exactly, whatever rounding made of it)
+    if (p < a.P) a.pattern_ll[(size_t)e * a.P + p] = a.pattern_blank[p] ? 0.0 : ll;
+  }
   ll = p < a.P ? w * ll : 0.0;
   ll = wave_sum(ll);
   if (lane == 0) a.ll_part[(size_t)e * a.ll_tiles + tile] = ll;
@@ -190,7 +197,7 @@ __global__ __launch_bounds__(kTile) void loglik_onchip_kernel(LikArgs a) {
 // per SIMD (28 MAC/clk/SIMD, 1.8x the FP64 VALU peak), and the VALU stays free
 // for the element-wise products.
 // ------------------------------------------------------------------------
-template <int R, bool RESCALE, bool MULTI>
+template <int R, bool RESCALE, bool MULTI, bool PATTERN_LL = false>
 // (kTile, 5): LDS allows ~20 waves per CU for typical trees; and with at most 256 registers per lane the compiler keeps the products in
 // ordinary vector registers; without the bound it places them in accumulation registers
 // and spends two v_accvgpr_read per product to get them back
@@ -607,7 +614,10 @@ __global__ __launch_bounds__(kTile, LL_WAVES) void loglik_mfma_kernel(LikArgs a)
         a.site_lik[at] = sv;
         if (RESCALE) a.site_exp[at] = ev;
       }
-      ll += wv * (RESCALE ? log(sv) + ev * 0.69314718055994530942 : log(sv));
+      const double lv = RESCALE ? log(sv) + ev * 0.69314718055994530942 : log(sv);
+      // (unweighted; a pattern without information has likelihood 1 exactly, whatever rounding made of it)
+      if constexpr (PATTERN_LL) a.pattern_ll[(size_t)e * a.P + pv] = a.pattern_blank[pv] ? 0.0 : lv;
+      ll += wv * lv;
     }
   }
   ll = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, ll, 0.0, 0, 0, 0);  // the four rows
@@ -717,6 +727,16 @@ static void launch_loglik_mfma(const LikArgs& a_in, int count, bool rescale, int
     hipLaunchKernelGGL(kernel, grid, block, lds, s, a);
   };
   const bool multi = a.K > 4;
+  if (a.pattern_ll) {
+    if (rescale) {
+      if (multi) go(loglik_mfma_kernel<kLogR, true, true, true>);
+      else go(loglik_mfma_kernel<kLogR, true, false, true>);
+    } else {
+      if (multi) go(loglik_mfma_kernel<kLogR, false, true, true>);
+      else go(loglik_mfma_kernel<kLogR, false, false, true>);
+    }
+    return;
+  }
   if (rescale) {
     if (multi) go(loglik_mfma_kernel<kLogR, true, true>);
     else go(loglik_mfma_kernel<kLogR, true, false>);
@@ -737,6 +757,16 @@ void launch_loglik(const LikArgs& a_in, int count, bool rescale, int max_slots, 
   const dim3 grid(a.tiles, count), block(kTile);
   const size_t lds = (size_t)max_slots * 4 * kTile * sizeof(double) + (size_t)a.n * kTile;
   const bool tp = a.tip_partials != nullptr;
+  if (a.pattern_ll) {
+    if (rescale) {
+      if (tp) hipLaunchKernelGGL((loglik_onchip_kernel<true, true, true>), grid, block, lds, s, a);
+      else hipLaunchKernelGGL((loglik_onchip_kernel<true, false, true>), grid, block, lds, s, a);
+    } else {
+      if (tp) hipLaunchKernelGGL((loglik_onchip_kernel<false, true, true>), grid, block, lds, s, a);
+      else hipLaunchKernelGGL((loglik_onchip_kernel<false, false, true>), grid, block, lds, s, a);
+    }
+    return;
+  }
   if (rescale) {
     if (tp) hipLaunchKernelGGL((loglik_onchip_kernel<true, true>), grid, block, lds, s, a);
     else hipLaunchKernelGGL((loglik_onchip_kernel<true, false>), grid, block, lds, s, a);

@@ -241,6 +241,7 @@ std::string plan_path(const mi_engine* e, const CallPlan& p) {
   path += p.fuse_setup ? " setup=in-walk" : (p.setup_records ? " setup=with-records" : " setup=own-launch");
   if (p.kind == kHessianCall) path += " hess";
   if (p.kind == kNniCall) path += " nni";
+  if (p.pattern_ll) path += " pattern_ll";
   if (p.tile_regs > kLlR) path += " tile=wide";
   if (p.fd_pass) path += " fd=16";
   if (p.site_pass) path += " site-pass";
@@ -280,6 +281,8 @@ int reserve(mi_engine* e, const CallPlan& p) {
     HIP_TRY(hipDeviceSynchronize());
   }
   if (e->ll_sum.ensure(sizeof(double) * (size_t)p.E)) return 1;
+  // (the per-pattern call's log-likelihoods when its caller wants none)
+  if (p.kind == kLogLikCall && !p.rooted && e->pattern_ll_out.ensure(sizeof(double) * (size_t)T)) return 1;
   if (gradient && e->g_sum.ensure(sizeof(double) * (size_t)p.Eg * 2 * N)) return 1;
   if (gradient) {
     // the HBM-streamed kernel is the fallback for rescaling / trees that do not fit
@@ -474,6 +477,8 @@ LikArgs lik_args(const mi_engine* e, const DeviceCall& d, const CallPlan& p) {
   la.tip_tiles = e->have_tip_masks && e->tip_tiles.ptr && e->sw.tip_tiles ? e->tip_tiles.as<uint8_t>() : nullptr;
   la.tip_codes = e->have_tip_codes ? e->tip_codes.as<uint8_t>() : nullptr;
   la.tile_regs = p.tile_regs;
+  la.pattern_ll = p.pattern_ll ? d.out_pattern_ll : nullptr;
+  la.pattern_blank = e->pattern_blank.as<uint8_t>();
   return la;
 }
 
@@ -504,13 +509,15 @@ int check_call(const mi_engine* e, const DeviceCall& d, const void* output) {
 }  // namespace
 
 // Enqueue one engine call; every pointer in `d` is a device pointer.
-int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
+int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d_in) {
   // (a caller driving several GPUs from one thread may have another device current)
   HIP_TRY(hipSetDevice(e->spec.device));
-  if (e->s == kAa) return aa_run_device(e, s, d);
-  if (check_call(e, d, d.out_ll)) return 1;
-  const CallPlan p = plan_call(e, d.gradient ? kGradientCall : kLogLikCall, d);
+  if (e->s == kAa) return d_in.out_pattern_ll ? fail(kPatternLl4State) : aa_run_device(e, s, d_in);
+  if (check_call(e, d_in, d_in.out_pattern_ll ? d_in.out_pattern_ll : d_in.out_ll)) return 1;
+  const CallPlan p = plan_call(e, d_in.gradient ? kGradientCall : kLogLikCall, d_in);
   if (reserve(e, p)) return 1;
+  DeviceCall d = d_in;
+  if (!d.out_ll) d.out_ll = e->pattern_ll_out.as<double>();  // (the per-pattern call: nobody wants the sums)
   const int n = e->n, N = e->N, T = d.T;
   // (the status word is sticky: cleared when it is read, check_status -- not per call: one
   // dispatch less on the small-batch path)

@@ -22,6 +22,11 @@ namespace {
 // (engine creation, tips in mask form on the device: the log-likelihood kernel's pre-tiled copy)
 int build_tip_tiles(mi_engine* e) {
   e->tile_regs = engine_tile_regs(e);
+  if (e->s == kStates) {  // which patterns carry no information (the per-pattern call reports them as exactly 0)
+    if (e->pattern_blank.ensure((size_t)e->P)) return 1;
+    launch_pattern_blank(e->have_tip_masks ? e->tip_masks.as<uint8_t>() : nullptr, e->tip_partials.as<double>(), e->n,
+                         e->P, e->pattern_blank.as<uint8_t>(), e->stream);
+  }
   if (!e->have_tip_masks || e->K > kMaxCategories) return 0;
   if (e->tip_tiles.ensure(loglik_tip_tiles_bytes(e->n, e->P, e->K))) return 1;
   launch_tip_tiles(e->tip_masks.as<uint8_t>(), e->tip_tiles.as<uint8_t>(), e->n, e->P, e->K, e->stream);
@@ -85,6 +90,7 @@ const char kShardedDeviceCall[] =
     "process per GPU), or the host-pointer entry points";
 const char kHessian4State[] = "the branch-length Hessian call is 4-state only";
 const char kNni4State[] = "the NNI neighbourhood scan is 4-state only";
+const char kPatternLl4State[] = "per-pattern log-likelihoods are 4-state only";
 
 extern "C" {
 
@@ -436,7 +442,8 @@ void mi_engine_destroy(mi_engine* e) {
         &e->ll_sum, &e->g_sum, &e->status, &e->ready, &e->weibull_x, &e->aa_model, &e->aa_matP, &e->aa_matPT,
         &e->aa_tipP, &e->aa_tipPQ, &e->aa_exp_cum, &e->aa_exp_loc, &e->aa_root_val,
         &e->aa_root_exp, &e->aa_root_scale, &e->red_ll, &e->red_g, &e->red_site, &e->red_sort,
-        &e->in_pack, &e->out_pack, &e->opt_ws, &e->nni_apply_ws, &e->nni_search_ws})
+        &e->in_pack, &e->out_pack, &e->opt_ws, &e->nni_apply_ws, &e->nni_search_ws,
+        &e->pattern_blank, &e->pattern_ll_out, &e->rell_ws, &e->rell_s})
     b->release();
   if (e->opt_word) (void)hipHostFree(e->opt_word);
   e->pinned.release();

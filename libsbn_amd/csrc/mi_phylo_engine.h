@@ -7,6 +7,7 @@
 //   mi_phylo_branch_opt.cpp   branch-length optimisation
 //   mi_phylo_nni.cpp          mi_nni_neighbour, the scan's best move on the host (no device code)
 //   mi_phylo_nni_search.cpp   NNI moves on the device, the NNI hill-climbing search
+//   mi_phylo_rell.cpp         per-pattern log-likelihoods (device form), RELL re-summation, tree mixtures
 //   mi_phylo_host_calls.cpp   host-pointer entry points, sharded handles
 //   mi_phylo_engine_aa.cpp    20-state call sequence
 #pragma once
@@ -181,6 +182,11 @@ struct mi_engine {
   // NNI moves and the NNI search (mi_engine_nni_{apply,search}_unrooted*)
   Buffer nni_apply_ws;   // the apply kernel's working arrays of trees too large for LDS
   Buffer nni_search_ws;  // the pair of tree buffers, a round's results, packed inputs, maps, counters
+  // per-pattern log-likelihoods and RELL (mi_engine_pattern_log_likelihoods_unrooted*, mi_engine_rell*)
+  Buffer pattern_blank;   // [P] 1 where every tip vector of the pattern is all ones (once per engine: launch_pattern_blank)
+  Buffer pattern_ll_out;  // [T] the call's log-likelihoods when the caller wants none (mi_engine_reserve)
+  Buffer rell_ws;         // [B][T] product (when the caller wants none) | row maxima, 1 / denominators [B] each | counts [T] (mi_engine_reserve_rell)
+  Buffer rell_s;          // the fused host call: [T][P] per-pattern values nobody downloads
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)
   std::vector<hipEvent_t> prof_events;  // kProfEvents per call: [begin, end, mark 0..4]
@@ -240,6 +246,7 @@ struct CallPlan {
   bool fd_pass, site_pass;  // the 16 finite-difference passes / the perturbed-model site pass run
   bool loglik_runs;         // a log-likelihood kernel runs at all
   bool loglik_is_valu;      // ... the VALU one (else the matrix-core one)
+  bool pattern_ll;          // a log-likelihood call that also hands out the per-pattern values (its kernels' PATTERN_LL variant)
   bool need_tip_tables;     // the transition launch fills the per-state tip tables (VALU log-likelihood kernel)
   // reservation only: what does not follow from this call alone
   size_t mmats_bytes_per_eval;  // macro-ordered matrices of either walk generation this engine can take
@@ -271,6 +278,8 @@ struct DeviceCall {
   // NNI neighbourhood scan (run_nni_device): out_ll / out_best may be nullptr there
   double* out_nni = nullptr;    // [T][N][2]
   int32_t* out_best = nullptr;  // [T]
+  // per-pattern log-likelihoods (a log-likelihood call; out_ll may be nullptr there)
+  double* out_pattern_ll = nullptr;  // [T][P]
   // ... as one pass of the branch-length optimisation: the batch size the kernel and its store
   // are chosen for (the whole batch's, so that a tree's results do not depend on how many
   // trees are still active); 0: T
@@ -280,7 +289,9 @@ struct DeviceCall {
 CallPlan plan_call(const mi_engine* e, CallKind kind, int T, bool rescaling, int route_T = 0,
                    bool rooted = false, bool want_site = true, bool want_subst = true);
 inline CallPlan plan_call(const mi_engine* e, CallKind kind, const DeviceCall& d) {
-  return plan_call(e, kind, d.T, d.rescaling, d.route_T, d.rooted, d.out_site != nullptr, d.out_subst != nullptr);
+  CallPlan p = plan_call(e, kind, d.T, d.rescaling, d.route_T, d.rooted, d.out_site != nullptr, d.out_subst != nullptr);
+  p.pattern_ll = kind == kLogLikCall && d.out_pattern_ll != nullptr;
+  return p;
 }
 std::string plan_path(const mi_engine* e, const CallPlan& p);  // mi_engine_last_call_path
 bool walk3_possible(const mi_engine* e);  // (engine creation: the look-up walk's pre-tiled tip codes)
@@ -323,7 +334,7 @@ int check_branch_opt_options(const mi_branch_opt_options& o);
 int run_branch_opt_device(mi_engine* e, hipStream_t s, const BranchOptCall& c);
 
 // ---- mi_phylo_engine.cpp ----
-extern const char kShardedDeviceCall[], kHessian4State[], kNni4State[];
+extern const char kShardedDeviceCall[], kHessian4State[], kNni4State[], kPatternLl4State[];
 int check_status(mi_engine* e, hipStream_t s);
 inline hipStream_t pick_stream(mi_engine* e, void* stream) {
   return stream ? static_cast<hipStream_t>(stream) : e->stream;
@@ -356,6 +367,13 @@ struct OutPiece {
 int upload_pack(mi_engine* e, std::initializer_list<InPiece> pieces);
 int place_out_pack(mi_engine* e, std::initializer_list<OutPiece> pieces);
 int download_pack(mi_engine* e, std::initializer_list<OutPiece> pieces);
+
+// ---- mi_phylo_rell.cpp ----
+// the workspace of a RELL call over B replicates and T trees (mi_engine_reserve_rell)
+int reserve_rell(mi_engine* e, int B, int T);
+// enqueue the product, the row pass and the column pass; every pointer a device pointer
+int run_rell_device(mi_engine* e, hipStream_t s, int B, int T, int P, const double* pattern_ll, const double* weights,
+                    double* out_c, int32_t* out_best, double* out_bp, double* out_elw);
 
 // mi_phylo_engine_aa.cpp
 int aa_engine_init(mi_engine* e, const double* exchangeabilities, const double* frequencies);

@@ -33,6 +33,9 @@ struct HostCall {
   bool nni = false;
   double* out_nni = nullptr;    // [T][N][2]
   int32_t* out_best = nullptr;  // [T] or null
+  // per-pattern log-likelihoods (mi_engine_pattern_log_likelihoods_unrooted): out_ll may be null there
+  bool pattern = false;
+  double* out_pattern = nullptr;  // [T][P]
   // fused reductions of a variational-inference step (mi_engine_gradients_unrooted_reduced)
   bool reduced = false;
   const int32_t* branch_index = nullptr;  // [T][N]
@@ -167,6 +170,16 @@ int begin_host_call(mi_engine* e, const HostCall& h) {
       return 1;
     return download_pack(e, outs);
   }
+  if (h.pattern) {
+    double* o_p;
+    const std::initializer_list<OutPiece> outs = {{h.out_ll, h.out_ll ? (size_t)T : 0, &o_ll},
+                                                  {h.out_pattern, (size_t)T * e->P, &o_p}};
+    if (place_out_pack(e, outs)) return 1;
+    if (mi_engine_pattern_log_likelihoods_unrooted_device(e, e->stream, T, P32(d_parent), F64(d_bl), F64(d_params),
+                                                          h.rescaling, h.out_ll ? o_ll : nullptr, o_p))
+      return 1;
+    return download_pack(e, outs);
+  }
   if (!h.gradient) {
     const std::initializer_list<OutPiece> outs = {{h.out_ll, (size_t)T, &o_ll}};
     if (place_out_pack(e, outs)) return 1;
@@ -273,6 +286,7 @@ int run_sharded(mi_engine* e, const HostCall& h) {
       if (h.out_s) s.out_s = h.out_s + (size_t)b * N;
       if (h.out_nni) s.out_nni = h.out_nni + (size_t)b * N * 2;
       if (h.out_best) s.out_best = h.out_best + b;
+      if (h.out_pattern) s.out_pattern = h.out_pattern + (size_t)b * e->P;
       if (h.reduced) {
         s.branch_index = h.branch_index + (size_t)b * N;
         if (h.tree_weights) s.tree_weights = h.tree_weights + b;
@@ -300,6 +314,9 @@ int run_sharded(mi_engine* e, const HostCall& h) {
     return 0;
   }
   // pattern shards: only what is a plain sum over site patterns
+  if (h.pattern)
+    return fail("pattern-sharded engines do not hand out per-pattern log-likelihoods (each shard holds a "
+                "block of columns): use MI_SHARD_TREES or a single engine");
   if (h.rooted)
     return fail("pattern-sharded engines evaluate unrooted calls only (the log-det-Jacobian "
                 "and the rooted chain rule are not sums over site patterns)");
@@ -462,6 +479,23 @@ int32_t mi_engine_nni_scan_unrooted(mi_engine* e, int32_t T, const int32_t* pare
   h.out_ll = out_ll;
   h.out_nni = out_delta;
   h.out_best = out_best;
+  return run_host(e, h);
+}
+
+int32_t mi_engine_pattern_log_likelihoods_unrooted(mi_engine* e, int32_t T, const int32_t* parent_ids,
+                                                   const double* bl, const double* params, int32_t rescaling,
+                                                   double* out_ll, double* out_pattern_ll) {
+  if (!out_pattern_ll) return fail("null per-pattern log-likelihood output");
+  if (e && e->s == kAa) return fail(kPatternLl4State);
+  HostCall h;
+  h.pattern = true;
+  h.T = T;
+  h.rescaling = rescaling;
+  h.parent_ids = parent_ids;
+  h.bl = bl;
+  h.params = params;
+  h.out_ll = out_ll;
+  h.out_pattern = out_pattern_ll;
   return run_host(e, h);
 }
 

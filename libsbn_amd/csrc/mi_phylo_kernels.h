@@ -129,6 +129,8 @@ struct LikArgs {
   int32_t* status;             // [4]: code, tree (schedule does not fit the kernel's LDS slots), [2]: 1 + tree of a walk wave of the one-launch call that waited in vain
   const int32_t* slot_need;    // [T] arena gradient kernel: LDS slots each tree's schedule uses
   int lds_lo;                  // arena gradient kernel: this launch takes trees with lds_lo < need <= lds_slots
+  double* pattern_ll;          // [T][P] log-likelihood kernels' PATTERN_LL variant: unweighted log L_p per (tree, pattern); else nullptr
+  const uint8_t* pattern_blank;  // [P] PATTERN_LL variant: 1 where every tip vector of the pattern is all ones (L_p = 1 exactly: reported as 0.0)
 };
 
 // How many logL partial sums each evaluation's walk kernel wrote (the kernels tile the
@@ -313,6 +315,33 @@ struct NniSearchStepArgs {
   int32_t* active;                           // this round's word: trees that moved
 };
 void launch_nni_search_step(const NniSearchStepArgs& a, hipStream_t s);
+// RELL re-summation and the tree-mixture marginal (kernels_rell.hip)
+struct RellArgs {
+  int B, T, P;
+  const double* pattern_ll;  // [T][P]
+  const double* weights;     // [B][P]
+  double* c;                 // [B][T] the product (the caller's or the engine's)
+  double* row_max;           // [B] row maxima m_b
+  double* row_inv;           // [B] 1 / sum_t exp(C[b][t] - m_b)
+  int32_t* counts;           // [T] replicates won (zeroed before the launch)
+  int32_t* best;             // [B] or nullptr
+  double* bp;                // [T]
+  double* elw;               // [T] or nullptr
+};
+void launch_rell(const RellArgs& a, hipStream_t s);  // product, row pass, column pass
+// once per 4-state engine: blank[p] = 1 where every tip vector of pattern p is all ones (an all-gap
+// column), from the state masks [n][P] or, without them, the partials [n][P][4]
+void launch_pattern_blank(const uint8_t* masks, const double* partials, int n, int P, uint8_t* blank, hipStream_t s);
+const char* rell_product_kernel_name();
+struct MixtureArgs {
+  int T, P;
+  const double* pattern_ll;       // [T][P]
+  const double* log_weights;      // [T] or nullptr: log(1/T) each
+  const double* pattern_weights;  // [P]
+  double* out_pattern;            // [P]
+  double* out_total;              // [1]
+};
+void launch_pattern_mixture(const MixtureArgs& a, hipStream_t s);
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
 // the first, gradient_mfma_kernel, was retired in round 6): all categories of a group of four
 // per instruction; they also write the log-likelihood partial sums, so no separate logL pass is

@@ -86,6 +86,33 @@ class NniSearchResult:
     branch_opt_status: np.ndarray
 
 
+@dataclass
+class RellResult:
+    """What Engine.rell_bootstrap returns: log-likelihoods [T], per-pattern log-likelihoods
+    [T][P] (unweighted), replicate log-likelihoods C [B][T], the best tree per replicate [B]
+    (lowest index among equals), bootstrap proportions [T] and expected-likelihood weights [T]."""
+    log_likelihood: np.ndarray
+    pattern_log_likelihood: np.ndarray
+    replicate_log_likelihood: np.ndarray
+    best_tree: np.ndarray
+    bootstrap_proportion: np.ndarray
+    expected_likelihood_weight: np.ndarray
+
+
+def rell_weights(weights, replicates, seed):
+    """Replicate weights of a RELL bootstrap: multinomial resampling of sum(weights) sites over
+    the patterns with numpy.random.default_rng(seed).  Returns float64 [replicates][P]; host
+    arithmetic only.  Pattern weights that are no site counts (non-integer) are refused."""
+    w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w.size == 0 or not np.all(np.isfinite(w)) or np.any(w < 0) or np.any(w != np.rint(w)):
+        raise RuntimeError("rell_weights: pattern weights must be non-negative integer site counts")
+    total = int(w.sum())
+    if total <= 0:
+        raise RuntimeError("rell_weights: the pattern weights sum to 0")
+    rng = np.random.default_rng(seed)
+    return rng.multinomial(total, w / w.sum(), size=int(replicates)).astype(np.float64)
+
+
 def _nni_search_options(max_moves, pack_active, min_gain, branch_opt):
     o = _capi.NniSearchOptions()
     o.max_moves, o.pack_active, o.min_gain = int(max_moves), int(bool(pack_active)), float(min_gain)
@@ -376,6 +403,76 @@ class Engine:
             _ptr(best)))
         return ll, delta, best
 
+    def pattern_log_likelihoods(self, parent_ids, branch_lengths, params=None, rescaling=False):
+        """Per-pattern log-likelihoods per tree (mi_engine_pattern_log_likelihoods_unrooted; an
+        extension, 4-state engines): returns (log-likelihoods [T] -- what log_likelihoods returns,
+        bit for bit --, log L_p [T][P], unweighted; a pattern of likelihood 0 gives -inf)."""
+        n, P = self.taxon_count, self.pattern_count
+        pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
+        T = pid.shape[0]
+        if T == 0:
+            return np.empty(0), np.empty((0, P))
+        bl = _np(branch_lengths, np.float64).reshape(T, 2 * n - 2)
+        pr = self._params(params, T)
+        ll, s = np.empty(T), np.empty((T, P))
+        self._check(self._lib.mi_engine_pattern_log_likelihoods_unrooted(
+            self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), _ptr(ll), _ptr(s)))
+        return ll, s
+
+    def rell(self, pattern_log_likelihoods, replicate_weights, replicate_log_likelihoods=True):
+        """RELL re-summation (mi_engine_rell): s [T][P], W [B][P] -> (C [B][T] = W s^T or None,
+        best tree [B], bootstrap proportions [T], expected-likelihood weights [T]).  Any engine
+        serves: P is the matrices'.  replicate_log_likelihoods=False: C stays on the device."""
+        s = _np(pattern_log_likelihoods, np.float64)
+        w = _np(replicate_weights, np.float64)
+        if s.ndim != 2 or w.ndim != 2 or s.shape[1] != w.shape[1]:
+            raise RuntimeError("rell: pattern log-likelihoods [T][P] and replicate weights [B][P] "
+                               f"must share P; got {s.shape} and {w.shape}")
+        (T, P), B = s.shape, w.shape[0]
+        c = np.empty((B, T)) if replicate_log_likelihoods else None
+        best, bp, elw = np.empty(B, np.int32), np.empty(T), np.empty(T)
+        self._check(self._lib.mi_engine_rell(self._h, B, T, P, _ptr(s), _ptr(w), _ptr(c), _ptr(best),
+                                             _ptr(bp), _ptr(elw)))
+        return c, best, bp, elw
+
+    def rell_bootstrap(self, parent_ids, branch_lengths, replicate_weights, params=None,
+                       rescaling=False):
+        """Per-pattern log-likelihoods and their RELL re-summation in one host call
+        (mi_engine_rell_bootstrap_unrooted; single-device 4-state engines): replicate_weights
+        [B][P] (rell_weights makes them).  Returns a RellResult."""
+        n, P = self.taxon_count, self.pattern_count
+        pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
+        T = pid.shape[0]
+        w = _np(replicate_weights, np.float64)
+        if w.ndim != 2 or w.shape[1] != P:
+            raise RuntimeError(f"replicate weights must be [B][{P}]; got {w.shape}")
+        B = w.shape[0]
+        bl = _np(branch_lengths, np.float64).reshape(T, 2 * n - 2)
+        pr = self._params(params, T)
+        out = RellResult(np.empty(T), np.empty((T, P)), np.empty((B, T)), np.empty(B, np.int32),
+                         np.empty(T), np.empty(T))
+        self._check(self._lib.mi_engine_rell_bootstrap_unrooted(
+            self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), B, _ptr(w),
+            _ptr(out.log_likelihood), _ptr(out.pattern_log_likelihood),
+            _ptr(out.replicate_log_likelihood), _ptr(out.best_tree), _ptr(out.bootstrap_proportion),
+            _ptr(out.expected_likelihood_weight)))
+        return out
+
+    def pattern_mixture(self, pattern_log_likelihoods, pattern_weights, tree_log_weights=None):
+        """Marginal of a mixture of trees (mi_engine_pattern_mixture): s [T][P], pattern weights
+        [P], log tree weights [T] (None: log(1/T) each) -> (logsumexp_t(s[t][p] + lw_t) [P], its
+        weighted sum over the patterns).  Any engine serves."""
+        s = _np(pattern_log_likelihoods, np.float64)
+        if s.ndim != 2:
+            raise RuntimeError("pattern_mixture: pattern log-likelihoods must be [T][P]")
+        T, P = s.shape
+        pw = _np(pattern_weights, np.float64).reshape(P)
+        lw = None if tree_log_weights is None else _np(tree_log_weights, np.float64).reshape(T)
+        out, total = np.empty(P), np.empty(1)
+        self._check(self._lib.mi_engine_pattern_mixture(self._h, T, P, _ptr(s), _ptr(lw), _ptr(pw),
+                                                        _ptr(out), _ptr(total)))
+        return out, float(total[0])
+
     def optimize_branch_lengths(self, parent_ids, start_branch_lengths, params=None,
                                 rescaling=False, max_iterations=100, check_interval=4,
                                 pack_active=True, tolerance=1e-6, min_length=1e-8,
@@ -591,6 +688,33 @@ class Engine:
     def reserve_nni_search(self, tree_count):
         """mi_engine_reserve_nni_search: workspace of a search or apply call of that size."""
         self._check(self._lib.mi_engine_reserve_nni_search(self._h, int(tree_count)))
+
+    def pattern_log_likelihoods_device(self, stream, T, parent_ids, branch_lengths, params,
+                                       out_pattern_ll, out_ll=None, rescaling=False):
+        """mi_engine_pattern_log_likelihoods_unrooted_device: device pointers, enqueued on
+        `stream` (no allocation after reserve(T, False))."""
+        self._check(self._lib.mi_engine_pattern_log_likelihoods_unrooted_device(
+            self._h, stream, T, parent_ids, branch_lengths, params, int(rescaling), out_ll,
+            out_pattern_ll))
+
+    def rell_device(self, stream, B, T, P, pattern_ll, replicate_weights, out_bp, out_replicate_ll=None,
+                    out_best=None, out_elw=None):
+        """mi_engine_rell_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_rell_device(
+            self._h, stream, int(B), int(T), int(P), pattern_ll, replicate_weights, out_replicate_ll,
+            out_best, out_bp, out_elw))
+
+    def reserve_rell(self, replicate_count, tree_count, pattern_count):
+        """mi_engine_reserve_rell: workspace of a RELL call of that size."""
+        self._check(self._lib.mi_engine_reserve_rell(self._h, int(replicate_count), int(tree_count),
+                                                     int(pattern_count)))
+
+    def pattern_mixture_device(self, stream, T, P, pattern_ll, pattern_weights, out_pattern_log_marginal,
+                               out_log_marginal, tree_log_weights=None):
+        """mi_engine_pattern_mixture_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_pattern_mixture_device(
+            self._h, stream, int(T), int(P), pattern_ll, tree_log_weights, pattern_weights,
+            out_pattern_log_marginal, out_log_marginal))
 
     def reserve_reduced(self, tree_count, index_count):
         """mi_engine_reserve_reduced: workspace of a fused-reduction call (graph capture)."""
