@@ -266,6 +266,46 @@ int32_t mi_engine_pattern_log_likelihoods_unrooted(mi_engine* engine, int32_t tr
                                                    double* out_log_likelihoods /* [T] or NULL */,
                                                    double* out_pattern_log_likelihoods /* [T][P] */);
 
+/* Marginal ancestral-state and rate-category posteriors per pattern (an extension: no
+ * counterpart in the reference's Engine), from one post-order and pre-order
+ * walk per tree.  The tree is unrooted, in the caller's form: leaves 0..n-1, internal nodes
+ * n..2n-3 in post-order, the trifurcating root 2n-3.  The model has 4 states, K categories with
+ * weights c_k and rates r_k and stationary frequencies pi.  For an internal node v below the
+ * root L_v,k is the post-order vector at v and q_v,k the pre-order vector at the bottom of the
+ * branch above v (the Hessian call's convention: L_p = sum_k c_k q . L at every branch); at the
+ * root q = pi and L is the product of the three child messages.  Per tree t and pattern p:
+ *   J[v][s]                          = sum_k c_k q_v,k[s] L_v,k[s]
+ *   out_state_posteriors[t][v-n][p][s] = J[v][s] / sum_s' J[v][s']        v = n .. 2n-3
+ *   out_map_state[t][v-n][p]         = the s of the largest posterior, the lowest among equals
+ *   C[k]                             = c_k sum_s pi_s L_root,k[s]
+ *   out_category_posteriors[t][p][k] = C[k] / sum_k' C[k']
+ *   out_pattern_rate[t][p]           = sum_k r_k out_category_posteriors[t][p][k]
+ *   out_tip_posteriors[t][v][p][s]   = (q_v o L_v) normalised in the same way at the leaves
+ *                                      v = 0 .. n-1: the tip vector itself for an unambiguous
+ *                                      tip, an imputation for gaps, 0/1 masks and tip partials
+ * The denominator is the sum of the numerators as computed (the pattern likelihood from
+ * elsewhere is not used), so a row sums to 1 to rounding.  Under rescaling one power of two is
+ * removed per node and pattern across all categories; it sits in every numerator alike and
+ * cancels: rescaled and unrescaled results agree to rounding, not bit for bit.  Values are
+ * unweighted; patterns of weight 0 are reported like the others.  A pattern of likelihood 0
+ * gives NaN rows (0/0) and map state 0.  K = 1 gives category posterior 1 exactly and
+ * out_pattern_rate = r_0.  out_log_likelihoods is that of a gradient call on the HBM path, bit
+ * for bit.  One evaluation per tree with the tree's own model row (a GTR engine: no
+ * finite-difference passes).  Only out_state_posteriors is required; every other output may be
+ * NULL and then costs no work.  4-state engines only: a 20-state engine returns nonzero.
+ * Sharded handles: MI_SHARD_TREES deals the trees as the other calls do, rows in tree order;
+ * MI_SHARD_PATTERNS is refused (each shard holds a block of columns). */
+int32_t mi_engine_ancestral_states_unrooted(mi_engine* engine, int32_t tree_count,
+                                            const int32_t* parent_ids,     /* [T][2n-3] */
+                                            const double* branch_lengths,  /* [T][2n-2] */
+                                            const double* params, int32_t rescaling,
+                                            double* out_log_likelihoods /* [T] or NULL */,
+                                            double* out_state_posteriors /* [T][n-2][P][4] */,
+                                            int8_t* out_map_state /* [T][n-2][P] or NULL */,
+                                            double* out_category_posteriors /* [T][P][K] or NULL */,
+                                            double* out_pattern_rate /* [T][P] or NULL */,
+                                            double* out_tip_posteriors /* [T][n][P][4] or NULL */);
+
 /* RELL re-summation (resampling of estimated log-likelihoods) and its reductions (an extension;
  * DESIGN.md 4.12), for B replicates, T trees and P patterns -- P is an argument: any engine
  * serves (the alignment plays no part), a sharded handle lets its first shard do it.
@@ -520,6 +560,15 @@ int32_t mi_engine_nni_scan_unrooted_device(mi_engine* engine, void* stream, int3
                                            double* out_log_likelihoods, double* out_nni_delta,
                                            int32_t* out_best_move);
 
+/* The device form of mi_engine_ancestral_states_unrooted: it only enqueues -- no allocation
+ * and no synchronisation after mi_engine_reserve_ancestral(engine, tree_count), so it can be
+ * captured in a hipGraph.  Output addresses are multiples of 16 bytes. */
+int32_t mi_engine_ancestral_states_unrooted_device(
+    mi_engine* engine, void* stream, int32_t tree_count, const int32_t* parent_ids,
+    const double* branch_lengths, const double* params, int32_t rescaling, double* out_log_likelihoods,
+    double* out_state_posteriors, int8_t* out_map_state, double* out_category_posteriors,
+    double* out_pattern_rate, double* out_tip_posteriors);
+
 /* The device forms of mi_engine_pattern_log_likelihoods_unrooted, mi_engine_rell and
  * mi_engine_pattern_mixture: they only enqueue -- no allocation and no synchronisation after
  * mi_engine_reserve(tree_count, 0), mi_engine_reserve_rell and (the mixture) a first call of
@@ -590,6 +639,10 @@ int32_t mi_engine_reserve_hessian(mi_engine* engine, int32_t tree_count);
 /* The workspace of mi_engine_nni_scan_unrooted[_device] for `tree_count` trees: a *_device
  * call of at most that size then allocates nothing (hipGraph capture).  4-state engines only. */
 int32_t mi_engine_reserve_nni_scan(mi_engine* engine, int32_t tree_count);
+/* The workspace of mi_engine_ancestral_states_unrooted[_device] for `tree_count` trees, of
+ * either rescaling setting: a *_device call of at most that size then allocates nothing
+ * (hipGraph capture).  4-state engines only. */
+int32_t mi_engine_reserve_ancestral(mi_engine* engine, int32_t tree_count);
 /* The workspace of mi_engine_optimize_branch_lengths_unrooted[_device] for `tree_count` trees
  * (the Hessian call's included): a *_device call of at most that size then allocates
  * nothing.  4-state engines only. */

@@ -73,6 +73,17 @@ struct RellBootstrapResult {
   std::vector<double> bootstrap_proportion_, expected_likelihood_weight_;
 };
 
+// Engine::AncestralStates, per tree (an extension, include/mi_phylo.h), per pattern and
+// unweighted: state_posteriors_ [n-2][P][4] of the internal nodes n .. 2n-3 (row v - n) and, asked
+// for, map_states_ [n-2][P], category_posteriors_ [P][K] with pattern_rates_ [P], and
+// tip_posteriors_ [n][P][4]; what was not asked for stays empty
+struct AncestralStatePosteriors {
+  double log_likelihood_ = 0.;
+  std::vector<double> state_posteriors_;
+  std::vector<int8_t> map_states_;
+  std::vector<double> category_posteriors_, pattern_rates_, tip_posteriors_;
+};
+
 // Engine::OptimizeBranchLengths, per tree (an extension, include/mi_phylo.h): the
 // maximum-likelihood branch lengths [2n-2] and the Hessian call's outputs at them [2n-1]
 struct BranchOptimum {
@@ -278,6 +289,39 @@ class Engine {
       out[t].log_likelihood_ = ll[t];
       out[t].delta_.assign(d.begin() + t * N * 2, d.begin() + (t + 1) * N * 2);
       out[t].best_move_ = best[t];
+    }
+    return out;
+  }
+
+  // Marginal ancestral-state posteriors per tree, internal node and pattern (an extension;
+  // 4-state engines): mi_engine_ancestral_states_unrooted.
+  std::vector<AncestralStatePosteriors> AncestralStates(const UnrootedTreeCollection& trees,
+                                                        const ParamMatrix& params, const bool rescaling,
+                                                        const bool map_states = false, const bool categories = false,
+                                                        const bool tips = false) const {
+    const size_t T = trees.size(), n = site_pattern_.SequenceCount(), P = site_pattern_.PatternCount();
+    const size_t K = static_cast<size_t>(category_count_), rows = (n - 2) * P;
+    std::vector<int32_t> parents;
+    std::vector<double> bl;
+    Flatten(trees, params, false, &parents, &bl);
+    if (trees.empty()) return {};
+    std::vector<double> ll(T), state(T * rows * 4), cat(categories ? T * P * K : 0), rate(categories ? T * P : 0),
+        tip(tips ? T * n * P * 4 : 0);
+    std::vector<int8_t> map(map_states ? T * rows : 0);
+    Check(mi_engine_ancestral_states_unrooted(handle_, static_cast<int32_t>(T), parents.data(), bl.data(),
+                                              params.data.data(), rescaling, ll.data(), state.data(),
+                                              map_states ? map.data() : nullptr, categories ? cat.data() : nullptr,
+                                              categories ? rate.data() : nullptr, tips ? tip.data() : nullptr));
+    std::vector<AncestralStatePosteriors> out(T);
+    for (size_t t = 0; t < T; t++) {
+      out[t].log_likelihood_ = ll[t];
+      out[t].state_posteriors_.assign(state.begin() + t * rows * 4, state.begin() + (t + 1) * rows * 4);
+      if (map_states) out[t].map_states_.assign(map.begin() + t * rows, map.begin() + (t + 1) * rows);
+      if (categories) {
+        out[t].category_posteriors_.assign(cat.begin() + t * P * K, cat.begin() + (t + 1) * P * K);
+        out[t].pattern_rates_.assign(rate.begin() + t * P, rate.begin() + (t + 1) * P);
+      }
+      if (tips) out[t].tip_posteriors_.assign(tip.begin() + t * n * P * 4, tip.begin() + (t + 1) * n * P * 4);
     }
     return out;
   }

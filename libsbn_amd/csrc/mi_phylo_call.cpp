@@ -136,6 +136,15 @@ CallPlan plan_call(const mi_engine* e, CallKind kind, int T, bool rescaling, int
     p.dominant = nni_scan_kernel_name();
     return p;
   }
+  if (kind == kAncestralCall) {
+    // Ancestral-state and rate-category posteriors: as the scan -- one evaluation
+    // per tree with the tree's own model, node-ordered matrices, the HBM-streamed kernel.
+    p.Eg = T;
+    p.g_tiles = e->tiles;
+    p.store = kStoreHbm;
+    p.dominant = ancestral_kernel_name();
+    return p;
+  }
   // on-chip gradient kernels: the matrix-core one (K <= 4; rescaling supported) or the
   // VALU one (no rescaling); everything else takes the HBM-streamed kernel
   p.mfma = gradient && matrix_core_gradient(e, rescaling, p.loglik_is_valu);
@@ -241,6 +250,7 @@ std::string plan_path(const mi_engine* e, const CallPlan& p) {
   path += p.fuse_setup ? " setup=in-walk" : (p.setup_records ? " setup=with-records" : " setup=own-launch");
   if (p.kind == kHessianCall) path += " hess";
   if (p.kind == kNniCall) path += " nni";
+  if (p.kind == kAncestralCall) path += " ancestral";
   if (p.pattern_ll) path += " pattern_ll";
   if (p.tile_regs > kLlR) path += " tile=wide";
   if (p.fd_pass) path += " fd=16";
@@ -467,6 +477,14 @@ LikArgs lik_args(const mi_engine* e, const DeviceCall& d, const CallPlan& p) {
   la.status = e->status.as<int32_t>();
   la.slot_need = e->slot_need.as<int32_t>();
   la.store = p.store;  // (the launchers follow the choice the schedules were made for)
+  if (p.kind == kAncestralCall) {
+    la.anc_state = d.out_anc_state;
+    la.anc_map = d.out_anc_map;
+    la.anc_cat = d.out_anc_cat;
+    la.anc_rate = d.out_anc_rate;
+    la.anc_tip = d.out_anc_tip;
+    return la;
+  }
   if (p.kind == kHessianCall || p.kind == kNniCall) return la;  // (their kernels read none of the following)
   la.tip_tables = e->tip_tables.as<double>();
   la.mphi = e->mphi.as<double>();
@@ -827,6 +845,62 @@ int run_nni_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   fa.out_delta = d.out_nni;
   fa.out_best = d.out_best;
   launch_nni_finalize(fa, s);
+  PROF_MARK(e, marks, 4, s);
+  if (prof) e->prof_used++;
+  note_call(e, p, first, walk_launches);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- ancestral-state and rate-category posteriors (mi_engine_ancestral_states_unrooted*) ----
+// Tree set-up and model instances, the node-ordered matrices, the kernel over the vector arena in
+// parts (it writes the posteriors itself, by the call's tree index); one launch sums the tiles'
+// log-likelihood partials when the caller wants the log-likelihoods.
+int reserve_ancestral(mi_engine* e, const CallPlan& p) {
+  const int n = e->n, N = e->N, T = p.T;
+  const size_t per = plv_bytes_per_eval(e);
+  const size_t chunk = std::max<size_t>(1, std::min<size_t>(T, e->plv_budget / per));
+  if (e->plv.ensure(per * chunk)) return 1;
+  if (e->tree_scratch.ensure(sizeof(int32_t) * (size_t)T * 13 * N)) return 1;
+  if (e->sched.ensure(sizeof(SchedEntry) * (size_t)T * (n - 1))) return 1;
+  if (e->macro_count.ensure(sizeof(int32_t) * (size_t)T)) return 1;
+  if (e->bl_eff.ensure(sizeof(double) * (size_t)T * N)) return 1;
+  if (e->models.ensure(sizeof(DevModel) * (size_t)T)) return 1;
+  if (e->mats.ensure(sizeof(double) * (size_t)T * (N - 1) * e->K * 16)) return 1;
+  if (e->ll_part.ensure(sizeof(double) * (size_t)T * e->ll_stride)) return 1;
+  return e->status.ensure(sizeof(int32_t) * kStatusWords);
+}
+// (the plan does not depend on the rescaling setting: one reservation serves both)
+int reserve_ancestral_calls(mi_engine* e, int T) { return reserve_ancestral(e, plan_call(e, kAncestralCall, T, false)); }
+
+int run_ancestral_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
+  HIP_TRY(hipSetDevice(e->spec.device));
+  if (e->s == kAa) return fail(kAncestral4State);
+  if (check_call(e, d, d.out_anc_state)) return 1;
+  const CallPlan p = plan_call(e, kAncestralCall, d);
+  if (reserve_ancestral(e, p)) return 1;
+  const int T = d.T;
+  const bool prof = e->prof_used < e->prof_capacity;
+  const bool marks = prof && e->prof_phases;
+  PROF_MARK(e, marks, 0, s);
+  launch_setup(tree_setup_args(e, d, p), model_setup_args(e, d, p), e->sw, s);
+  launch_transition(transition_args(e, d, p), s);
+
+  const LikArgs la = lik_args(e, d, p);
+  if (prof) HIP_TRY(hipEventRecord(prof_event(e, 0), s));
+  PROF_MARK(e, marks, 1, s);
+  PROF_MARK(e, marks, 2, s);
+  // (a launch covers what the vector arena holds)
+  int walk_launches = 0;
+  const int first = launch_in_parts(e, T, vector_bytes_per_eval(e, p), walk_launches, [&](int done, int part) {
+    LikArgs g = la;
+    g.eval_offset = done;
+    g.grad_offset = done;
+    launch_ancestral_hbm(g, part, d.rescaling, s);
+  });
+  if (prof) HIP_TRY(hipEventRecord(prof_event(e, 1), s));
+  PROF_MARK(e, marks, 3, s);
+  launch_ancestral_finalize(e->ll_part.as<double>(), T, e->ll_stride, p.g_tiles, d.out_ll, s);
   PROF_MARK(e, marks, 4, s);
   if (prof) e->prof_used++;
   note_call(e, p, first, walk_launches);

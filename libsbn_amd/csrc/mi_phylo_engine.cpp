@@ -91,6 +91,7 @@ const char kShardedDeviceCall[] =
 const char kHessian4State[] = "the branch-length Hessian call is 4-state only";
 const char kNni4State[] = "the NNI neighbourhood scan is 4-state only";
 const char kPatternLl4State[] = "per-pattern log-likelihoods are 4-state only";
+const char kAncestral4State[] = "the ancestral-state call is 4-state only";
 
 extern "C" {
 
@@ -700,6 +701,39 @@ int32_t mi_engine_reserve_nni_scan(mi_engine* e, int32_t tree_count) {
   if (!e->shards.empty()) return for_each_shard(e, tree_count, mi_engine_reserve_nni_scan);
   HIP_TRY(hipSetDevice(e->spec.device));
   return reserve_nni_calls(e, tree_count);
+}
+
+int32_t mi_engine_ancestral_states_unrooted_device(mi_engine* e, void* stream, int32_t T,
+                                                   const int32_t* parent_ids, const double* bl,
+                                                   const double* params, int32_t rescaling, double* out_ll,
+                                                   double* out_state, int8_t* out_map, double* out_cat,
+                                                   double* out_rate, double* out_tip) {
+  if (!e) return fail("null engine");
+  if (e->s == kAa) return fail(kAncestral4State);
+  if (!e->shards.empty()) return fail(kShardedDeviceCall);
+  if (!out_state) return fail("null state-posterior output");
+  DeviceCall d;
+  d.T = T;
+  d.rescaling = rescaling != 0;
+  d.parent_ids = parent_ids;
+  d.bl = bl;
+  d.params = params;
+  d.out_ll = out_ll;
+  d.out_anc_state = out_state;
+  d.out_anc_map = out_map;
+  d.out_anc_cat = out_cat;
+  d.out_anc_rate = out_rate;
+  d.out_anc_tip = out_tip;
+  return run_ancestral_device(e, pick_stream(e, stream), d);
+}
+
+int32_t mi_engine_reserve_ancestral(mi_engine* e, int32_t tree_count) {
+  if (!e) return fail("null engine");
+  if (tree_count <= 0) return fail("tree_count must be positive");
+  if (e->s == kAa) return fail(kAncestral4State);
+  if (!e->shards.empty()) return for_each_shard(e, tree_count, mi_engine_reserve_ancestral);
+  HIP_TRY(hipSetDevice(e->spec.device));
+  return reserve_ancestral_calls(e, tree_count);
 }
 
 int32_t mi_engine_log_likelihoods_rooted_device(mi_engine* e, void* stream, int32_t T,

@@ -3,7 +3,7 @@
 //   mi_phylo_engine.cpp       engine creation / destruction, status, profiling, the thin
 //                             device-pointer entry points of the C ABI
 //   mi_phylo_call.cpp         the call plan (which route a call takes: plan_call), reservation,
-//                             the argument-block builders, the 4-state, Hessian and NNI-scan call sequences
+//                             the argument-block builders, the 4-state, Hessian, NNI-scan and ancestral-state call sequences
 //   mi_phylo_branch_opt.cpp   branch-length optimisation
 //   mi_phylo_nni.cpp          mi_nni_neighbour, the scan's best move on the host (no device code)
 //   mi_phylo_nni_search.cpp   NNI moves on the device, the NNI hill-climbing search
@@ -222,7 +222,7 @@ inline hipEvent_t prof_event(mi_engine* e, int which) {
 // (reserve, reserve_hessian), the argument-block builders, the call sequences and the path
 // string (plan_path) read the plan -- so a reserve cannot guess differently from the call it
 // reserves for (and leave that call to allocate inside a hipGraph capture).
-enum CallKind { kLogLikCall, kGradientCall, kHessianCall, kNniCall };
+enum CallKind { kLogLikCall, kGradientCall, kHessianCall, kNniCall, kAncestralCall };
 enum WalkStore { kStoreHbm = 0, kStoreLds = 1, kStoreArena = 2 };  // (LikArgs::store: 0 = not a matrix-core walk)
 struct CallPlan {
   CallKind kind;
@@ -280,6 +280,12 @@ struct DeviceCall {
   int32_t* out_best = nullptr;  // [T]
   // per-pattern log-likelihoods (a log-likelihood call; out_ll may be nullptr there)
   double* out_pattern_ll = nullptr;  // [T][P]
+  // ancestral states (run_ancestral_device): all but out_anc_state, and out_ll, may be nullptr there
+  double* out_anc_state = nullptr;  // [T][n-2][P][4]
+  int8_t* out_anc_map = nullptr;    // [T][n-2][P]
+  double* out_anc_cat = nullptr;    // [T][P][K]
+  double* out_anc_rate = nullptr;   // [T][P]
+  double* out_anc_tip = nullptr;    // [T][n][P][4]
   // ... as one pass of the branch-length optimisation: the batch size the kernel and its store
   // are chosen for (the whole batch's, so that a tree's results do not depend on how many
   // trees are still active); 0: T
@@ -308,6 +314,9 @@ int run_hessian_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
 int reserve_nni(mi_engine* e, const CallPlan& p);
 int reserve_nni_calls(mi_engine* e, int T);  // of either rescaling setting (mi_engine_reserve_nni_scan)
 int run_nni_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
+int reserve_ancestral(mi_engine* e, const CallPlan& p);
+int reserve_ancestral_calls(mi_engine* e, int T);  // of either rescaling setting (mi_engine_reserve_ancestral)
+int run_ancestral_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
 // the scan's best move from a tree's delta [N][2] (what the finalize kernel does; pattern shards)
 int32_t nni_best_move(int n, const double* delta);
 
@@ -334,7 +343,7 @@ int check_branch_opt_options(const mi_branch_opt_options& o);
 int run_branch_opt_device(mi_engine* e, hipStream_t s, const BranchOptCall& c);
 
 // ---- mi_phylo_engine.cpp ----
-extern const char kShardedDeviceCall[], kHessian4State[], kNni4State[], kPatternLl4State[];
+extern const char kShardedDeviceCall[], kHessian4State[], kNni4State[], kPatternLl4State[], kAncestral4State[];
 int check_status(mi_engine* e, hipStream_t s);
 inline hipStream_t pick_stream(mi_engine* e, void* stream) {
   return stream ? static_cast<hipStream_t>(stream) : e->stream;

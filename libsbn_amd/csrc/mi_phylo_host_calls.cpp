@@ -36,6 +36,13 @@ struct HostCall {
   // per-pattern log-likelihoods (mi_engine_pattern_log_likelihoods_unrooted): out_ll may be null there
   bool pattern = false;
   double* out_pattern = nullptr;  // [T][P]
+  // ancestral states (mi_engine_ancestral_states_unrooted): out_ll and all but out_anc_state may be null there
+  bool ancestral = false;
+  double* out_anc_state = nullptr;  // [T][n-2][P][4]
+  int8_t* out_anc_map = nullptr;    // [T][n-2][P]
+  double* out_anc_cat = nullptr;    // [T][P][K]
+  double* out_anc_rate = nullptr;   // [T][P]
+  double* out_anc_tip = nullptr;    // [T][n][P][4]
   // fused reductions of a variational-inference step (mi_engine_gradients_unrooted_reduced)
   bool reduced = false;
   const int32_t* branch_index = nullptr;  // [T][N]
@@ -180,6 +187,25 @@ int begin_host_call(mi_engine* e, const HostCall& h) {
       return 1;
     return download_pack(e, outs);
   }
+  if (h.ancestral) {
+    // (what nobody asked for is neither computed nor placed nor copied)
+    double *o_state, *o_map, *o_cat, *o_rate, *o_tip;
+    const size_t P = e->P, rows = (size_t)T * (n - 2) * P;
+    const std::initializer_list<OutPiece> outs = {{h.out_ll, h.out_ll ? (size_t)T : 0, &o_ll},
+                                                  {h.out_anc_state, rows * 4, &o_state},
+                                                  {h.out_anc_map, h.out_anc_map ? rows : 0, &o_map, sizeof(int8_t)},
+                                                  {h.out_anc_cat, h.out_anc_cat ? (size_t)T * P * e->K : 0, &o_cat},
+                                                  {h.out_anc_rate, h.out_anc_rate ? (size_t)T * P : 0, &o_rate},
+                                                  {h.out_anc_tip, h.out_anc_tip ? (size_t)T * n * P * 4 : 0, &o_tip}};
+    if (place_out_pack(e, outs)) return 1;
+    if (mi_engine_ancestral_states_unrooted_device(e, e->stream, T, P32(d_parent), F64(d_bl), F64(d_params), h.rescaling,
+                                                   h.out_ll ? o_ll : nullptr, o_state,
+                                                   h.out_anc_map ? reinterpret_cast<int8_t*>(o_map) : nullptr,
+                                                   h.out_anc_cat ? o_cat : nullptr, h.out_anc_rate ? o_rate : nullptr,
+                                                   h.out_anc_tip ? o_tip : nullptr))
+      return 1;
+    return download_pack(e, outs);
+  }
   if (!h.gradient) {
     const std::initializer_list<OutPiece> outs = {{h.out_ll, (size_t)T, &o_ll}};
     if (place_out_pack(e, outs)) return 1;
@@ -287,6 +313,11 @@ int run_sharded(mi_engine* e, const HostCall& h) {
       if (h.out_nni) s.out_nni = h.out_nni + (size_t)b * N * 2;
       if (h.out_best) s.out_best = h.out_best + b;
       if (h.out_pattern) s.out_pattern = h.out_pattern + (size_t)b * e->P;
+      if (h.out_anc_state) s.out_anc_state = h.out_anc_state + (size_t)b * (n - 2) * e->P * 4;
+      if (h.out_anc_map) s.out_anc_map = h.out_anc_map + (size_t)b * (n - 2) * e->P;
+      if (h.out_anc_cat) s.out_anc_cat = h.out_anc_cat + (size_t)b * e->P * e->K;
+      if (h.out_anc_rate) s.out_anc_rate = h.out_anc_rate + (size_t)b * e->P;
+      if (h.out_anc_tip) s.out_anc_tip = h.out_anc_tip + (size_t)b * n * e->P * 4;
       if (h.reduced) {
         s.branch_index = h.branch_index + (size_t)b * N;
         if (h.tree_weights) s.tree_weights = h.tree_weights + b;
@@ -317,6 +348,9 @@ int run_sharded(mi_engine* e, const HostCall& h) {
   if (h.pattern)
     return fail("pattern-sharded engines do not hand out per-pattern log-likelihoods (each shard holds a "
                 "block of columns): use MI_SHARD_TREES or a single engine");
+  if (h.ancestral)
+    return fail("pattern-sharded engines do not hand out per-pattern posteriors (each shard holds a block of "
+                "columns): use MI_SHARD_TREES or a single engine");
   if (h.rooted)
     return fail("pattern-sharded engines evaluate unrooted calls only (the log-det-Jacobian "
                 "and the rooted chain rule are not sums over site patterns)");
@@ -496,6 +530,28 @@ int32_t mi_engine_pattern_log_likelihoods_unrooted(mi_engine* e, int32_t T, cons
   h.params = params;
   h.out_ll = out_ll;
   h.out_pattern = out_pattern_ll;
+  return run_host(e, h);
+}
+
+int32_t mi_engine_ancestral_states_unrooted(mi_engine* e, int32_t T, const int32_t* parent_ids, const double* bl,
+                                            const double* params, int32_t rescaling, double* out_ll,
+                                            double* out_state, int8_t* out_map, double* out_cat, double* out_rate,
+                                            double* out_tip) {
+  if (!out_state) return fail("null state-posterior output");
+  if (e && e->s == kAa) return fail(kAncestral4State);
+  HostCall h;
+  h.ancestral = true;
+  h.T = T;
+  h.rescaling = rescaling;
+  h.parent_ids = parent_ids;
+  h.bl = bl;
+  h.params = params;
+  h.out_ll = out_ll;
+  h.out_anc_state = out_state;
+  h.out_anc_map = out_map;
+  h.out_anc_cat = out_cat;
+  h.out_anc_rate = out_rate;
+  h.out_anc_tip = out_tip;
   return run_host(e, h);
 }
 

@@ -131,6 +131,13 @@ struct LikArgs {
   int lds_lo;                  // arena gradient kernel: this launch takes trees with lds_lo < need <= lds_slots
   double* pattern_ll;          // [T][P] log-likelihood kernels' PATTERN_LL variant: unweighted log L_p per (tree, pattern); else nullptr
   const uint8_t* pattern_blank;  // [P] PATTERN_LL variant: 1 where every tip vector of the pattern is all ones (L_p = 1 exactly: reported as 0.0)
+  // ancestral_hbm_kernel (kernels_ancestral.hip) only, by the call's tree index; nullptr in every
+  // other call, and there each but anc_state may be nullptr (no work, no stores)
+  double* anc_state;  // [T][n-2][P][4] state posteriors of the internal nodes n .. 2n-3
+  int8_t* anc_map;    // [T][n-2][P] their largest entry
+  double* anc_cat;    // [T][P][K] rate-category posteriors
+  double* anc_rate;   // [T][P] posterior mean rate
+  double* anc_tip;    // [T][n][P][4] state posteriors at the leaves
 };
 
 // How many logL partial sums each evaluation's walk kernel wrote (the kernels tile the
@@ -231,6 +238,15 @@ struct NniFinalizeArgs {
   int32_t* out_best;      // [T] or nullptr: 2 v + i of the largest delta (-1: no inner edge)
 };
 void launch_nni_finalize(const NniFinalizeArgs& a, hipStream_t s);
+// Marginal ancestral-state and rate-category posteriors (kernels_ancestral.hip):
+// the HBM-streamed walk with, per internal node and pattern, the normalised joint of the node's
+// state and the data (LikArgs::anc_*); one evaluation per tree.  Its log-likelihoods from the
+// tile partials [T][ll_tiles], the first ll_used of each, in the scan's order (out_ll == nullptr:
+// no launch).
+void launch_ancestral_hbm(const LikArgs& a, int count, bool rescale, hipStream_t s);
+void launch_ancestral_finalize(const double* ll_part, int T, int ll_tiles, int ll_used, double* out_ll,
+                               hipStream_t s);
+const char* ancestral_kernel_name();
 // Branch-length optimisation (kernels_branch_opt.hip): the step between two
 // Hessian passes and the packing of the active trees.  "Packed" arrays hold the trees that
 // are still being evaluated, in `map` order (map == nullptr: all trees, in their own order).

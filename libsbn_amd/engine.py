@@ -99,6 +99,23 @@ class RellResult:
     expected_likelihood_weight: np.ndarray
 
 
+@dataclass
+class AncestralStates:
+    """What Engine.ancestral_states returns, per tree and pattern, unweighted: the marginal
+    posterior of the state at the internal nodes n .. 2n-3 [T][n-2][P][4] (row v - n: node v; the
+    last row is the root) and the log-likelihoods [T]; on request the state of the largest
+    posterior [T][n-2][P] (int8, the lowest among equals), the rate-category posteriors [T][P][K]
+    with the posterior mean rates [T][P], and the state posteriors at the leaves [T][n][P][4]
+    (the tip vector itself for an unambiguous tip, an imputation otherwise).  A pattern of
+    likelihood 0 has NaN rows and map state 0."""
+    state_posteriors: np.ndarray
+    log_likelihoods: np.ndarray
+    map_states: np.ndarray = None
+    category_posteriors: np.ndarray = None
+    pattern_rates: np.ndarray = None
+    tip_posteriors: np.ndarray = None
+
+
 def rell_weights(weights, replicates, seed):
     """Replicate weights of a RELL bootstrap: multinomial resampling of sum(weights) sites over
     the patterns with numpy.random.default_rng(seed).  Returns float64 [replicates][P]; host
@@ -403,6 +420,29 @@ class Engine:
             _ptr(best)))
         return ll, delta, best
 
+    def ancestral_states(self, parent_ids, branch_lengths, params=None, rescaling=False,
+                         map_states=False, categories=False, tips=False):
+        """Marginal ancestral-state posteriors per tree, internal node and pattern
+        (mi_engine_ancestral_states_unrooted; an extension, 4-state engines): an AncestralStates
+        with state_posteriors and log_likelihoods -- those of a gradient call on the HBM path,
+        bit for bit -- and, asked for, map_states, category_posteriors with pattern_rates
+        (categories=True) and tip_posteriors.  What is not asked for is not computed."""
+        n, P, K = self.taxon_count, self.pattern_count, self.category_count
+        pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
+        T = pid.shape[0]
+        state, ll = np.empty((T, n - 2, P, 4)), np.empty(T)
+        mp = np.empty((T, n - 2, P), np.int8) if map_states else None
+        cat = np.empty((T, P, K)) if categories else None
+        rate = np.empty((T, P)) if categories else None
+        tip = np.empty((T, n, P, 4)) if tips else None
+        if T:
+            bl = _np(branch_lengths, np.float64).reshape(T, 2 * n - 2)
+            pr = self._params(params, T)
+            self._check(self._lib.mi_engine_ancestral_states_unrooted(
+                self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), _ptr(ll), _ptr(state),
+                _ptr(mp), _ptr(cat), _ptr(rate), _ptr(tip)))
+        return AncestralStates(state, ll, mp, cat, rate, tip)
+
     def pattern_log_likelihoods(self, parent_ids, branch_lengths, params=None, rescaling=False):
         """Per-pattern log-likelihoods per tree (mi_engine_pattern_log_likelihoods_unrooted; an
         extension, 4-state engines): returns (log-likelihoods [T] -- what log_likelihoods returns,
@@ -646,6 +686,21 @@ class Engine:
     def reserve_nni_scan(self, tree_count):
         """mi_engine_reserve_nni_scan: workspace of an NNI scan (graph capture)."""
         self._check(self._lib.mi_engine_reserve_nni_scan(self._h, int(tree_count)))
+
+    def ancestral_states_device(self, stream, T, parent_ids, branch_lengths, params,
+                                out_state_posteriors, out_ll=None, out_map_states=None,
+                                out_category_posteriors=None, out_pattern_rates=None,
+                                out_tip_posteriors=None, rescaling=False):
+        """mi_engine_ancestral_states_unrooted_device: device pointers, enqueued on `stream` (no
+        allocation after reserve_ancestral(T))."""
+        self._check(self._lib.mi_engine_ancestral_states_unrooted_device(
+            self._h, stream, T, parent_ids, branch_lengths, params, int(rescaling), out_ll,
+            out_state_posteriors, out_map_states, out_category_posteriors, out_pattern_rates,
+            out_tip_posteriors))
+
+    def reserve_ancestral(self, tree_count):
+        """mi_engine_reserve_ancestral: workspace of an ancestral-state call (graph capture)."""
+        self._check(self._lib.mi_engine_reserve_ancestral(self._h, int(tree_count)))
 
     def optimize_branch_lengths_device(self, stream, T, parent_ids, start_branch_lengths, params,
                                        out_branch_lengths, out_ll, out_status, out_branch=None,
