@@ -181,59 +181,11 @@ int run_branch_opt_device(mi_engine* e, hipStream_t s, const BranchOptCall& c) {
   return 0;
 }
 
-namespace {
-
-// The host-pointer form of the branch-length optimisation on one engine: inputs up in one
-// copy, the loop (which synchronises at its check points), outputs back in one copy and the
-// call's one error check.
-int run_branch_opt_host(mi_engine* e, const BranchOptCall& h) {
-  const int T = h.T, n = e->n, N = e->N;
-  if (T <= 0) return fail("tree_count must be positive");
-  if (!h.parent_ids || !h.start) return fail("null tree arrays");
-  if (!h.out_bl || !h.out_ll || !h.out_status) return fail("null output pointer");
-  if (e->param_count > 0 && !h.params) return fail("null parameter matrix");
-  HIP_TRY(hipSetDevice(e->spec.device));
-  e->fused_timed_out = false;
-  e->pinned.reset();
-  HIP_TRY(hipMemsetAsync(e->status.ptr, 0, sizeof(int32_t) * kStatusWords, e->stream));
-  const void *d_parent, *d_bl, *d_params;
-  if (upload_pack(e, {{h.parent_ids, sizeof(int32_t) * (size_t)T * (2 * n - 3), &d_parent},
-                      {h.start, sizeof(double) * (size_t)T * (2 * n - 2), &d_bl},
-                      {e->param_count > 0 ? h.params : nullptr, sizeof(double) * (size_t)T * e->param_count, &d_params}}))
-    return 1;
-  if (!d_params) d_params = e->in_pack.ptr;
-  double *o_bl, *o_ll, *o_g, *o_h, *o_iters, *o_status;  // (the last two: [T] int32)
-  const std::initializer_list<OutPiece> outs = {{h.out_bl, (size_t)T * (N - 1), &o_bl},
-                                                {h.out_ll, (size_t)T, &o_ll},
-                                                {h.out_g, h.out_g ? (size_t)T * N : 0, &o_g},
-                                                {h.out_h, h.out_h ? (size_t)T * N : 0, &o_h},
-                                                {h.out_iters, (size_t)T, &o_iters, sizeof(int32_t)},
-                                                {h.out_status, (size_t)T, &o_status, sizeof(int32_t)}};
-  if (place_out_pack(e, outs)) return 1;
-  BranchOptCall c = h;
-  c.parent_ids = static_cast<const int32_t*>(d_parent);
-  c.start = static_cast<const double*>(d_bl);
-  c.params = static_cast<const double*>(d_params);
-  c.out_bl = o_bl;
-  c.out_ll = o_ll;
-  c.out_g = h.out_g ? o_g : nullptr;
-  c.out_h = h.out_h ? o_h : nullptr;
-  c.out_iters = reinterpret_cast<int32_t*>(o_iters);
-  c.out_status = reinterpret_cast<int32_t*>(o_status);
-  if (run_branch_opt_device(e, e->stream, c)) return 1;
-  // one copy back; the pieces are handed over after the error check below
-  if (download_pack(e, outs)) return 1;
-  int rc = check_status(e, e->stream);
-  e->fused_timed_out = false;
-  if (rc == 0) e->pinned.flush();
-  e->pinned.reset();
-  return rc;
-}
-
-}  // namespace
-
 extern "C" {
 
+// The host-pointer form: inputs up in one copy, the loop (which synchronises at its check
+// points), outputs back in one copy and the call's one error check.  Each tree shard of a handle
+// optimises its block of trees independently, one shard after the other.
 int32_t mi_engine_optimize_branch_lengths_unrooted(
     mi_engine* e, int32_t T, const int32_t* parent_ids, const double* start, const double* params,
     int32_t rescaling, const mi_branch_opt_options* options, double* out_bl, double* out_ll,
@@ -242,55 +194,39 @@ int32_t mi_engine_optimize_branch_lengths_unrooted(
   if (e->s == kAa) return fail(kHessian4State);
   if (T <= 0) return fail("tree_count must be positive");
   if (check_branch_opt_options(options ? *options : kBranchOptDefaults)) return 1;
-  BranchOptCall c;
+  if (!e->shards.empty()) {
+    if (e->shard_mode != MI_SHARD_TREES)
+      return fail("pattern-sharded engines do not optimise branch lengths (every iteration would "
+                  "need a sum across the shards): use MI_SHARD_TREES or a single engine");
+    if (!parent_ids || !start || !out_bl || !out_ll || !out_status) return fail("null tree / output pointer");
+  }
+  if (!parent_ids || !start) return fail("null tree arrays");
+  if (!out_bl || !out_ll || !out_status) return fail("null output pointer");
+  if (e->param_count > 0 && !params) return fail("null parameter matrix");
+  enum { kBl, kLl, kG, kH, kIters, kStatus };
+  HostCall c;
   c.T = T;
-  c.rescaling = rescaling != 0;
-  c.parent_ids = parent_ids;
-  c.start = start;
-  c.params = params;
-  c.options = options;
-  c.out_bl = out_bl;
-  c.out_ll = out_ll;
-  c.out_g = out_g;
-  c.out_h = out_h;
-  c.out_iters = out_iters;
-  c.out_status = out_status;
-  if (e->shards.empty()) {
-    if (run_branch_opt_host(e, c)) {
-      e->pinned.reset();
-      return 1;
-    }
-    return 0;
-  }
-  if (e->shard_mode != MI_SHARD_TREES)
-    return fail("pattern-sharded engines do not optimise branch lengths (every iteration would "
-                "need a sum across the shards): use MI_SHARD_TREES or a single engine");
-  if (!parent_ids || !start || !out_bl || !out_ll || !out_status) return fail("null tree / output pointer");
-  // Each shard optimises its block of trees independently, one shard after the other (the
-  // loop synchronises its device at every check point).
-  const int D = (int)e->shards.size(), n = e->n, N = e->N;
-  for (int i = 0; i < D; i++) {
-    int32_t b = 0, cnt = 0;
-    mi_shard_range(T, D, i, &b, &cnt);
-    if (cnt == 0) continue;
-    BranchOptCall sc = c;
-    sc.T = cnt;
-    sc.parent_ids = parent_ids + (size_t)b * (2 * n - 3);
-    sc.start = start + (size_t)b * (2 * n - 2);
-    if (params) sc.params = params + (size_t)b * e->param_count;
-    sc.out_bl = out_bl + (size_t)b * (N - 1);
-    sc.out_ll = out_ll + b;
-    if (out_g) sc.out_g = out_g + (size_t)b * N;
-    if (out_h) sc.out_h = out_h + (size_t)b * N;
-    if (out_iters) sc.out_iters = out_iters + b;
-    sc.out_status = out_status + b;
-    e->shards[i]->status_tree_offset = b;
-    if (run_branch_opt_host(e->shards[i], sc)) {
-      e->shards[i]->pinned.reset();
-      return 1;
-    }
-  }
-  return 0;
+  c.one_by_one = true;
+  c.in = tree_inputs(e, parent_ids, start, params);
+  c.out = {per_tree(out_bl, e->N - 1), per_tree(out_ll, 1), per_tree(out_g, e->N),
+           per_tree(out_h, e->N),      per_tree(out_iters, 1), per_tree(out_status, 1)};
+  c.enqueue = [=](mi_engine* e, int T, const HostArray* in, const HostArray* out) {
+    BranchOptCall d;
+    d.T = T;
+    d.rescaling = rescaling != 0;
+    d.parent_ids = in[kInParent].at<const int32_t>();
+    d.start = in[kInBl].at<const double>();
+    d.params = params_on_device(e, in);
+    d.options = options;
+    d.out_bl = out[kBl].at<double>();
+    d.out_ll = out[kLl].at<double>();
+    d.out_g = out[kG].at<double>();
+    d.out_h = out[kH].at<double>();
+    d.out_iters = out[kIters].at<int32_t>();
+    d.out_status = out[kStatus].at<int32_t>();
+    return run_branch_opt_device(e, e->stream, d);
+  };
+  return run_host_call(e, c);
 }
 
 int32_t mi_engine_optimize_branch_lengths_unrooted_device(

@@ -64,7 +64,7 @@ int check_status(mi_engine* e, hipStream_t s) {
     // in the same batch -- status[0] keeps the FIRST code -- cannot hide it.  This engine takes
     // the four-launch sequence from now on (a hipGraph captured BEFORE this point still replays
     // the one-launch kernel: re-capture it); a host-pointer entry point runs the call again at
-    // once and returns its results (finish_host_call), a *_device caller gets the message
+    // once and returns its results (finish_host), a *_device caller gets the message
     // below.  (reduce_finalize has cleared every tree's hand-off word already; the memset makes
     // the "zero between calls" invariant independent of that.)
     e->fused_setup = false;

@@ -8,18 +8,19 @@
 //   mi_phylo_nni.cpp          mi_nni_neighbour, the scan's best move on the host (no device code)
 //   mi_phylo_nni_search.cpp   NNI moves on the device, the NNI hill-climbing search
 //   mi_phylo_rell.cpp         per-pattern log-likelihoods (device form), RELL re-summation, tree mixtures
-//   mi_phylo_host_calls.cpp   host-pointer entry points, sharded handles
+//   mi_phylo_host_calls.cpp   what runs a host-pointer call (staging, status, shards), the plain entry points
 //   mi_phylo_engine_aa.cpp    20-state call sequence
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
-#include <initializer_list>
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "../../include/mi_phylo.h"
+#include "mi_phylo_host_arrays.h"
 #include "mi_phylo_kernels.h"
 
 namespace miphylo {
@@ -174,7 +175,7 @@ struct mi_engine {
   long red_ws_entries = -1;  // what red_ws_bytes (the sort's workspace size) was computed for
   int red_ws_bits = 0;
   size_t red_ws_bytes = 0;
-  // staging for the host-pointer entry points: one block each way per call (begin_host_call)
+  // staging for the host-pointer entry points: one block each way per call (run_on_engine)
   Buffer in_pack, out_pack;
   // branch-length optimisation (mi_engine_optimize_branch_lengths_unrooted*)
   Buffer opt_ws;                // trial points, kept derivatives, packed inputs, maps, counters
@@ -361,21 +362,34 @@ int for_each_shard(mi_engine* e, int tree_count, F one) {
   return 0;
 }
 
-// ---- mi_phylo_host_calls.cpp: one DMA each way per host-pointer call ----
-struct InPiece {
-  const void* host;
-  size_t bytes;
-  const void** dev;
+// ---- mi_phylo_host_calls.cpp: what every host-pointer entry point is run by ----
+// A host-pointer call lists its arrays once (HostArray: mi_phylo_host_arrays.h) and says how its
+// device work is enqueued, given their device addresses.  Staging (one copy each way), the one
+// synchronisation with its status check and the shards of a handle are driven by the lists.
+struct HostCall {
+  int T = 0;  // trees (what per-tree arrays are counted in)
+  std::vector<HostArray> in, out;
+  // enqueue the device work on e->stream; the lists are the call's own, with `dev` filled in
+  std::function<int(mi_engine* e, int T, const HostArray* in, const HostArray* out)> enqueue;
+  bool retry = false;       // a one-launch time-out: run again through the four-launch sequence
+  bool one_by_one = false;  // tree shards run shard after shard (the work synchronises its device)
 };
-struct OutPiece {
-  void* host;    // may be null: not wanted
-  size_t count;  // elements
-  double** dev;
-  size_t elem = sizeof(double);  // bytes per element
-};
-int upload_pack(mi_engine* e, std::initializer_list<InPiece> pieces);
-int place_out_pack(mi_engine* e, std::initializer_list<OutPiece> pieces);
-int download_pack(mi_engine* e, std::initializer_list<OutPiece> pieces);
+int run_host_call(mi_engine* e, HostCall& c);   // on an engine, or dealt to the shards of a handle
+int run_on_engine(mi_engine* e, HostCall& c);   // on this engine
+// (calls that need no alignment: a sharded handle of either kind lets its first shard take them)
+inline mi_engine* first_engine(mi_engine* e) { return e->shards.empty() ? e : e->shards[0]; }
+// the three inputs every tree call begins its list with
+enum { kInParent, kInBl, kInParams, kTreeInputs };
+inline std::vector<HostArray> tree_inputs(const mi_engine* e, const int32_t* parent_ids, const double* bl,
+                                          const double* params, bool rooted = false) {
+  const size_t np = rooted ? 2 * e->n - 2 : 2 * e->n - 3;
+  return {per_tree(parent_ids, np), per_tree(bl, np + 1),
+          per_tree(e->param_count > 0 ? params : nullptr, e->param_count)};
+}
+// (an engine without parameters still hands the kernels a valid pointer)
+inline const double* params_on_device(const mi_engine* e, const HostArray* in) {
+  return in[kInParams].dev ? in[kInParams].at<const double>() : e->in_pack.as<const double>();
+}
 
 // ---- mi_phylo_rell.cpp ----
 // the workspace of a RELL call over B replicates and T trees (mi_engine_reserve_rell)

@@ -274,92 +274,6 @@ int run_nni_search_device(mi_engine* e, hipStream_t s, const NniSearchCall& c) {
   return 0;
 }
 
-// The host-pointer forms on one engine: inputs up in one copy, the work, outputs back in one
-// copy and the call's one error check.
-int begin_host(mi_engine* e) {
-  HIP_TRY(hipSetDevice(e->spec.device));
-  e->fused_timed_out = false;
-  e->pinned.reset();
-  if (e->status.ensure(sizeof(int32_t) * kStatusWords)) return 1;
-  HIP_TRY(hipMemsetAsync(e->status.ptr, 0, sizeof(int32_t) * kStatusWords, e->stream));
-  return 0;
-}
-int finish_host(mi_engine* e) {
-  int rc = check_status(e, e->stream);
-  e->fused_timed_out = false;
-  if (rc == 0) e->pinned.flush();
-  e->pinned.reset();
-  return rc;
-}
-
-int run_nni_apply_host(mi_engine* e, int T, const int32_t* parent_ids, const double* bl, const int32_t* moves,
-                       int32_t* out_pid, double* out_bl) {
-  const int n = e->n;
-  if (T <= 0) return fail("tree_count must be positive");
-  if (!parent_ids || !bl || !moves) return fail("null tree / move arrays");
-  if (!out_pid || !out_bl) return fail("null output pointer");
-  if (begin_host(e)) return 1;
-  const void *d_parent, *d_bl, *d_moves;
-  if (upload_pack(e, {{parent_ids, sizeof(int32_t) * (size_t)T * (2 * n - 3), &d_parent},
-                      {bl, sizeof(double) * (size_t)T * (2 * n - 2), &d_bl},
-                      {moves, sizeof(int32_t) * (size_t)T, &d_moves}}))
-    return 1;
-  double *o_pid, *o_bl;  // (the first: int32)
-  const std::initializer_list<OutPiece> outs = {{out_pid, (size_t)T * (2 * n - 3), &o_pid, sizeof(int32_t)},
-                                                {out_bl, (size_t)T * (2 * n - 2), &o_bl}};
-  if (place_out_pack(e, outs)) return 1;
-  if (run_nni_apply_device(e, e->stream, T, static_cast<const int32_t*>(d_parent), static_cast<const double*>(d_bl),
-                           static_cast<const int32_t*>(d_moves), reinterpret_cast<int32_t*>(o_pid), o_bl))
-    return 1;
-  if (download_pack(e, outs)) return 1;
-  return finish_host(e);
-}
-
-int run_nni_search_host(mi_engine* e, const NniSearchCall& h) {
-  const int T = h.T, n = e->n;
-  if (T <= 0) return fail("tree_count must be positive");
-  if (!h.parent_ids || !h.start) return fail("null tree arrays");
-  if (!h.out_pid || !h.out_bl || !h.out_ll || !h.out_move_count || !h.out_status) return fail("null output pointer");
-  if (e->param_count > 0 && !h.params) return fail("null parameter matrix");
-  mi_nni_search_options o;
-  if (search_options(h.options, &o)) return 1;
-  if (begin_host(e)) return 1;
-  const void *d_parent, *d_bl, *d_params;
-  if (upload_pack(e, {{h.parent_ids, sizeof(int32_t) * (size_t)T * (2 * n - 3), &d_parent},
-                      {h.start, sizeof(double) * (size_t)T * (2 * n - 2), &d_bl},
-                      {e->param_count > 0 ? h.params : nullptr, sizeof(double) * (size_t)T * e->param_count, &d_params}}))
-    return 1;
-  if (!d_params) d_params = e->in_pack.ptr;
-  const size_t log = (size_t)T * o.max_moves;
-  double *o_pid, *o_bl, *o_ll, *o_delta, *o_count, *o_log, *o_gain, *o_status, *o_opt;
-  const std::initializer_list<OutPiece> outs = {{h.out_pid, (size_t)T * (2 * n - 3), &o_pid, sizeof(int32_t)},
-                                                {h.out_bl, (size_t)T * (2 * n - 2), &o_bl},
-                                                {h.out_ll, (size_t)T, &o_ll},
-                                                {h.out_best_delta, h.out_best_delta ? (size_t)T : 0, &o_delta},
-                                                {h.out_move_count, (size_t)T, &o_count, sizeof(int32_t)},
-                                                {h.out_move_log, h.out_move_log ? log : 0, &o_log, sizeof(int32_t)},
-                                                {h.out_move_gain, h.out_move_gain ? log : 0, &o_gain},
-                                                {h.out_status, (size_t)T, &o_status, sizeof(int32_t)},
-                                                {h.out_opt_status, h.out_opt_status ? (size_t)T : 0, &o_opt, sizeof(int32_t)}};
-  if (place_out_pack(e, outs)) return 1;
-  NniSearchCall c = h;
-  c.parent_ids = static_cast<const int32_t*>(d_parent);
-  c.start = static_cast<const double*>(d_bl);
-  c.params = static_cast<const double*>(d_params);
-  c.out_pid = reinterpret_cast<int32_t*>(o_pid);
-  c.out_bl = o_bl;
-  c.out_ll = o_ll;
-  c.out_best_delta = h.out_best_delta ? o_delta : nullptr;
-  c.out_move_count = reinterpret_cast<int32_t*>(o_count);
-  c.out_move_log = h.out_move_log ? reinterpret_cast<int32_t*>(o_log) : nullptr;
-  c.out_move_gain = h.out_move_gain ? o_gain : nullptr;
-  c.out_status = reinterpret_cast<int32_t*>(o_status);
-  c.out_opt_status = h.out_opt_status ? reinterpret_cast<int32_t*>(o_opt) : nullptr;
-  if (run_nni_search_device(e, e->stream, c)) return 1;
-  if (download_pack(e, outs)) return 1;
-  return finish_host(e);
-}
-
 }  // namespace
 
 extern "C" {
@@ -367,14 +281,20 @@ extern "C" {
 int32_t mi_engine_nni_apply_unrooted(mi_engine* e, int32_t T, const int32_t* parent_ids, const double* bl,
                                      const int32_t* moves, int32_t* out_parent_ids, double* out_bl) {
   if (!e) return fail("null engine");
+  if (T <= 0) return fail("tree_count must be positive");
+  if (!parent_ids || !bl || !moves) return fail("null tree / move arrays");
+  if (!out_parent_ids || !out_bl) return fail("null output pointer");
+  const size_t np = 2 * e->n - 3;
+  HostCall c;
+  c.T = T;
+  c.in = {per_tree(parent_ids, np), per_tree(bl, np + 1), per_tree(moves, 1)};
+  c.out = {per_tree(out_parent_ids, np), per_tree(out_bl, np + 1)};
+  c.enqueue = [](mi_engine* e, int T, const HostArray* in, const HostArray* out) {
+    return run_nni_apply_device(e, e->stream, T, in[0].at<const int32_t>(), in[1].at<const double>(),
+                                in[2].at<const int32_t>(), out[0].at<int32_t>(), out[1].at<double>());
+  };
   // (a move needs no alignment: a sharded handle of either kind lets its first shard take them all)
-  mi_engine* one = e->shards.empty() ? e : e->shards[0];
-  one->status_tree_offset = 0;
-  if (run_nni_apply_host(one, T, parent_ids, bl, moves, out_parent_ids, out_bl)) {
-    one->pinned.reset();
-    return 1;
-  }
-  return 0;
+  return run_on_engine(first_engine(e), c);
 }
 
 int32_t mi_engine_nni_apply_unrooted_device(mi_engine* e, void* stream, int32_t T, const int32_t* parent_ids,
@@ -385,6 +305,9 @@ int32_t mi_engine_nni_apply_unrooted_device(mi_engine* e, void* stream, int32_t 
   return run_nni_apply_device(e, pick_stream(e, stream), T, parent_ids, bl, moves, out_parent_ids, out_bl);
 }
 
+// The host-pointer form of the search: inputs up in one copy, the rounds, outputs back in one copy
+// and the call's one error check.  Each tree shard of a handle searches from its block of trees,
+// one shard after the other (the loop synchronises its device every round).
 int32_t mi_engine_nni_search_unrooted(mi_engine* e, int32_t T, const int32_t* parent_ids, const double* start,
                                       const double* params, int32_t rescaling,
                                       const mi_nni_search_options* options, int32_t* out_parent_ids,
@@ -396,60 +319,45 @@ int32_t mi_engine_nni_search_unrooted(mi_engine* e, int32_t T, const int32_t* pa
   if (T <= 0) return fail("tree_count must be positive");
   mi_nni_search_options o;
   if (search_options(options, &o)) return 1;
-  NniSearchCall c;
+  if (!e->shards.empty()) {
+    if (e->shard_mode != MI_SHARD_TREES) return fail(kSearchPatternShards);
+    if (!parent_ids || !start || !out_parent_ids || !out_bl || !out_ll || !out_move_count || !out_status)
+      return fail("null tree / output pointer");
+  }
+  if (!parent_ids || !start) return fail("null tree arrays");
+  if (!out_parent_ids || !out_bl || !out_ll || !out_move_count || !out_status) return fail("null output pointer");
+  if (e->param_count > 0 && !params) return fail("null parameter matrix");
+  enum { kPid, kBl, kLl, kDelta, kCount, kLog, kGain, kStatus, kOpt };
+  const size_t np = 2 * e->n - 3;
+  HostCall c;
   c.T = T;
-  c.rescaling = rescaling != 0;
-  c.parent_ids = parent_ids;
-  c.start = start;
-  c.params = params;
-  c.options = options;
-  c.out_pid = out_parent_ids;
-  c.out_bl = out_bl;
-  c.out_ll = out_ll;
-  c.out_best_delta = out_best_delta;
-  c.out_move_count = out_move_count;
-  c.out_move_log = out_move_log;
-  c.out_move_gain = out_move_gain;
-  c.out_status = out_status;
-  c.out_opt_status = out_opt_status;
-  if (e->shards.empty()) {
-    if (run_nni_search_host(e, c)) {
-      e->pinned.reset();
-      return 1;
-    }
-    return 0;
-  }
-  if (e->shard_mode != MI_SHARD_TREES) return fail(kSearchPatternShards);
-  if (!parent_ids || !start || !out_parent_ids || !out_bl || !out_ll || !out_move_count || !out_status)
-    return fail("null tree / output pointer");
-  // Each shard searches from its block of trees, one shard after the other (the loop
-  // synchronises its device every round).
-  const int D = (int)e->shards.size(), n = e->n;
-  for (int i = 0; i < D; i++) {
-    int32_t b = 0, cnt = 0;
-    mi_shard_range(T, D, i, &b, &cnt);
-    if (cnt == 0) continue;
-    NniSearchCall sc = c;
-    sc.T = cnt;
-    sc.parent_ids = parent_ids + (size_t)b * (2 * n - 3);
-    sc.start = start + (size_t)b * (2 * n - 2);
-    if (params) sc.params = params + (size_t)b * e->param_count;
-    sc.out_pid = out_parent_ids + (size_t)b * (2 * n - 3);
-    sc.out_bl = out_bl + (size_t)b * (2 * n - 2);
-    sc.out_ll = out_ll + b;
-    if (out_best_delta) sc.out_best_delta = out_best_delta + b;
-    sc.out_move_count = out_move_count + b;
-    if (out_move_log) sc.out_move_log = out_move_log + (size_t)b * o.max_moves;
-    if (out_move_gain) sc.out_move_gain = out_move_gain + (size_t)b * o.max_moves;
-    sc.out_status = out_status + b;
-    if (out_opt_status) sc.out_opt_status = out_opt_status + b;
-    e->shards[i]->status_tree_offset = b;
-    if (run_nni_search_host(e->shards[i], sc)) {
-      e->shards[i]->pinned.reset();
-      return 1;
-    }
-  }
-  return 0;
+  c.one_by_one = true;
+  c.in = tree_inputs(e, parent_ids, start, params);
+  c.out = {per_tree(out_parent_ids, np),          per_tree(out_bl, np + 1),
+           per_tree(out_ll, 1),                   per_tree(out_best_delta, 1),
+           per_tree(out_move_count, 1),           per_tree(out_move_log, o.max_moves),
+           per_tree(out_move_gain, o.max_moves),  per_tree(out_status, 1),
+           per_tree(out_opt_status, 1)};
+  c.enqueue = [=](mi_engine* e, int T, const HostArray* in, const HostArray* out) {
+    NniSearchCall d;
+    d.T = T;
+    d.rescaling = rescaling != 0;
+    d.parent_ids = in[kInParent].at<const int32_t>();
+    d.start = in[kInBl].at<const double>();
+    d.params = params_on_device(e, in);
+    d.options = options;
+    d.out_pid = out[kPid].at<int32_t>();
+    d.out_bl = out[kBl].at<double>();
+    d.out_ll = out[kLl].at<double>();
+    d.out_best_delta = out[kDelta].at<double>();
+    d.out_move_count = out[kCount].at<int32_t>();
+    d.out_move_log = out[kLog].at<int32_t>();
+    d.out_move_gain = out[kGain].at<double>();
+    d.out_status = out[kStatus].at<int32_t>();
+    d.out_opt_status = out[kOpt].at<int32_t>();
+    return run_nni_search_device(e, e->stream, d);
+  };
+  return run_host_call(e, c);
 }
 
 int32_t mi_engine_nni_search_unrooted_device(mi_engine* e, void* stream, int32_t T, const int32_t* parent_ids,

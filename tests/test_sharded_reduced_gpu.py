@@ -319,3 +319,159 @@ def test_reduced_device_call_allocates_nothing_after_reserve_reduced():
     with pytest.raises(RuntimeError, match="index_count"):
         eng.reserve_reduced(T, -1)
     eng.close(); warm.close()
+
+
+# ---- the host-call layer behind a sharded handle: slicing, summing, error reporting ----
+
+def _tiny(T, seed):
+    rng = np.random.default_rng(seed)
+    n, P = 8, 40
+    tips, w = TU.random_alignment(n, P, rng)
+    pids, bls = TU.random_trees(n, T, rng)
+    return n, P, tips, w, pids, bls, rng
+
+
+def _gtr_params(T, rng):
+    r, f = TU.random_gtr_params(T, rng)
+    return np.hstack([r, f, rng.uniform(0.5, 1.5, (T, 1)), np.ones((T, 1))])
+
+
+def _shard_range(total, count, shard):
+    import ctypes
+    from libsbn_amd import _capi
+    b, c = ctypes.c_int32(), ctypes.c_int32()
+    assert _capi.load().mi_shard_range(total, count, shard, ctypes.byref(b), ctypes.byref(c)) == 0
+    return b.value, b.value + c.value
+
+
+def test_pattern_shards_are_the_block_engines_added_in_shard_order():
+    """A pattern-sharded handle is one ordinary engine per column block mi_shard_range gives, and
+    every output that is a sum over patterns is those engines' outputs added from zero in shard
+    order: bit for bit, for every call kind that pattern shards serve."""
+    import libsbn_amd as L
+    import nni_ref as R
+    T, D = 5, 3
+    n, P, tips, w, pids, bls, rng = _tiny(T, 11)
+    N = 2 * n - 1
+    spec = L.PhyloModelSpecification("GTR", "weibull+4", "strict")
+    pr = _gtr_params(T, rng)
+    many = L.Engine(spec, tips, w, shard_devices=[0] * D, shard_mode="patterns")
+    blocks = []
+    for i in range(D):
+        lo, hi = _shard_range(P, D, i)
+        blocks.append(L.Engine(spec, np.ascontiguousarray(tips[:, lo:hi]), w[lo:hi].copy()))
+
+    def added(parts):
+        acc = np.zeros_like(np.asarray(parts[0], dtype=np.float64))
+        for x in parts:
+            acc = acc + x
+        return acc
+
+    assert np.array_equal(many.log_likelihoods(pids, bls, pr),
+                          added([e.log_likelihoods(pids, bls, pr) for e in blocks]))
+
+    got = many.gradients(pids, bls, pr)
+    parts = [e.gradients(pids, bls, pr) for e in blocks]
+    assert np.array_equal(np.array([g.log_likelihood for g in got]),
+                          added([np.array([g.log_likelihood for g in p]) for p in parts]))
+    assert sorted(got[0].gradient) == ["branch_lengths", "site_model", "substitution_model"]
+    for key in got[0].gradient:
+        assert np.array_equal(np.stack([g.gradient[key] for g in got]),
+                              added([np.stack([g.gradient[key] for g in p]) for p in parts])), key
+
+    got = many.branch_hessian(pids, bls, pr, squared_gradient=True)
+    parts = [e.branch_hessian(pids, bls, pr, squared_gradient=True) for e in blocks]
+    for k, name in enumerate(("log_likelihood", "gradient", "hessian", "squared_gradient")):
+        assert np.array_equal(got[k], added([p[k] for p in parts])), name
+
+    ll, delta, best = many.nni_scan(pids, bls, pr)
+    parts = [e.nni_scan(pids, bls, pr) for e in blocks]
+    assert np.array_equal(ll, added([p[0] for p in parts]))
+    want_delta = added([p[1] for p in parts])
+    assert np.array_equal(delta, want_delta)
+    assert np.array_equal(best, np.array([R.best_move(n, want_delta[t]) for t in range(T)], np.int32))
+
+    index_count = 9
+    bi = rng.integers(0, index_count, size=(T, N)).astype(np.int32)
+    bi[:, -2:] = -1
+    for tw in (None, rng.uniform(0.1, 2.0, T)):
+        got = many.gradients_reduced(pids, bls, pr, bi, index_count, tw)
+        parts = [e.gradients_reduced(pids, bls, pr, bi, index_count, tw) for e in blocks]
+        for k, name in enumerate(("sum_ll", "sum_site", "index_gradient", "log_likelihoods")):
+            assert np.array_equal(np.asarray(got[k]), added([np.asarray(p[k]) for p in parts])), name
+
+
+def test_tree_shards_report_the_callers_tree_index():
+    """Blocks of 2, 2 and 1 trees; the invalid parent id sits in the last shard's only tree, whose
+    index there is 0.  The message names the caller's tree 4, and the next (valid) call on the
+    same handle gives the single engine's results bit for bit."""
+    import libsbn_amd as L
+    T = 5
+    n, P, tips, w, pids, bls, rng = _tiny(T, 12)
+    spec = L.PhyloModelSpecification("JC69", "weibull+4", "strict")
+    pr = np.ones((T, 2)); pr[:, 0] = rng.uniform(0.5, 1.5, T)
+    one = L.Engine(spec, tips, w)
+    many = L.Engine(spec, tips, w, shard_devices=[0, 0, 0])
+    bad = pids.copy()
+    bad[4, 5] = 2  # a tip as a parent: not the reference's id form
+
+    def grads(e, p):
+        g = e.gradients(p, bls, pr)
+        return [np.array([x.log_likelihood for x in g])] + [np.stack([x.gradient[k] for x in g])
+                                                             for k in sorted(g[0].gradient)]
+
+    def opt(e, p):
+        r = e.optimize_branch_lengths(p, bls, pr)
+        return [r.branch_lengths, r.log_likelihood, r.gradient, r.hessian, r.iterations, r.status]
+
+    calls = {"gradients": grads,
+             "branch_hessian": lambda e, p: e.branch_hessian(p, bls, pr, squared_gradient=True),
+             "pattern_log_likelihoods": lambda e, p: e.pattern_log_likelihoods(p, bls, pr),
+             "optimize_branch_lengths": opt}
+    for name, call in calls.items():
+        with pytest.raises(RuntimeError, match=r"\(tree 4\)"):
+            call(many, bad)
+        want, got = call(one, pids), call(many, pids)
+        assert len(want) == len(got)
+        for a, b in zip(want, got):
+            assert np.array_equal(a, b), name
+
+
+def test_empty_tree_shards_and_optional_outputs():
+    """Two trees on three tree shards (the third gets none): outputs nobody asked for, int32 and
+    int8 outputs, and the calls that run shard after shard or on the first shard only are the
+    single engine's, bit for bit."""
+    import libsbn_amd as L
+    T = 2
+    n, P, tips, w, pids, bls, rng = _tiny(T, 13)
+    spec = L.PhyloModelSpecification("GTR", "weibull+4", "strict")
+    pr = _gtr_params(T, rng)
+    one = L.Engine(spec, tips, w)
+    many = L.Engine(spec, tips, w, shard_devices=[0, 0, 0])
+
+    ga = one.gradients(pids, bls, pr, gradient_blocks=("branch_lengths",))
+    gb = many.gradients(pids, bls, pr, gradient_blocks=("branch_lengths",))
+    for a, b in zip(ga, gb):
+        assert a.log_likelihood == b.log_likelihood and list(b.gradient) == ["branch_lengths"]
+        assert np.array_equal(a.gradient["branch_lengths"], b.gradient["branch_lengths"])
+
+    fields = ("state_posteriors", "log_likelihoods", "map_states", "category_posteriors", "pattern_rates",
+              "tip_posteriors")
+    for on in (False, True):
+        a = one.ancestral_states(pids, bls, pr, map_states=on, categories=on, tips=on)
+        b = many.ancestral_states(pids, bls, pr, map_states=on, categories=on, tips=on)
+        for name in fields:
+            x, y = getattr(a, name), getattr(b, name)
+            assert (x is None) == (y is None) == (not on and name not in fields[:2]), name
+            if x is not None:
+                assert x.dtype == y.dtype and np.array_equal(x, y, equal_nan=True), name
+
+    a, b = one.nni_search(pids, bls, pr, max_moves=3), many.nni_search(pids, bls, pr, max_moves=3)
+    for name in ("parent_ids", "branch_lengths", "log_likelihood", "best_delta", "move_count", "move_log",
+                 "move_gain", "status", "branch_opt_status"):
+        assert np.array_equal(getattr(a, name), getattr(b, name)), name
+
+    moves = one.nni_scan(pids, bls, pr)[2]
+    assert np.all(moves >= 0)
+    for x, y in zip(one.nni_apply(pids, bls, moves), many.nni_apply(pids, bls, moves)):
+        assert np.array_equal(x, y)
