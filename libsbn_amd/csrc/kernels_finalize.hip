@@ -7,6 +7,7 @@
 #include <string>
 
 #include "mi_phylo_device_utils.h"
+#include "mi_phylo_hbm_walk_device.h"
 #include "mi_phylo_kernels.h"
 
 namespace miphylo {
@@ -650,38 +651,21 @@ __global__ __launch_bounds__(256) void reduce_finalize_kernel(ReduceArgs ra, Fin
 // ------------------------------------------------------------------------
 // Branch-length Hessian call: tile reduction and finalize in one launch, a workgroup per tree.
 // g_part [T][g_tiles][3][N] by node id (gradient_hbm_hess_kernel).  Every column is summed in
-// the order reduce_tiles_body sums it -- wave w's share (tiles w, w + 8, ... and w + 4, w + 12,
-// ...), then (w0 + w1) + (w2 + w3) -- here by one thread per column, so that the
-// log-likelihood and the gradient are bit for bit those of a gradient call on the HBM path.
+// the order reduce_tiles_body sums it (tile_column_sum, mi_phylo_hbm_walk_device.h: one thread
+// per column), so that the log-likelihood and the gradient are bit for bit those of a gradient
+// call on the HBM path.
 // Root and fixed node (the last two entries) are 0, as in the gradient.
 // ------------------------------------------------------------------------
-__device__ __forceinline__ double hess_wave_share(const double* src, int W, int g_tiles, int col, int wv) {
-  double s0 = 0, s1 = 0;
-  int i = wv;
-  for (; i + 4 < g_tiles; i += 8) {
-    s0 += src[(size_t)i * W + col];
-    s1 += src[(size_t)(i + 4) * W + col];
-  }
-  if (i < g_tiles) s0 += src[(size_t)i * W + col];
-  return s0 + s1;
-}
 __global__ __launch_bounds__(256) void hessian_finalize_kernel(HessFinalizeArgs a) {
   __shared__ double llw[4];
-  const int t = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int t = blockIdx.x;
   const int N = a.N, W = 3 * N;
-  double llp = 0;
-  for (int i = threadIdx.x; i < a.ll_used; i += 256) llp += a.ll_part[(size_t)t * a.ll_tiles + i];
-  llp = wave_sum(llp);
-  if (lane == 0) llw[wv] = llp;
+  ll_tile_shares(a.ll_part + (size_t)t * a.ll_tiles, a.ll_used, llw);
   const double* src = a.g_part + (size_t)t * a.g_tiles * W;
   for (int v = threadIdx.x; v < N; v += 256) {
     double r[3];
 #pragma unroll
-    for (int q = 0; q < 3; q++) {
-      const int c = q * N + v;
-      r[q] = (hess_wave_share(src, W, a.g_tiles, c, 0) + hess_wave_share(src, W, a.g_tiles, c, 1)) +
-             (hess_wave_share(src, W, a.g_tiles, c, 2) + hess_wave_share(src, W, a.g_tiles, c, 3));
-    }
+    for (int q = 0; q < 3; q++) r[q] = tile_column_sum(src, W, a.g_tiles, q * N + v);
     const bool edge = v < N - 2;
     const size_t o = (size_t)t * N + v;
     if (a.out_branch) a.out_branch[o] = edge ? r[0] : 0.0;
@@ -689,7 +673,7 @@ __global__ __launch_bounds__(256) void hessian_finalize_kernel(HessFinalizeArgs 
     if (a.out_gsq) a.out_gsq[o] = edge ? r[2] : 0.0;
   }
   __syncthreads();
-  if (threadIdx.x == 0 && a.out_ll) a.out_ll[t] = (llw[0] + llw[1]) + (llw[2] + llw[3]);
+  if (threadIdx.x == 0 && a.out_ll) a.out_ll[t] = ll_tile_total(llw);
 }
 // The same for the walk form (gradient_walk_hess_kernel): positional sums, g_part
 // [T][g_tiles][g_width] = [Mmax][6][2] {D1, D2} then [Mmax][6] S, mapped to node ids through the
@@ -698,13 +682,10 @@ __global__ __launch_bounds__(256) void hessian_finalize_kernel(HessFinalizeArgs 
 __global__ __launch_bounds__(256) void hessian_walk_finalize_kernel(HessFinalizeArgs a) {
   extern __shared__ double hf[];
   __shared__ double llw[4];
-  const int t = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int t = blockIdx.x;
   const int N = a.N, W = a.g_width, Mmax = max_macros(a.n);
   for (int v = threadIdx.x; v < 3 * N; v += 256) hf[v] = 0.0;
-  double llp = 0;
-  for (int i = threadIdx.x; i < a.ll_used; i += 256) llp += a.ll_part[(size_t)t * a.ll_tiles + i];
-  llp = wave_sum(llp);
-  if (lane == 0) llw[wv] = llp;
+  ll_tile_shares(a.ll_part + (size_t)t * a.ll_tiles, a.ll_used, llw);
   __syncthreads();
   const int M = a.macro_count[t];
   const MacroEntry* mac = a.macros + (size_t)t * macro_stride(a.n);
@@ -728,8 +709,7 @@ __global__ __launch_bounds__(256) void hessian_walk_finalize_kernel(HessFinalize
     const bool exists = pos < 2 || ((me.shape >> (2 * ((pos - 2) >> 1))) & 3) == 2;
     if (!exists) continue;
     const int node = pos < 2 ? me.child[pos] : me.grand[pos - 2];
-    hf[q * N + node] = (hess_wave_share(src, W, a.g_tiles, col, 0) + hess_wave_share(src, W, a.g_tiles, col, 1)) +
-                       (hess_wave_share(src, W, a.g_tiles, col, 2) + hess_wave_share(src, W, a.g_tiles, col, 3));
+    hf[q * N + node] = tile_column_sum(src, W, a.g_tiles, col);
   }
   __syncthreads();
   for (int v = threadIdx.x; v < N; v += 256) {
@@ -739,7 +719,7 @@ __global__ __launch_bounds__(256) void hessian_walk_finalize_kernel(HessFinalize
     a.out_hess[o] = edge ? hf[N + v] - hf[2 * N + v] : 0.0;
     if (a.out_gsq) a.out_gsq[o] = edge ? hf[2 * N + v] : 0.0;
   }
-  if (threadIdx.x == 0 && a.out_ll) a.out_ll[t] = (llw[0] + llw[1]) + (llw[2] + llw[3]);
+  if (threadIdx.x == 0 && a.out_ll) a.out_ll[t] = ll_tile_total(llw);
 }
 
 }  // namespace

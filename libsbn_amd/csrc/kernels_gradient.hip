@@ -1,6 +1,7 @@
-// Gradient kernel with partial vectors streamed through HBM (real-valued tip partials, trees no
-// on-chip walk fits), and what the on-chip walks (kernels_walk.hip, kernels_walk3.hip) share:
-// tile counts, the arena variant's slot assignment (macro_slots kernels), device queries.
+// The gradient and Hessian kernels of the HBM-streamed family (real-valued tip partials, trees no
+// on-chip walk fits; what the family shares is in mi_phylo_hbm_walk_device.h), and
+// what the on-chip walks (kernels_walk.hip, kernels_walk3.hip) share: tile counts, the arena
+// variant's slot assignment (macro_slots kernels), device queries.
 // (The first-generation matrix-core walk, gradient_mfma_kernel, lived here until round 6: the
 // second generation covers every call it took, the third the shapes it was still chosen for.)
 // (gfx950 / CDNA4, wave64; see DESIGN.md for the mapping and what bounds each kernel.)
@@ -11,6 +12,7 @@
 #include <string>
 
 #include "mi_phylo_device_utils.h"
+#include "mi_phylo_hbm_walk_device.h"
 #include "mi_phylo_kernels.h"
 #include "mi_phylo_macro_slots_device.h"
 
@@ -20,128 +22,43 @@ namespace {
 using namespace dev;
 
 // ------------------------------------------------------------------------
-// Gradient v1 (B4-B11): post-order, pre-order and edge derivatives in one
-// launch, partial-likelihood vectors streamed through HBM in the layout
-// [evaluation][node][category][pattern][state] (32 B per lane, a wave reads or
-// writes 2 KiB contiguous).  Each lane only ever re-reads what it wrote itself,
-// so no inter-wave synchronisation is needed.  The pre-order vector of a node
-// overwrites its post-order vector in place once the latter is dead.
+// Gradient v1 (B4-B11): post-order, pre-order and edge derivatives in one launch.  The lane
+// context, the post-order pass, a visit's operands and the child stores are the family's
+// (mi_phylo_hbm_walk_device.h); this kernel's own: the two Q products and the four wave sums per
+// visit.  g_part is [Eg][tiles][2][N] by node id: {sum w D1/L by rate, by d rate / d shape}.
 // ------------------------------------------------------------------------
 template <bool RESCALE, bool TIP_PARTIALS>
 __global__ __launch_bounds__(kTile) void gradient_hbm_kernel(LikArgs a) {
-  const int lane = threadIdx.x;
-  const TileEval te = xcd_tile_eval();
-  const int tile = te.tile;
-  const int e = a.eval_offset + te.eval;
-  const int gi = a.grad_offset + te.eval;
-  int t, mi;
-  a.map.decode(e, t, mi);
-  const DevModel* __restrict__ model = a.models + mi;
-  const SchedEntry* __restrict__ sched = a.sched + (size_t)t * (a.n - 1);
-  const int p = tile * kTile + lane;
-  const int pc = p < a.P ? p : a.P - 1;
-  const double w = p < a.P ? a.weights[pc] : 0.0;
-  const int K = a.K, n = a.n, N = a.N;
-  const size_t ppad = (size_t)a.tiles * kTile;
-  const double* __restrict__ mats_e = a.mats + (size_t)e * (N - 1) * K * 16;
-  double* plv_e = a.plv + (size_t)te.eval * (n - 1) * K * ppad * 4 + (size_t)p * 4;
-  double* gout = a.g_part + ((size_t)gi * a.g_tiles + tile) * 2 * N;
+  const HbmLane<TIP_PARTIALS> c(a);
+  const DevModel* __restrict__ model = c.model;
+  const int lane = c.lane, p = c.p, K = c.K, n = c.n, N = c.N;
+  const double w = c.w;
+  double* gout = c.g_row(2 * N);
 
-  auto plv_at = [&](int node, int k) { return plv_e + ((size_t)(node - n) * K + k) * ppad * 4; };
-  auto tip_L = [&](int node) {
-    if (TIP_PARTIALS) return load4(a.tip_partials + ((size_t)node * a.P + pc) * 4);
-    return tip_vector(a.tip_states[(size_t)node * a.P + pc]);
-  };
-
-  // ---- post-order ----
-  int cum_exp = 0;
-  double site = 0.0;
-  for (int i = 0; i < n - 1; i++) {
-    const SchedEntry s = sched[i];
-    const bool is_root = i == n - 2;
-    double mx = 0.0;
-    for (int k = 0; k < K; k++) {
-      const double* __restrict__ M0 = mats_e + ((size_t)s.child0 * K + k) * 16;
-      const double* __restrict__ M1 = mats_e + ((size_t)s.child1 * K + k) * 16;
-      const D4 L0 = s.child0 < n ? tip_L(s.child0) : load4(plv_at(s.child0, k));
-      const D4 L1 = s.child1 < n ? tip_L(s.child1) : load4(plv_at(s.child1, k));
-      const D4 L = mul4(matvec(M0, L0), matvec(M1, L1));
-      if (RESCALE) mx = fmax(mx, max4(L));
-      if (is_root && !RESCALE) {
-        site += model->cat_weight[k] * (model->pi[0] * L.x0 + model->pi[1] * L.x1 +
-                                        model->pi[2] * L.x2 + model->pi[3] * L.x3);
-      } else {
-        store4(plv_at(s.node, k), L);
-      }
-    }
-    if (RESCALE) {
-      // common exponent across categories (the ratio in the edge derivative needs it)
-      const int ex = max_exponent(mx);
-      cum_exp += ex;
-      for (int k = 0; k < K; k++) {
-        const D4 L = scale4(load4(plv_at(s.node, k)), -ex);
-        if (is_root)
-          site += model->cat_weight[k] * (model->pi[0] * L.x0 + model->pi[1] * L.x1 +
-                                          model->pi[2] * L.x2 + model->pi[3] * L.x3);
-        else
-          store4(plv_at(s.node, k), L);
-      }
-    }
-  }
-  {
-    double ll = log(site);
-    if (RESCALE) ll += cum_exp * 0.6931471805599453;
-    ll = p < a.P ? w * ll : 0.0;
-    ll = wave_sum(ll);
-    if (lane == 0) a.ll_part[(size_t)e * a.ll_tiles + tile] = ll;
-  }
+  hbm_post_order<RESCALE>(c);
 
   // ---- pre-order + edge derivatives, parents before children ----
   for (int i = n - 2; i >= 0; i--) {
-    const SchedEntry s = sched[i];
+    const SchedEntry s = c.sched[i];
     const bool is_root = i == n - 2;
     double nb0 = 0, ns0 = 0, den0 = 0, nb1 = 0, ns1 = 0, den1 = 0;
     double mx0 = 0, mx1 = 0;
     for (int k = 0; k < K; k++) {
-      const double* __restrict__ M0 = mats_e + ((size_t)s.child0 * K + k) * 16;
-      const double* __restrict__ M1 = mats_e + ((size_t)s.child1 * K + k) * 16;
-      const D4 qv = is_root ? D4{model->pi[0], model->pi[1], model->pi[2], model->pi[3]}
-                            : load4(plv_at(s.node, k));
-      const D4 L0 = s.child0 < n ? tip_L(s.child0) : load4(plv_at(s.child0, k));
-      const D4 L1 = s.child1 < n ? tip_L(s.child1) : load4(plv_at(s.child1, k));
-      const D4 A = matvec(M0, L0), B = matvec(M1, L1);
-      const D4 q0 = matTvec(M0, mul4(qv, B));
-      const D4 q1 = matTvec(M1, mul4(qv, A));
+      const HbmVisit v = hbm_visit_operands(c, s, is_root, k);
+      const D4 q0 = matTvec(v.M0, mul4(v.qv, v.B));
+      const D4 q1 = matTvec(v.M1, mul4(v.qv, v.A));
       const double cw = model->cat_weight[k];
-      const double n0 = cw * dot4(q0, matvec(model->Q, L0));
-      const double n1 = cw * dot4(q1, matvec(model->Q, L1));
+      const double n0 = cw * dot4(q0, matvec(model->Q, v.L0));
+      const double n1 = cw * dot4(q1, matvec(model->Q, v.L1));
       nb0 += model->cat_rate[k] * n0;
       ns0 += model->cat_drate[k] * n0;
-      den0 += cw * dot4(q0, L0);
+      den0 += cw * dot4(q0, v.L0);
       nb1 += model->cat_rate[k] * n1;
       ns1 += model->cat_drate[k] * n1;
-      den1 += cw * dot4(q1, L1);
-      if (s.child0 >= n) {
-        store4(plv_at(s.child0, k), q0);
-        if (RESCALE) mx0 = fmax(mx0, max4(q0));
-      }
-      if (s.child1 >= n) {
-        store4(plv_at(s.child1, k), q1);
-        if (RESCALE) mx1 = fmax(mx1, max4(q1));
-      }
+      den1 += cw * dot4(q1, v.L1);
+      hbm_store_children<RESCALE>(c, s, k, q0, q1, mx0, mx1);
     }
-    if (RESCALE) {
-      if (s.child0 >= n) {
-        const int ex = max_exponent(mx0);
-        for (int k = 0; k < K; k++)
-          store4(plv_at(s.child0, k), scale4(load4(plv_at(s.child0, k)), -ex));
-      }
-      if (s.child1 >= n) {
-        const int ex = max_exponent(mx1);
-        for (int k = 0; k < K; k++)
-          store4(plv_at(s.child1, k), scale4(load4(plv_at(s.child1, k)), -ex));
-      }
-    }
+    hbm_rescale_children<RESCALE>(c, s, mx0, mx1);
     const double gb0 = wave_sum(p < a.P ? w * (nb0 / den0) : 0.0);
     const double gs0 = wave_sum(p < a.P ? w * (ns0 / den0) : 0.0);
     const double gb1 = wave_sum(p < a.P ? w * (nb1 / den1) : 0.0);
@@ -163,122 +80,39 @@ __global__ __launch_bounds__(kTile) void gradient_hbm_kernel(LikArgs a) {
 // The branch-length Hessian call: the kernel above with, per edge, the second
 // derivative D2_p = sum_k c_k r_k^2 q.(Q^2 L), Q^2 L = Q (Q L), and the squared per-pattern
 // first derivative instead of the site-model sum.  g_part is [Eg][tiles][3][N] by node id:
-// {sum w D1/L, sum w D2/L, sum w (D1/L)^2}.  (A kernel of its own rather than a template flag
-// on the one above: that kernel's code stays exactly as it was.)  One evaluation per tree.
+// {sum w D1/L, sum w D2/L, sum w (D1/L)^2}.  One evaluation per tree.
 // ------------------------------------------------------------------------
 template <bool RESCALE, bool TIP_PARTIALS>
 __global__ __launch_bounds__(kTile) void gradient_hbm_hess_kernel(LikArgs a) {
-  const int lane = threadIdx.x;
-  const TileEval te = xcd_tile_eval();
-  const int tile = te.tile;
-  const int e = a.eval_offset + te.eval;
-  const int gi = a.grad_offset + te.eval;
-  int t, mi;
-  a.map.decode(e, t, mi);
-  const DevModel* __restrict__ model = a.models + mi;
-  const SchedEntry* __restrict__ sched = a.sched + (size_t)t * (a.n - 1);
-  const int p = tile * kTile + lane;
-  const int pc = p < a.P ? p : a.P - 1;
-  const double w = p < a.P ? a.weights[pc] : 0.0;
-  const int K = a.K, n = a.n, N = a.N;
-  const size_t ppad = (size_t)a.tiles * kTile;
-  const double* __restrict__ mats_e = a.mats + (size_t)e * (N - 1) * K * 16;
-  double* plv_e = a.plv + (size_t)te.eval * (n - 1) * K * ppad * 4 + (size_t)p * 4;
-  double* gout = a.g_part + ((size_t)gi * a.g_tiles + tile) * 3 * N;
+  const HbmLane<TIP_PARTIALS> c(a);
+  const DevModel* __restrict__ model = c.model;
+  const int lane = c.lane, p = c.p, K = c.K, n = c.n, N = c.N;
+  const double w = c.w;
+  double* gout = c.g_row(3 * N);
 
-  auto plv_at = [&](int node, int k) { return plv_e + ((size_t)(node - n) * K + k) * ppad * 4; };
-  auto tip_L = [&](int node) {
-    if (TIP_PARTIALS) return load4(a.tip_partials + ((size_t)node * a.P + pc) * 4);
-    return tip_vector(a.tip_states[(size_t)node * a.P + pc]);
-  };
-
-  // ---- post-order (as gradient_hbm_kernel) ----
-  int cum_exp = 0;
-  double site = 0.0;
-  for (int i = 0; i < n - 1; i++) {
-    const SchedEntry s = sched[i];
-    const bool is_root = i == n - 2;
-    double mx = 0.0;
-    for (int k = 0; k < K; k++) {
-      const double* __restrict__ M0 = mats_e + ((size_t)s.child0 * K + k) * 16;
-      const double* __restrict__ M1 = mats_e + ((size_t)s.child1 * K + k) * 16;
-      const D4 L0 = s.child0 < n ? tip_L(s.child0) : load4(plv_at(s.child0, k));
-      const D4 L1 = s.child1 < n ? tip_L(s.child1) : load4(plv_at(s.child1, k));
-      const D4 L = mul4(matvec(M0, L0), matvec(M1, L1));
-      if (RESCALE) mx = fmax(mx, max4(L));
-      if (is_root && !RESCALE) {
-        site += model->cat_weight[k] * (model->pi[0] * L.x0 + model->pi[1] * L.x1 +
-                                        model->pi[2] * L.x2 + model->pi[3] * L.x3);
-      } else {
-        store4(plv_at(s.node, k), L);
-      }
-    }
-    if (RESCALE) {
-      const int ex = max_exponent(mx);
-      cum_exp += ex;
-      for (int k = 0; k < K; k++) {
-        const D4 L = scale4(load4(plv_at(s.node, k)), -ex);
-        if (is_root)
-          site += model->cat_weight[k] * (model->pi[0] * L.x0 + model->pi[1] * L.x1 +
-                                          model->pi[2] * L.x2 + model->pi[3] * L.x3);
-        else
-          store4(plv_at(s.node, k), L);
-      }
-    }
-  }
-  {
-    double ll = log(site);
-    if (RESCALE) ll += cum_exp * 0.6931471805599453;
-    ll = p < a.P ? w * ll : 0.0;
-    ll = wave_sum(ll);
-    if (lane == 0) a.ll_part[(size_t)e * a.ll_tiles + tile] = ll;
-  }
+  hbm_post_order<RESCALE>(c);
 
   // ---- pre-order + first and second edge derivatives, parents before children ----
   for (int i = n - 2; i >= 0; i--) {
-    const SchedEntry s = sched[i];
+    const SchedEntry s = c.sched[i];
     const bool is_root = i == n - 2;
     double nb0 = 0, hb0 = 0, den0 = 0, nb1 = 0, hb1 = 0, den1 = 0;
     double mx0 = 0, mx1 = 0;
     for (int k = 0; k < K; k++) {
-      const double* __restrict__ M0 = mats_e + ((size_t)s.child0 * K + k) * 16;
-      const double* __restrict__ M1 = mats_e + ((size_t)s.child1 * K + k) * 16;
-      const D4 qv = is_root ? D4{model->pi[0], model->pi[1], model->pi[2], model->pi[3]}
-                            : load4(plv_at(s.node, k));
-      const D4 L0 = s.child0 < n ? tip_L(s.child0) : load4(plv_at(s.child0, k));
-      const D4 L1 = s.child1 < n ? tip_L(s.child1) : load4(plv_at(s.child1, k));
-      const D4 A = matvec(M0, L0), B = matvec(M1, L1);
-      const D4 q0 = matTvec(M0, mul4(qv, B));
-      const D4 q1 = matTvec(M1, mul4(qv, A));
+      const HbmVisit v = hbm_visit_operands(c, s, is_root, k);
+      const D4 q0 = matTvec(v.M0, mul4(v.qv, v.B));
+      const D4 q1 = matTvec(v.M1, mul4(v.qv, v.A));
       const double cw = model->cat_weight[k], r = model->cat_rate[k];
-      const D4 QL0 = matvec(model->Q, L0), QL1 = matvec(model->Q, L1);
+      const D4 QL0 = matvec(model->Q, v.L0), QL1 = matvec(model->Q, v.L1);
       nb0 += r * (cw * dot4(q0, QL0));
       hb0 += r * r * (cw * dot4(q0, matvec(model->Q, QL0)));
-      den0 += cw * dot4(q0, L0);
+      den0 += cw * dot4(q0, v.L0);
       nb1 += r * (cw * dot4(q1, QL1));
       hb1 += r * r * (cw * dot4(q1, matvec(model->Q, QL1)));
-      den1 += cw * dot4(q1, L1);
-      if (s.child0 >= n) {
-        store4(plv_at(s.child0, k), q0);
-        if (RESCALE) mx0 = fmax(mx0, max4(q0));
-      }
-      if (s.child1 >= n) {
-        store4(plv_at(s.child1, k), q1);
-        if (RESCALE) mx1 = fmax(mx1, max4(q1));
-      }
+      den1 += cw * dot4(q1, v.L1);
+      hbm_store_children<RESCALE>(c, s, k, q0, q1, mx0, mx1);
     }
-    if (RESCALE) {
-      if (s.child0 >= n) {
-        const int ex = max_exponent(mx0);
-        for (int k = 0; k < K; k++)
-          store4(plv_at(s.child0, k), scale4(load4(plv_at(s.child0, k)), -ex));
-      }
-      if (s.child1 >= n) {
-        const int ex = max_exponent(mx1);
-        for (int k = 0; k < K; k++)
-          store4(plv_at(s.child1, k), scale4(load4(plv_at(s.child1, k)), -ex));
-      }
-    }
+    hbm_rescale_children<RESCALE>(c, s, mx0, mx1);
     // D1/L per pattern before it is squared: w (D1/L)^2 carries w once; padding lanes add 0
     const double d0 = nb0 / den0, d1 = nb1 / den1;
     const double g0 = wave_sum(p < a.P ? w * d0 : 0.0);
@@ -309,28 +143,14 @@ __global__ __launch_bounds__(kTile) void gradient_hbm_hess_kernel(LikArgs a) {
 // Launch wrappers
 // ------------------------------------------------------------------------
 void launch_gradient_hbm(const LikArgs& a, int count, bool rescale, hipStream_t s) {
-  if (count <= 0) return;
-  const dim3 grid(a.tiles, count), block(kTile);
-  const bool tp = a.tip_partials != nullptr;
-  if (rescale) {
-    if (tp) hipLaunchKernelGGL((gradient_hbm_kernel<true, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((gradient_hbm_kernel<true, false>), grid, block, 0, s, a);
-  } else {
-    if (tp) hipLaunchKernelGGL((gradient_hbm_kernel<false, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((gradient_hbm_kernel<false, false>), grid, block, 0, s, a);
-  }
+  launch_hbm_member(a, count, rescale, 0, s, [](auto R, auto TP) -> HbmKernel {
+    return gradient_hbm_kernel<decltype(R)::value, decltype(TP)::value>;
+  });
 }
 void launch_gradient_hbm_hessian(const LikArgs& a, int count, bool rescale, hipStream_t s) {
-  if (count <= 0) return;
-  const dim3 grid(a.tiles, count), block(kTile);
-  const bool tp = a.tip_partials != nullptr;
-  if (rescale) {
-    if (tp) hipLaunchKernelGGL((gradient_hbm_hess_kernel<true, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((gradient_hbm_hess_kernel<true, false>), grid, block, 0, s, a);
-  } else {
-    if (tp) hipLaunchKernelGGL((gradient_hbm_hess_kernel<false, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((gradient_hbm_hess_kernel<false, false>), grid, block, 0, s, a);
-  }
+  launch_hbm_member(a, count, rescale, 0, s, [](auto R, auto TP) -> HbmKernel {
+    return gradient_hbm_hess_kernel<decltype(R)::value, decltype(TP)::value>;
+  });
 }
 int gradient_mfma_width(int n, bool subst) {
   return max_macros(n) * kMacroPositions * 2 + (subst ? kSubstExtra : 0);

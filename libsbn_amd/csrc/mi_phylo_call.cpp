@@ -693,29 +693,13 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d_in) {
   return 0;
 }
 
-// ---- the branch-length Hessian call (mi_engine_branch_hessian_unrooted*, DESIGN.md 4.8) ----
-// Tree set-up and model instances, the walk's macro-ordered matrices or the HBM kernel's
-// node-ordered ones (plan_call), the Hessian form of that kernel; one launch reduces the
-// tiles and writes the outputs.
-int reserve_hessian(mi_engine* e, const CallPlan& p) {
-  const int n = e->n, N = e->N, T = p.T;
-  if (p.mfma) {
-    if (e->macros.ensure(sizeof(MacroEntry) * (size_t)T * macro_stride(n))) return 1;
-    if (e->mmats.ensure(gradient_walk_mats_bytes_per_eval(n, e->K) * (size_t)T)) return 1;
-    if (e->g_part.ensure(sizeof(double) * (size_t)T * p.g_tiles * max_macros(n) * kMacroPositions * 3)) return 1;
-    if (p.reserve_arena) {
-      const size_t aper = gradient_arena_bytes_per_eval(n, e->P, e->K);
-      const size_t achunk = std::max<size_t>(1, std::min<size_t>(T, e->plv_budget / aper));
-      if (e->plv.ensure(aper * achunk)) return 1;
-      if (e->arena_macros.ensure(sizeof(MacroEntry) * (size_t)T * macro_stride(n))) return 1;
-      if (e->slot_need.ensure(sizeof(int32_t) * (size_t)T)) return 1;
-    }
-  } else {
-    const size_t per = plv_bytes_per_eval(e);
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(T, e->plv_budget / per));
-    if (e->plv.ensure(per * chunk)) return 1;
-    if (e->g_part.ensure(sizeof(double) * (size_t)T * e->tiles * 3 * N)) return 1;
-  }
+// ---- the calls of the HBM-streamed kernel family ----
+// One evaluation per tree with the tree's own model, the node-ordered matrices, the member's
+// kernel over the vector arena in parts, one finalize launch: the Hessian call where no
+// matrix-core walk takes it, the NNI scan, the ancestral-state call.
+// (trees, models, node-ordered matrices, log-likelihood partials: the Hessian call's walk form too)
+static int reserve_per_tree(mi_engine* e, int T) {
+  const int n = e->n, N = e->N;
   if (e->tree_scratch.ensure(sizeof(int32_t) * (size_t)T * 13 * N)) return 1;
   if (e->sched.ensure(sizeof(SchedEntry) * (size_t)T * (n - 1))) return 1;
   if (e->macro_count.ensure(sizeof(int32_t) * (size_t)T)) return 1;
@@ -724,6 +708,66 @@ int reserve_hessian(mi_engine* e, const CallPlan& p) {
   if (e->mats.ensure(sizeof(double) * (size_t)T * (N - 1) * e->K * 16)) return 1;
   if (e->ll_part.ensure(sizeof(double) * (size_t)T * e->ll_stride)) return 1;
   return e->status.ensure(sizeof(int32_t) * kStatusWords);
+}
+// What every such call needs; g_width: doubles of g_part per (tree, tile), 0: the kernel has none.
+static int reserve_hbm_family(mi_engine* e, int T, int g_width) {
+  const size_t per = plv_bytes_per_eval(e);
+  const size_t chunk = std::max<size_t>(1, std::min<size_t>(T, e->plv_budget / per));
+  if (e->plv.ensure(per * chunk)) return 1;
+  if (g_width && e->g_part.ensure(sizeof(double) * (size_t)T * e->tiles * g_width)) return 1;
+  return reserve_per_tree(e, T);
+}
+// The sequence after check, plan and reservation: set-up, matrices, launch(args, count, rescale,
+// stream) over the vector arena in parts, finalize().
+template <typename Launch, typename Finalize>
+int run_hbm_family(mi_engine* e, hipStream_t s, const DeviceCall& d, const CallPlan& p, Launch launch,
+                   Finalize finalize) {
+  const int T = d.T;
+  const bool prof = e->prof_used < e->prof_capacity;
+  const bool marks = prof && e->prof_phases;
+  PROF_MARK(e, marks, 0, s);
+  launch_setup(tree_setup_args(e, d, p), model_setup_args(e, d, p), e->sw, s);
+  launch_transition(transition_args(e, d, p), s);
+
+  const LikArgs la = lik_args(e, d, p);
+  if (prof) HIP_TRY(hipEventRecord(prof_event(e, 0), s));
+  PROF_MARK(e, marks, 1, s);
+  PROF_MARK(e, marks, 2, s);
+  // (a launch covers what the vector arena holds)
+  int walk_launches = 0;
+  const int first = launch_in_parts(e, T, vector_bytes_per_eval(e, p), walk_launches, [&](int done, int part) {
+    LikArgs g = la;
+    g.eval_offset = done;
+    g.grad_offset = done;
+    launch(g, part, d.rescaling, s);
+  });
+  if (prof) HIP_TRY(hipEventRecord(prof_event(e, 1), s));
+  PROF_MARK(e, marks, 3, s);
+  finalize();
+  PROF_MARK(e, marks, 4, s);
+  if (prof) e->prof_used++;
+  note_call(e, p, first, walk_launches);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- the branch-length Hessian call (mi_engine_branch_hessian_unrooted*, DESIGN.md 4.8) ----
+// The Hessian form of the second-generation walk with its macro-ordered matrices, or of the
+// HBM-streamed gradient kernel (plan_call); one launch reduces the tiles and writes the outputs.
+int reserve_hessian(mi_engine* e, const CallPlan& p) {
+  const int n = e->n, T = p.T;
+  if (!p.mfma) return reserve_hbm_family(e, T, 3 * e->N);
+  if (e->macros.ensure(sizeof(MacroEntry) * (size_t)T * macro_stride(n))) return 1;
+  if (e->mmats.ensure(gradient_walk_mats_bytes_per_eval(n, e->K) * (size_t)T)) return 1;
+  if (e->g_part.ensure(sizeof(double) * (size_t)T * p.g_tiles * max_macros(n) * kMacroPositions * 3)) return 1;
+  if (p.reserve_arena) {
+    const size_t aper = gradient_arena_bytes_per_eval(n, e->P, e->K);
+    const size_t achunk = std::max<size_t>(1, std::min<size_t>(T, e->plv_budget / aper));
+    if (e->plv.ensure(aper * achunk)) return 1;
+    if (e->arena_macros.ensure(sizeof(MacroEntry) * (size_t)T * macro_stride(n))) return 1;
+    if (e->slot_need.ensure(sizeof(int32_t) * (size_t)T)) return 1;
+  }
+  return reserve_per_tree(e, T);
 }
 // (both rescaling settings: a later *_device call of either allocates nothing)
 int reserve_hessian_calls(mi_engine* e, int T) {
@@ -737,46 +781,49 @@ int run_hessian_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   const CallPlan p = plan_call(e, kHessianCall, d);
   if (reserve_hessian(e, p)) return 1;
   const int n = e->n, N = e->N, T = d.T;
+  auto finalize = [&] {
+    HessFinalizeArgs fa{};
+    fa.N = N;
+    fa.T = T;
+    fa.g_tiles = p.g_tiles;
+    fa.ll_tiles = e->ll_stride;
+    fa.ll_used = p.g_tiles;
+    fa.n = n;
+    fa.g_width = p.mfma ? max_macros(n) * kMacroPositions * 3 : 3 * N;
+    fa.macros = p.mfma ? walk_macros(e, p) : nullptr;
+    fa.macro_count = e->macro_count.as<int32_t>();
+    fa.ll_part = e->ll_part.as<double>();
+    fa.g_part = e->g_part.as<double>();
+    fa.out_ll = d.out_ll;
+    fa.out_branch = d.out_branch;
+    fa.out_hess = d.out_hess;
+    fa.out_gsq = d.out_gsq;
+    launch_hessian_finalize(fa, s);
+  };
+  if (!p.mfma) return run_hbm_family(e, s, d, p, launch_gradient_hbm_hessian, finalize);
+  // the walk form: LDS slots of the arena variant, macro-ordered matrices
   const bool prof = e->prof_used < e->prof_capacity;
   const bool marks = prof && e->prof_phases;
   PROF_MARK(e, marks, 0, s);
   const bool slots_done = launch_setup(tree_setup_args(e, d, p), model_setup_args(e, d, p), e->sw, s);
   if (p.store == kStoreArena && !slots_done) macro_slots(e, T, s);
-  if (p.mfma) launch_transition_macro(transition_macro_args(e, d, p, 0, 0, T), s);
-  else launch_transition(transition_args(e, d, p), s);
+  launch_transition_macro(transition_macro_args(e, d, p, 0, 0, T), s);
 
   const LikArgs la = lik_args(e, d, p);
   if (prof) HIP_TRY(hipEventRecord(prof_event(e, 0), s));
   PROF_MARK(e, marks, 1, s);
   PROF_MARK(e, marks, 2, s);
-  // (a launch covers what the vector arena holds: the HBM kernel's, or the walk's arena)
+  // (a launch covers what the walk's arena holds)
   int walk_launches = 0;
   const int first = launch_in_parts(e, T, vector_bytes_per_eval(e, p), walk_launches, [&](int done, int part) {
     LikArgs g = la;
     g.eval_offset = done;
     g.grad_offset = done;
-    if (p.mfma) launch_gradient_walk_hessian(g, part, d.rescaling, s);
-    else launch_gradient_hbm_hessian(g, part, d.rescaling, s);
+    launch_gradient_walk_hessian(g, part, d.rescaling, s);
   });
   if (prof) HIP_TRY(hipEventRecord(prof_event(e, 1), s));
   PROF_MARK(e, marks, 3, s);
-  HessFinalizeArgs fa{};
-  fa.N = N;
-  fa.T = T;
-  fa.g_tiles = p.g_tiles;
-  fa.ll_tiles = e->ll_stride;
-  fa.ll_used = p.g_tiles;
-  fa.n = n;
-  fa.g_width = p.mfma ? max_macros(n) * kMacroPositions * 3 : 3 * N;
-  fa.macros = p.mfma ? walk_macros(e, p) : nullptr;
-  fa.macro_count = e->macro_count.as<int32_t>();
-  fa.ll_part = e->ll_part.as<double>();
-  fa.g_part = e->g_part.as<double>();
-  fa.out_ll = d.out_ll;
-  fa.out_branch = d.out_branch;
-  fa.out_hess = d.out_hess;
-  fa.out_gsq = d.out_gsq;
-  launch_hessian_finalize(fa, s);
+  finalize();
   PROF_MARK(e, marks, 4, s);
   if (prof) e->prof_used++;
   note_call(e, p, first, walk_launches);
@@ -785,125 +832,46 @@ int run_hessian_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
 }
 
 // ---- the NNI neighbourhood scan (mi_engine_nni_scan_unrooted*) ----
-// Tree set-up and model instances, the node-ordered matrices, the scan kernel over the vector
-// arena in parts; one launch reduces the tiles and writes logL, delta and the best move.
-int reserve_nni(mi_engine* e, const CallPlan& p) {
-  const int n = e->n, N = e->N, T = p.T;
-  const size_t per = plv_bytes_per_eval(e);
-  const size_t chunk = std::max<size_t>(1, std::min<size_t>(T, e->plv_budget / per));
-  if (e->plv.ensure(per * chunk)) return 1;
-  if (e->g_part.ensure(sizeof(double) * (size_t)T * e->tiles * 2 * N)) return 1;
-  if (e->tree_scratch.ensure(sizeof(int32_t) * (size_t)T * 13 * N)) return 1;
-  if (e->sched.ensure(sizeof(SchedEntry) * (size_t)T * (n - 1))) return 1;
-  if (e->macro_count.ensure(sizeof(int32_t) * (size_t)T)) return 1;
-  if (e->bl_eff.ensure(sizeof(double) * (size_t)T * N)) return 1;
-  if (e->models.ensure(sizeof(DevModel) * (size_t)T)) return 1;
-  if (e->mats.ensure(sizeof(double) * (size_t)T * (N - 1) * e->K * 16)) return 1;
-  if (e->ll_part.ensure(sizeof(double) * (size_t)T * e->ll_stride)) return 1;
-  return e->status.ensure(sizeof(int32_t) * kStatusWords);
-}
+// The scan kernel; one launch reduces the tiles and writes logL, delta and the best move.
 // (the plan does not depend on the rescaling setting: one reservation serves both)
-int reserve_nni_calls(mi_engine* e, int T) { return reserve_nni(e, plan_call(e, kNniCall, T, false)); }
+int reserve_nni_calls(mi_engine* e, int T) { return reserve_hbm_family(e, T, 2 * e->N); }
 
 int run_nni_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   HIP_TRY(hipSetDevice(e->spec.device));
   if (e->s == kAa) return fail(kNni4State);
   if (check_call(e, d, d.out_nni)) return 1;
   const CallPlan p = plan_call(e, kNniCall, d);
-  if (reserve_nni(e, p)) return 1;
-  const int T = d.T;
-  const bool prof = e->prof_used < e->prof_capacity;
-  const bool marks = prof && e->prof_phases;
-  PROF_MARK(e, marks, 0, s);
-  launch_setup(tree_setup_args(e, d, p), model_setup_args(e, d, p), e->sw, s);
-  launch_transition(transition_args(e, d, p), s);
-
-  const LikArgs la = lik_args(e, d, p);
-  if (prof) HIP_TRY(hipEventRecord(prof_event(e, 0), s));
-  PROF_MARK(e, marks, 1, s);
-  PROF_MARK(e, marks, 2, s);
-  // (a launch covers what the vector arena holds)
-  int walk_launches = 0;
-  const int first = launch_in_parts(e, T, vector_bytes_per_eval(e, p), walk_launches, [&](int done, int part) {
-    LikArgs g = la;
-    g.eval_offset = done;
-    g.grad_offset = done;
-    launch_nni_scan_hbm(g, part, d.rescaling, s);
+  if (reserve_nni_calls(e, d.T)) return 1;
+  return run_hbm_family(e, s, d, p, launch_nni_scan_hbm, [&] {
+    NniFinalizeArgs fa{};
+    fa.N = e->N;
+    fa.n = e->n;
+    fa.T = d.T;
+    fa.g_tiles = p.g_tiles;
+    fa.ll_tiles = e->ll_stride;
+    fa.ll_used = p.g_tiles;
+    fa.ll_part = e->ll_part.as<double>();
+    fa.g_part = e->g_part.as<double>();
+    fa.out_ll = d.out_ll;
+    fa.out_delta = d.out_nni;
+    fa.out_best = d.out_best;
+    launch_nni_finalize(fa, s);
   });
-  if (prof) HIP_TRY(hipEventRecord(prof_event(e, 1), s));
-  PROF_MARK(e, marks, 3, s);
-  NniFinalizeArgs fa{};
-  fa.N = e->N;
-  fa.n = e->n;
-  fa.T = T;
-  fa.g_tiles = p.g_tiles;
-  fa.ll_tiles = e->ll_stride;
-  fa.ll_used = p.g_tiles;
-  fa.ll_part = e->ll_part.as<double>();
-  fa.g_part = e->g_part.as<double>();
-  fa.out_ll = d.out_ll;
-  fa.out_delta = d.out_nni;
-  fa.out_best = d.out_best;
-  launch_nni_finalize(fa, s);
-  PROF_MARK(e, marks, 4, s);
-  if (prof) e->prof_used++;
-  note_call(e, p, first, walk_launches);
-  HIP_TRY(hipGetLastError());
-  return 0;
 }
 
 // ---- ancestral-state and rate-category posteriors (mi_engine_ancestral_states_unrooted*) ----
-// Tree set-up and model instances, the node-ordered matrices, the kernel over the vector arena in
-// parts (it writes the posteriors itself, by the call's tree index); one launch sums the tiles'
+// The kernel writes the posteriors itself, by the call's tree index; one launch sums the tiles'
 // log-likelihood partials when the caller wants the log-likelihoods.
-int reserve_ancestral(mi_engine* e, const CallPlan& p) {
-  const int n = e->n, N = e->N, T = p.T;
-  const size_t per = plv_bytes_per_eval(e);
-  const size_t chunk = std::max<size_t>(1, std::min<size_t>(T, e->plv_budget / per));
-  if (e->plv.ensure(per * chunk)) return 1;
-  if (e->tree_scratch.ensure(sizeof(int32_t) * (size_t)T * 13 * N)) return 1;
-  if (e->sched.ensure(sizeof(SchedEntry) * (size_t)T * (n - 1))) return 1;
-  if (e->macro_count.ensure(sizeof(int32_t) * (size_t)T)) return 1;
-  if (e->bl_eff.ensure(sizeof(double) * (size_t)T * N)) return 1;
-  if (e->models.ensure(sizeof(DevModel) * (size_t)T)) return 1;
-  if (e->mats.ensure(sizeof(double) * (size_t)T * (N - 1) * e->K * 16)) return 1;
-  if (e->ll_part.ensure(sizeof(double) * (size_t)T * e->ll_stride)) return 1;
-  return e->status.ensure(sizeof(int32_t) * kStatusWords);
-}
 // (the plan does not depend on the rescaling setting: one reservation serves both)
-int reserve_ancestral_calls(mi_engine* e, int T) { return reserve_ancestral(e, plan_call(e, kAncestralCall, T, false)); }
+int reserve_ancestral_calls(mi_engine* e, int T) { return reserve_hbm_family(e, T, 0); }
 
 int run_ancestral_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   HIP_TRY(hipSetDevice(e->spec.device));
   if (e->s == kAa) return fail(kAncestral4State);
   if (check_call(e, d, d.out_anc_state)) return 1;
   const CallPlan p = plan_call(e, kAncestralCall, d);
-  if (reserve_ancestral(e, p)) return 1;
-  const int T = d.T;
-  const bool prof = e->prof_used < e->prof_capacity;
-  const bool marks = prof && e->prof_phases;
-  PROF_MARK(e, marks, 0, s);
-  launch_setup(tree_setup_args(e, d, p), model_setup_args(e, d, p), e->sw, s);
-  launch_transition(transition_args(e, d, p), s);
-
-  const LikArgs la = lik_args(e, d, p);
-  if (prof) HIP_TRY(hipEventRecord(prof_event(e, 0), s));
-  PROF_MARK(e, marks, 1, s);
-  PROF_MARK(e, marks, 2, s);
-  // (a launch covers what the vector arena holds)
-  int walk_launches = 0;
-  const int first = launch_in_parts(e, T, vector_bytes_per_eval(e, p), walk_launches, [&](int done, int part) {
-    LikArgs g = la;
-    g.eval_offset = done;
-    g.grad_offset = done;
-    launch_ancestral_hbm(g, part, d.rescaling, s);
+  if (reserve_ancestral_calls(e, d.T)) return 1;
+  return run_hbm_family(e, s, d, p, launch_ancestral_hbm, [&] {
+    launch_ancestral_finalize(e->ll_part.as<double>(), d.T, e->ll_stride, p.g_tiles, d.out_ll, s);
   });
-  if (prof) HIP_TRY(hipEventRecord(prof_event(e, 1), s));
-  PROF_MARK(e, marks, 3, s);
-  launch_ancestral_finalize(e->ll_part.as<double>(), T, e->ll_stride, p.g_tiles, d.out_ll, s);
-  PROF_MARK(e, marks, 4, s);
-  if (prof) e->prof_used++;
-  note_call(e, p, first, walk_launches);
-  HIP_TRY(hipGetLastError());
-  return 0;
 }

@@ -312,10 +312,8 @@ ModelSetupArgs model_setup_args(const mi_engine* e, const DeviceCall& d, const C
 FinalizeArgs finalize_args(const mi_engine* e, const DeviceCall& d);  // what comes from the engine and the call
 int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
 int run_hessian_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
-int reserve_nni(mi_engine* e, const CallPlan& p);
 int reserve_nni_calls(mi_engine* e, int T);  // of either rescaling setting (mi_engine_reserve_nni_scan)
 int run_nni_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
-int reserve_ancestral(mi_engine* e, const CallPlan& p);
 int reserve_ancestral_calls(mi_engine* e, int T);  // of either rescaling setting (mi_engine_reserve_ancestral)
 int run_ancestral_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
 // the scan's best move from a tree's delta [N][2] (what the finalize kernel does; pattern shards)
