@@ -355,6 +355,94 @@ int32_t mi_engine_pattern_mixture(mi_engine* engine, int32_t tree_count, int32_t
                                   double* out_pattern_log_marginal /* [P] */,
                                   double* out_log_marginal /* [1] */);
 
+/* Starting trees from the engine's alignment (an extension; 4-state engines):
+ * pairwise maximum-likelihood distances for B sets of pattern weights, neighbour joining of B
+ * distance matrices, and the two in one call.  With the replicate weights of a bootstrap
+ * (what RELL resamples with) B distance matrices give B neighbour-joining trees: a batch of
+ * starts for mi_engine_nni_search_unrooted, and a distance bootstrap.
+ *
+ * Counts.  For taxa i < j and states a, b
+ *   N_r[i][j][a][b] = sum_p W[r][p] [tip_i(p) = a] [tip_j(p) = b]     (FP64 matrix cores)
+ * A tip counts as state a when its compact code is a or -- an engine made from tip partials --
+ * its vector is exactly the unit vector e_a; every other tip (gap, 0/1 mask, real-valued
+ * partial) is missing, and a pattern with a missing tip at i or j adds nothing to that pair
+ * (pairwise deletion).  Every count has one accumulator that takes the patterns in ascending
+ * order, four per step, from p = 0, whatever B, n and the pair's place in the launch: with
+ * integer weights the counts are exact, and equal rows of W give bit-identical counts and
+ * distances.  replicate_weights NULL: one replicate, the engine's pattern weights.  The weights
+ * must be finite (they are not checked: a non-finite one makes NaN counts).
+ *
+ * Distance.  With the rates r_k and weights c_k of the model row's site model and P(.) of its
+ * substitution model (ONE row params[param_count] for the call),
+ *   d = argmax over t in [min_length, max_length] of l(t) = sum_ab N[a][b] log sum_k c_k P_ab(r_k t)
+ * by a safeguarded Newton iteration on l': a bracket kept by the sign of l', a step that
+ * leaves it (one that lands on an end has not) or an l'' >= 0 replaced by the bracket's
+ * midpoint, started at the JC69 closed form
+ * of the pair's mismatch share clamped into the box, stopped when |step| <= tolerance max(t, 1e-3)
+ * or after max_iterations.  l'(min_length) <= 0 gives min_length, l'(max_length) >= 0
+ * max_length, a pair with no comparable pattern (sum N = 0) max_length.
+ *   out_distances   [B][n][n]            symmetric, zero diagonal
+ *   out_pair_counts [B][n(n-1)/2][16]    or NULL; pairs in lexicographic (i, j) order, 4 a + b
+ *   out_pair_status [B][n(n-1)/2]        or NULL; MI_DISTANCE_*
+ * The counts of B replicates are worked off in chunks that keep the count workspace within
+ * MI_PHYLO_PLV_BYTES (mi_engine_last_call_launches: the chunks; mi_engine_last_call_path:
+ * "pair_counts B=<B> chunks=<c>").  Sharded handles: a tree-sharded handle lets its first shard
+ * do the work (every shard holds the whole alignment); MI_SHARD_PATTERNS is refused. */
+enum {
+  MI_DISTANCE_CONVERGED = 0,
+  MI_DISTANCE_LOWER_BOUND = 1,
+  MI_DISTANCE_UPPER_BOUND = 2,
+  MI_DISTANCE_NO_DATA = 3,
+  MI_DISTANCE_ITERATION_LIMIT = 4
+};
+typedef struct {
+  int32_t max_iterations; /* Newton iterations per pair, 1..1000 (default 50) */
+  int32_t reserved0;      /* 0 */
+  double tolerance;       /* default 1e-10 */
+  double min_length;      /* default 1e-8 */
+  double max_length;      /* default 10 */
+  int32_t reserved[4];    /* 0 */
+} mi_distance_options;    /* a field left at 0 takes its default */
+int32_t mi_engine_pairwise_distances(mi_engine* engine, int32_t replicate_count,
+                                     const double* replicate_weights /* [B][P] or NULL */,
+                                     const double* params /* [param_count] */,
+                                     const mi_distance_options* options /* NULL: the defaults */,
+                                     double* out_distances /* [B][n][n] */,
+                                     double* out_pair_counts /* [B][n(n-1)/2][16] or NULL */,
+                                     int8_t* out_pair_status /* [B][n(n-1)/2] or NULL */);
+
+/* Neighbour joining (Saitou & Nei) of B distance matrices [B][n][n], of which only i < j is
+ * read; n is an argument: any engine serves (the alignment plays no part), a sharded handle
+ * lets its first shard do it.  The trees come in the form every unrooted call takes: leaves
+ * 0..n-1, internal nodes in post-order with the children ordered by largest leaf id, the
+ * trifurcating root 2n-3, its length entry 0.  The rule, so that it is reproducible: clusters
+ * live in slots 0..n-1; joining slots i < j puts the new cluster in slot i and kills slot j;
+ * with r live slots and R_i = sum_k d(i, k) over the live slots in ascending order, the pair
+ * that minimises Q(i, j) = (r-2) d(i, j) - R_i - R_j is joined, the lowest (i, j) among equals;
+ * delta_i = d(i, j) / 2 + (R_i - R_j) / (2 (r-2)), delta_j = d(i, j) - delta_i,
+ * d(u, k) = (d(i, k) + d(j, k) - d(i, j)) / 2; the last three clusters a < b < c hang under the
+ * root with (d_ab + d_ac - d_bc) / 2 and its two rotations; n = 3 is that step alone.  Every
+ * operation is rounded once, in the order written (the kernel is compiled without
+ * floating-point contraction), so a host implementation in IEEE doubles gives the same bits.  The lengths are clamped into
+ * [min_length, max_length] on their way out (raw lengths can be negative), never in the
+ * matrix.  A distance that is not finite is an error that names its matrix ("... (matrix b)").
+ * mi_engine_last_call_path: "nj n=<n> store=lds|global". */
+int32_t mi_engine_neighbour_joining(mi_engine* engine, int32_t replicate_count, int32_t taxon_count,
+                                    const double* distances /* [B][n][n] */, double min_length,
+                                    double max_length, int32_t* out_parent_ids /* [B][2n-3] */,
+                                    double* out_branch_lengths /* [B][2n-2] */);
+
+/* mi_engine_pairwise_distances followed by mi_engine_neighbour_joining (clamped into the
+ * options' box) on the engine's alignment; nothing returns to the host in between.
+ * out_distances may be NULL.  The results are those of the two calls, bit for bit. */
+int32_t mi_engine_starting_trees_unrooted(mi_engine* engine, int32_t replicate_count,
+                                          const double* replicate_weights /* [B][P] or NULL */,
+                                          const double* params /* [param_count] */,
+                                          const mi_distance_options* options /* NULL: the defaults */,
+                                          int32_t* out_parent_ids /* [B][2n-3] */,
+                                          double* out_branch_lengths /* [B][2n-2] */,
+                                          double* out_distances /* [B][n][n] or NULL */);
+
 /* Maximum-likelihood branch lengths of unrooted trees under box bounds (an extension: the
  * consumer of the Hessian call's outputs).  Every tree of the batch is
  * iterated on the device: an evaluation is one Hessian pass at a trial point, a step is a
@@ -657,6 +745,37 @@ int32_t mi_engine_reserve_nni_search(mi_engine* engine, int32_t tree_count);
  * *_device call of at most that size then allocates nothing.  `pattern_count` needs none. */
 int32_t mi_engine_reserve_rell(mi_engine* engine, int32_t replicate_count, int32_t tree_count,
                                int32_t pattern_count);
+/* The device forms of mi_engine_pairwise_distances, mi_engine_neighbour_joining and
+ * mi_engine_starting_trees_unrooted: every array a device pointer (the options stay a host
+ * struct).  They only enqueue; after mi_engine_reserve_start_trees they allocate nothing and
+ * synchronise nothing, so they can be captured in a hipGraph: the iteration counts inside the
+ * kernels are bounded by max_iterations and n, nothing is read back.  Per-call input errors (a
+ * distance that is not finite, GTR parameters that do not sum to 1) go to the status word
+ * (mi_engine_check_status). */
+int32_t mi_engine_pairwise_distances_device(mi_engine* engine, void* stream, int32_t replicate_count,
+                                            const double* replicate_weights, const double* params,
+                                            const mi_distance_options* options, double* out_distances,
+                                            double* out_pair_counts, int8_t* out_pair_status);
+int32_t mi_engine_neighbour_joining_device(mi_engine* engine, void* stream, int32_t replicate_count,
+                                           int32_t taxon_count, const double* distances,
+                                           double min_length, double max_length,
+                                           int32_t* out_parent_ids, double* out_branch_lengths);
+int32_t mi_engine_starting_trees_unrooted_device(mi_engine* engine, void* stream,
+                                                 int32_t replicate_count,
+                                                 const double* replicate_weights, const double* params,
+                                                 const mi_distance_options* options,
+                                                 int32_t* out_parent_ids, double* out_branch_lengths,
+                                                 double* out_distances);
+/* The workspace of the three calls above for `replicate_count` replicates of the engine's own
+ * alignment and taxon count (the tip codes, the model instance, the count workspace of a
+ * chunk, the distances nobody asked for, neighbour joining's working sets).  It covers the
+ * engine's OWN taxon count only: mi_engine_neighbour_joining_device with another taxon_count
+ * allocates its workspace (beyond 128 taxa) and opts its kernel into large LDS at its first
+ * call of that size -- run one such call before capturing it in a graph.  (Engines of several
+ * hundred taxa: the set-up kernel that instantiates the model opts into large LDS at ITS first
+ * launch, as in every other call -- there too, one call before the capture.)  4-state engines
+ * only; a sharded handle reserves on its first shard. */
+int32_t mi_engine_reserve_start_trees(mi_engine* engine, int32_t replicate_count);
 /* Synchronise `stream` and report the first per-tree error since the last check (the status
  * word is sticky and cleared when an error is reported: calls themselves never clear it). */
 int32_t mi_engine_check_status(mi_engine* engine, void* stream);

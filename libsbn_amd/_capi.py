@@ -33,6 +33,12 @@ class NniSearchOptions(C.Structure):
                 ("reserved", C.c_int32 * 4), ("branch_opt", BranchOptOptions)]
 
 
+class DistanceOptions(C.Structure):
+    """mi_distance_options (include/mi_phylo.h)."""
+    _fields_ = [("max_iterations", C.c_int32), ("reserved0", C.c_int32), ("tolerance", C.c_double),
+                ("min_length", C.c_double), ("max_length", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
 # Every symbol include/mi_phylo.h declares: (restype, argtypes)
 _V = C.c_void_p
 SYMBOLS = {
@@ -118,6 +124,16 @@ SYMBOLS = {
     "mi_engine_pattern_mixture": (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),
     "mi_engine_pattern_mixture_device":
         (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),
+    "mi_engine_pairwise_distances": (C.c_int32, [_V, C.c_int32, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_pairwise_distances_device": (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_neighbour_joining":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, _V, C.c_double, C.c_double, _V, _V]),
+    "mi_engine_neighbour_joining_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, C.c_double, C.c_double, _V, _V]),
+    "mi_engine_starting_trees_unrooted": (C.c_int32, [_V, C.c_int32, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_starting_trees_unrooted_device":
+        (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_reserve_start_trees": (C.c_int32, [_V, C.c_int32]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),
     "mi_engine_profile_begin": (C.c_int32, [_V, C.c_int32]),
     "mi_engine_profile_collect": (C.c_int32, [_V, F64P, C.c_int32, I32P]),

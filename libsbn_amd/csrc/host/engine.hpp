@@ -73,6 +73,22 @@ struct RellBootstrapResult {
   std::vector<double> bootstrap_proportion_, expected_likelihood_weight_;
 };
 
+// Engine::PairwiseDistances (an extension, include/mi_phylo.h): distances_ [B][n][n] (symmetric,
+// zero diagonal), the substitution counts pair_counts_ [B][n(n-1)/2][16] of the pairs in
+// lexicographic (i, j) order and the solver's status per pair [B][n(n-1)/2] (MI_DISTANCE_*)
+struct PairwiseDistanceResult {
+  std::vector<double> distances_, pair_counts_;
+  std::vector<int8_t> pair_status_;
+};
+
+// Engine::NeighbourJoining / Engine::StartingTrees (extensions, include/mi_phylo.h): per matrix /
+// replicate the tree in the form every unrooted call takes, parent_ids_ [B][2n-3] and
+// branch_lengths_ [B][2n-2], and (StartingTrees) the distances_ [B][n][n] they were joined from
+struct StartingTreeResult {
+  std::vector<int32_t> parent_ids_;
+  std::vector<double> branch_lengths_, distances_;
+};
+
 // Engine::AncestralStates, per tree (an extension, include/mi_phylo.h), per pattern and
 // unweighted: state_posteriors_ [n-2][P][4] of the internal nodes n .. 2n-3 (row v - n) and, asked
 // for, map_states_ [n-2][P], category_posteriors_ [P][K] with pattern_rates_ [P], and
@@ -370,6 +386,58 @@ class Engine {
     return out;
   }
 
+  // Maximum-likelihood distances of all pairs of taxa for `replicates` rows of replicate weights
+  // [B][P] (empty: one replicate, the engine's pattern weights) under ONE parameter row (an
+  // extension; 4-state engines): mi_engine_pairwise_distances.  options == nullptr: the defaults
+  // of include/mi_phylo.h.
+  PairwiseDistanceResult PairwiseDistances(const size_t replicates, const std::vector<double>& replicate_weights,
+                                           const std::vector<double>& param_row,
+                                           const mi_distance_options* options = nullptr) const {
+    const size_t n = site_pattern_.SequenceCount(), B = CheckReplicates(replicates, replicate_weights, param_row);
+    PairwiseDistanceResult out;
+    out.distances_.resize(B * n * n);
+    out.pair_counts_.resize(B * (n * (n - 1) / 2) * 16);
+    out.pair_status_.resize(B * (n * (n - 1) / 2));
+    Check(mi_engine_pairwise_distances(handle_, static_cast<int32_t>(B),
+                                       replicate_weights.empty() ? nullptr : replicate_weights.data(),
+                                       param_row.data(), options, out.distances_.data(), out.pair_counts_.data(),
+                                       out.pair_status_.data()));
+    return out;
+  }
+
+  // Neighbour joining of `matrices` distance matrices [B][n][n] of `taxon_count` taxa (an
+  // extension; any engine): mi_engine_neighbour_joining.  Lengths clamped into the box.
+  StartingTreeResult NeighbourJoining(const size_t matrices, const size_t taxon_count,
+                                      const std::vector<double>& distances, const double min_length = 1e-8,
+                                      const double max_length = 10.) const {
+    const size_t B = matrices, n = taxon_count;
+    if (B < 1 || n < 3 || distances.size() != B * n * n)
+      Failwith("NeighbourJoining: distances must be [matrices][taxa][taxa], at least three taxa.");
+    StartingTreeResult out;
+    out.parent_ids_.resize(B * (2 * n - 3));
+    out.branch_lengths_.resize(B * (2 * n - 2));
+    Check(mi_engine_neighbour_joining(handle_, static_cast<int32_t>(B), static_cast<int32_t>(n), distances.data(),
+                                      min_length, max_length, out.parent_ids_.data(), out.branch_lengths_.data()));
+    return out;
+  }
+
+  // PairwiseDistances followed by NeighbourJoining in one call, nothing returning to the host in
+  // between (an extension; 4-state engines): mi_engine_starting_trees_unrooted.
+  StartingTreeResult StartingTrees(const size_t replicates, const std::vector<double>& replicate_weights,
+                                   const std::vector<double>& param_row,
+                                   const mi_distance_options* options = nullptr) const {
+    const size_t n = site_pattern_.SequenceCount(), B = CheckReplicates(replicates, replicate_weights, param_row);
+    StartingTreeResult out;
+    out.parent_ids_.resize(B * (2 * n - 3));
+    out.branch_lengths_.resize(B * (2 * n - 2));
+    out.distances_.resize(B * n * n);
+    Check(mi_engine_starting_trees_unrooted(handle_, static_cast<int32_t>(B),
+                                            replicate_weights.empty() ? nullptr : replicate_weights.data(),
+                                            param_row.data(), options, out.parent_ids_.data(),
+                                            out.branch_lengths_.data(), out.distances_.data()));
+    return out;
+  }
+
   // Maximum-likelihood branch lengths per tree, started from the trees' own lengths
   // (an extension; 4-state engines): mi_engine_optimize_branch_lengths_unrooted.
   // options == nullptr: the defaults of include/mi_phylo.h.
@@ -501,6 +569,17 @@ class Engine {
   // the C handle behind it)
   mutable std::vector<int32_t> scratch_parents_;
   mutable std::vector<double> scratch_bl_, scratch_ll_, scratch_a_, scratch_site_, scratch_subst_;
+
+  // the replicate count of a starting-tree call (empty weights: one replicate, the engine's own)
+  size_t CheckReplicates(const size_t replicates, const std::vector<double>& replicate_weights,
+                         const std::vector<double>& param_row) const {
+    const size_t P = site_pattern_.PatternCount(), B = replicate_weights.empty() ? 1 : replicates;
+    if (B < 1 || (!replicate_weights.empty() && replicate_weights.size() != B * P))
+      Failwith("replicate weights must be [replicates][patterns], at least one replicate.");
+    if (param_row.size() != static_cast<size_t>(ParameterCount()))
+      Failwith("pairwise distances take ONE parameter row.");
+    return B;
+  }
 
   static void Check(int rc) {
     if (rc != 0) Failwith(mi_last_error());

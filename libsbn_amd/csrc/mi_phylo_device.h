@@ -89,6 +89,7 @@ enum StatusCode : int32_t {
   kTooManySlots = 7,
   kFusedTimeout = 8,
   kBadNniMove = 9,
+  kBadDistance = 10,
 };
 
 }  // namespace miphylo

@@ -79,7 +79,8 @@ int check_status(mi_engine* e, hipStream_t s) {
     HIP_TRY(hipMemsetAsync(e->status.ptr, 0, sizeof(int32_t) * kStatusWords, s));
     HIP_TRY(hipStreamSynchronize(s));
     // (a shard of a sharded handle reports the caller's tree index, not its own)
-    return fail(std::string(status_message(st[0])) + " (tree " +
+    // (neighbour joining counts matrices, not trees)
+    return fail(std::string(status_message(st[0])) + (st[0] == kBadDistance ? " (matrix " : " (tree ") +
                 std::to_string(st[1] + e->status_tree_offset) + ")");
   }
   return 0;
@@ -444,7 +445,8 @@ void mi_engine_destroy(mi_engine* e) {
         &e->aa_tipP, &e->aa_tipPQ, &e->aa_exp_cum, &e->aa_exp_loc, &e->aa_root_val,
         &e->aa_root_exp, &e->aa_root_scale, &e->red_ll, &e->red_g, &e->red_site, &e->red_sort,
         &e->in_pack, &e->out_pack, &e->opt_ws, &e->nni_apply_ws, &e->nni_search_ws,
-        &e->pattern_blank, &e->pattern_ll_out, &e->rell_ws, &e->rell_s})
+        &e->pattern_blank, &e->pattern_ll_out, &e->rell_ws, &e->rell_s, &e->dist_codes, &e->dist_model,
+        &e->dist_counts, &e->dist_matrix, &e->nj_ws})
     b->release();
   if (e->opt_word) (void)hipHostFree(e->opt_word);
   e->pinned.release();

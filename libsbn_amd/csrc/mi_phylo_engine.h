@@ -8,6 +8,7 @@
 //   mi_phylo_nni.cpp          mi_nni_neighbour, the scan's best move on the host (no device code)
 //   mi_phylo_nni_search.cpp   NNI moves on the device, the NNI hill-climbing search
 //   mi_phylo_rell.cpp         per-pattern log-likelihoods (device form), RELL re-summation, tree mixtures
+//   mi_phylo_start_trees.cpp  pairwise distances, neighbour joining, starting trees (device forms, reservation)
 //   mi_phylo_host_calls.cpp   what runs a host-pointer call (staging, status, shards), the plain entry points
 //   mi_phylo_engine_aa.cpp    20-state call sequence
 #pragma once
@@ -131,6 +132,7 @@ inline const char* status_message(int code) {
       return "internal error: the walk waves of the one-launch call waited in vain for their "
              "tree's set-up waves (MI_PHYLO_FUSED_SETUP=0 selects the four-launch sequence)";
     case kBadNniMove: return "NNI move is neither -1 nor the code 2 v + i of an inner edge";
+    case kBadDistance: return "neighbour joining: a distance is not finite";
     default: return "unknown device status";
   }
 }
@@ -188,6 +190,12 @@ struct mi_engine {
   Buffer pattern_ll_out;  // [T] the call's log-likelihoods when the caller wants none (mi_engine_reserve)
   Buffer rell_ws;         // [B][T] product (when the caller wants none) | row maxima, 1 / denominators [B] each | counts [T] (mi_engine_reserve_rell)
   Buffer rell_s;          // the fused host call: [T][P] per-pattern values nobody downloads
+  // starting trees (mi_engine_pairwise_distances*, mi_engine_neighbour_joining*, mi_engine_starting_trees_unrooted*)
+  Buffer dist_codes;   // [n4][Pp] one-byte tip codes of the count kernel (once per engine: launch_distance_codes)
+  Buffer dist_model;   // the call's one model instance
+  Buffer dist_counts;  // a chunk of replicates' counts [chunk][n(n-1)/2][16]
+  Buffer dist_matrix;  // starting trees: [B][n][n] distances nobody asked for
+  Buffer nj_ws;        // neighbour joining: the working sets of matrices too large for LDS
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)
   std::vector<hipEvent_t> prof_events;  // kProfEvents per call: [begin, end, mark 0..4]
@@ -395,6 +403,28 @@ int reserve_rell(mi_engine* e, int B, int T);
 // enqueue the product, the row pass and the column pass; every pointer a device pointer
 int run_rell_device(mi_engine* e, hipStream_t s, int B, int T, int P, const double* pattern_ll, const double* weights,
                     double* out_c, int32_t* out_best, double* out_bp, double* out_elw);
+
+// ---- mi_phylo_start_trees.cpp ----
+// One call of the starting-tree family with every pointer a device pointer.  weights nullptr:
+// one replicate, the engine's pattern weights.
+struct PairDistanceCall {
+  int B = 0;
+  const double* weights = nullptr;  // [B][P]
+  const double* params = nullptr;   // [param_count]
+  const mi_distance_options* options = nullptr;
+  double* out_dist = nullptr;       // [B][n][n]
+  double* out_counts = nullptr;     // [B][n(n-1)/2][16] or nullptr
+  int8_t* out_status = nullptr;     // [B][n(n-1)/2] or nullptr
+};
+extern const mi_distance_options kDistanceDefaults;
+extern const char kDistance4State[], kDistancePatternShards[];
+int distance_options(const mi_distance_options* in, mi_distance_options* out);  // defaults filled in, checked
+int check_distance_call(const mi_engine* e, int B);  // what every entry point of calls 1 and 3 checks first
+int run_pair_distances_device(mi_engine* e, hipStream_t s, const PairDistanceCall& c);
+int run_nj_device(mi_engine* e, hipStream_t s, int B, int n, const double* dist, double tmin, double tmax,
+                  int32_t* out_parent_ids, double* out_bl);
+int run_start_trees_device(mi_engine* e, hipStream_t s, const PairDistanceCall& c, int32_t* out_parent_ids,
+                           double* out_bl);
 
 // mi_phylo_engine_aa.cpp
 int aa_engine_init(mi_engine* e, const double* exchangeabilities, const double* frequencies);

@@ -307,6 +307,84 @@ int32_t mi_engine_ancestral_states_unrooted(mi_engine* e, int32_t T, const int32
   return run_plain(e, c);
 }
 
+// Starting trees: arrays of fixed counts, no per-tree ones -- a tree-sharded
+// handle lets its first shard do the work (every shard holds the whole alignment); neighbour
+// joining needs no alignment and goes to the first shard of any handle.  No retry.
+int32_t mi_engine_pairwise_distances(mi_engine* e, int32_t B, const double* weights, const double* params,
+                                     const mi_distance_options* options, double* out_dist, double* out_counts,
+                                     int8_t* out_status) {
+  if (check_distance_call(e, B)) return 1;
+  e = first_engine(e);
+  if (!weights && B != 1) return fail("pairwise distances: without replicate weights replicate_count is 1");
+  if (e->param_count > 0 && !params) return fail("null parameter row");
+  if (!out_dist) return fail("null distance output");
+  mi_distance_options o;
+  if (distance_options(options, &o)) return 1;
+  const size_t n = e->n, pairs = n * (n - 1) / 2;
+  HostCall c;
+  c.in = {fixed(weights, (size_t)B * e->P), fixed(e->param_count > 0 ? params : nullptr, e->param_count)};
+  c.out = {fixed(out_dist, (size_t)B * n * n), fixed(out_counts, (size_t)B * pairs * 16),
+           fixed(out_status, (size_t)B * pairs)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    PairDistanceCall d;
+    d.B = B;
+    d.weights = in[0].at<const double>();
+    d.params = in[1].dev ? in[1].at<const double>() : e->in_pack.as<const double>();
+    d.options = &o;
+    d.out_dist = out[0].at<double>();
+    d.out_counts = out[1].at<double>();
+    d.out_status = out[2].at<int8_t>();
+    return run_pair_distances_device(e, e->stream, d);
+  };
+  return run_on_engine(e, c);
+}
+
+int32_t mi_engine_neighbour_joining(mi_engine* e, int32_t B, int32_t n, const double* dist, double min_length,
+                                    double max_length, int32_t* out_parent_ids, double* out_bl) {
+  if (!e) return fail("null engine");
+  if (B < 1) return fail("replicate_count must be positive");
+  if (n < 3) return fail("neighbour joining needs at least 3 taxa");
+  if (!dist) return fail("null distance matrices");
+  if (!out_parent_ids || !out_bl) return fail("null output pointer");
+  if (!(min_length < max_length)) return fail("neighbour joining: need min_length < max_length");
+  const size_t np = 2 * (size_t)n - 3;
+  HostCall c;
+  c.in = {fixed(dist, (size_t)B * n * n)};
+  c.out = {fixed(out_parent_ids, (size_t)B * np), fixed(out_bl, (size_t)B * (np + 1))};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    return run_nj_device(e, e->stream, B, n, in[0].at<const double>(), min_length, max_length,
+                         out[0].at<int32_t>(), out[1].at<double>());
+  };
+  return run_on_engine(first_engine(e), c);
+}
+
+int32_t mi_engine_starting_trees_unrooted(mi_engine* e, int32_t B, const double* weights, const double* params,
+                                          const mi_distance_options* options, int32_t* out_parent_ids,
+                                          double* out_bl, double* out_dist) {
+  if (check_distance_call(e, B)) return 1;
+  e = first_engine(e);
+  if (!weights && B != 1) return fail("pairwise distances: without replicate weights replicate_count is 1");
+  if (e->param_count > 0 && !params) return fail("null parameter row");
+  if (!out_parent_ids || !out_bl) return fail("null output pointer");
+  mi_distance_options o;
+  if (distance_options(options, &o)) return 1;
+  const size_t n = e->n, np = 2 * n - 3;
+  HostCall c;
+  c.in = {fixed(weights, (size_t)B * e->P), fixed(e->param_count > 0 ? params : nullptr, e->param_count)};
+  c.out = {fixed(out_parent_ids, (size_t)B * np), fixed(out_bl, (size_t)B * (np + 1)),
+           fixed(out_dist, (size_t)B * n * n)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    PairDistanceCall d;
+    d.B = B;
+    d.weights = in[0].at<const double>();
+    d.params = in[1].dev ? in[1].at<const double>() : e->in_pack.as<const double>();
+    d.options = &o;
+    d.out_dist = out[2].at<double>();
+    return run_start_trees_device(e, e->stream, d, out[0].at<int32_t>(), out[1].at<double>());
+  };
+  return run_on_engine(e, c);
+}
+
 int32_t mi_engine_gradients_unrooted_reduced(mi_engine* e, int32_t T, const int32_t* parent_ids,
                                              const double* bl, const double* params,
                                              int32_t rescaling, const int32_t* branch_index,

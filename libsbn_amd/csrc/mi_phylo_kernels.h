@@ -358,6 +358,51 @@ struct MixtureArgs {
   double* out_total;              // [1]
 };
 void launch_pattern_mixture(const MixtureArgs& a, hipStream_t s);
+// Starting trees.  kernels_distance.hip: the substitution counts of all pairs of
+// taxa for B sets of pattern weights on the matrix cores, and each pair's maximum-likelihood
+// distance.  The tip codes [distance_code_rows(n)][distance_code_stride(P)] (a byte each: the
+// state, 4 = missing, the padding included) are made once per engine.
+inline __host__ __device__ int distance_code_rows(int n) { return (n + 3) & ~3; }
+inline __host__ __device__ int distance_code_stride(int P) { return (P + 15) & ~15; }
+void launch_distance_codes(const int8_t* states, const double* partials /* or nullptr: the states */, int n, int P,
+                           uint8_t* codes, hipStream_t s);
+struct DistanceArgs {
+  int n, n4, P, Pp, K;
+  int B;                  // replicates of this launch (a chunk of the call's)
+  const uint8_t* codes;   // [n4][Pp]
+  const double* weights;  // [B][P]
+  double* counts;         // [B][n(n-1)/2][16] workspace
+  const DevModel* model;  // the call's one model instance
+  double tmin, tmax, tol;
+  int max_iter;
+  double* out_dist;      // [B][n][n]
+  double* out_counts;    // [B][n(n-1)/2][16] or nullptr
+  int8_t* out_status;    // [B][n(n-1)/2] or nullptr
+};
+void launch_pair_distances(const DistanceArgs& a, hipStream_t s);  // counts, then distances
+const char* pair_counts_kernel_name();
+// kernels_nj.hip: neighbour joining of B distance matrices, a wave per matrix, the tree written in
+// the reference's numbering.  The working set of a matrix (nj_ws_bytes) is in LDS up to
+// kNjLdsTaxa taxa, else in `ws`.
+constexpr int kNjLdsTaxa = 128;
+inline __host__ __device__ size_t nj_ws_bytes(int n) {  // per matrix, a multiple of 256
+  const size_t R = 2 * (size_t)n - 2;
+  const size_t doubles = (size_t)n * n + n + R, words = n + R + kNniApplyArrays * R + kNniApplyExtra;
+  return (8 * doubles + 4 * words + 255) & ~(size_t)255;
+}
+struct NjArgs {
+  int n, B;
+  double tmin, tmax;
+  const double* dist;        // [B][n][n], i < j read
+  char* ws;                  // [B][nj_ws_bytes(n)] (n > kNjLdsTaxa)
+  int32_t* status;           // the engine's status word
+  int32_t* out_parent_ids;   // [B][2n-3]
+  double* out_bl;            // [B][2n-2]
+};
+// the large-LDS opt-in of the kernel for n taxa: launch_nj makes it on a first launch of that
+// size, which must not happen inside a graph capture -- a reservation calls this beforehand
+void nj_prepare(int n);
+void launch_nj(const NjArgs& a, hipStream_t s);
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
 // the first, gradient_mfma_kernel, was retired in round 6): all categories of a group of four
 // per instruction; they also write the log-likelihood partial sums, so no separate logL pass is

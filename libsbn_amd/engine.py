@@ -100,6 +100,32 @@ class RellResult:
 
 
 @dataclass
+class StartingTrees:
+    """What Engine.starting_trees returns: per replicate the neighbour-joining tree of its
+    maximum-likelihood distances -- parent ids [B][2n-3] and branch lengths [B][2n-2] in the form
+    every unrooted call takes -- and, on request, the distance matrices [B][n][n]."""
+    parent_ids: np.ndarray
+    branch_lengths: np.ndarray
+    distances: np.ndarray = None
+
+
+@dataclass
+class PairwiseDistances:
+    """What Engine.pairwise_distances returns: distances [B][n][n] (symmetric, zero diagonal);
+    on request the substitution counts [B][n(n-1)/2][4][4] of the pairs in lexicographic (i, j)
+    order and the solver's status per pair [B][n(n-1)/2] (int8: 0 converged, 1 lower bound,
+    2 upper bound, 3 no data, 4 iteration limit)."""
+    distances: np.ndarray
+    pair_counts: np.ndarray = None
+    pair_status: np.ndarray = None
+
+
+def _distance_options(min_length, max_length, tolerance, max_iterations):
+    return _capi.DistanceOptions(int(max_iterations), 0, float(tolerance), float(min_length),
+                                 float(max_length))
+
+
+@dataclass
 class AncestralStates:
     """What Engine.ancestral_states returns, per tree and pattern, unweighted: the marginal
     posterior of the state at the internal nodes n .. 2n-3 [T][n-2][P][4] (row v - n: node v; the
@@ -498,6 +524,77 @@ class Engine:
             _ptr(out.expected_likelihood_weight)))
         return out
 
+    def _replicates(self, replicate_weights):
+        if replicate_weights is None:  # one replicate: the engine's pattern weights
+            return None, 1
+        w = _np(replicate_weights, np.float64)
+        if w.ndim != 2 or w.shape[1] != self.pattern_count:
+            raise RuntimeError(f"replicate weights must be [B][{self.pattern_count}]; got {w.shape}")
+        return w, w.shape[0]
+
+    def _model_row(self, params):
+        if self.param_count == 0:
+            return None
+        if params is None:
+            raise RuntimeError(f"the model needs one parameter row of {self.param_count} entries")
+        pr = _np(params, np.float64).reshape(-1)
+        if pr.shape != (self.param_count,):
+            raise RuntimeError(f"pairwise distances take ONE parameter row of {self.param_count} "
+                               f"entries; got {pr.shape}")
+        return pr
+
+    def pairwise_distances(self, replicate_weights=None, params=None, pair_counts=False,
+                           pair_status=False, min_length=1e-8, max_length=10.0, tolerance=1e-10,
+                           max_iterations=50):
+        """Maximum-likelihood distances of all pairs of taxa (mi_engine_pairwise_distances; an
+        extension, 4-state engines) for every row of replicate_weights [B][P] (None: the
+        engine's pattern weights, B = 1) under ONE model row.  Returns a PairwiseDistances."""
+        n = self.taxon_count
+        w, B = self._replicates(replicate_weights)
+        pr = self._model_row(params)
+        opts = _distance_options(min_length, max_length, tolerance, max_iterations)
+        pairs = n * (n - 1) // 2
+        out = PairwiseDistances(np.empty((B, n, n)),
+                                np.empty((B, pairs, 4, 4)) if pair_counts else None,
+                                np.empty((B, pairs), np.int8) if pair_status else None)
+        self._check(self._lib.mi_engine_pairwise_distances(
+            self._h, B, _ptr(w), _ptr(pr), C.addressof(opts), _ptr(out.distances),
+            _ptr(out.pair_counts), _ptr(out.pair_status)))
+        return out
+
+    def neighbour_joining(self, distances, min_length=1e-8, max_length=10.0):
+        """Neighbour joining of distance matrices [B][n][n] (mi_engine_neighbour_joining; only
+        i < j is read; any engine serves: n is the matrices').  Returns (parent ids [B][2n-3],
+        branch lengths [B][2n-2], clamped into [min_length, max_length]) in the form every
+        unrooted call takes."""
+        d = _np(distances, np.float64)
+        if d.ndim == 2:
+            d = d[None]
+        if d.ndim != 3 or d.shape[1] != d.shape[2] or d.shape[1] < 3 or d.shape[0] < 1:
+            raise RuntimeError(f"neighbour joining takes distances [B][n][n], n >= 3; got {d.shape}")
+        B, n = d.shape[:2]
+        d = np.ascontiguousarray(d)
+        pid, bl = np.empty((B, 2 * n - 3), np.int32), np.empty((B, 2 * n - 2))
+        self._check(self._lib.mi_engine_neighbour_joining(
+            self._h, B, n, _ptr(d), float(min_length), float(max_length), _ptr(pid), _ptr(bl)))
+        return pid, bl
+
+    def starting_trees(self, replicate_weights=None, params=None, distances=False, min_length=1e-8,
+                       max_length=10.0, tolerance=1e-10, max_iterations=50):
+        """Neighbour-joining trees of the maximum-likelihood distances in one host call
+        (mi_engine_starting_trees_unrooted): pairwise_distances followed by neighbour_joining,
+        bit for bit, nothing returning to the host in between.  Returns a StartingTrees."""
+        n = self.taxon_count
+        w, B = self._replicates(replicate_weights)
+        pr = self._model_row(params)
+        opts = _distance_options(min_length, max_length, tolerance, max_iterations)
+        out = StartingTrees(np.empty((B, 2 * n - 3), np.int32), np.empty((B, 2 * n - 2)),
+                            np.empty((B, n, n)) if distances else None)
+        self._check(self._lib.mi_engine_starting_trees_unrooted(
+            self._h, B, _ptr(w), _ptr(pr), C.addressof(opts), _ptr(out.parent_ids),
+            _ptr(out.branch_lengths), _ptr(out.distances)))
+        return out
+
     def pattern_mixture(self, pattern_log_likelihoods, pattern_weights, tree_log_weights=None):
         """Marginal of a mixture of trees (mi_engine_pattern_mixture): s [T][P], pattern weights
         [P], log tree weights [T] (None: log(1/T) each) -> (logsumexp_t(s[t][p] + lw_t) [P], its
@@ -763,6 +860,36 @@ class Engine:
         """mi_engine_reserve_rell: workspace of a RELL call of that size."""
         self._check(self._lib.mi_engine_reserve_rell(self._h, int(replicate_count), int(tree_count),
                                                      int(pattern_count)))
+
+    def pairwise_distances_device(self, stream, B, replicate_weights, params, out_distances,
+                                  out_pair_counts=None, out_pair_status=None, min_length=1e-8,
+                                  max_length=10.0, tolerance=1e-10, max_iterations=50):
+        """mi_engine_pairwise_distances_device: device pointers, enqueued on `stream`."""
+        opts = _distance_options(min_length, max_length, tolerance, max_iterations)
+        self._check(self._lib.mi_engine_pairwise_distances_device(
+            self._h, stream, int(B), replicate_weights, params, C.addressof(opts), out_distances,
+            out_pair_counts, out_pair_status))
+
+    def neighbour_joining_device(self, stream, B, n, distances, out_parent_ids, out_branch_lengths,
+                                 min_length=1e-8, max_length=10.0):
+        """mi_engine_neighbour_joining_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_neighbour_joining_device(
+            self._h, stream, int(B), int(n), distances, float(min_length), float(max_length),
+            out_parent_ids, out_branch_lengths))
+
+    def starting_trees_device(self, stream, B, replicate_weights, params, out_parent_ids,
+                              out_branch_lengths, out_distances=None, min_length=1e-8,
+                              max_length=10.0, tolerance=1e-10, max_iterations=50):
+        """mi_engine_starting_trees_unrooted_device: device pointers, enqueued on `stream`."""
+        opts = _distance_options(min_length, max_length, tolerance, max_iterations)
+        self._check(self._lib.mi_engine_starting_trees_unrooted_device(
+            self._h, stream, int(B), replicate_weights, params, C.addressof(opts), out_parent_ids,
+            out_branch_lengths, out_distances))
+
+    def reserve_start_trees(self, replicate_count):
+        """mi_engine_reserve_start_trees: workspace of the three calls above for that many
+        replicates (their *_device forms then allocate nothing: graph capture)."""
+        self._check(self._lib.mi_engine_reserve_start_trees(self._h, int(replicate_count)))
 
     def pattern_mixture_device(self, stream, T, P, pattern_ll, pattern_weights, out_pattern_log_marginal,
                                out_log_marginal, tree_log_weights=None):
