@@ -306,6 +306,62 @@ int32_t mi_engine_ancestral_states_unrooted(mi_engine* engine, int32_t tree_coun
                                             double* out_pattern_rate /* [T][P] or NULL */,
                                             double* out_tip_posteriors /* [T][n][P][4] or NULL */);
 
+/* Phylogenetic placement (an extension: no counterpart in the reference's Engine; DESIGN.md
+ * 4.17): score Q query sequences on every edge of trees that are already built.  The trees are
+ * unrooted, in the caller's form; edge e = 0 .. 2n-4 is the branch above node e, of length
+ * t_e = branch_lengths[e] (the root 2n-3 has none): E = 2n-3 edges.  Placing a query on e with
+ * pendant length l is the tree on n+1 taxa in which a new node splits e into two halves of
+ * length t_e / 2 and the query hangs from that node by a branch of length l, under the tree's own
+ * model row and rate categories.  Only the midpoint is scored.  With g_e,k the pre-order vector
+ * at the top of e (it carries pi), L_e,k the post-order vector at its bottom, H = P(r_k t_e / 2)
+ * and R_g,k = P(r_k l_g), per tree t, edge e, pendant length g and pattern p:
+ *   M_e,k[j]         = (H^T g_e,k)[j] (H L_e,k)[j]
+ *   Z[a]             = sum_k c_k sum_j M_e,k[j] R_g,k[j][a]                 a = 0..3
+ *   S[t][e][g][a][p] = s[t][p] + log(Z[a] / ((Z[0] + Z[1]) + (Z[2] + Z[3])))  a = 0..3
+ *   S[t][e][g][4][p] = s[t][p]                                              a gap: any code >= 4
+ * s[t][p] is the per-pattern log-likelihood of the tree as the call's post-order pass forms it.
+ * Powers of two that rescaling removed sit in numerator and denominator alike and cancel.
+ * A query is a row of compact states x[q][c] over C columns (0..3; anything else is a gap);
+ * column_pattern[c] in [0, P) names the engine pattern column c extends; column_weights[c]
+ * (NULL: 1) weighs it.
+ *   ll[t][q][e][g]   = sum_c column_weights[c] S[t][e][g][x[q][c]][column_pattern[c]]
+ *   edge_ll[t][q][e] = max_g ll,  pendant_index[t][q][e] = the lowest such g
+ *   best_edge[t][q]  = the e of the largest edge_ll, the lowest among equals
+ *   lwr[t][q][e]     = exp(edge_ll - m) / sum_e' exp(edge_ll[e'] - m),  m = max_e edge_ll
+ *                      (likelihood weight ratio; the sum in ascending e')
+ * Columns of weight 0 are skipped whatever their table entry.  A table entry of -inf (pendant
+ * length 0 on a zero-length leaf edge of another state) propagates as IEEE says.
+ * THE ORDER of every sum ll[t][q][e][g] is fixed and depends on C alone -- not on Q, E, G, T, the
+ * place of the (query, edge) pair in a launch, how the call was cut into launches, or where the
+ * table was read from: 64 running sums, number l taking the columns c = l, l + 64, l + 128, ...
+ * in ascending c, each term by one fused multiply-add fma(w_c, S, sum) from +0.0; then the 64
+ * are added pairwise by an xor butterfly: v[i] += v[i ^ 32], then ^ 16, 8, 4, 2, 1 (every
+ * position ends with the same value).  Equal query rows give bit-identical output rows; there
+ * are no floating-point atomics.
+ * 1 <= pendant_count <= MI_PLACEMENT_MAX_PENDANTS, every pendant length finite and >= 0;
+ * query_count >= 1, column_count >= 1.  out_log_likelihoods is that of a gradient call on the HBM
+ * path, bit for bit.  Only out_edge_log_likelihoods is required; a NULL output costs neither
+ * arithmetic nor stores.  4-state engines and unrooted trees only.  Sharded handles:
+ * MI_SHARD_TREES deals the trees, rows in tree order, every shard gets all queries;
+ * MI_SHARD_PATTERNS is refused (each shard holds a block of columns).  The table workspace
+ * counts against MI_PHYLO_PLV_BYTES: a batch over the budget is cut into launches over trees and
+ * writes the same bytes; one tree's table over the budget is refused. */
+#define MI_PLACEMENT_MAX_PENDANTS 4
+int32_t mi_engine_placement_unrooted(mi_engine* engine, int32_t tree_count,
+                                     const int32_t* parent_ids,     /* [T][2n-3] */
+                                     const double* branch_lengths,  /* [T][2n-2] */
+                                     const double* params, int32_t rescaling, int32_t query_count,
+                                     int32_t column_count, const int8_t* query_states /* [Q][C] */,
+                                     const int32_t* column_pattern /* [C] */,
+                                     const double* column_weights /* [C] or NULL */, int32_t pendant_count,
+                                     const double* pendant_lengths /* [G] */,
+                                     double* out_log_likelihoods /* [T] or NULL */,
+                                     double* out_edge_log_likelihoods /* [T][Q][2n-3] */,
+                                     int8_t* out_pendant_index /* [T][Q][2n-3] or NULL */,
+                                     int32_t* out_best_edge /* [T][Q] or NULL */,
+                                     double* out_lwr /* [T][Q][2n-3] or NULL */,
+                                     double* out_edge_tables /* [T][2n-3][G][5][P] or NULL */);
+
 /* RELL re-summation (resampling of estimated log-likelihoods) and its reductions (an extension;
  * DESIGN.md 4.12), for B replicates, T trees and P patterns -- P is an argument: any engine
  * serves (the alignment plays no part), a sharded handle lets its first shard do it.
@@ -657,6 +713,19 @@ int32_t mi_engine_ancestral_states_unrooted_device(
     double* out_state_posteriors, int8_t* out_map_state, double* out_category_posteriors,
     double* out_pattern_rate, double* out_tip_posteriors);
 
+/* The device form of mi_engine_placement_unrooted: every array a device pointer (the pendant
+ * lengths too); it only enqueues -- no allocation and no synchronisation after
+ * mi_engine_reserve_placement, so it can be captured in a hipGraph.  A column_pattern entry
+ * outside [0, P) or a bad pendant length is reported through the status word
+ * (mi_engine_check_status); the scoring clamps such an entry and reads nothing out of bounds. */
+int32_t mi_engine_placement_unrooted_device(
+    mi_engine* engine, void* stream, int32_t tree_count, const int32_t* parent_ids,
+    const double* branch_lengths, const double* params, int32_t rescaling, int32_t query_count,
+    int32_t column_count, const int8_t* query_states, const int32_t* column_pattern,
+    const double* column_weights, int32_t pendant_count, const double* pendant_lengths,
+    double* out_log_likelihoods, double* out_edge_log_likelihoods, int8_t* out_pendant_index,
+    int32_t* out_best_edge, double* out_lwr, double* out_edge_tables);
+
 /* The device forms of mi_engine_pattern_log_likelihoods_unrooted, mi_engine_rell and
  * mi_engine_pattern_mixture: they only enqueue -- no allocation and no synchronisation after
  * mi_engine_reserve(tree_count, 0), mi_engine_reserve_rell and (the mixture) a first call of
@@ -731,6 +800,12 @@ int32_t mi_engine_reserve_nni_scan(mi_engine* engine, int32_t tree_count);
  * either rescaling setting: a *_device call of at most that size then allocates nothing
  * (hipGraph capture).  4-state engines only. */
 int32_t mi_engine_reserve_ancestral(mi_engine* engine, int32_t tree_count);
+/* The workspace of mi_engine_placement_unrooted[_device] for `tree_count` trees and
+ * `pendant_count` pendant lengths, of either rescaling setting: a *_device call of at most that
+ * size then allocates nothing (hipGraph capture).  query_count and column_count are checked;
+ * the workspace does not depend on them.  4-state engines only. */
+int32_t mi_engine_reserve_placement(mi_engine* engine, int32_t tree_count, int32_t query_count,
+                                    int32_t column_count, int32_t pendant_count);
 /* The workspace of mi_engine_optimize_branch_lengths_unrooted[_device] for `tree_count` trees
  * (the Hessian call's included): a *_device call of at most that size then allocates
  * nothing.  4-state engines only. */

@@ -115,6 +115,13 @@ SYMBOLS = {
     "mi_engine_ancestral_states_unrooted_device":
         (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V, _V, _V]),
     "mi_engine_reserve_ancestral": (C.c_int32, [_V, C.c_int32]),
+    "mi_engine_placement_unrooted":
+        (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, _V,
+                     _V, _V, _V, _V, _V, _V]),
+    "mi_engine_placement_unrooted_device":
+        (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32,
+                     _V, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_reserve_placement": (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mi_engine_rell": (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V]),
     "mi_engine_rell_device":
         (C.c_int32, [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V]),

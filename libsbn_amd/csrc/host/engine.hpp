@@ -100,6 +100,17 @@ struct AncestralStatePosteriors {
   std::vector<double> category_posteriors_, pattern_rates_, tip_posteriors_;
 };
 
+// Engine::Placement, per tree (an extension, include/mi_phylo.h) for Q queries and E = 2n-3 edges:
+// edge_log_likelihoods_ [Q][E] and best_edge_ [Q], and, asked for, pendant_index_ [Q][E], lwr_
+// [Q][E] and tables_ [E][G][5][P]; what was not asked for stays empty
+struct PlacementResult {
+  double log_likelihood_ = 0.;
+  std::vector<double> edge_log_likelihoods_;
+  std::vector<int32_t> best_edge_;
+  std::vector<int8_t> pendant_index_;
+  std::vector<double> lwr_, tables_;
+};
+
 // Engine::OptimizeBranchLengths, per tree (an extension, include/mi_phylo.h): the
 // maximum-likelihood branch lengths [2n-2] and the Hessian call's outputs at them [2n-1]
 struct BranchOptimum {
@@ -338,6 +349,42 @@ class Engine {
         out[t].pattern_rates_.assign(rate.begin() + t * P, rate.begin() + (t + 1) * P);
       }
       if (tips) out[t].tip_posteriors_.assign(tip.begin() + t * n * P * 4, tip.begin() + (t + 1) * n * P * 4);
+    }
+    return out;
+  }
+
+  // Phylogenetic placement (an extension; 4-state engines): mi_engine_placement_unrooted.  queries
+  // [Q][C] compact states, column_pattern [C], column_weights [C] or empty (1 per column).
+  std::vector<PlacementResult> Placement(const UnrootedTreeCollection& trees, const ParamMatrix& params,
+                                         const bool rescaling, const std::vector<int8_t>& queries,
+                                         const std::vector<int32_t>& column_pattern,
+                                         const std::vector<double>& column_weights,
+                                         const std::vector<double>& pendant_lengths, const bool pendant_index = false,
+                                         const bool lwr = false, const bool tables = false) const {
+    const size_t T = trees.size(), n = site_pattern_.SequenceCount(), P = site_pattern_.PatternCount();
+    const size_t E = 2 * n - 3, C = column_pattern.size(), G = pendant_lengths.size();
+    const size_t Q = C ? queries.size() / C : 0, QE = Q * E, tab = E * G * 5 * P;
+    std::vector<int32_t> parents;
+    std::vector<double> bl;
+    Flatten(trees, params, false, &parents, &bl);
+    if (trees.empty()) return {};
+    std::vector<double> ll(T), edge(T * QE), w(lwr ? T * QE : 0), tb(tables ? T * tab : 0);
+    std::vector<int32_t> best(T * Q);
+    std::vector<int8_t> pend(pendant_index ? T * QE : 0);
+    Check(mi_engine_placement_unrooted(
+        handle_, static_cast<int32_t>(T), parents.data(), bl.data(), params.data.data(), rescaling,
+        static_cast<int32_t>(Q), static_cast<int32_t>(C), queries.data(), column_pattern.data(),
+        column_weights.empty() ? nullptr : column_weights.data(), static_cast<int32_t>(G), pendant_lengths.data(),
+        ll.data(), edge.data(), pendant_index ? pend.data() : nullptr, best.data(), lwr ? w.data() : nullptr,
+        tables ? tb.data() : nullptr));
+    std::vector<PlacementResult> out(T);
+    for (size_t t = 0; t < T; t++) {
+      out[t].log_likelihood_ = ll[t];
+      out[t].edge_log_likelihoods_.assign(edge.begin() + t * QE, edge.begin() + (t + 1) * QE);
+      out[t].best_edge_.assign(best.begin() + t * Q, best.begin() + (t + 1) * Q);
+      if (pendant_index) out[t].pendant_index_.assign(pend.begin() + t * QE, pend.begin() + (t + 1) * QE);
+      if (lwr) out[t].lwr_.assign(w.begin() + t * QE, w.begin() + (t + 1) * QE);
+      if (tables) out[t].tables_.assign(tb.begin() + t * tab, tb.begin() + (t + 1) * tab);
     }
     return out;
   }

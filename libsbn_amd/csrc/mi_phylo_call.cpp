@@ -145,6 +145,15 @@ CallPlan plan_call(const mi_engine* e, CallKind kind, int T, bool rescaling, int
     p.dominant = ancestral_kernel_name();
     return p;
   }
+  if (kind == kPlacementCall) {
+    // Placement: as the ancestral-state call -- one evaluation per tree with the
+    // tree's own model, node-ordered matrices, the HBM-streamed kernel.
+    p.Eg = T;
+    p.g_tiles = e->tiles;
+    p.store = kStoreHbm;
+    p.dominant = placement_kernel_name();
+    return p;
+  }
   // on-chip gradient kernels: the matrix-core one (K <= 4; rescaling supported) or the
   // VALU one (no rescaling); everything else takes the HBM-streamed kernel
   p.mfma = gradient && matrix_core_gradient(e, rescaling, p.loglik_is_valu);
@@ -251,6 +260,7 @@ std::string plan_path(const mi_engine* e, const CallPlan& p) {
   if (p.kind == kHessianCall) path += " hess";
   if (p.kind == kNniCall) path += " nni";
   if (p.kind == kAncestralCall) path += " ancestral";
+  if (p.kind == kPlacementCall) path += " placement";
   if (p.pattern_ll) path += " pattern_ll";
   if (p.tile_regs > kLlR) path += " tile=wide";
   if (p.fd_pass) path += " fd=16";
@@ -485,6 +495,13 @@ LikArgs lik_args(const mi_engine* e, const DeviceCall& d, const CallPlan& p) {
     la.anc_tip = d.out_anc_tip;
     return la;
   }
+  if (p.kind == kPlacementCall) {
+    la.place_half = e->place_half.as<double>();
+    la.place_pend = e->place_pend.as<double>();
+    la.place_table = e->place_table.as<double>();
+    la.place_G = d.G;
+    return la;
+  }
   if (p.kind == kHessianCall || p.kind == kNniCall) return la;  // (their kernels read none of the following)
   la.tip_tables = e->tip_tables.as<double>();
   la.mphi = e->mphi.as<double>();
@@ -696,7 +713,7 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d_in) {
 // ---- the calls of the HBM-streamed kernel family ----
 // One evaluation per tree with the tree's own model, the node-ordered matrices, the member's
 // kernel over the vector arena in parts, one finalize launch: the Hessian call where no
-// matrix-core walk takes it, the NNI scan, the ancestral-state call.
+// matrix-core walk takes it, the NNI scan, the ancestral-state call, placement.
 // (trees, models, node-ordered matrices, log-likelihood partials: the Hessian call's walk form too)
 static int reserve_per_tree(mi_engine* e, int T) {
   const int n = e->n, N = e->N;
@@ -874,4 +891,115 @@ int run_ancestral_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   return run_hbm_family(e, s, d, p, launch_ancestral_hbm, [&] {
     launch_ancestral_finalize(e->ll_part.as<double>(), d.T, e->ll_stride, p.g_tiles, d.out_ll, s);
   });
+}
+
+// ---- placement (mi_engine_placement_unrooted*) ----
+// The table kernel over the vector arena in parts, as every member; inside a part, over what the
+// table workspace holds: table launch, scoring launch (and the copy of the table, if wanted) per
+// sub-part.  One launch at the end for best edges, weight ratios and log-likelihoods.  The
+// half-length and pendant matrices are two more launches of the transition kernel, in front of
+// the first table launch (the effective lengths exist once the set-up launch has run).
+int check_placement_shape(const mi_engine* e, int Q, int C, int G) {
+  if (Q < 1) return fail("placement: query_count must be positive");
+  if (C < 1) return fail("placement: column_count must be positive");
+  if (G < 1 || G > kPlacementMaxPendants)
+    return fail("placement: pendant_count must be in [1, " + std::to_string(kPlacementMaxPendants) + "]");
+  return 0;
+}
+
+static size_t placement_table_bytes_per_tree(const mi_engine* e, int G) {
+  return sizeof(double) * (size_t)(2 * e->n - 3) * G * 5 * e->tiles * kTile;
+}
+// trees a table launch covers: what the budget holds
+static int placement_table_trees(const mi_engine* e, int T, int G) {
+  return (int)std::max<size_t>(1, std::min<size_t>(T, e->plv_budget / placement_table_bytes_per_tree(e, G)));
+}
+
+int reserve_placement_calls(mi_engine* e, int T, int G) {
+  const int N = e->N;
+  const size_t per = placement_table_bytes_per_tree(e, G);
+  if (per > e->plv_budget)
+    return fail("placement: the table of one tree (" + std::to_string(per) + " bytes: 2n-3 edges x " +
+                std::to_string(G) + " pendant lengths x 5 x padded patterns x 8) exceeds the arena budget (" +
+                std::to_string(e->plv_budget) + " bytes, MI_PHYLO_PLV_BYTES)");
+  if (e->place_bl.ensure(sizeof(double) * (size_t)T * (N + kPlacementMaxPendants + 1))) return 1;
+  if (e->place_half.ensure(sizeof(double) * (size_t)T * (N - 1) * e->K * 16)) return 1;
+  if (e->place_pend.ensure(sizeof(double) * (size_t)T * kPlacementMaxPendants * e->K * 16)) return 1;
+  if (e->place_table.ensure(per * placement_table_trees(e, T, G))) return 1;
+  return reserve_hbm_family(e, T, 0);
+}
+
+int run_placement_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
+  HIP_TRY(hipSetDevice(e->spec.device));
+  if (e->s == kAa) return fail(kPlacement4State);
+  if (check_call(e, d, d.out_place_edge_ll)) return 1;
+  if (check_placement_shape(e, d.Q, d.C, d.G)) return 1;
+  const CallPlan p = plan_call(e, kPlacementCall, d);
+  if (reserve_placement_calls(e, d.T, d.G)) return 1;
+  const int T = d.T, N = e->N, G = d.G, E = 2 * e->n - 3;
+  const size_t ppad = (size_t)e->tiles * kTile;
+  const int table_trees = placement_table_trees(e, T, G);
+  double* half_bl = e->place_bl.as<double>();
+  double* pend_bl = half_bl + (size_t)T * N;
+  int table_launches = 0;
+  const int rc = run_hbm_family(
+      e, s, d, p,
+      [&](const LikArgs& g, int part, bool rescale, hipStream_t s) {
+        if (g.eval_offset == 0) {
+          PlacePrepareArgs pa{};
+          pa.T = T, pa.N = N, pa.G = G, pa.C = d.C, pa.P = e->P;
+          pa.bl_eff = e->bl_eff.as<double>();
+          pa.pendant_lengths = d.pendant_lengths;
+          pa.column_pattern = d.column_pattern;
+          pa.half_bl = half_bl;
+          pa.pend_bl = pend_bl;
+          pa.status = e->status.as<int32_t>();
+          launch_placement_prepare(pa, s);
+          TransitionArgs tr = transition_args(e, d, p);
+          tr.bl_eff = half_bl;
+          tr.mats = e->place_half.as<double>();
+          launch_transition(tr, s);
+          tr.N = G + 1;  // (G "edges" per tree: the pendant branches)
+          tr.bl_eff = pend_bl;
+          tr.mats = e->place_pend.as<double>();
+          launch_transition(tr, s);
+        }
+        for (int done = 0; done < part; done += table_trees) {
+          const int count = std::min(table_trees, part - done);
+          LikArgs h = g;
+          h.eval_offset = g.eval_offset + done;
+          h.grad_offset = h.eval_offset;
+          h.place_tree0 = h.eval_offset;
+          launch_placement_table_hbm(h, count, rescale, s);
+          table_launches++;
+          PlaceScoreArgs sa{};
+          sa.trees = count, sa.tree0 = h.eval_offset;
+          sa.E = E, sa.G = G, sa.P = e->P, sa.Q = d.Q, sa.C = d.C;
+          sa.ppad = ppad;
+          sa.use_lds = !e->sw.place_table_global && placement_table_fits_lds(G, ppad);
+          sa.table = e->place_table.as<double>();
+          sa.query_states = d.query_states;
+          sa.column_pattern = d.column_pattern;
+          sa.column_weights = d.column_weights;
+          sa.edge_ll = d.out_place_edge_ll;
+          sa.pendant_index = d.out_place_pendant;
+          launch_placement_score(sa, s);
+          if (d.out_place_tables)
+            launch_placement_table_copy(sa.table, count, sa.tree0, E, G, e->P, ppad, d.out_place_tables, s);
+        }
+      },
+      [&] {
+        PlaceFinalizeArgs fa{};
+        fa.T = T, fa.Q = d.Q, fa.E = E;
+        fa.ll_tiles = e->ll_stride;
+        fa.ll_used = p.g_tiles;
+        fa.ll_part = e->ll_part.as<double>();
+        fa.edge_ll = d.out_place_edge_ll;
+        fa.out_ll = d.out_ll;
+        fa.out_best_edge = d.out_place_best;
+        fa.out_lwr = d.out_place_lwr;
+        launch_placement_finalize(fa, s);
+      });
+  if (rc == 0) e->last_walk_launches = table_launches;
+  return rc;
 }

@@ -90,6 +90,8 @@ enum StatusCode : int32_t {
   kFusedTimeout = 8,
   kBadNniMove = 9,
   kBadDistance = 10,
+  kBadColumnPattern = 11,
+  kBadPendantLength = 12,
 };
 
 }  // namespace miphylo

@@ -80,6 +80,10 @@ int check_status(mi_engine* e, hipStream_t s) {
     HIP_TRY(hipStreamSynchronize(s));
     // (a shard of a sharded handle reports the caller's tree index, not its own)
     // (neighbour joining counts matrices, not trees)
+    // (placement counts columns and pendant lengths)
+    if (st[0] == kBadColumnPattern || st[0] == kBadPendantLength)
+      return fail(std::string(status_message(st[0])) + (st[0] == kBadColumnPattern ? " (column " : " (pendant ") +
+                  std::to_string(st[1]) + ")");
     return fail(std::string(status_message(st[0])) + (st[0] == kBadDistance ? " (matrix " : " (tree ") +
                 std::to_string(st[1] + e->status_tree_offset) + ")");
   }
@@ -93,6 +97,7 @@ const char kHessian4State[] = "the branch-length Hessian call is 4-state only";
 const char kNni4State[] = "the NNI neighbourhood scan is 4-state only";
 const char kPatternLl4State[] = "per-pattern log-likelihoods are 4-state only";
 const char kAncestral4State[] = "the ancestral-state call is 4-state only";
+const char kPlacement4State[] = "the placement call is 4-state only";
 
 extern "C" {
 
@@ -446,7 +451,8 @@ void mi_engine_destroy(mi_engine* e) {
         &e->aa_root_exp, &e->aa_root_scale, &e->red_ll, &e->red_g, &e->red_site, &e->red_sort,
         &e->in_pack, &e->out_pack, &e->opt_ws, &e->nni_apply_ws, &e->nni_search_ws,
         &e->pattern_blank, &e->pattern_ll_out, &e->rell_ws, &e->rell_s, &e->dist_codes, &e->dist_model,
-        &e->dist_counts, &e->dist_matrix, &e->nj_ws})
+        &e->dist_counts, &e->dist_matrix, &e->nj_ws, &e->place_bl, &e->place_half, &e->place_pend,
+        &e->place_table})
     b->release();
   if (e->opt_word) (void)hipHostFree(e->opt_word);
   e->pinned.release();
@@ -736,6 +742,56 @@ int32_t mi_engine_reserve_ancestral(mi_engine* e, int32_t tree_count) {
   if (!e->shards.empty()) return for_each_shard(e, tree_count, mi_engine_reserve_ancestral);
   HIP_TRY(hipSetDevice(e->spec.device));
   return reserve_ancestral_calls(e, tree_count);
+}
+
+int32_t mi_engine_placement_unrooted_device(mi_engine* e, void* stream, int32_t T, const int32_t* parent_ids,
+                                            const double* bl, const double* params, int32_t rescaling, int32_t Q,
+                                            int32_t C, const int8_t* query_states, const int32_t* column_pattern,
+                                            const double* column_weights, int32_t G, const double* pendant_lengths,
+                                            double* out_ll, double* out_edge_ll, int8_t* out_pendant_index,
+                                            int32_t* out_best_edge, double* out_lwr, double* out_edge_tables) {
+  if (!e) return fail("null engine");
+  if (e->s == kAa) return fail(kPlacement4State);
+  if (!e->shards.empty()) return fail(kShardedDeviceCall);
+  if (check_placement_shape(e, Q, C, G)) return 1;
+  if (!query_states || !column_pattern || !pendant_lengths) return fail("null query / column / pendant array");
+  if (!out_edge_ll) return fail("null edge log-likelihood output");
+  DeviceCall d;
+  d.T = T;
+  d.rescaling = rescaling != 0;
+  d.parent_ids = parent_ids;
+  d.bl = bl;
+  d.params = params;
+  d.Q = Q;
+  d.C = C;
+  d.G = G;
+  d.query_states = query_states;
+  d.column_pattern = column_pattern;
+  d.column_weights = column_weights;
+  d.pendant_lengths = pendant_lengths;
+  d.out_ll = out_ll;
+  d.out_place_edge_ll = out_edge_ll;
+  d.out_place_pendant = out_pendant_index;
+  d.out_place_best = out_best_edge;
+  d.out_place_lwr = out_lwr;
+  d.out_place_tables = out_edge_tables;
+  return run_placement_device(e, pick_stream(e, stream), d);
+}
+
+int32_t mi_engine_reserve_placement(mi_engine* e, int32_t tree_count, int32_t query_count, int32_t column_count,
+                                    int32_t pendant_count) {
+  if (!e) return fail("null engine");
+  if (tree_count <= 0) return fail("tree_count must be positive");
+  if (e->s == kAa) return fail(kPlacement4State);
+  if (check_placement_shape(e, query_count, column_count, pendant_count)) return 1;
+  if (!e->shards.empty()) {
+    if (e->shard_mode != MI_SHARD_TREES) return fail("pattern-sharded engines do not place queries");
+    return for_each_shard(e, tree_count, [=](mi_engine* shard, int32_t count) {
+      return mi_engine_reserve_placement(shard, count, query_count, column_count, pendant_count);
+    });
+  }
+  HIP_TRY(hipSetDevice(e->spec.device));
+  return reserve_placement_calls(e, tree_count, pendant_count);
 }
 
 int32_t mi_engine_log_likelihoods_rooted_device(mi_engine* e, void* stream, int32_t T,

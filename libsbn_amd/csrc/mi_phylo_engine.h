@@ -3,7 +3,7 @@
 //   mi_phylo_engine.cpp       engine creation / destruction, status, profiling, the thin
 //                             device-pointer entry points of the C ABI
 //   mi_phylo_call.cpp         the call plan (which route a call takes: plan_call), reservation,
-//                             the argument-block builders, the 4-state, Hessian, NNI-scan and ancestral-state call sequences
+//                             the argument-block builders, the 4-state, Hessian, NNI-scan, ancestral-state and placement call sequences
 //   mi_phylo_branch_opt.cpp   branch-length optimisation
 //   mi_phylo_nni.cpp          mi_nni_neighbour, the scan's best move on the host (no device code)
 //   mi_phylo_nni_search.cpp   NNI moves on the device, the NNI hill-climbing search
@@ -133,6 +133,8 @@ inline const char* status_message(int code) {
              "tree's set-up waves (MI_PHYLO_FUSED_SETUP=0 selects the four-launch sequence)";
     case kBadNniMove: return "NNI move is neither -1 nor the code 2 v + i of an inner edge";
     case kBadDistance: return "neighbour joining: a distance is not finite";
+    case kBadColumnPattern: return "placement: a column_pattern entry is outside [0, pattern_count)";
+    case kBadPendantLength: return "placement: a pendant length is not finite or is negative";
     default: return "unknown device status";
   }
 }
@@ -196,6 +198,11 @@ struct mi_engine {
   Buffer dist_counts;  // a chunk of replicates' counts [chunk][n(n-1)/2][16]
   Buffer dist_matrix;  // starting trees: [B][n][n] distances nobody asked for
   Buffer nj_ws;        // neighbour joining: the working sets of matrices too large for LDS
+  // placement (mi_engine_placement_unrooted*)
+  Buffer place_bl;     // [T][N] halved effective lengths | [T][G+1] the pendant lengths, a row per tree
+  Buffer place_half;   // [T][N-1][K][16] P(r_k t_e / 2) by node id
+  Buffer place_pend;   // [T][G][K][16] P(r_k l_g)
+  Buffer place_table;  // [trees of a table launch][2n-3][G][5][tiles*64]: counts against plv_budget
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)
   std::vector<hipEvent_t> prof_events;  // kProfEvents per call: [begin, end, mark 0..4]
@@ -231,7 +238,7 @@ inline hipEvent_t prof_event(mi_engine* e, int which) {
 // (reserve, reserve_hessian), the argument-block builders, the call sequences and the path
 // string (plan_path) read the plan -- so a reserve cannot guess differently from the call it
 // reserves for (and leave that call to allocate inside a hipGraph capture).
-enum CallKind { kLogLikCall, kGradientCall, kHessianCall, kNniCall, kAncestralCall };
+enum CallKind { kLogLikCall, kGradientCall, kHessianCall, kNniCall, kAncestralCall, kPlacementCall };
 enum WalkStore { kStoreHbm = 0, kStoreLds = 1, kStoreArena = 2 };  // (LikArgs::store: 0 = not a matrix-core walk)
 struct CallPlan {
   CallKind kind;
@@ -295,6 +302,17 @@ struct DeviceCall {
   double* out_anc_cat = nullptr;    // [T][P][K]
   double* out_anc_rate = nullptr;   // [T][P]
   double* out_anc_tip = nullptr;    // [T][n][P][4]
+  // placement (run_placement_device): all outputs but out_place_edge_ll, and out_ll, may be nullptr
+  int Q = 0, C = 0, G = 0;                // queries, columns, pendant lengths
+  const int8_t* query_states = nullptr;   // [Q][C]
+  const int32_t* column_pattern = nullptr;  // [C]
+  const double* column_weights = nullptr;   // [C] or nullptr
+  const double* pendant_lengths = nullptr;  // [G]
+  double* out_place_edge_ll = nullptr;    // [T][Q][2n-3]
+  int8_t* out_place_pendant = nullptr;    // [T][Q][2n-3]
+  int32_t* out_place_best = nullptr;      // [T][Q]
+  double* out_place_lwr = nullptr;        // [T][Q][2n-3]
+  double* out_place_tables = nullptr;     // [T][2n-3][G][5][P]
   // ... as one pass of the branch-length optimisation: the batch size the kernel and its store
   // are chosen for (the whole batch's, so that a tree's results do not depend on how many
   // trees are still active); 0: T
@@ -324,6 +342,11 @@ int reserve_nni_calls(mi_engine* e, int T);  // of either rescaling setting (mi_
 int run_nni_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
 int reserve_ancestral_calls(mi_engine* e, int T);  // of either rescaling setting (mi_engine_reserve_ancestral)
 int run_ancestral_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
+// placement: what both entry points refuse before any device work; the workspace
+// of a call of T trees and G pendant lengths, of either rescaling setting; the call itself
+int check_placement_shape(const mi_engine* e, int Q, int C, int G);
+int reserve_placement_calls(mi_engine* e, int T, int G);
+int run_placement_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
 // the scan's best move from a tree's delta [N][2] (what the finalize kernel does; pattern shards)
 int32_t nni_best_move(int n, const double* delta);
 
@@ -350,7 +373,7 @@ int check_branch_opt_options(const mi_branch_opt_options& o);
 int run_branch_opt_device(mi_engine* e, hipStream_t s, const BranchOptCall& c);
 
 // ---- mi_phylo_engine.cpp ----
-extern const char kShardedDeviceCall[], kHessian4State[], kNni4State[], kPatternLl4State[], kAncestral4State[];
+extern const char kShardedDeviceCall[], kHessian4State[], kNni4State[], kPatternLl4State[], kAncestral4State[], kPlacement4State[];
 int check_status(mi_engine* e, hipStream_t s);
 inline hipStream_t pick_stream(mi_engine* e, void* stream) {
   return stream ? static_cast<hipStream_t>(stream) : e->stream;

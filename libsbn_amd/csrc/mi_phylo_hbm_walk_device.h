@@ -1,7 +1,7 @@
 // What the HBM-streamed kernel family shares: gradient_hbm_kernel and
-// gradient_hbm_hess_kernel (kernels_gradient.hip), nni_scan_hbm_kernel (kernels_nni.hip) and
-// ancestral_hbm_kernel (kernels_ancestral.hip), with the finalize kernels that sum their tile
-// partials.  One lane per pattern, one wave per (evaluation, 64-pattern tile), partial-likelihood
+// gradient_hbm_hess_kernel (kernels_gradient.hip), nni_scan_hbm_kernel (kernels_nni.hip),
+// ancestral_hbm_kernel (kernels_ancestral.hip) and placement_table_hbm_kernel
+// (kernels_placement.hip), with the finalize kernels that sum their tile partials.  One lane per pattern, one wave per (evaluation, 64-pattern tile), partial-likelihood
 // vectors through the `plv` arena as [evaluation][node][category][pattern][state] (32 B per lane,
 // a wave reads or writes 2 KiB contiguous).  Each lane only ever re-reads what it wrote itself,
 // so no inter-wave synchronisation is needed; the pre-order vector of a node overwrites its
@@ -80,10 +80,11 @@ struct HbmLane {
 
 // ------------------------------------------------------------------------
 // Post-order pass: every internal node's vector into the arena (the root's is contracted with
-// pi instead), then the tile's log-likelihood partial into ll_part.
+// pi instead), then the tile's log-likelihood partial into ll_part.  Returns the lane's own
+// unweighted log-likelihood (its pattern's; a padding lane: that of pattern P - 1).
 // ------------------------------------------------------------------------
 template <bool RESCALE, bool TIP_PARTIALS>
-__device__ __forceinline__ void hbm_post_order(const HbmLane<TIP_PARTIALS>& c) {
+__device__ __forceinline__ double hbm_post_order(const HbmLane<TIP_PARTIALS>& c) {
   const int n = c.n, K = c.K;
   int cum_exp = 0;
   double site = 0.0;
@@ -116,9 +117,11 @@ __device__ __forceinline__ void hbm_post_order(const HbmLane<TIP_PARTIALS>& c) {
   }
   double ll = log(site);
   if (RESCALE) ll += cum_exp * 0.6931471805599453;
+  const double lane_ll = ll;
   ll = c.live() ? c.w * ll : 0.0;
   ll = wave_sum(ll);
   if (c.lane == 0) c.a.ll_part[(size_t)c.e * c.a.ll_tiles + c.tile] = ll;
+  return lane_ll;
 }
 
 // ------------------------------------------------------------------------

@@ -307,6 +307,47 @@ int32_t mi_engine_ancestral_states_unrooted(mi_engine* e, int32_t T, const int32
   return run_plain(e, c);
 }
 
+int32_t mi_engine_placement_unrooted(mi_engine* e, int32_t T, const int32_t* parent_ids, const double* bl,
+                                     const double* params, int32_t rescaling, int32_t Q, int32_t C,
+                                     const int8_t* query_states, const int32_t* column_pattern,
+                                     const double* column_weights, int32_t G, const double* pendant_lengths,
+                                     double* out_ll, double* out_edge_ll, int8_t* out_pendant_index,
+                                     int32_t* out_best_edge, double* out_lwr, double* out_edge_tables) {
+  if (!out_edge_ll) return fail("null edge log-likelihood output");
+  if (e && e->s == kAa) return fail(kPlacement4State);
+  if (check_tree_call(e, T, parent_ids, bl, params,
+                      "pattern-sharded engines do not place queries (each shard holds a block of columns): use "
+                      "MI_SHARD_TREES or a single engine"))
+    return 1;
+  if (check_placement_shape(e, Q, C, G)) return 1;
+  if (!query_states || !column_pattern || !pendant_lengths) return fail("null query / column / pendant array");
+  for (int g = 0; g < G; g++)
+    if (!(pendant_lengths[g] >= 0.0 && pendant_lengths[g] <= 1.79769313486231570e308))
+      return fail(std::string(status_message(kBadPendantLength)) + " (pendant " + std::to_string(g) + ")");
+  for (int c = 0; c < C; c++)
+    if (column_pattern[c] < 0 || column_pattern[c] >= e->P)
+      return fail(std::string(status_message(kBadColumnPattern)) + " (column " + std::to_string(c) + ")");
+  enum { kInQuery = kTreeInputs, kInColumn, kInWeights, kInPendant };
+  const size_t E = 2 * (size_t)e->n - 3, QE = (size_t)Q * E;
+  HostCall c;
+  c.T = T;
+  c.in = tree_inputs(e, parent_ids, bl, params);
+  c.in.push_back(fixed(query_states, (size_t)Q * C));
+  c.in.push_back(fixed(column_pattern, C));
+  c.in.push_back(fixed(column_weights, C));
+  c.in.push_back(fixed(pendant_lengths, G));
+  c.out = {per_tree(out_ll, 1),           per_tree(out_edge_ll, QE), per_tree(out_pendant_index, QE),
+           per_tree(out_best_edge, Q),    per_tree(out_lwr, QE),     per_tree(out_edge_tables, E * G * 5 * e->P)};
+  c.enqueue = [=](mi_engine* e, int T, const HostArray* in, const HostArray* out) {
+    return mi_engine_placement_unrooted_device(
+        e, e->stream, T, in[kInParent].at<const int32_t>(), in[kInBl].at<const double>(), params_on_device(e, in),
+        rescaling, Q, C, in[kInQuery].at<const int8_t>(), in[kInColumn].at<const int32_t>(),
+        in[kInWeights].at<const double>(), G, in[kInPendant].at<const double>(), out[0].at<double>(),
+        out[1].at<double>(), out[2].at<int8_t>(), out[3].at<int32_t>(), out[4].at<double>(), out[5].at<double>());
+  };
+  return run_plain(e, c);
+}
+
 // Starting trees: arrays of fixed counts, no per-tree ones -- a tree-sharded
 // handle lets its first shard do the work (every shard holds the whole alignment); neighbour
 // joining needs no alignment and goes to the first shard of any handle.  No retry.

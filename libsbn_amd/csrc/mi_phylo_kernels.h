@@ -138,6 +138,12 @@ struct LikArgs {
   double* anc_cat;    // [T][P][K] rate-category posteriors
   double* anc_rate;   // [T][P] posterior mean rate
   double* anc_tip;    // [T][n][P][4] state posteriors at the leaves
+  // placement_table_hbm_kernel (kernels_placement.hip) only; nullptr / 0 in every other call
+  const double* place_half;  // [T][N-1][K][16] P(r_k t_e / 2) by node id, as `mats`
+  const double* place_pend;  // [T][G][K][16] P(r_k l_g) of the pendant lengths
+  double* place_table;       // [trees of the table launch][2n-3][G][5][tiles*64]: S of DESIGN.md 4.17
+  int place_G;               // pendant lengths, 1 .. kPlacementMaxPendants
+  int place_tree0;           // the call's tree that row 0 of place_table belongs to
 };
 
 // How many logL partial sums each evaluation's walk kernel wrote (the kernels tile the
@@ -247,6 +253,52 @@ void launch_ancestral_hbm(const LikArgs& a, int count, bool rescale, hipStream_t
 void launch_ancestral_finalize(const double* ll_part, int T, int ll_tiles, int ll_used, double* out_ll,
                                hipStream_t s);
 const char* ancestral_kernel_name();
+// Phylogenetic placement (kernels_placement.hip): the HBM-streamed walk with, per
+// caller edge, pendant length and pattern, the five log-likelihoods of "the query shows A / C / G /
+// T / gap" at the edge's midpoint (LikArgs::place_*); the gather-and-sum of the queries over that
+// table; best edge and likelihood weight ratios per (tree, query).
+constexpr int kPlacementMaxPendants = 4;  // MI_PLACEMENT_MAX_PENDANTS
+constexpr int kPlacementQueryBlock = 128;  // queries a scoring workgroup streams through its edge's table
+void launch_placement_table_hbm(const LikArgs& a, int count, bool rescale, hipStream_t s);
+const char* placement_kernel_name();
+// halved effective lengths [T][N], the pendant lengths as rows [T][G+1] (what launch_transition
+// reads), and the checks a device-pointer call cannot make on the host (status word)
+struct PlacePrepareArgs {
+  int T, N, G, C, P;
+  const double* bl_eff;           // [T][N]
+  const double* pendant_lengths;  // [G]
+  const int32_t* column_pattern;  // [C]
+  double* half_bl;                // [T][N]
+  double* pend_bl;                // [T][G+1]
+  int32_t* status;
+};
+void launch_placement_prepare(const PlacePrepareArgs& a, hipStream_t s);
+struct PlaceScoreArgs {
+  int trees, tree0;  // trees of `table`, the call's tree of its row 0
+  int E, G, P, Q, C;
+  size_t ppad;       // patterns of a table row (tiles * 64)
+  int use_lds;       // 1: a workgroup copies its edge's [G][5][ppad] into LDS; 0: it gathers from `table`
+  const double* table;            // [trees][E][G][5][ppad]
+  const int8_t* query_states;     // [Q][C]
+  const int32_t* column_pattern;  // [C]
+  const double* column_weights;   // [C] or nullptr: 1
+  double* edge_ll;                // [T][Q][E] by the call's tree
+  int8_t* pendant_index;          // [T][Q][E] or nullptr
+};
+bool placement_table_fits_lds(int G, size_t ppad);
+void launch_placement_score(const PlaceScoreArgs& a, hipStream_t s);
+// S itself for the caller: [trees][E][G][5][ppad] -> out [T][E][G][5][P] by the call's tree
+void launch_placement_table_copy(const double* table, int trees, int tree0, int E, int G, int P, size_t ppad,
+                                 double* out, hipStream_t s);
+struct PlaceFinalizeArgs {
+  int T, Q, E, ll_tiles, ll_used;
+  const double* ll_part;   // [T][ll_tiles]
+  const double* edge_ll;   // [T][Q][E]
+  double* out_ll;          // [T] or nullptr
+  int32_t* out_best_edge;  // [T][Q] or nullptr
+  double* out_lwr;         // [T][Q][E] or nullptr
+};
+void launch_placement_finalize(const PlaceFinalizeArgs& a, hipStream_t s);
 // Branch-length optimisation (kernels_branch_opt.hip): the step between two
 // Hessian passes and the packing of the active trees.  "Packed" arrays hold the trees that
 // are still being evaluated, in `map` order (map == nullptr: all trees, in their own order).

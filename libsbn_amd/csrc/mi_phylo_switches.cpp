@@ -92,6 +92,7 @@ bool parse_switches(Switches& out, std::string& error) {
   s.fused_spin_ticks = (int)(r.number("MI_PHYLO_FUSED_SPIN_MS", 0.01, 2.0e4, "[0.01, 20000]", 0.0) * 1.0e5);
   s.fused_debug_skip = (int)r.integer("MI_PHYLO_DEBUG_FUSED_SKIP", 0, INT_MAX, 0);
   s.plv_bytes = r.integer("MI_PHYLO_PLV_BYTES", 0, LLONG_MAX, -1);
+  s.place_table_global = r.choice("MI_PHYLO_PLACE_TABLE", "lds|global", 0) == 1;
   s.aa_jacobi_seq = r.choice("MI_PHYLO_AA_JACOBI", "wave|seq", 0) == 1;
   s.aa_post_wave = r.choice("MI_PHYLO_AA_POST", "wg|wave", 0) == 1;
   s.aa_pre_wave = r.choice("MI_PHYLO_AA_PRE", "wg|wave", 0) == 1;

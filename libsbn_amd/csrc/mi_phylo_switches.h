@@ -37,6 +37,8 @@ struct Switches {
   int fused_debug_skip = 0;    // DEBUG_FUSED_SKIP=t+1: tree t's set-up never reports (testing)
   // memory
   long long plv_bytes = -1;    // PLV_BYTES: the arena budget (-1: the engine's default)
+  // placement
+  bool place_table_global = false;  // PLACE_TABLE=global: the scoring gathers from memory even where the table fits LDS
   // 20-state kernels
   bool aa_jacobi_seq = false;        // AA_JACOBI=seq
   bool aa_post_wave = false;         // AA_POST=wave

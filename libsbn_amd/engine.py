@@ -142,6 +142,23 @@ class AncestralStates:
     tip_posteriors: np.ndarray = None
 
 
+@dataclass
+class Placement:
+    """What Engine.placement returns: the trees' log-likelihoods [T], per (tree, query, edge) the
+    log-likelihood of the query on the edge's midpoint at the best of the pendant lengths
+    edge_log_likelihoods [T][Q][2n-3] (edge e: the branch above node e) and best_edge [T][Q]
+    (int32, the lowest among equals); on request pendant_index [T][Q][2n-3] (int8: which pendant
+    length), lwr [T][Q][2n-3] (likelihood weight ratios, rows sum to 1) and tables
+    [T][2n-3][G][5][P] (per edge, pendant length and pattern the log-likelihood of "the query shows
+    A / C / G / T / gap")."""
+    log_likelihoods: np.ndarray
+    edge_log_likelihoods: np.ndarray
+    best_edge: np.ndarray
+    pendant_index: np.ndarray = None
+    lwr: np.ndarray = None
+    tables: np.ndarray = None
+
+
 def rell_weights(weights, replicates, seed):
     """Replicate weights of a RELL bootstrap: multinomial resampling of sum(weights) sites over
     the patterns with numpy.random.default_rng(seed).  Returns float64 [replicates][P]; host
@@ -259,8 +276,10 @@ class Engine:
             self._h = h
             self.param_count = self._lib.mi_engine_param_count(h)
             self.is_gtr = model_specification.substitution == "GTR"
+            self._weights = None
             return
         weights = _np(weights, np.float64)
+        self._weights = weights
         if tip_partials is not None:
             tip_partials = _np(tip_partials, np.float64)
             n, P = tip_partials.shape[:2]
@@ -468,6 +487,53 @@ class Engine:
                 self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), _ptr(ll), _ptr(state),
                 _ptr(mp), _ptr(cat), _ptr(rate), _ptr(tip)))
         return AncestralStates(state, ll, mp, cat, rate, tip)
+
+    def placement(self, parent_ids, branch_lengths, queries, pendant_lengths, params=None, rescaling=False,
+                  column_pattern=None, column_weights=None, pendant_index=False, lwr=False, tables=False):
+        """Phylogenetic placement (mi_engine_placement_unrooted; an extension, 4-state engines):
+        every query row of `queries` [Q][C] (compact states 0..3, anything else a gap) scored on
+        the midpoint of every edge of every tree, at each of the 1..4 pendant_lengths.
+        column_pattern [C] names the engine pattern each query column extends and column_weights
+        [C] weighs it (None: 1); column_pattern=None means C = P, the identity map and the
+        engine's pattern weights.  Returns a Placement; what is not asked for is not computed."""
+        n, P = self.taxon_count, self.pattern_count
+        E = 2 * n - 3
+        pid = _np(parent_ids, np.int32).reshape(-1, E)
+        T = pid.shape[0]
+        x = _np(queries, np.int8)
+        if x.ndim != 2:
+            raise RuntimeError("queries must be [query][column]")
+        Q, Cn = x.shape
+        if column_pattern is None:
+            if column_weights is None:
+                if self._weights is None:
+                    raise RuntimeError("an engine made from device tips keeps no pattern weights on the host: "
+                                       "pass column_pattern and column_weights")
+                column_weights = self._weights
+            col = np.arange(P, dtype=np.int32)
+        else:
+            col = _np(column_pattern, np.int32).reshape(-1)
+        if col.shape != (Cn,):
+            raise RuntimeError(f"queries have {Cn} columns, the column map {col.shape[0]}")
+        cw = None
+        if column_weights is not None:
+            cw = _np(column_weights, np.float64).reshape(-1)
+            if cw.shape != (Cn,):
+                raise RuntimeError("column_weights must have one entry per query column")
+        pend = _np(pendant_lengths, np.float64).reshape(-1)
+        G = pend.shape[0]
+        ll, edge = np.empty(T), np.empty((T, Q, E))
+        best = np.empty((T, Q), np.int32)
+        pi = np.empty((T, Q, E), np.int8) if pendant_index else None
+        lw = np.empty((T, Q, E)) if lwr else None
+        tab = np.empty((T, E, G, 5, P)) if tables else None
+        if T:
+            bl = _np(branch_lengths, np.float64).reshape(T, 2 * n - 2)
+            pr = self._params(params, T)
+            self._check(self._lib.mi_engine_placement_unrooted(
+                self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), Q, Cn, _ptr(x), _ptr(col), _ptr(cw),
+                G, _ptr(pend), _ptr(ll), _ptr(edge), _ptr(pi), _ptr(best), _ptr(lw), _ptr(tab)))
+        return Placement(ll, edge, best, pi, lw, tab)
 
     def pattern_log_likelihoods(self, parent_ids, branch_lengths, params=None, rescaling=False):
         """Per-pattern log-likelihoods per tree (mi_engine_pattern_log_likelihoods_unrooted; an
@@ -798,6 +864,22 @@ class Engine:
     def reserve_ancestral(self, tree_count):
         """mi_engine_reserve_ancestral: workspace of an ancestral-state call (graph capture)."""
         self._check(self._lib.mi_engine_reserve_ancestral(self._h, int(tree_count)))
+
+    def placement_device(self, stream, T, parent_ids, branch_lengths, params, Q, C, query_states,
+                         column_pattern, column_weights, G, pendant_lengths, out_edge_ll, out_ll=None,
+                         out_pendant_index=None, out_best_edge=None, out_lwr=None, out_tables=None,
+                         rescaling=False):
+        """mi_engine_placement_unrooted_device: device pointers (the pendant lengths too), enqueued
+        on `stream` (no allocation after reserve_placement)."""
+        self._check(self._lib.mi_engine_placement_unrooted_device(
+            self._h, stream, T, parent_ids, branch_lengths, params, int(rescaling), Q, C, query_states,
+            column_pattern, column_weights, G, pendant_lengths, out_ll, out_edge_ll, out_pendant_index,
+            out_best_edge, out_lwr, out_tables))
+
+    def reserve_placement(self, tree_count, query_count, column_count, pendant_count):
+        """mi_engine_reserve_placement: workspace of a placement call (graph capture)."""
+        self._check(self._lib.mi_engine_reserve_placement(self._h, int(tree_count), int(query_count),
+                                                          int(column_count), int(pendant_count)))
 
     def optimize_branch_lengths_device(self, stream, T, parent_ids, start_branch_lengths, params,
                                        out_branch_lengths, out_ll, out_status, out_branch=None,
