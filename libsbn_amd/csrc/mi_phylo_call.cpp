@@ -734,17 +734,17 @@ static int reserve_hbm_family(mi_engine* e, int T, int g_width) {
   if (g_width && e->g_part.ensure(sizeof(double) * (size_t)T * e->tiles * g_width)) return 1;
   return reserve_per_tree(e, T);
 }
-// The sequence after check, plan and reservation: set-up, matrices, launch(args, count, rescale,
-// stream) over the vector arena in parts, finalize().
-template <typename Launch, typename Finalize>
-int run_hbm_family(mi_engine* e, hipStream_t s, const DeviceCall& d, const CallPlan& p, Launch launch,
-                   Finalize finalize) {
+// The sequence of a call with one evaluation per tree, after check, plan and reservation:
+// prepare() -- set-up and matrices --, launch(args, count, rescale, stream) over the vector arena
+// in parts, finalize().
+template <typename Prepare, typename Launch, typename Finalize>
+int run_per_tree_call(mi_engine* e, hipStream_t s, const DeviceCall& d, const CallPlan& p, Prepare prepare,
+                      Launch launch, Finalize finalize) {
   const int T = d.T;
   const bool prof = e->prof_used < e->prof_capacity;
   const bool marks = prof && e->prof_phases;
   PROF_MARK(e, marks, 0, s);
-  launch_setup(tree_setup_args(e, d, p), model_setup_args(e, d, p), e->sw, s);
-  launch_transition(transition_args(e, d, p), s);
+  prepare();
 
   const LikArgs la = lik_args(e, d, p);
   if (prof) HIP_TRY(hipEventRecord(prof_event(e, 0), s));
@@ -766,6 +766,16 @@ int run_hbm_family(mi_engine* e, hipStream_t s, const DeviceCall& d, const CallP
   note_call(e, p, first, walk_launches);
   HIP_TRY(hipGetLastError());
   return 0;
+}
+// ... of a member of the HBM-streamed family: set-up, node-ordered matrices
+template <typename Launch, typename Finalize>
+int run_hbm_family(mi_engine* e, hipStream_t s, const DeviceCall& d, const CallPlan& p, Launch launch,
+                   Finalize finalize) {
+  auto prepare = [&] {
+    launch_setup(tree_setup_args(e, d, p), model_setup_args(e, d, p), e->sw, s);
+    launch_transition(transition_args(e, d, p), s);
+  };
+  return run_per_tree_call(e, s, d, p, prepare, launch, finalize);
 }
 
 // ---- the branch-length Hessian call (mi_engine_branch_hessian_unrooted*) ----
@@ -819,33 +829,12 @@ int run_hessian_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
   };
   if (!p.mfma) return run_hbm_family(e, s, d, p, launch_gradient_hbm_hessian, finalize);
   // the walk form: LDS slots of the arena variant, macro-ordered matrices
-  const bool prof = e->prof_used < e->prof_capacity;
-  const bool marks = prof && e->prof_phases;
-  PROF_MARK(e, marks, 0, s);
-  const bool slots_done = launch_setup(tree_setup_args(e, d, p), model_setup_args(e, d, p), e->sw, s);
-  if (p.store == kStoreArena && !slots_done) macro_slots(e, T, s);
-  launch_transition_macro(transition_macro_args(e, d, p, 0, 0, T), s);
-
-  const LikArgs la = lik_args(e, d, p);
-  if (prof) HIP_TRY(hipEventRecord(prof_event(e, 0), s));
-  PROF_MARK(e, marks, 1, s);
-  PROF_MARK(e, marks, 2, s);
-  // (a launch covers what the walk's arena holds)
-  int walk_launches = 0;
-  const int first = launch_in_parts(e, T, vector_bytes_per_eval(e, p), walk_launches, [&](int done, int part) {
-    LikArgs g = la;
-    g.eval_offset = done;
-    g.grad_offset = done;
-    launch_gradient_walk_hessian(g, part, d.rescaling, s);
-  });
-  if (prof) HIP_TRY(hipEventRecord(prof_event(e, 1), s));
-  PROF_MARK(e, marks, 3, s);
-  finalize();
-  PROF_MARK(e, marks, 4, s);
-  if (prof) e->prof_used++;
-  note_call(e, p, first, walk_launches);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  auto prepare = [&] {
+    const bool slots_done = launch_setup(tree_setup_args(e, d, p), model_setup_args(e, d, p), e->sw, s);
+    if (p.store == kStoreArena && !slots_done) macro_slots(e, T, s);
+    launch_transition_macro(transition_macro_args(e, d, p, 0, 0, T), s);
+  };
+  return run_per_tree_call(e, s, d, p, prepare, launch_gradient_walk_hessian, finalize);
 }
 
 // ---- the NNI neighbourhood scan (mi_engine_nni_scan_unrooted*) ----
