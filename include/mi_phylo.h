@@ -362,6 +362,67 @@ int32_t mi_engine_placement_unrooted(mi_engine* engine, int32_t tree_count,
                                      double* out_lwr /* [T][Q][2n-3] or NULL */,
                                      double* out_edge_tables /* [T][2n-3][G][5][P] or NULL */);
 
+/* The SPR neighbourhood scan (an extension: no counterpart in the reference's Engine; DESIGN.md
+ * 4.18): for trees at given branch lengths, the log-likelihood change of every subtree-prune-and-
+ * regraft move "cut this edge, re-attach the loose part on the midpoint of that edge".  The trees
+ * are unrooted, in the caller's form: leaves 0..n-1, internal nodes in post-order, trifurcating
+ * root 2n-3; edge e = 0 .. 2n-4 is the branch above node e, of length t_e; E = 2n-3 edges.
+ * A move is (s, dir, f).
+ * dir = 0, the clade moves: edge s is cut at its top; clade s keeps its branch of length t_s.
+ *   The parent u of s is removed.  If u is not the root, its other child y and the edge above u
+ *   become one edge of length t_y + t_u; if u is the root, with other children y1 and y2, these
+ *   are joined by one edge of length t_y1 + t_y2.  The target edge f of the remaining tree is
+ *   split at its midpoint, both halves t_f / 2, and the clade is hung there on its branch t_s.
+ *   Valid targets: every edge that is none of s, an edge inside clade s, y and u (at the root:
+ *   y1, y2) -- those two name the merged edge and would give the topology back.
+ * dir = 1, the rest moves: s must be an internal node, with children a and b.  Edge s is cut at
+ *   its bottom; everything outside clade s keeps the branch t_s.  Node s is removed, a and b are
+ *   joined by an edge of length t_a + t_b.  The target f is an edge strictly inside clade a or
+ *   clade b, split at its midpoint, and the rest is hung there on t_s.  A leaf s has no dir = 1
+ *   moves.
+ * Distance and radius: the distance of a move is the number of nodes of the pruned tree on the
+ * path between the merged edge and f; the edges touching the merged edge are at distance 1.
+ * radius >= 1 keeps the moves of distance <= radius, radius = 0 keeps all; a negative radius is
+ * refused.
+ * The gain: delta[t][s][dir][f] = logL(neighbour) - logL(tree t), under the same model row and
+ * the branch lengths just described, formed per pattern as sum_p w_p log(L'_p / L_p), never as a
+ * difference of two totals (patterns of weight 0 are skipped).
+ * Outputs:
+ *   out_log_likelihoods [T] (or NULL): bit for bit the gradient call's on the HBM path
+ *   out_best_target [T][E][2] (int32), out_best_delta [T][E][2]: per (s, dir) the target of the
+ *     largest delta, the lowest f among equals; -1 and -inf where (s, dir) has no valid move
+ *     within the radius
+ *   out_best_move [T][3] (or NULL): (s, dir, f) of the largest delta of the tree, among equals
+ *     the lowest code (2 s + dir) E + f; (-1, -1, -1) where the tree has no move (n = 3)
+ *   out_delta [T][E][2][E] (or NULL): the whole table; every entry that is no valid move within
+ *     the radius is -inf
+ * Sums over patterns are formed tile by tile in one fixed order: a tree's outputs do not depend
+ * on the batch it came in or on how the call was cut into launches.  4-state engines and
+ * unrooted trees only.  Sharded handles: MI_SHARD_TREES deals the trees; MI_SHARD_PATTERNS is
+ * refused.  The scan's workspace (a second vector arena, rescaling exponents, the per-tile table)
+ * counts against MI_PHYLO_PLV_BYTES: a batch over the budget is cut into launches over trees and
+ * writes the same bytes; one tree's workspace over the budget is refused. */
+int32_t mi_engine_spr_scan_unrooted(mi_engine* engine, int32_t tree_count,
+                                    const int32_t* parent_ids,    /* [T][2n-3] */
+                                    const double* branch_lengths, /* [T][2n-2] */
+                                    const double* params, int32_t rescaling, int32_t radius,
+                                    double* out_log_likelihoods /* [T] or NULL */,
+                                    int32_t* out_best_target /* [T][2n-3][2] */,
+                                    double* out_best_delta /* [T][2n-3][2] */,
+                                    int32_t* out_best_move /* [T][3] or NULL */,
+                                    double* out_delta /* [T][2n-3][2][2n-3] or NULL */);
+
+/* The tree the move (s, dir, f) of mi_engine_spr_scan_unrooted leads to, in the reference's
+ * numbering: leaves keep their ids, internal nodes in post-order, children ordered by largest
+ * leaf id.  It is rooted at the caller's root node if that node survives, else (dir = 0 with
+ * parent(s) the root) at the new attachment node.  Every length goes with its edge (edges on a
+ * reversed path carry their length along); the merged edge is t_y + t_u, the halves 0.5 * t_f;
+ * the entry of 2n-3 is copied.  Host arithmetic only.  Nonzero for a triple that is no valid move
+ * (any radius) or a parent-id vector that is no tree. */
+int32_t mi_spr_neighbour(int32_t taxon_count, const int32_t* parent_ids /* [2n-3] */,
+                         const double* branch_lengths /* [2n-2] */, int32_t s, int32_t dir, int32_t f,
+                         int32_t* out_parent_ids /* [2n-3] */, double* out_branch_lengths /* [2n-2] */);
+
 /* RELL re-summation (resampling of estimated log-likelihoods) and its reductions (an extension;
  * DESIGN.md 4.12), for B replicates, T trees and P patterns -- P is an argument: any engine
  * serves (the alignment plays no part), a sharded handle lets its first shard do it.
@@ -726,6 +787,16 @@ int32_t mi_engine_placement_unrooted_device(
     double* out_log_likelihoods, double* out_edge_log_likelihoods, int8_t* out_pendant_index,
     int32_t* out_best_edge, double* out_lwr, double* out_edge_tables);
 
+/* The device form of mi_engine_spr_scan_unrooted: every array a device pointer; it only enqueues
+ * -- no allocation and no synchronisation after mi_engine_reserve_spr_scan, so it can be captured
+ * in a hipGraph.  A parent-id vector that is no tree is reported through the status word
+ * (mi_engine_check_status); such a tree's rows hold no move. */
+int32_t mi_engine_spr_scan_unrooted_device(mi_engine* engine, void* stream, int32_t tree_count,
+                                           const int32_t* parent_ids, const double* branch_lengths,
+                                           const double* params, int32_t rescaling, int32_t radius,
+                                           double* out_log_likelihoods, int32_t* out_best_target,
+                                           double* out_best_delta, int32_t* out_best_move, double* out_delta);
+
 /* The device forms of mi_engine_pattern_log_likelihoods_unrooted, mi_engine_rell and
  * mi_engine_pattern_mixture: they only enqueue -- no allocation and no synchronisation after
  * mi_engine_reserve(tree_count, 0), mi_engine_reserve_rell and (the mixture) a first call of
@@ -800,6 +871,10 @@ int32_t mi_engine_reserve_nni_scan(mi_engine* engine, int32_t tree_count);
  * either rescaling setting: a *_device call of at most that size then allocates nothing
  * (hipGraph capture).  4-state engines only. */
 int32_t mi_engine_reserve_ancestral(mi_engine* engine, int32_t tree_count);
+/* The workspace of mi_engine_spr_scan_unrooted[_device] for `tree_count` trees, of either
+ * rescaling setting and any radius: a *_device call of at most that size then allocates nothing
+ * (hipGraph capture).  4-state engines only. */
+int32_t mi_engine_reserve_spr_scan(mi_engine* engine, int32_t tree_count);
 /* The workspace of mi_engine_placement_unrooted[_device] for `tree_count` trees and
  * `pendant_count` pendant lengths, of either rescaling setting: a *_device call of at most that
  * size then allocates nothing (hipGraph capture).  query_count and column_count are checked;

@@ -122,6 +122,12 @@ SYMBOLS = {
         (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32,
                      _V, _V, _V, _V, _V, _V, _V]),
     "mi_engine_reserve_placement": (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mi_engine_spr_scan_unrooted":
+        (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),
+    "mi_engine_spr_scan_unrooted_device":
+        (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),
+    "mi_engine_reserve_spr_scan": (C.c_int32, [_V, C.c_int32]),
+    "mi_spr_neighbour": (C.c_int32, [C.c_int32, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V]),
     "mi_engine_rell": (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V]),
     "mi_engine_rell_device":
         (C.c_int32, [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V]),

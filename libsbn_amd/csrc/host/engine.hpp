@@ -111,6 +111,18 @@ struct PlacementResult {
   std::vector<double> lwr_, tables_;
 };
 
+// Engine::SprScan, per tree (an extension, include/mi_phylo.h) with E = 2n-3 edges: per (pruned
+// edge s, direction) the target of the largest log-likelihood change best_target_ [E][2] (-1: no
+// move) and that change best_delta_ [E][2] (-inf: no move); best_move_ = (s, direction, f) of the
+// tree's largest change; asked for, delta_ [E][2][E], the whole table (-inf: no move)
+struct SprNeighbourhood {
+  double log_likelihood_ = 0.;
+  std::vector<int32_t> best_target_;
+  std::vector<double> best_delta_;
+  int32_t best_move_[3] = {-1, -1, -1};
+  std::vector<double> delta_;
+};
+
 // Engine::OptimizeBranchLengths, per tree (an extension, include/mi_phylo.h): the
 // maximum-likelihood branch lengths [2n-2] and the Hessian call's outputs at them [2n-1]
 struct BranchOptimum {
@@ -316,6 +328,33 @@ class Engine {
       out[t].log_likelihood_ = ll[t];
       out[t].delta_.assign(d.begin() + t * N * 2, d.begin() + (t + 1) * N * 2);
       out[t].best_move_ = best[t];
+    }
+    return out;
+  }
+
+  // Log-likelihood change of every subtree-prune-and-regraft move per tree (an extension; 4-state
+  // engines): mi_engine_spr_scan_unrooted.  radius 0: every move.  mi_spr_neighbour builds the
+  // tree of a move.
+  std::vector<SprNeighbourhood> SprScan(const UnrootedTreeCollection& trees, const ParamMatrix& params,
+                                        const bool rescaling, const int32_t radius = 0,
+                                        const bool table = false) const {
+    const size_t T = trees.size(), E = 2 * site_pattern_.SequenceCount() - 3;
+    std::vector<int32_t> parents;
+    std::vector<double> bl;
+    Flatten(trees, params, false, &parents, &bl);
+    if (trees.empty()) return {};
+    std::vector<double> ll(T), best(T * 2 * E), d(table ? T * 2 * E * E : 0);
+    std::vector<int32_t> target(T * 2 * E), move(T * 3);
+    Check(mi_engine_spr_scan_unrooted(handle_, static_cast<int32_t>(T), parents.data(), bl.data(),
+                                      params.data.data(), rescaling, radius, ll.data(), target.data(), best.data(),
+                                      move.data(), table ? d.data() : nullptr));
+    std::vector<SprNeighbourhood> out(T);
+    for (size_t t = 0; t < T; t++) {
+      out[t].log_likelihood_ = ll[t];
+      out[t].best_target_.assign(target.begin() + t * 2 * E, target.begin() + (t + 1) * 2 * E);
+      out[t].best_delta_.assign(best.begin() + t * 2 * E, best.begin() + (t + 1) * 2 * E);
+      std::copy(move.begin() + t * 3, move.begin() + (t + 1) * 3, out[t].best_move_);
+      if (table) out[t].delta_.assign(d.begin() + t * 2 * E * E, d.begin() + (t + 1) * 2 * E * E);
     }
     return out;
   }

@@ -154,6 +154,15 @@ CallPlan plan_call(const mi_engine* e, CallKind kind, int T, bool rescaling, int
     p.dominant = placement_kernel_name();
     return p;
   }
+  if (kind == kSprCall) {
+    // The SPR neighbourhood scan: as the NNI scan -- one evaluation per tree with
+    // the tree's own model, node-ordered matrices, the HBM-streamed kernel.
+    p.Eg = T;
+    p.g_tiles = e->tiles;
+    p.store = kStoreHbm;
+    p.dominant = spr_kernel_name();
+    return p;
+  }
   // on-chip gradient kernels: the matrix-core one (K <= 4; rescaling supported) or the
   // VALU one (no rescaling); everything else takes the HBM-streamed kernel
   p.mfma = gradient && matrix_core_gradient(e, rescaling, p.loglik_is_valu);
@@ -261,6 +270,7 @@ std::string plan_path(const mi_engine* e, const CallPlan& p) {
   if (p.kind == kNniCall) path += " nni";
   if (p.kind == kAncestralCall) path += " ancestral";
   if (p.kind == kPlacementCall) path += " placement";
+  if (p.kind == kSprCall) path += " spr";
   if (p.pattern_ll) path += " pattern_ll";
   if (p.tile_regs > kLlR) path += " tile=wide";
   if (p.fd_pass) path += " fd=16";
@@ -502,7 +512,7 @@ LikArgs lik_args(const mi_engine* e, const DeviceCall& d, const CallPlan& p) {
     la.place_G = d.G;
     return la;
   }
-  if (p.kind == kHessianCall || p.kind == kNniCall) return la;  // (their kernels read none of the following)
+  if (p.kind == kHessianCall || p.kind == kNniCall || p.kind == kSprCall) return la;  // (their kernels read none of the following)
   la.tip_tables = e->tip_tables.as<double>();
   la.mphi = e->mphi.as<double>();
   // (MI_PHYLO_TIP_TILES=0: the kernels stage their tip bytes from tip_masks / tip_codes themselves
@@ -713,7 +723,7 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d_in) {
 // ---- the calls of the HBM-streamed kernel family ----
 // One evaluation per tree with the tree's own model, the node-ordered matrices, the member's
 // kernel over the vector arena in parts, one finalize launch: the Hessian call where no
-// matrix-core walk takes it, the NNI scan, the ancestral-state call, placement.
+// matrix-core walk takes it, the NNI scan, the ancestral-state call, placement, the SPR scan.
 // (trees, models, node-ordered matrices, log-likelihood partials: the Hessian call's walk form too)
 static int reserve_per_tree(mi_engine* e, int T) {
   const int n = e->n, N = e->N;
@@ -990,5 +1000,137 @@ int run_placement_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
         launch_placement_finalize(fa, s);
       });
   if (rc == 0) e->last_walk_launches = table_launches;
+  return rc;
+}
+
+// ---- the SPR neighbourhood scan (mi_engine_spr_scan_unrooted*) ----
+// The vectors kernel over the vector arena in parts, as every member; inside a part, over what the
+// scan's own workspace holds: vectors, regraft walk and finalize launch per sub-part (the finalize
+// launch writes the sub-part's trees, log-likelihoods included: nothing is left for the end).
+// The half-length matrices are one more launch of the transition kernel in front of the first.
+int check_spr_shape(const mi_engine* e, int radius) {
+  if (radius < 0) return fail("SPR scan: radius must be 0 (every move) or positive, not " + std::to_string(radius));
+  if (!spr_regraft_fits_lds(e->n, e->n))
+    return fail("SPR scan: a tree of " + std::to_string(e->n) + " taxa does not fit the regraft walk's LDS");
+  return 0;
+}
+
+namespace {
+// what one tree of a launch holds in spr_ws: doubles (second arena, L_p, partial table), int32s
+// (exponents below, exponents above, that of L_p)
+struct SprLayout {
+  size_t ppad, up, site, part, exp_down, exp_up, site_exp;  // elements per tree
+  size_t doubles() const { return up + site + part; }
+  size_t ints() const { return exp_down + exp_up + site_exp; }
+  size_t bytes() const { return sizeof(double) * doubles() + sizeof(int32_t) * ints(); }
+};
+SprLayout spr_layout(const mi_engine* e) {
+  SprLayout l;
+  const size_t n = e->n, E = 2 * n - 3;
+  l.ppad = (size_t)e->tiles * kTile;
+  l.up = (2 * n - 2) * e->K * l.ppad * 4;
+  l.site = l.ppad;
+  l.part = (size_t)e->tiles * 2 * E * E;
+  l.exp_down = (n - 1) * l.ppad;
+  l.exp_up = (2 * n - 2) * l.ppad;
+  l.site_exp = l.ppad;
+  return l;
+}
+// trees a launch covers: what the budget holds
+int spr_launch_trees(const mi_engine* e, int T) {
+  return (int)std::max<size_t>(1, std::min<size_t>(T, e->plv_budget / spr_layout(e).bytes()));
+}
+// The regraft waves' paths: a wave per job (tree, tile, pruned edge) of a call of T trees, at most
+// kSprWaves waves, fewer where a path of n messages is long (1 GiB in all).
+constexpr int kSprWaves = 2048;
+size_t spr_path_bytes_per_wave(const mi_engine* e, int slots) {
+  return sizeof(double) * (size_t)(slots + 1) * e->K * kTile * 4 + sizeof(int32_t) * (size_t)slots * kTile;
+}
+int spr_waves(const mi_engine* e, int T) {
+  const size_t jobs = (size_t)T * e->tiles * (2 * (size_t)e->n - 3);
+  const size_t fit = ((size_t)1 << 30) / spr_path_bytes_per_wave(e, e->n);
+  return (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(kSprWaves, jobs), fit));
+}
+}  // namespace
+
+int reserve_spr_calls(mi_engine* e, int T) {
+  const int N = e->N;
+  const size_t per = spr_layout(e).bytes();
+  if (per > e->plv_budget)
+    return fail("SPR scan: the workspace of one tree (" + std::to_string(per) + " bytes: second arena, exponents and "
+                "the per-tile table of 2 (2n-3)^2 moves) exceeds the arena budget (" + std::to_string(e->plv_budget) +
+                " bytes, MI_PHYLO_PLV_BYTES)");
+  if (e->spr_bl.ensure(sizeof(double) * (size_t)T * N)) return 1;
+  if (e->spr_half.ensure(sizeof(double) * (size_t)T * (N - 1) * e->K * 16)) return 1;
+  if (e->spr_ws.ensure(per * spr_launch_trees(e, T))) return 1;
+  if (e->spr_path.ensure(spr_path_bytes_per_wave(e, e->n) * spr_waves(e, T))) return 1;
+  return reserve_hbm_family(e, T, 0);
+}
+
+int run_spr_device(mi_engine* e, hipStream_t s, const DeviceCall& d) {
+  HIP_TRY(hipSetDevice(e->spec.device));
+  if (e->s == kAa) return fail(kSpr4State);
+  if (check_spr_shape(e, d.spr_radius)) return 1;
+  if (check_call(e, d, d.out_spr_target)) return 1;
+  if (!d.out_spr_delta) return fail("null best-delta output");
+  const CallPlan p = plan_call(e, kSprCall, d);
+  if (reserve_spr_calls(e, d.T)) return 1;
+  const int T = d.T, n = e->n, N = e->N;
+  const int launch_trees = spr_launch_trees(e, T);
+  const SprLayout l = spr_layout(e);
+  SprArgs base{};
+  base.n = n, base.K = e->K, base.P = e->P, base.tiles = e->tiles;
+  base.radius = d.spr_radius;
+  base.depth_slots = d.spr_radius ? std::min(n, d.spr_radius) : n;
+  base.waves = spr_waves(e, T);
+  base.ll_tiles = e->ll_stride, base.ll_used = p.g_tiles;
+  base.models = e->models.as<DevModel>();
+  base.sched = e->sched.as<SchedEntry>();
+  base.mats = e->mats.as<double>();
+  base.half = e->spr_half.as<double>();
+  base.weights = e->weights.as<double>();
+  base.tip_states = e->tip_states.as<int8_t>();
+  base.tip_partials = e->spec.use_tip_states ? nullptr : e->tip_partials.as<double>();
+  base.down = e->plv.as<double>();
+  base.up = e->spr_ws.as<double>();
+  base.site = base.up + l.up * launch_trees;
+  base.part = base.site + l.site * launch_trees;
+  base.exp_down = reinterpret_cast<int32_t*>(base.part + l.part * launch_trees);
+  base.exp_up = base.exp_down + l.exp_down * launch_trees;
+  base.site_exp = base.exp_up + l.exp_up * launch_trees;
+  base.path = e->spr_path.as<double>();
+  base.path_exp = reinterpret_cast<int32_t*>(base.path + (size_t)base.waves * (base.depth_slots + 1) * e->K * kTile * 4);
+  base.ll_part = e->ll_part.as<double>();
+  base.out_ll = d.out_ll;
+  base.out_best_target = d.out_spr_target;
+  base.out_best_delta = d.out_spr_delta;
+  base.out_best_move = d.out_spr_move;
+  base.out_delta = d.out_spr_table;
+  int launches = 0;
+  const int rc = run_hbm_family(
+      e, s, d, p,
+      [&](const LikArgs& g, int part, bool rescale, hipStream_t s) {
+        if (g.eval_offset == 0) {
+          launch_spr_half_lengths(e->bl_eff.as<double>(), (size_t)T * N, e->spr_bl.as<double>(), s);
+          TransitionArgs tr = transition_args(e, d, p);
+          tr.bl_eff = e->spr_bl.as<double>();
+          tr.mats = e->spr_half.as<double>();
+          launch_transition(tr, s);
+        }
+        for (int done = 0; done < part; done += launch_trees) {
+          LikArgs h = g;
+          h.eval_offset = g.eval_offset + done;
+          h.grad_offset = h.eval_offset;
+          SprArgs w = base;
+          w.trees = std::min(launch_trees, part - done);
+          w.tree0 = h.eval_offset;
+          launch_spr_vectors_hbm(h, w, w.trees, rescale, s);
+          launch_spr_regraft(w, rescale, s);
+          launch_spr_finalize(w, s);
+          launches++;
+        }
+      },
+      [] {});
+  if (rc == 0) e->last_walk_launches = launches;
   return rc;
 }

@@ -98,6 +98,7 @@ const char kNni4State[] = "the NNI neighbourhood scan is 4-state only";
 const char kPatternLl4State[] = "per-pattern log-likelihoods are 4-state only";
 const char kAncestral4State[] = "the ancestral-state call is 4-state only";
 const char kPlacement4State[] = "the placement call is 4-state only";
+const char kSpr4State[] = "the SPR neighbourhood scan is 4-state only";
 
 extern "C" {
 
@@ -452,7 +453,7 @@ void mi_engine_destroy(mi_engine* e) {
         &e->in_pack, &e->out_pack, &e->opt_ws, &e->nni_apply_ws, &e->nni_search_ws,
         &e->pattern_blank, &e->pattern_ll_out, &e->rell_ws, &e->rell_s, &e->dist_codes, &e->dist_model,
         &e->dist_counts, &e->dist_matrix, &e->nj_ws, &e->place_bl, &e->place_half, &e->place_pend,
-        &e->place_table})
+        &e->place_table, &e->spr_bl, &e->spr_half, &e->spr_ws, &e->spr_path})
     b->release();
   if (e->opt_word) (void)hipHostFree(e->opt_word);
   e->pinned.release();
@@ -792,6 +793,43 @@ int32_t mi_engine_reserve_placement(mi_engine* e, int32_t tree_count, int32_t qu
   }
   HIP_TRY(hipSetDevice(e->spec.device));
   return reserve_placement_calls(e, tree_count, pendant_count);
+}
+
+int32_t mi_engine_spr_scan_unrooted_device(mi_engine* e, void* stream, int32_t T, const int32_t* parent_ids,
+                                           const double* bl, const double* params, int32_t rescaling,
+                                           int32_t radius, double* out_ll, int32_t* out_best_target,
+                                           double* out_best_delta, int32_t* out_best_move, double* out_delta) {
+  if (!e) return fail("null engine");
+  if (e->s == kAa) return fail(kSpr4State);
+  if (!e->shards.empty()) return fail(kShardedDeviceCall);
+  if (check_spr_shape(e, radius)) return 1;
+  if (!out_best_target || !out_best_delta) return fail("null best-target / best-delta output");
+  DeviceCall d;
+  d.T = T;
+  d.rescaling = rescaling != 0;
+  d.parent_ids = parent_ids;
+  d.bl = bl;
+  d.params = params;
+  d.spr_radius = radius;
+  d.out_ll = out_ll;
+  d.out_spr_target = out_best_target;
+  d.out_spr_delta = out_best_delta;
+  d.out_spr_move = out_best_move;
+  d.out_spr_table = out_delta;
+  return run_spr_device(e, pick_stream(e, stream), d);
+}
+
+int32_t mi_engine_reserve_spr_scan(mi_engine* e, int32_t tree_count) {
+  if (!e) return fail("null engine");
+  if (tree_count <= 0) return fail("tree_count must be positive");
+  if (e->s == kAa) return fail(kSpr4State);
+  if (!e->shards.empty()) {
+    if (e->shard_mode != MI_SHARD_TREES) return fail("pattern-sharded engines do not scan SPR neighbourhoods");
+    return for_each_shard(e, tree_count, mi_engine_reserve_spr_scan);
+  }
+  if (check_spr_shape(e, 0)) return 1;
+  HIP_TRY(hipSetDevice(e->spec.device));
+  return reserve_spr_calls(e, tree_count);
 }
 
 int32_t mi_engine_log_likelihoods_rooted_device(mi_engine* e, void* stream, int32_t T,

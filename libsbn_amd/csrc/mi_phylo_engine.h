@@ -3,9 +3,10 @@
 //   mi_phylo_engine.cpp       engine creation / destruction, status, profiling, the thin
 //                             device-pointer entry points of the C ABI
 //   mi_phylo_call.cpp         the call plan (which route a call takes: plan_call), reservation,
-//                             the argument-block builders, the 4-state, Hessian, NNI-scan, ancestral-state and placement call sequences
+//                             the argument-block builders, the 4-state, Hessian, NNI-scan, ancestral-state, placement and SPR-scan call sequences
 //   mi_phylo_branch_opt.cpp   branch-length optimisation
 //   mi_phylo_nni.cpp          mi_nni_neighbour, the scan's best move on the host (no device code)
+//   mi_phylo_spr.cpp          mi_spr_neighbour (no device code)
 //   mi_phylo_nni_search.cpp   NNI moves on the device, the NNI hill-climbing search
 //   mi_phylo_rell.cpp         per-pattern log-likelihoods (device form), RELL re-summation, tree mixtures
 //   mi_phylo_start_trees.cpp  pairwise distances, neighbour joining, starting trees (device forms, reservation)
@@ -203,6 +204,11 @@ struct mi_engine {
   Buffer place_half;   // [T][N-1][K][16] P(r_k t_e / 2) by node id
   Buffer place_pend;   // [T][G][K][16] P(r_k l_g)
   Buffer place_table;  // [trees of a table launch][2n-3][G][5][tiles*64]: counts against plv_budget
+  // the SPR neighbourhood scan (mi_engine_spr_scan_unrooted*)
+  Buffer spr_bl;    // [T][N] halved effective lengths
+  Buffer spr_half;  // [T][N-1][K][16] P(r_k t_e / 2) by node id
+  Buffer spr_ws;    // per tree of a launch: second arena, exponents, L_p, per-tile partial table: counts against plv_budget
+  Buffer spr_path;  // [waves] the regraft waves' paths: messages and their exponents
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)
   std::vector<hipEvent_t> prof_events;  // kProfEvents per call: [begin, end, mark 0..4]
@@ -238,7 +244,7 @@ inline hipEvent_t prof_event(mi_engine* e, int which) {
 // (reserve, reserve_hessian), the argument-block builders, the call sequences and the path
 // string (plan_path) read the plan -- so a reserve cannot guess differently from the call it
 // reserves for (and leave that call to allocate inside a hipGraph capture).
-enum CallKind { kLogLikCall, kGradientCall, kHessianCall, kNniCall, kAncestralCall, kPlacementCall };
+enum CallKind { kLogLikCall, kGradientCall, kHessianCall, kNniCall, kAncestralCall, kPlacementCall, kSprCall };
 enum WalkStore { kStoreHbm = 0, kStoreLds = 1, kStoreArena = 2 };  // (LikArgs::store: 0 = not a matrix-core walk)
 struct CallPlan {
   CallKind kind;
@@ -313,6 +319,12 @@ struct DeviceCall {
   int32_t* out_place_best = nullptr;      // [T][Q]
   double* out_place_lwr = nullptr;        // [T][Q][2n-3]
   double* out_place_tables = nullptr;     // [T][2n-3][G][5][P]
+  // the SPR scan (run_spr_device): out_spr_target and out_spr_delta are required
+  int spr_radius = 0;                     // 0: every move
+  int32_t* out_spr_target = nullptr;      // [T][2n-3][2]
+  double* out_spr_delta = nullptr;        // [T][2n-3][2]
+  int32_t* out_spr_move = nullptr;        // [T][3]
+  double* out_spr_table = nullptr;        // [T][2n-3][2][2n-3]
   // ... as one pass of the branch-length optimisation: the batch size the kernel and its store
   // are chosen for (the whole batch's, so that a tree's results do not depend on how many
   // trees are still active); 0: T
@@ -347,6 +359,11 @@ int run_ancestral_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
 int check_placement_shape(const mi_engine* e, int Q, int C, int G);
 int reserve_placement_calls(mi_engine* e, int T, int G);
 int run_placement_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
+// the SPR scan: what both entry points refuse before any device work; the
+// workspace of a call of T trees, of either rescaling setting and any radius; the call itself
+int check_spr_shape(const mi_engine* e, int radius);
+int reserve_spr_calls(mi_engine* e, int T);
+int run_spr_device(mi_engine* e, hipStream_t s, const DeviceCall& d);
 // the scan's best move from a tree's delta [N][2] (what the finalize kernel does; pattern shards)
 int32_t nni_best_move(int n, const double* delta);
 
@@ -373,7 +390,7 @@ int check_branch_opt_options(const mi_branch_opt_options& o);
 int run_branch_opt_device(mi_engine* e, hipStream_t s, const BranchOptCall& c);
 
 // ---- mi_phylo_engine.cpp ----
-extern const char kShardedDeviceCall[], kHessian4State[], kNni4State[], kPatternLl4State[], kAncestral4State[], kPlacement4State[];
+extern const char kShardedDeviceCall[], kHessian4State[], kNni4State[], kPatternLl4State[], kAncestral4State[], kPlacement4State[], kSpr4State[];
 int check_status(mi_engine* e, hipStream_t s);
 inline hipStream_t pick_stream(mi_engine* e, void* stream) {
   return stream ? static_cast<hipStream_t>(stream) : e->stream;

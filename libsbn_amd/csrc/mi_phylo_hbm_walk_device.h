@@ -1,7 +1,7 @@
 // What the HBM-streamed kernel family shares: gradient_hbm_kernel and
 // gradient_hbm_hess_kernel (kernels_gradient.hip), nni_scan_hbm_kernel (kernels_nni.hip),
-// ancestral_hbm_kernel (kernels_ancestral.hip) and placement_table_hbm_kernel
-// (kernels_placement.hip), with the finalize kernels that sum their tile partials.  One lane per pattern, one wave per (evaluation, 64-pattern tile), partial-likelihood
+// ancestral_hbm_kernel (kernels_ancestral.hip), placement_table_hbm_kernel
+// (kernels_placement.hip) and spr_vectors_hbm_kernel (kernels_spr.hip), with the finalize kernels that sum their tile partials.  One lane per pattern, one wave per (evaluation, 64-pattern tile), partial-likelihood
 // vectors through the `plv` arena as [evaluation][node][category][pattern][state] (32 B per lane,
 // a wave reads or writes 2 KiB contiguous).  Each lane only ever re-reads what it wrote itself,
 // so no inter-wave synchronisation is needed; the pre-order vector of a node overwrites its
@@ -82,9 +82,15 @@ struct HbmLane {
 // Post-order pass: every internal node's vector into the arena (the root's is contracted with
 // pi instead), then the tile's log-likelihood partial into ll_part.  Returns the lane's own
 // unweighted log-likelihood (its pattern's; a padding lane: that of pattern P - 1).
+// `tap` sees what the pass otherwise throws away: node(entry, ex) the power of two taken out of
+// a node's vectors (rescaling only), root(site, cum_exp) the lane's likelihood site 2^cum_exp.
 // ------------------------------------------------------------------------
-template <bool RESCALE, bool TIP_PARTIALS>
-__device__ __forceinline__ double hbm_post_order(const HbmLane<TIP_PARTIALS>& c) {
+struct HbmNoTap {
+  __device__ __forceinline__ void node(const SchedEntry&, int) const {}
+  __device__ __forceinline__ void root(double, int) const {}
+};
+template <bool RESCALE, bool TIP_PARTIALS, typename Tap = HbmNoTap>
+__device__ __forceinline__ double hbm_post_order(const HbmLane<TIP_PARTIALS>& c, const Tap& tap = Tap{}) {
   const int n = c.n, K = c.K;
   int cum_exp = 0;
   double site = 0.0;
@@ -106,6 +112,7 @@ __device__ __forceinline__ double hbm_post_order(const HbmLane<TIP_PARTIALS>& c)
       // common exponent across categories (the ratio in the edge derivative needs it)
       const int ex = max_exponent(mx);
       cum_exp += ex;
+      tap.node(s, ex);
       for (int k = 0; k < K; k++) {
         const D4 L = scale4(load4(c.plv_at(s.node, k)), -ex);
         if (is_root)
@@ -115,6 +122,7 @@ __device__ __forceinline__ double hbm_post_order(const HbmLane<TIP_PARTIALS>& c)
       }
     }
   }
+  tap.root(site, cum_exp);
   double ll = log(site);
   if (RESCALE) ll += cum_exp * 0.6931471805599453;
   const double lane_ll = ll;

@@ -348,6 +348,32 @@ int32_t mi_engine_placement_unrooted(mi_engine* e, int32_t T, const int32_t* par
   return run_plain(e, c);
 }
 
+int32_t mi_engine_spr_scan_unrooted(mi_engine* e, int32_t T, const int32_t* parent_ids, const double* bl,
+                                    const double* params, int32_t rescaling, int32_t radius, double* out_ll,
+                                    int32_t* out_best_target, double* out_best_delta, int32_t* out_best_move,
+                                    double* out_delta) {
+  if (!out_best_target || !out_best_delta) return fail("null best-target / best-delta output");
+  if (e && e->s == kAa) return fail(kSpr4State);
+  if (check_tree_call(e, T, parent_ids, bl, params,
+                      "pattern-sharded engines do not scan SPR neighbourhoods (the best target of a prune is no sum "
+                      "over site patterns): use MI_SHARD_TREES or a single engine"))
+    return 1;
+  if (check_spr_shape(e, radius)) return 1;
+  const size_t E = 2 * (size_t)e->n - 3;
+  HostCall c;
+  c.T = T;
+  c.in = tree_inputs(e, parent_ids, bl, params);
+  c.out = {per_tree(out_ll, 1), per_tree(out_best_target, 2 * E), per_tree(out_best_delta, 2 * E),
+           per_tree(out_best_move, 3), per_tree(out_delta, 2 * E * E)};
+  c.enqueue = [=](mi_engine* e, int T, const HostArray* in, const HostArray* out) {
+    return mi_engine_spr_scan_unrooted_device(e, e->stream, T, in[kInParent].at<const int32_t>(),
+                                              in[kInBl].at<const double>(), params_on_device(e, in), rescaling, radius,
+                                              out[0].at<double>(), out[1].at<int32_t>(), out[2].at<double>(),
+                                              out[3].at<int32_t>(), out[4].at<double>());
+  };
+  return run_plain(e, c);
+}
+
 // Starting trees: arrays of fixed counts, no per-tree ones -- a tree-sharded
 // handle lets its first shard do the work (every shard holds the whole alignment); neighbour
 // joining needs no alignment and goes to the first shard of any handle.  No retry.

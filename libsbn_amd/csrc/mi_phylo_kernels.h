@@ -299,6 +299,48 @@ struct PlaceFinalizeArgs {
   double* out_lwr;         // [T][Q][E] or nullptr
 };
 void launch_placement_finalize(const PlaceFinalizeArgs& a, hipStream_t s);
+// The SPR neighbourhood scan (kernels_spr.hip): the HBM-streamed walk that keeps
+// the vectors of both directions at every edge with their cumulative rescaling exponents
+// (spr_vectors_hbm_kernel: LikArgs as every member, SprArgs beside it), the regraft walk over
+// every (tree, tile, pruned edge), and the tile sums with the best target per (s, dir) and the best
+// move per tree.  One SprArgs describes a launch of `trees` trees; the workspaces are indexed by
+// the tree of the launch, the outputs by the call's tree (tree0 + ...).  E = 2n-3.
+struct SprArgs {
+  int n, K, P, tiles;
+  int trees, tree0;
+  int radius;       // 0: every move; else moves of distance <= radius
+  int depth_slots;  // messages of a regraft wave's path
+  int waves;        // regraft waves of a launch: each owns a path workspace and takes job after job
+  int ll_tiles, ll_used;
+  const DevModel* models;       // [T]
+  const SchedEntry* sched;      // [T][n-1]
+  const double* mats;           // [T][2n-2][K][16] by node id
+  const double* half;           // [T][2n-2][K][16] P(r_k t_e / 2) by node id
+  const double* weights;        // [P]
+  const int8_t* tip_states;     // [n][P]
+  const double* tip_partials;   // [n][P][4] or nullptr
+  const double* down;           // LikArgs::plv: [trees][n-1][K][tiles*64][4] post-order vectors
+  double* up;                   // [trees][2n-2][K][tiles*64][4] vectors at the top of every edge
+  int32_t* exp_down;            // [trees][n-1][tiles*64] cumulative exponents of `down` (rescaling)
+  int32_t* exp_up;              // [trees][2n-2][tiles*64] ... of `up`
+  double* site;                 // [trees][tiles*64] L_p = site 2^site_exp
+  int32_t* site_exp;            // [trees][tiles*64]
+  double* path;                 // [waves][depth_slots + 1][K][64][4] messages of the current path, the moving part
+  int32_t* path_exp;            // [waves][depth_slots][64] their exponents (rescaling)
+  double* part;                 // [trees][tiles][2E][E] per-tile partial sums of w_p log(L'_p / L_p)
+  const double* ll_part;        // [T][ll_tiles]
+  double* out_ll;               // [T] or nullptr
+  int32_t* out_best_target;     // [T][E][2]
+  double* out_best_delta;       // [T][E][2]
+  int32_t* out_best_move;       // [T][3] or nullptr
+  double* out_delta;            // [T][E][2][E] or nullptr
+};
+void launch_spr_half_lengths(const double* bl_eff, size_t count, double* half_bl, hipStream_t s);
+void launch_spr_vectors_hbm(const LikArgs& a, const SprArgs& w, int count, bool rescale, hipStream_t s);
+const char* spr_kernel_name();
+bool spr_regraft_fits_lds(int n, int depth_slots);  // the tree and the walk's frames in 64 KiB
+void launch_spr_regraft(const SprArgs& a, bool rescale, hipStream_t s);
+void launch_spr_finalize(const SprArgs& a, hipStream_t s);
 // Branch-length optimisation (kernels_branch_opt.hip): the step between two
 // Hessian passes and the packing of the active trees.  "Packed" arrays hold the trees that
 // are still being evaluated, in `map` order (map == nullptr: all trees, in their own order).

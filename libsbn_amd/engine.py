@@ -143,6 +143,21 @@ class AncestralStates:
 
 
 @dataclass
+class SprScan:
+    """What Engine.spr_scan returns, with E = 2n-3 edges (edge e: the branch above node e): the
+    trees' log-likelihoods [T]; per (tree, pruned edge s, direction) the target edge of the
+    largest log-likelihood change best_target [T][E][2] (int32, -1: no move) and that change
+    best_delta [T][E][2] (-inf: no move); best_move [T][3] = (s, direction, f) of the tree's
+    largest change ((-1, -1, -1): none); on request delta [T][E][2][E], the whole table, -inf
+    where (s, direction, f) is no move within the radius."""
+    log_likelihoods: np.ndarray
+    best_target: np.ndarray
+    best_delta: np.ndarray
+    best_move: np.ndarray
+    delta: np.ndarray = None
+
+
+@dataclass
 class Placement:
     """What Engine.placement returns: the trees' log-likelihoods [T], per (tree, query, edge) the
     log-likelihood of the query on the edge's midpoint at the best of the pendant lengths
@@ -196,6 +211,20 @@ def nni_neighbour(taxon_count, parent_ids, branch_lengths, node, which):
     bl = _np(branch_lengths, np.float64).reshape(2 * n - 2)
     out_pid, out_bl = np.empty(2 * n - 3, np.int32), np.empty(2 * n - 2)
     if _capi.load().mi_nni_neighbour(n, _ptr(pid), _ptr(bl), int(node), int(which), _ptr(out_pid),
+                                     _ptr(out_bl)):
+        raise RuntimeError(_capi.last_error())
+    return out_pid, out_bl
+
+
+def spr_neighbour(taxon_count, parent_ids, branch_lengths, s, direction, f):
+    """The tree the SPR move (s, direction, f) of one unrooted tree leads to (mi_spr_neighbour:
+    the trees Engine.spr_scan scores): (parent ids [2n-3], branch lengths [2n-2]) renumbered in
+    the reference's convention.  Host arithmetic only."""
+    n = int(taxon_count)
+    pid = _np(parent_ids, np.int32).reshape(2 * n - 3)
+    bl = _np(branch_lengths, np.float64).reshape(2 * n - 2)
+    out_pid, out_bl = np.empty(2 * n - 3, np.int32), np.empty(2 * n - 2)
+    if _capi.load().mi_spr_neighbour(n, _ptr(pid), _ptr(bl), int(s), int(direction), int(f), _ptr(out_pid),
                                      _ptr(out_bl)):
         raise RuntimeError(_capi.last_error())
     return out_pid, out_bl
@@ -464,6 +493,28 @@ class Engine:
             self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), _ptr(ll), _ptr(delta),
             _ptr(best)))
         return ll, delta, best
+
+    def spr_scan(self, parent_ids, branch_lengths, params=None, rescaling=False, radius=0, table=False):
+        """Log-likelihood change of every subtree-prune-and-regraft move per tree
+        (mi_engine_spr_scan_unrooted; an extension, 4-state engines): move (s, direction, f) cuts
+        edge s (direction 0: clade s moves, 1: the rest moves) and re-attaches the loose part on
+        the midpoint of edge f.  radius 0 scans every move, radius r those at most r nodes from the
+        prune point.  Returns an SprScan (table=True: with the whole table); spr_neighbour builds
+        the tree a move leads to."""
+        n = self.taxon_count
+        E = 2 * n - 3
+        pid = _np(parent_ids, np.int32).reshape(-1, E)
+        T = pid.shape[0]
+        ll, target, best = np.empty(T), np.empty((T, E, 2), np.int32), np.empty((T, E, 2))
+        move = np.empty((T, 3), np.int32)
+        delta = np.empty((T, E, 2, E)) if table else None
+        if T:
+            bl = _np(branch_lengths, np.float64).reshape(T, 2 * n - 2)
+            pr = self._params(params, T)
+            self._check(self._lib.mi_engine_spr_scan_unrooted(
+                self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), int(radius), _ptr(ll), _ptr(target),
+                _ptr(best), _ptr(move), _ptr(delta)))
+        return SprScan(ll, target, best, move, delta)
 
     def ancestral_states(self, parent_ids, branch_lengths, params=None, rescaling=False,
                          map_states=False, categories=False, tips=False):
@@ -845,6 +896,18 @@ class Engine:
         self._check(self._lib.mi_engine_nni_scan_unrooted_device(
             self._h, stream, T, parent_ids, branch_lengths, params, int(rescaling), out_ll,
             out_delta, out_best))
+
+    def spr_scan_device(self, stream, T, parent_ids, branch_lengths, params, out_best_target, out_best_delta,
+                        out_ll=None, out_best_move=None, out_delta=None, rescaling=False, radius=0):
+        """mi_engine_spr_scan_unrooted_device: device pointers, enqueued on `stream` (no allocation
+        after reserve_spr_scan)."""
+        self._check(self._lib.mi_engine_spr_scan_unrooted_device(
+            self._h, stream, T, parent_ids, branch_lengths, params, int(rescaling), int(radius), out_ll,
+            out_best_target, out_best_delta, out_best_move, out_delta))
+
+    def reserve_spr_scan(self, tree_count):
+        """mi_engine_reserve_spr_scan: workspace of an SPR scan (graph capture)."""
+        self._check(self._lib.mi_engine_reserve_spr_scan(self._h, int(tree_count)))
 
     def reserve_nni_scan(self, tree_count):
         """mi_engine_reserve_nni_scan: workspace of an NNI scan (graph capture)."""
