@@ -665,6 +665,85 @@ int32_t mi_engine_nni_search_unrooted(
     double* out_move_gain /* [T][max_moves] or NULL */, int32_t* out_status /* [T] */,
     int32_t* out_branch_opt_status /* [T] or NULL */);
 
+/* Taking SPR moves on the device (an extension): for every tree of the batch
+ * the tree mi_spr_neighbour(n, parent_ids[t], branch_lengths[t], s, dir, f, ...) returns for
+ * moves[t] = (s, dir, f) (what out_best_move of mi_engine_spr_scan_unrooted gives), bit for bit
+ * -- leaves keep their ids, internal nodes in post-order with the children ordered by largest
+ * leaf id, the trifurcating root 2n-3, rooted at the caller's root if that node survives and at
+ * the new attachment node otherwise, every length with its edge (along a reversed path too),
+ * the merged edge the sum of the two doubles, the two halves 0.5 t_f, the entry of 2n-3 copied
+ * -- or a copy of the tree for moves[t] = (-1, -1, -1).  Moves are triples, not packed codes:
+ * (2 s + dir) (2n-3) + f leaves int32 for trees this call still takes.  A triple that
+ * mi_spr_neighbour refuses (s or f out of range, dir neither 0 nor 1, dir = 1 on a leaf edge, f
+ * in the moving part or a name of the merged edge), or a parent-id vector that is no tree in
+ * the reference's form, is a per-tree error ("... (tree t)"); that tree's outputs are a copy of
+ * its inputs and the engine stays usable.  No output may overlap an input.  Any engine serves
+ * (the alignment plays no part); a sharded handle lets its first shard do it. */
+int32_t mi_engine_spr_apply_unrooted(mi_engine* engine, int32_t tree_count,
+                                     const int32_t* parent_ids /* [T][2n-3] */,
+                                     const double* branch_lengths /* [T][2n-2] */,
+                                     const int32_t* moves /* [T][3]: (s, dir, f), or (-1,-1,-1): copy the tree */,
+                                     int32_t* out_parent_ids /* [T][2n-3] */,
+                                     double* out_branch_lengths /* [T][2n-2] */);
+
+/* SPR hill climbing of unrooted trees on the device (an extension): the
+ * definition of mi_engine_nni_search_unrooted with the SPR scan in place of the NNI scan.  Per
+ * tree, a round optimises the branch lengths by the rule of
+ * mi_engine_optimize_branch_lengths_unrooted, unchanged, from the lengths the tree carries
+ * (the caller's at first), and scans the neighbourhood (mi_engine_spr_scan_unrooted, within
+ * `radius`) at the optimised lengths.  If the largest best_delta[s][dir] exceeds min_gain and
+ * the tree has taken fewer than max_moves moves, it takes the scan's best_move (the lowest code
+ * (2 s + dir) (2n-3) + f among equals), logs the triple -- in the ids of the tree AT THAT ROUND
+ * -- and its delta, and goes round again with the lengths the move carries along (the merged
+ * edge, the two halves, t_s).  Otherwise it stops: MI_SPR_SEARCH_LOCAL_OPTIMUM when no delta
+ * exceeds min_gain, MI_SPR_SEARCH_MOVE_LIMIT otherwise.  A three-taxon tree stops after one
+ * optimisation with 0 moves.
+ *   out_parent_ids / out_branch_lengths  topology and lengths of the tree's LAST optimisation
+ *   out_log_likelihoods   [T]       that optimisation's logL (the Hessian call's)
+ *   out_best_delta        [T] or NULL: the largest delta of the scan there (0 when n == 3)
+ *   out_move_count        [T]       moves taken
+ *   out_move_log          [T][max_moves][3] or NULL: the triple of every move taken; unused: -1
+ *   out_move_gain         [T][max_moves] or NULL: its delta; unused entries are 0
+ *   out_status            [T]       MI_SPR_SEARCH_*
+ *   out_branch_opt_status [T] or NULL: MI_BRANCH_OPT_* of that optimisation
+ * min_gain and termination: the neighbour enters the next optimisation at logL + delta (the
+ * scan's delta is formed per pattern, against the same tree's L_p), and the optimiser lets logL
+ * fall by at most 2^-48 |logL| per pass, so with the default 1e-3 -- about five orders above
+ * that at |logL| = 1e4 -- every round's logL is strictly above the last and no topology can
+ * recur.  Below about 1e-8 |logL| that argument no longer holds (such values are accepted):
+ * max_moves is then what ends the loop.
+ * Every round runs on the trees that are still searching (pack_active), routed as the whole
+ * batch would be, so a tree's numbers do not depend on which others are still searching.  The
+ * scan's workspace is large; a batch over MI_PHYLO_PLV_BYTES is cut into
+ * launches by the scan itself.
+ * Returns 0 when it ran, whatever the per-tree statuses; nonzero for bad arguments (max_moves,
+ * min_gain, a negative radius -- refused before any device work --, the optimiser's own checks)
+ * and per-tree input errors.  4-state engines only.  Sharded handles: MI_SHARD_TREES deals the
+ * trees as the other calls do (each shard searches from its block, one after the other; results
+ * in tree order); MI_SHARD_PATTERNS is refused, for the optimiser's reason.
+ * mi_engine_last_call_path is the last Hessian pass's path plus
+ * " spr-search radius=<r> rounds=<r> moves=<total> batches=<trees>x<rounds>,..."; the
+ * evaluation count of mi_engine_last_call_info is the tree evaluations done: the optimiser's
+ * plus one per scan. */
+enum { MI_SPR_SEARCH_LOCAL_OPTIMUM = 0, MI_SPR_SEARCH_MOVE_LIMIT = 1 };
+typedef struct {
+  int32_t max_moves;   /* moves per tree, 0..10000 (default 100); 0: optimise and scan only */
+  int32_t pack_active; /* 1: rounds run on the trees still searching (default); 0: on all T */
+  double min_gain;     /* a move is taken when its delta exceeds this; >= 0, default 1e-3 */
+  int32_t radius;      /* the scan's: 0 (default) every move, >= 1 moves of distance <= radius */
+  int32_t reserved[3]; /* 0 */
+  mi_branch_opt_options branch_opt; /* the optimiser's options for every round (zeros: its defaults) */
+} mi_spr_search_options;
+int32_t mi_engine_spr_search_unrooted(
+    mi_engine* engine, int32_t tree_count, const int32_t* parent_ids /* [T][2n-3] */,
+    const double* start_branch_lengths /* [T][2n-2] */, const double* params, int32_t rescaling,
+    const mi_spr_search_options* options /* NULL: the defaults */,
+    int32_t* out_parent_ids /* [T][2n-3] */, double* out_branch_lengths /* [T][2n-2] */,
+    double* out_log_likelihoods /* [T] */, double* out_best_delta /* [T] or NULL */,
+    int32_t* out_move_count /* [T] */, int32_t* out_move_log /* [T][max_moves][3] or NULL */,
+    double* out_move_gain /* [T][max_moves] or NULL */, int32_t* out_status /* [T] */,
+    int32_t* out_branch_opt_status /* [T] or NULL */);
+
 /* Engine::LogLikelihoods(const RootedTreeCollection&) when with_jacobian != 0
  * (branch lengths x rates, + log-det-Jacobian, fat_beagle.cpp:82-104), or
  * Engine::UnrootedLogLikelihoods(const RootedTreeCollection&) when 0
@@ -845,6 +924,25 @@ int32_t mi_engine_nni_search_unrooted_device(
     double* out_log_likelihoods, double* out_best_delta, int32_t* out_move_count,
     int32_t* out_move_log, double* out_move_gain, int32_t* out_status,
     int32_t* out_branch_opt_status);
+/* The device form of mi_engine_spr_apply_unrooted: asynchronous, allocation-free after its
+ * first call of that size (or mi_engine_reserve_spr_search), capturable in a hipGraph like the
+ * other *_device calls; per-tree errors go to the status word (mi_engine_check_status). */
+int32_t mi_engine_spr_apply_unrooted_device(mi_engine* engine, void* stream, int32_t tree_count,
+                                            const int32_t* parent_ids, const double* branch_lengths,
+                                            const int32_t* moves, int32_t* out_parent_ids,
+                                            double* out_branch_lengths);
+/* The device form of mi_engine_spr_search_unrooted.  Like the optimiser's it SYNCHRONISES
+ * `stream` -- the optimiser at its check points, the search once per round, to read the number
+ * of trees that moved -- so it cannot be captured in a hipGraph; when it returns, every kernel
+ * it needed has been enqueued, and the outputs are complete once the stream is.  It allocates
+ * nothing after mi_engine_reserve_spr_search. */
+int32_t mi_engine_spr_search_unrooted_device(
+    mi_engine* engine, void* stream, int32_t tree_count, const int32_t* parent_ids,
+    const double* start_branch_lengths, const double* params, int32_t rescaling,
+    const mi_spr_search_options* options, int32_t* out_parent_ids, double* out_branch_lengths,
+    double* out_log_likelihoods, double* out_best_delta, int32_t* out_move_count,
+    int32_t* out_move_log, double* out_move_gain, int32_t* out_status,
+    int32_t* out_branch_opt_status);
 
 /* Make sure the workspace for `tree_count` trees exists (so that a following
  * *_device call allocates nothing and can be captured in a hipGraph).  20-state engines: if
@@ -890,6 +988,11 @@ int32_t mi_engine_reserve_branch_opt(mi_engine* engine, int32_t tree_count);
  * included): a *_device call of at most that size then allocates nothing.  4-state engines
  * only. */
 int32_t mi_engine_reserve_nni_search(mi_engine* engine, int32_t tree_count);
+/* The workspace of mi_engine_spr_search_unrooted[_device] and of
+ * mi_engine_spr_apply_unrooted[_device] for `tree_count` trees (the optimiser's and the SPR
+ * scan's included): a *_device call of at most that size then allocates nothing.  4-state
+ * engines only. */
+int32_t mi_engine_reserve_spr_search(mi_engine* engine, int32_t tree_count);
 /* The workspace of mi_engine_rell[_device] for `replicate_count` replicates and `tree_count`
  * trees (the [B][T] product when the caller wants none, the row statistics, the counts): a
  * *_device call of at most that size then allocates nothing.  `pattern_count` needs none. */

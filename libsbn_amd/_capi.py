@@ -33,6 +33,12 @@ class NniSearchOptions(C.Structure):
                 ("reserved", C.c_int32 * 4), ("branch_opt", BranchOptOptions)]
 
 
+class SprSearchOptions(C.Structure):
+    """mi_spr_search_options (include/mi_phylo.h)."""
+    _fields_ = [("max_moves", C.c_int32), ("pack_active", C.c_int32), ("min_gain", C.c_double),
+                ("radius", C.c_int32), ("reserved", C.c_int32 * 3), ("branch_opt", BranchOptOptions)]
+
+
 class DistanceOptions(C.Structure):
     """mi_distance_options (include/mi_phylo.h)."""
     _fields_ = [("max_iterations", C.c_int32), ("reserved0", C.c_int32), ("tolerance", C.c_double),
@@ -128,6 +134,14 @@ SYMBOLS = {
         (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),
     "mi_engine_reserve_spr_scan": (C.c_int32, [_V, C.c_int32]),
     "mi_spr_neighbour": (C.c_int32, [C.c_int32, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V]),
+    "mi_engine_spr_apply_unrooted": (C.c_int32, [_V, C.c_int32, _V, _V, _V, _V, _V]),
+    "mi_engine_spr_apply_unrooted_device": (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, _V, _V]),
+    "mi_engine_spr_search_unrooted":
+        (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_spr_search_unrooted_device":
+        (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V,
+                     _V]),
+    "mi_engine_reserve_spr_search": (C.c_int32, [_V, C.c_int32]),
     "mi_engine_rell": (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V]),
     "mi_engine_rell_device":
         (C.c_int32, [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V]),

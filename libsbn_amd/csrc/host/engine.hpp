@@ -146,6 +146,18 @@ struct NniSearchEnd {
   int32_t branch_opt_status_ = 0;  // MI_BRANCH_OPT_*
 };
 
+// Engine::SprSearch, per tree (an extension, include/mi_phylo.h): as NniSearchEnd, with the
+// triples (s, dir, f) of the moves taken, three entries of moves_ per move
+struct SprSearchEnd {
+  std::vector<int32_t> parent_ids_;
+  std::vector<double> branch_lengths_;
+  double log_likelihood_ = 0., best_delta_ = 0.;
+  std::vector<int32_t> moves_;
+  std::vector<double> gains_;
+  int32_t status_ = 0;             // MI_SPR_SEARCH_*
+  int32_t branch_opt_status_ = 0;  // MI_BRANCH_OPT_*
+};
+
 struct ParamMatrix {  // row-major [rows x cols]
   size_t rows = 0, cols = 0;
   std::vector<double> data;
@@ -600,6 +612,62 @@ class Engine {
       out[i].log_likelihood_ = ll[i];
       out[i].best_delta_ = delta[i];
       out[i].moves_.assign(log.begin() + i * M, log.begin() + i * M + count[i]);
+      out[i].gains_.assign(gain.begin() + i * M, gain.begin() + i * M + count[i]);
+      out[i].status_ = status[i];
+      out[i].branch_opt_status_ = opt_status[i];
+    }
+    return out;
+  }
+
+  // One SPR move per tree on the device (an extension): mi_engine_spr_apply_unrooted.  moves
+  // holds a triple (s, dir, f) per tree as the SPR scan's best move gives it, or (-1, -1, -1): the
+  // tree as it is.  Returns per tree (parent ids [2n-3], branch lengths [2n-2]) in the reference's
+  // numbering.
+  std::vector<std::pair<std::vector<int32_t>, std::vector<double>>> SprApply(
+      const UnrootedTreeCollection& trees, const std::vector<int32_t>& moves) const {
+    const size_t T = trees.size(), N = 2 * site_pattern_.SequenceCount() - 1;
+    if (moves.size() != 3 * T) Failwith("SprApply needs one triple (s, dir, f) per tree.");
+    std::vector<int32_t> parents;
+    std::vector<double> bl;
+    Flatten(trees, ParamMatrix(T, ParameterCount()), false, &parents, &bl);
+    if (trees.empty()) return {};
+    std::vector<int32_t> out_pid(T * (N - 2));
+    std::vector<double> out_bl(T * (N - 1));
+    Check(mi_engine_spr_apply_unrooted(handle_, static_cast<int32_t>(T), parents.data(), bl.data(),
+                                       moves.data(), out_pid.data(), out_bl.data()));
+    std::vector<std::pair<std::vector<int32_t>, std::vector<double>>> out(T);
+    for (size_t t = 0; t < T; t++) {
+      out[t].first.assign(out_pid.begin() + t * (N - 2), out_pid.begin() + (t + 1) * (N - 2));
+      out[t].second.assign(out_bl.begin() + t * (N - 1), out_bl.begin() + (t + 1) * (N - 1));
+    }
+    return out;
+  }
+
+  // SPR hill climbing per tree, started from the trees' own lengths (an extension; 4-state
+  // engines): mi_engine_spr_search_unrooted.  options == nullptr: the defaults of
+  // include/mi_phylo.h.
+  std::vector<SprSearchEnd> SprSearch(const UnrootedTreeCollection& trees, const ParamMatrix& params,
+                                      const bool rescaling,
+                                      const mi_spr_search_options* options = nullptr) const {
+    const size_t T = trees.size(), N = 2 * site_pattern_.SequenceCount() - 1;
+    const size_t M = options ? static_cast<size_t>(std::max(options->max_moves, 0)) : 100;
+    std::vector<int32_t> parents;
+    std::vector<double> bl;
+    Flatten(trees, params, false, &parents, &bl);
+    if (trees.empty()) return {};
+    std::vector<int32_t> pid(T * (N - 2)), count(T), log(3 * T * M + 1), status(T), opt_status(T);
+    std::vector<double> t(T * (N - 1)), ll(T), delta(T), gain(T * M + 1);
+    Check(mi_engine_spr_search_unrooted(
+        handle_, static_cast<int32_t>(T), parents.data(), bl.data(), params.data.data(), rescaling,
+        options, pid.data(), t.data(), ll.data(), delta.data(), count.data(), log.data(), gain.data(),
+        status.data(), opt_status.data()));
+    std::vector<SprSearchEnd> out(T);
+    for (size_t i = 0; i < T; i++) {
+      out[i].parent_ids_.assign(pid.begin() + i * (N - 2), pid.begin() + (i + 1) * (N - 2));
+      out[i].branch_lengths_.assign(t.begin() + i * (N - 1), t.begin() + (i + 1) * (N - 1));
+      out[i].log_likelihood_ = ll[i];
+      out[i].best_delta_ = delta[i];
+      out[i].moves_.assign(log.begin() + 3 * i * M, log.begin() + 3 * (i * M + count[i]));
       out[i].gains_.assign(gain.begin() + i * M, gain.begin() + i * M + count[i]);
       out[i].status_ = status[i];
       out[i].branch_opt_status_ = opt_status[i];

@@ -92,6 +92,7 @@ enum StatusCode : int32_t {
   kBadDistance = 10,
   kBadColumnPattern = 11,
   kBadPendantLength = 12,
+  kBadSprMove = 13,
 };
 
 }  // namespace miphylo

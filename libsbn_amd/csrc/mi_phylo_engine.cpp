@@ -453,7 +453,8 @@ void mi_engine_destroy(mi_engine* e) {
         &e->in_pack, &e->out_pack, &e->opt_ws, &e->nni_apply_ws, &e->nni_search_ws,
         &e->pattern_blank, &e->pattern_ll_out, &e->rell_ws, &e->rell_s, &e->dist_codes, &e->dist_model,
         &e->dist_counts, &e->dist_matrix, &e->nj_ws, &e->place_bl, &e->place_half, &e->place_pend,
-        &e->place_table, &e->spr_bl, &e->spr_half, &e->spr_ws, &e->spr_path})
+        &e->place_table, &e->spr_bl, &e->spr_half, &e->spr_ws, &e->spr_path,
+        &e->spr_apply_ws, &e->spr_search_ws})
     b->release();
   if (e->opt_word) (void)hipHostFree(e->opt_word);
   e->pinned.release();

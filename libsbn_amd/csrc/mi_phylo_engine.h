@@ -8,6 +8,7 @@
 //   mi_phylo_nni.cpp          mi_nni_neighbour, the scan's best move on the host (no device code)
 //   mi_phylo_spr.cpp          mi_spr_neighbour (no device code)
 //   mi_phylo_nni_search.cpp   NNI moves on the device, the NNI hill-climbing search
+//   mi_phylo_spr_search.cpp   SPR moves on the device, the SPR hill-climbing search
 //   mi_phylo_rell.cpp         per-pattern log-likelihoods (device form), RELL re-summation, tree mixtures
 //   mi_phylo_start_trees.cpp  pairwise distances, neighbour joining, starting trees (device forms, reservation)
 //   mi_phylo_host_calls.cpp   what runs a host-pointer call (staging, status, shards), the plain entry points
@@ -136,6 +137,8 @@ inline const char* status_message(int code) {
     case kBadDistance: return "neighbour joining: a distance is not finite";
     case kBadColumnPattern: return "placement: a column_pattern entry is outside [0, pattern_count)";
     case kBadPendantLength: return "placement: a pendant length is not finite or is negative";
+    case kBadSprMove:
+      return "SPR move is neither (-1, -1, -1) nor a triple (s, dir, f) that mi_spr_neighbour takes";
     default: return "unknown device status";
   }
 }
@@ -209,6 +212,9 @@ struct mi_engine {
   Buffer spr_half;  // [T][N-1][K][16] P(r_k t_e / 2) by node id
   Buffer spr_ws;    // per tree of a launch: second arena, exponents, L_p, per-tile partial table: counts against plv_budget
   Buffer spr_path;  // [waves] the regraft waves' paths: messages and their exponents
+  // SPR moves and the SPR search (mi_engine_spr_{apply,search}_unrooted*)
+  Buffer spr_apply_ws;   // the apply kernel's working arrays of trees too large for LDS
+  Buffer spr_search_ws;  // the pair of tree buffers, a round's results, packed inputs, maps, counters
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)
   std::vector<hipEvent_t> prof_events;  // kProfEvents per call: [begin, end, mark 0..4]

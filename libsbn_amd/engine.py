@@ -87,6 +87,24 @@ class NniSearchResult:
 
 
 @dataclass
+class SprSearchResult:
+    """What Engine.spr_search returns: per tree the topology [T][2n-3] and branch lengths
+    [T][2n-2] of its last optimisation, the log-likelihood and the largest SPR delta there, the
+    moves taken, their triples (s, dir, f) [T][max_moves][3] (in the ids of the tree at that
+    round; -1: unused) and deltas [T][max_moves], the status (0 local optimum, 1 move limit) and
+    that optimisation's status."""
+    parent_ids: np.ndarray
+    branch_lengths: np.ndarray
+    log_likelihood: np.ndarray
+    best_delta: np.ndarray
+    move_count: np.ndarray
+    move_log: np.ndarray
+    move_gain: np.ndarray
+    status: np.ndarray
+    branch_opt_status: np.ndarray
+
+
+@dataclass
 class RellResult:
     """What Engine.rell_bootstrap returns: log-likelihoods [T], per-pattern log-likelihoods
     [T][P] (unweighted), replicate log-likelihoods C [B][T], the best tree per replicate [B]
@@ -199,6 +217,14 @@ def _nni_search_options(max_moves, pack_active, min_gain, branch_opt):
             raise RuntimeError(f"unknown branch_opt options: {sorted(unknown)}")
         keys.update(branch_opt)
         o.branch_opt = _branch_opt_options(**keys)
+    return o
+
+
+def _spr_search_options(max_moves, pack_active, min_gain, radius, branch_opt):
+    o = _capi.SprSearchOptions()
+    o.max_moves, o.pack_active, o.min_gain = int(max_moves), int(bool(pack_active)), float(min_gain)
+    o.radius = int(radius)
+    o.branch_opt = _nni_search_options(0, True, 0.0, branch_opt).branch_opt
     return o
 
 
@@ -794,6 +820,50 @@ class Engine:
             _ptr(out.status), _ptr(out.branch_opt_status)))
         return out
 
+    def spr_apply(self, parent_ids, branch_lengths, moves):
+        """Take one SPR move per tree on the device (mi_engine_spr_apply_unrooted): moves [T][3]
+        are triples (s, dir, f) as spr_scan's best_move gives them, or (-1, -1, -1) for a copy.
+        Returns (parent ids [T][2n-3], branch lengths [T][2n-2]): per tree what spr_neighbour
+        returns, bit for bit."""
+        n = self.taxon_count
+        pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
+        T = pid.shape[0]
+        if T == 0:
+            return np.empty((0, 2 * n - 3), np.int32), np.empty((0, 2 * n - 2))
+        bl = _np(branch_lengths, np.float64).reshape(T, 2 * n - 2)
+        mv = _np(moves, np.int32).reshape(T, 3)
+        out_pid, out_bl = np.empty((T, 2 * n - 3), np.int32), np.empty((T, 2 * n - 2))
+        self._check(self._lib.mi_engine_spr_apply_unrooted(
+            self._h, T, _ptr(pid), _ptr(bl), _ptr(mv), _ptr(out_pid), _ptr(out_bl)))
+        return out_pid, out_bl
+
+    def spr_search(self, parent_ids, start_branch_lengths, params=None, rescaling=False,
+                   max_moves=100, pack_active=True, min_gain=1e-3, radius=0, branch_opt=None):
+        """SPR hill climbing per tree on the device (mi_engine_spr_search_unrooted; an extension,
+        4-state engines): optimise the branch lengths, scan the SPR neighbourhood within `radius`
+        (0: every move), take the best move while its delta exceeds min_gain, at most max_moves
+        times.  branch_opt: a dict of optimize_branch_lengths' keyword options for every round.
+        Returns an SprSearchResult."""
+        n = self.taxon_count
+        pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
+        T = pid.shape[0]
+        opts = _spr_search_options(max_moves, pack_active, min_gain, radius, branch_opt)
+        M = max(int(max_moves), 0)
+        out = SprSearchResult(np.empty((T, 2 * n - 3), np.int32), np.empty((T, 2 * n - 2)),
+                              np.empty(T), np.empty(T), np.empty(T, np.int32),
+                              np.empty((T, M, 3), np.int32), np.empty((T, M)), np.empty(T, np.int32),
+                              np.empty(T, np.int32))
+        if T == 0:
+            return out
+        bl = _np(start_branch_lengths, np.float64).reshape(T, 2 * n - 2)
+        pr = self._params(params, T)
+        self._check(self._lib.mi_engine_spr_search_unrooted(
+            self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), C.addressof(opts),
+            _ptr(out.parent_ids), _ptr(out.branch_lengths), _ptr(out.log_likelihood),
+            _ptr(out.best_delta), _ptr(out.move_count), _ptr(out.move_log), _ptr(out.move_gain),
+            _ptr(out.status), _ptr(out.branch_opt_status)))
+        return out
+
     def _phylo_gradients(self, ll, blocks, site, subst):
         """Per-tree PhyloGradient objects over row views of the freshly allocated result
         arrays of one call (no per-tree copies: 1000 trees cost ~0.3 ms instead of ~1.1)."""
@@ -985,6 +1055,30 @@ class Engine:
     def reserve_nni_search(self, tree_count):
         """mi_engine_reserve_nni_search: workspace of a search or apply call of that size."""
         self._check(self._lib.mi_engine_reserve_nni_search(self._h, int(tree_count)))
+
+    def spr_apply_device(self, stream, T, parent_ids, branch_lengths, moves, out_parent_ids,
+                         out_branch_lengths):
+        """mi_engine_spr_apply_unrooted_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_spr_apply_unrooted_device(
+            self._h, stream, T, parent_ids, branch_lengths, moves, out_parent_ids,
+            out_branch_lengths))
+
+    def spr_search_device(self, stream, T, parent_ids, start_branch_lengths, params,
+                          out_parent_ids, out_branch_lengths, out_ll, out_move_count, out_status,
+                          out_best_delta=None, out_move_log=None, out_move_gain=None,
+                          out_branch_opt_status=None, rescaling=False, max_moves=100,
+                          pack_active=True, min_gain=1e-3, radius=0, branch_opt=None):
+        """mi_engine_spr_search_unrooted_device: device pointers.  The call synchronises `stream`
+        every round, so it cannot be captured in a graph."""
+        opts = _spr_search_options(max_moves, pack_active, min_gain, radius, branch_opt)
+        self._check(self._lib.mi_engine_spr_search_unrooted_device(
+            self._h, stream, T, parent_ids, start_branch_lengths, params, int(rescaling),
+            C.addressof(opts), out_parent_ids, out_branch_lengths, out_ll, out_best_delta,
+            out_move_count, out_move_log, out_move_gain, out_status, out_branch_opt_status))
+
+    def reserve_spr_search(self, tree_count):
+        """mi_engine_reserve_spr_search: workspace of a search or apply call of that size."""
+        self._check(self._lib.mi_engine_reserve_spr_search(self._h, int(tree_count)))
 
     def pattern_log_likelihoods_device(self, stream, T, parent_ids, branch_lengths, params,
                                        out_pattern_ll, out_ll=None, rescaling=False):

@@ -1,0 +1,473 @@
+"""The SPR hill-climbing search (mi_engine_spr_search_unrooted, Engine.spr_search): optimise,
+scan, move, per tree, on the device.  Against the independent CPU reference of
+tests/spr_search_ref.py on its committed cases (whose decisions tests/test_spr_search_ref.py
+shows to be clear of the optimiser's tolerance), and against a Python loop over the engine's own
+public calls."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import branch_opt_ref as R
+import nni_search_ref as NS
+import spr_ref as SR
+import spr_search_ref as S
+import tree_utils as TU
+
+pytestmark = pytest.mark.gpu
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIELDS = ("parent_ids", "branch_lengths", "log_likelihood", "best_delta", "move_count", "move_log", "move_gain",
+          "status", "branch_opt_status")
+FIVE_MOVES = S.CASES[4]  # its last tree takes five moves (tests/test_spr_search_ref.py prints them)
+SMALL = S.CASES[2]       # n = 8, one category: 0, 1 and 2 moves
+
+
+def _engine(subst, site, tips, w, **kw):
+    import libsbn_amd as L
+    return L.Engine(L.PhyloModelSpecification(subst, site, "strict"), tips, w, device=0, **kw)
+
+
+def _case_engine(case, **kw):
+    spec, tips, w, pids, start, pr = case.build()
+    return _engine(case.subst, case.site, tips, w, **kw)
+
+
+def _log(res, t):
+    return [tuple(m) for m in res.move_log[t, :res.move_count[t]].tolist()]
+
+
+def _python_loop(eng, pids, start, pr, rescaling=False, max_moves=100, min_gain=S.MIN_GAIN, radius=0):
+    """optimize_branch_lengths -> spr_scan -> spr_neighbour, always on all T trees (so that the
+    route is the search's) with stopped trees frozen at their optimum: (move logs, parent ids,
+    lengths, logL, best delta, status)."""
+    import libsbn_amd as L
+    n = eng.taxon_count
+    T = len(pids)
+    pid, bl = np.array(pids, np.int32), np.array(start, float)
+    logs = [[] for _ in range(T)]
+    searching = np.ones(T, bool)
+    out_pid, out_bl = pid.copy(), bl.copy()
+    out_ll, out_delta, out_status = np.zeros(T), np.zeros(T), np.zeros(T, np.int32)
+    while searching.any():
+        opt = eng.optimize_branch_lengths(pid, bl, pr, rescaling=rescaling)
+        scan = eng.spr_scan(pid, opt.branch_lengths, pr, rescaling=rescaling, radius=radius)
+        bl = opt.branch_lengths.copy()  # (a tree that has stopped is carried along at its optimum)
+        for t in np.flatnonzero(searching):
+            s, d, f = (int(x) for x in scan.best_move[t])
+            gain = scan.best_delta[t, s, d] if s >= 0 else 0.0
+            if gain > min_gain and len(logs[t]) < max_moves:
+                logs[t].append((s, d, f))
+                pid[t], bl[t] = L.spr_neighbour(n, pid[t], opt.branch_lengths[t], s, d, f)
+                continue
+            searching[t] = False
+            out_pid[t], out_bl[t], out_ll[t], out_delta[t] = pid[t], opt.branch_lengths[t], opt.log_likelihood[t], gain
+            out_status[t] = S.MOVE_LIMIT if gain > min_gain else S.LOCAL_OPTIMUM
+    return logs, out_pid, out_bl, out_ll, out_delta, out_status
+
+
+def _same_numbers(a_ll, a_bl, b_ll, b_bl):
+    """What tests/test_branch_opt_gpu.py allows between packed and unpacked runs."""
+    assert np.all(np.abs(a_ll - b_ll) <= 1e-9 * np.abs(b_ll)), (a_ll, b_ll)
+    for x, y in zip(a_bl, b_bl):
+        assert R.relative_length_error(x[:-1], y[:-1]) <= 1e-5
+        assert x[-1] == y[-1]
+
+
+def _matches_python_loop(eng, res, pids, start, pr, **kw):
+    logs, pid, bl, ll, delta, status = _python_loop(eng, pids, start, pr, **kw)
+    for t in range(len(pids)):
+        assert _log(res, t) == logs[t], (t, _log(res, t), logs[t])
+        assert np.all(res.move_log[t, res.move_count[t]:] == -1) and np.all(res.move_gain[t, res.move_count[t]:] == 0)
+        assert np.all(res.move_gain[t, :res.move_count[t]] > kw.get("min_gain", S.MIN_GAIN))
+    assert np.array_equal(res.parent_ids, pid)
+    assert np.array_equal(res.status, status)
+    _same_numbers(res.log_likelihood, res.branch_lengths, ll, bl)
+    return logs
+
+
+def _path(eng, radius=0):
+    p = eng.last_call_path()
+    assert " hess" in p and f" spr-search radius={radius} rounds=" in p and " moves=" in p and " batches=" in p, p
+    assert " opt iters=" not in p, p
+    return p
+
+
+# ---- 1. against the CPU reference ----
+
+def _gain_allowance(case, w):
+    """The engine's lengths may differ from the reference's by 1e-5, relatively (what
+    tests/test_branch_opt_gpu.py allows); a neighbour is not at ITS optimum, so its logL moves in
+    the first order: by at most 1e-5 |t dlogL'/dt| summed over the edges.  Per site and edge
+    |d log L_p / d log t| stays below about 1 while rate x length does (L_p = a + b exp(-mu t) with
+    a, a + b >= 0), so the sum is bounded by 1e-5 x sites x edges."""
+    return 1e-5 * float(np.sum(w)) * (2 * case.n - 3)
+
+
+@pytest.mark.parametrize("case", S.CASES, ids=repr)
+def test_matches_the_cpu_reference(case):
+    spec, tips, w, pids, start, pr = case.build()
+    eng = _case_engine(case)
+    res = eng.spr_search(pids, start, pr, radius=case.radius)
+    path = _path(eng, case.radius)
+    refs = case.reference()
+    print(path)
+    for t, ref in enumerate(refs):
+        err = R.relative_length_error(res.branch_lengths[t, :-1], ref.branch_lengths[:-1])
+        gains = res.move_gain[t, :res.move_count[t]]
+        print(f"{case} tree {t}: moves {_log(res, t)} reference {ref.moves} logL {res.log_likelihood[t]!r} "
+              f"- reference {res.log_likelihood[t] - ref.log_likelihood:.2e} lengths {err:.2e} "
+              f"gains - reference {(gains - np.array(ref.gains)).tolist() if len(gains) == len(ref.gains) else '?'}")
+        assert _log(res, t) == ref.moves and res.move_count[t] == len(ref.moves)
+        assert np.array_equal(res.parent_ids[t], ref.parent_ids)
+        assert res.status[t] == ref.status
+        assert abs(res.log_likelihood[t] - ref.log_likelihood) <= SR.REL * abs(ref.log_likelihood)
+        assert err <= 1e-5
+        assert np.all(np.abs(gains - np.array(ref.gains)) <= _gain_allowance(case, w))
+        assert abs(res.best_delta[t] - ref.best_delta) <= _gain_allowance(case, w)
+        # logL strictly rises over the move log: every round enters at logL + gain, the gains are positive
+        assert np.all(gains > S.MIN_GAIN)
+        lls = [d.log_likelihood for d in ref.decisions]
+        assert all(y > x for x, y in zip(lls, lls[1:])) and res.log_likelihood[t] >= lls[0] - SR.REL * abs(lls[0])
+        if ref.moves:
+            assert res.log_likelihood[t] > lls[0] + float(np.sum(gains)) - SR.REL * abs(lls[0]) * (len(gains) + 1)
+        if case.radius:
+            cur = pids[t]
+            for m in _log(res, t):  # a radius-limited search takes only moves of that distance
+                assert SR.targets(case.n, cur, m[0], m[1])[m[2]] <= case.radius
+                cur = SR.neighbour(case.n, cur, np.ones(2 * case.n - 2), *m)[0]
+    assert f"moves={sum(len(r.moves) for r in refs)} " in path, path
+    print("optimiser status", res.branch_opt_status.tolist())
+
+
+# ---- 2. against a Python loop over the engine's own calls ----
+
+@pytest.mark.parametrize("case", [S.CASES[2], S.CASES[3], S.CASES[4], S.CASES[5]], ids=repr)
+def test_matches_a_python_loop_over_the_public_calls(case):
+    spec, tips, w, pids, start, pr = case.build()
+    eng = _case_engine(case)
+    res = eng.spr_search(pids, start, pr, radius=case.radius)
+    _matches_python_loop(eng, res, pids, start, pr, radius=case.radius)
+
+
+# ---- 3. NNI hill climbing ends below ----
+
+def test_nni_search_ends_below_the_spr_search_from_the_same_start():
+    case = S.NNI_BELOW_SPR
+    spec, tips, w, pids, start, pr = case.build()
+    eng = _case_engine(case)
+    spr_ref = case.reference()[0]
+    nni_ref = NS.reference_search(spec, tips, w, pids[0], start[0], pr[0])
+    nni = eng.nni_search(pids, start, pr)
+    spr = eng.spr_search(pids, start, pr)
+    print(f"NNI {nni.move_log[0, :nni.move_count[0]].tolist()} logL {nni.log_likelihood[0]!r} (reference "
+          f"{nni_ref.log_likelihood!r}); SPR {_log(spr, 0)} logL {spr.log_likelihood[0]!r} (reference {spr_ref.log_likelihood!r})")
+    assert nni.status[0] == NS.LOCAL_OPTIMUM and spr.status[0] == S.LOCAL_OPTIMUM
+    assert _log(spr, 0) == spr_ref.moves and nni.move_log[0, :nni.move_count[0]].tolist() == nni_ref.moves
+    assert abs(spr.log_likelihood[0] - spr_ref.log_likelihood) <= SR.REL * abs(spr_ref.log_likelihood)
+    assert abs(nni.log_likelihood[0] - nni_ref.log_likelihood) <= 1e-7  # (what tests/test_nni_search_gpu.py allows)
+    assert nni_ref.log_likelihood < spr_ref.log_likelihood - S.MIN_GAIN
+    assert nni.log_likelihood[0] < spr.log_likelihood[0] - S.MIN_GAIN
+
+
+# ---- 4. max_moves = 0: optimise and scan only ----
+
+def test_no_moves_allowed_is_the_optimiser_and_the_scan():
+    case = FIVE_MOVES
+    spec, tips, w, pids, start, pr = case.build()
+    eng = _case_engine(case)
+    res = eng.spr_search(pids, start, pr, max_moves=0)
+    assert " rounds=1 moves=0 " in _path(eng)
+    opt = eng.optimize_branch_lengths(pids, start, pr)
+    scan = eng.spr_scan(pids, opt.branch_lengths, pr)
+    top = scan.best_delta.reshape(len(pids), -1).max(axis=1)
+    assert np.array_equal(res.branch_lengths, opt.branch_lengths)
+    assert np.array_equal(res.log_likelihood, opt.log_likelihood)
+    assert np.array_equal(res.branch_opt_status, opt.status)
+    assert np.array_equal(res.best_delta, top)
+    assert np.array_equal(res.parent_ids, pids)
+    assert np.array_equal(res.status == S.MOVE_LIMIT, top > S.MIN_GAIN) and np.all(res.status <= 1)
+    assert res.status[-1] == S.MOVE_LIMIT  # (the tree that would take five moves)
+    assert np.all(res.move_count == 0) and res.move_log.shape == (len(pids), 0, 3)
+
+
+# ---- 5. the move limit ----
+
+def test_one_move_of_five():
+    case = FIVE_MOVES
+    spec, tips, w, pids, start, pr = case.build()
+    t = len(pids) - 1
+    assert len(case.reference()[t].moves) >= 3
+    eng = _case_engine(case)
+    res = eng.spr_search(pids, start, pr, max_moves=1)
+    opt = eng.optimize_branch_lengths(pids, start, pr)
+    assert res.status[t] == S.MOVE_LIMIT and res.move_count[t] == 1
+    assert _log(res, t) == case.reference()[t].moves[:1] and res.move_log.shape == (len(pids), 1, 3)
+    ll = res.log_likelihood[t]
+    assert ll >= opt.log_likelihood[t] + S.MIN_GAIN - 2.0 ** -40 * abs(ll)
+    assert res.move_gain[t, 0] > S.MIN_GAIN
+
+
+# ---- 6. restart ----
+
+def test_restart_from_a_result_changes_nothing():
+    case = FIVE_MOVES
+    spec, tips, w, pids, start, pr = case.build()
+    eng = _case_engine(case)
+    first = eng.spr_search(pids, start, pr)
+    again = eng.spr_search(first.parent_ids, first.branch_lengths, pr)
+    assert np.all(again.move_count == 0) and np.all(again.status == S.LOCAL_OPTIMUM)
+    assert np.array_equal(again.parent_ids, first.parent_ids)
+    assert np.array_equal(again.branch_lengths, first.branch_lengths)
+
+
+# ---- 7. packing of the trees that are still searching; alone and in a batch ----
+
+def _pool(case, T, steps, seed):
+    """T starts `steps` random SPR moves from the tree the case's alignment evolved down."""
+    n = case.n
+    rng = np.random.default_rng(seed)
+    true_pid = TU.random_topology(n, np.random.default_rng(case.seed))
+    start = np.full((T, 2 * n - 2), 0.1)
+    start[:, -1] = 0.0
+    pool = np.stack([S.random_spr_walk(n, true_pid, start[0], steps, rng)[0] for _ in range(T)])
+    return pool, start, np.repeat(case.build()[5][:1], T, axis=0)
+
+
+def test_packing_changes_the_cost_not_the_results():
+    case = SMALL
+    n, T = case.n, 32
+    pool, start, pr = _pool(case, T, 3, 171)
+    eng = _case_engine(case)
+    first = eng.spr_search(pool, start, pr)
+    movers = np.flatnonzero(first.move_count >= 1)
+    assert len(movers) >= 8, first.move_count
+    fresh = np.arange(2, 32, 4)  # 8 trees that will move, spread over a batch of results
+    pids, bls = first.parent_ids.copy(), first.branch_lengths.copy()
+    pids[fresh], bls[fresh] = pool[movers[:8]], start[movers[:8]]
+    packed = eng.spr_search(pids, bls, pr)
+    path, evals = _path(eng), eng.last_call_info()[1]
+    assert "batches=32x1,8x" in path, path
+    plain = eng.spr_search(pids, bls, pr, pack_active=False)
+    plain_path, plain_evals = _path(eng), eng.last_call_info()[1]
+    print(path, "|", plain_path, "| evaluations", evals, plain_evals)
+    assert "batches=32x" in plain_path and "8x" not in plain_path and plain_path.endswith(" pack=off")
+    others = np.setdiff1d(np.arange(T), fresh)
+    assert np.all(packed.move_count[others] == 0) and np.all(packed.move_count[fresh] >= 1)
+    assert np.array_equal(packed.move_log, plain.move_log) and np.array_equal(packed.move_count, plain.move_count)
+    assert np.array_equal(packed.parent_ids, plain.parent_ids) and np.array_equal(packed.status, plain.status)
+    _same_numbers(packed.log_likelihood, packed.branch_lengths, plain.log_likelihood, plain.branch_lengths)
+    assert evals < plain_evals
+
+
+def test_a_tree_alone_and_in_a_batch_gives_the_same_bits():
+    """(In a batch of the same route: both batches are far below any threshold between kernels.)"""
+    case = SMALL
+    spec, tips, w, pids, start, pr = case.build()
+    eng = _case_engine(case)
+    batch = eng.spr_search(pids, start, pr)
+    t = len(pids) - 1
+    alone = eng.spr_search(pids[t:], start[t:], pr[t:])
+    for name in FIELDS:
+        assert np.array_equal(getattr(alone, name)[0], getattr(batch, name)[t]), name
+
+
+# ---- 8. other paths, each against the Python loop ----
+
+def test_rescaling():
+    case = S.CASES[3]
+    spec, tips, w, pids, start, pr = case.build()
+    eng = _case_engine(case)
+    res = eng.spr_search(pids, start, pr, rescaling=True, radius=case.radius)
+    assert " rescaled " in _path(eng, case.radius)
+    _matches_python_loop(eng, res, pids, start, pr, rescaling=True, radius=case.radius)
+
+
+def test_real_valued_tip_partials():
+    case = S.CASES[3]
+    spec, tips, w, pids, start, pr = case.build()
+    rng = np.random.default_rng(172)
+    n, P = tips.shape
+    parts = np.zeros((n, P, 4))
+    parts[np.arange(n)[:, None], np.arange(P)[None, :], tips] = 1.0
+    parts[0] = np.where(parts[0] > 0, 1.0, rng.uniform(0.05, 0.4, size=parts[0].shape))
+    eng = _engine(case.subst, case.site, None, w, use_tip_states=False, tip_partials=parts)
+    res = eng.spr_search(pids, start, pr)
+    assert _path(eng).startswith("gradient_hbm_hess_kernel ")
+    _matches_python_loop(eng, res, pids, start, pr)
+
+
+def test_six_categories_run_the_hbm_hessian_kernel():
+    case = S.Case("n8-jc-k6", 8, 200, "JC69", "weibull+6", 307, (1, 2, 3))
+    spec, tips, w, pids, start, pr = case.build()
+    eng = _case_engine(case)
+    res = eng.spr_search(pids, start, pr)
+    path = _path(eng)
+    assert path.startswith("gradient_hbm_hess_kernel ") and " K=6" in path, path
+    _matches_python_loop(eng, res, pids, start, pr)
+
+
+def test_arena_store_36_taxa(monkeypatch):
+    case = S.Case("n36-jc-k4", 36, 1812, "JC69", "weibull+4", 310, (1, 2))
+    spec, tips, w, pids, start, pr = case.build()
+    monkeypatch.setenv("MI_PHYLO_GRADIENT_STORE", "arena")
+    eng = _case_engine(case)
+    res = eng.spr_search(pids, start, pr, max_moves=2)
+    assert " store=arena " in _path(eng)
+    logs = _matches_python_loop(eng, res, pids, start, pr, max_moves=2)
+    print("moves", logs)
+    assert 1 <= max(len(m) for m in logs) <= 2
+
+
+# ---- 9. handles and refusals ----
+
+def test_tree_sharded_handle_gives_the_single_engines_results():
+    case = SMALL
+    spec, tips, w, pids, start, pr = case.build()
+    pids, start, pr = np.tile(pids, (3, 1)), np.tile(start, (3, 1)), np.tile(pr, (3, 1))
+    ref = _case_engine(case).spr_search(pids, start, pr)
+    trees = _case_engine(case, shard_devices=[0, 0])
+    got = trees.spr_search(pids, start, pr)
+    _path(trees)
+    for name in FIELDS:
+        assert np.array_equal(getattr(ref, name), getattr(got, name)), name
+
+
+def test_refusals():
+    import aa_utils as A
+    case = SMALL
+    spec, tips, w, pids, start, pr = case.build()
+    pats = _case_engine(case, shard_devices=[0, 0], shard_mode="patterns")
+    with pytest.raises(RuntimeError, match="pattern-sharded"):
+        pats.spr_search(pids, start, pr)
+    with pytest.raises(RuntimeError, match="pattern-sharded"):
+        pats.reserve_spr_search(3)
+    eng = _case_engine(case)
+    for bad in (-1, 10001):
+        with pytest.raises(RuntimeError, match="max_moves"):
+            eng.spr_search(pids, start, pr, max_moves=bad)
+    for bad in (-1e-3, float("nan")):
+        with pytest.raises(RuntimeError, match="min_gain"):
+            eng.spr_search(pids, start, pr, min_gain=bad)
+    with pytest.raises(RuntimeError, match="radius"):
+        eng.spr_search(pids, start, pr, radius=-1)
+    with pytest.raises(RuntimeError, match="max_iterations"):
+        eng.spr_search(pids, start, pr, branch_opt=dict(max_iterations=1001))
+    broken = pids.copy()
+    broken[1, 5] = 2  # a tip as a parent: not the reference's id form
+    with pytest.raises(RuntimeError, match=r"\(tree 1\)"):
+        eng.spr_search(broken, start, pr)
+    # (the engine is still usable, and the error does not stick)
+    assert np.all(eng.spr_search(pids, start, pr).status == S.LOCAL_OPTIMUM)
+    rng = np.random.default_rng(173)
+    atips, aw = A.random_aa_alignment(6, 20, rng)
+    apids, abls = TU.random_trees(6, 2, rng)
+    aa = _engine("WAG", "constant", atips, aw)
+    with pytest.raises(RuntimeError, match="4-state only"):
+        aa.spr_search(apids, abls, None)
+    with pytest.raises(RuntimeError, match="4-state only"):
+        aa.reserve_spr_search(2)
+
+
+def test_three_taxa_stop_after_one_optimisation():
+    rng = np.random.default_rng(174)
+    pids, bls = TU.random_trees(3, 2, rng)
+    tips, w = TU.random_alignment(3, 50, rng)
+    eng = _engine("JC69", "constant", tips, w)
+    res = eng.spr_search(pids, bls, None)
+    assert " rounds=1 moves=0 " in _path(eng)
+    opt = eng.optimize_branch_lengths(pids, bls, None)
+    assert np.all(res.move_count == 0) and np.all(res.status == S.LOCAL_OPTIMUM) and np.all(res.best_delta == 0)
+    assert np.array_equal(res.branch_lengths, opt.branch_lengths) and np.array_equal(res.parent_ids, pids)
+
+
+# ---- 10. the reserved device-pointer call ----
+
+def test_reserved_device_call_allocates_nothing_and_matches_the_host_call():
+    import torch
+    case = SMALL
+    spec, tips, w, pids, start, pr = case.build()
+    reps = 8
+    pids, start, pr = np.tile(pids, (reps, 1)), np.tile(start, (reps, 1)), np.tile(pr, (reps, 1))
+    T, n, M = len(pids), case.n, 6
+    other = _case_engine(case)
+    ref = other.spr_search(pids, start, pr, max_moves=M)
+    # (one tree in three stops at once, another after its one move: the call also packs)
+    assert f"batches={T}x2,{T // 3}x" in _path(other)
+    dev = torch.device("cuda", 0)
+    d_pid = torch.from_numpy(np.ascontiguousarray(pids, np.int32)).to(dev)
+    d_bl = torch.from_numpy(np.ascontiguousarray(start)).to(dev)
+    d_pr = torch.from_numpy(np.ascontiguousarray(pr)).to(dev) if pr.shape[1] else torch.zeros(1, dtype=torch.float64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    outs = dict(parent_ids=torch.zeros((T, 2 * n - 3), **i32), branch_lengths=torch.zeros((T, 2 * n - 2), **f64),
+                log_likelihood=torch.zeros(T, **f64), best_delta=torch.zeros(T, **f64),
+                move_count=torch.zeros(T, **i32), move_log=torch.zeros((T, M, 3), **i32),
+                move_gain=torch.zeros((T, M), **f64), status=torch.full((T,), 7, **i32),
+                branch_opt_status=torch.full((T,), 7, **i32))
+    stream = torch.cuda.Stream()
+
+    def call(engine):
+        o = {k: v.data_ptr() for k, v in outs.items()}
+        engine.spr_search_device(stream.cuda_stream, T, d_pid.data_ptr(), d_bl.data_ptr(), d_pr.data_ptr(),
+                                 o["parent_ids"], o["branch_lengths"], o["log_likelihood"], o["move_count"],
+                                 o["status"], out_best_delta=o["best_delta"], out_move_log=o["move_log"],
+                                 out_move_gain=o["move_gain"], out_branch_opt_status=o["branch_opt_status"],
+                                 max_moves=M)
+        torch.cuda.synchronize()
+
+    # (the same call of ANOTHER engine first, on the same stream: tests/test_branch_opt_gpu.py)
+    call(other)
+    for v in outs.values():
+        v.fill_(7)
+    eng = _case_engine(case)
+    eng.reserve_spr_search(T)
+    torch.cuda.synchronize()
+    free_before = torch.cuda.mem_get_info(0)[0]
+    call(eng)
+    free_after = torch.cuda.mem_get_info(0)[0]
+    _path(eng)
+    eng.check_status()
+    assert free_after == free_before, (free_before, free_after)
+    for name in FIELDS:
+        assert np.array_equal(outs[name].cpu().numpy(), getattr(ref, name)), name
+    host = eng.spr_search(pids, start, pr, max_moves=M)
+    for name in FIELDS:
+        assert np.array_equal(getattr(host, name), getattr(ref, name)), name
+
+
+# ---- 11. the C++ adapter ----
+
+def test_cpp_adapter_gives_the_python_result(tmp_path):
+    import libsbn_amd as L
+    exe = tmp_path / "spr_search_example"
+    lib = os.path.join(REPO, "libsbn_amd")
+    data = os.path.join(REPO, "tests/golden/data")
+    subprocess.run(["g++", "-std=c++17", "-O1", os.path.join(REPO, "tests/cpp/spr_search_example.cpp"),
+                    "-L" + lib, "-lmi_phylo", "-lmi_phylo_host", "-Wl,-rpath," + lib, "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe), data], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.endswith("done\n"), out.stdout + out.stderr
+    inst = L.unrooted_instance("ds1")
+    inst.read_nexus_file(os.path.join(data, "DS1.subsampled_10.t"))
+    inst.read_fasta_file(os.path.join(data, "DS1.fasta"))
+    inst.prepare_for_phylo_likelihood(L.PhyloModelSpecification("JC69", "constant", "strict"), 1)
+    pids, bls = inst._trees()
+    eng = inst.get_engine()
+    res = eng.spr_search(pids, bls, inst.get_phylo_model_params(), max_moves=2, radius=3)
+    first = np.where((res.move_count > 0)[:, None], res.move_log[:, 0], -1)
+    moved, _ = eng.spr_apply(pids, bls, first)
+    lines = out.stdout.splitlines()
+    assert len(lines) == 2 * len(pids) + 1
+    for t in range(len(pids)):
+        want = (f"tree {t} status {res.status[t]} opt {res.branch_opt_status[t]} ll {float(res.log_likelihood[t]).hex()} "
+                f"delta {float(res.best_delta[t]).hex()} moves" + "".join(f" {x}" for m in _log(res, t) for x in m) +
+                " parents" + "".join(f" {p}" for p in res.parent_ids[t]))
+        got = lines[t].split()
+        # (C's %a and Python's hex() write the same number differently: compare the values)
+        exp = want.split()
+        for i in (got.index("ll") + 1, got.index("delta") + 1):
+            got[i], exp[i] = float.fromhex(got[i]), float.fromhex(exp[i])
+        assert got == exp, (t, lines[t], want)
+        assert lines[len(pids) + t] == (f"applied {t} move {first[t][0]} {first[t][1]} {first[t][2]} parents" +
+                                        "".join(f" {p}" for p in moved[t]))
+    print("moves per tree:", res.move_count.tolist())
