@@ -20,7 +20,8 @@
 //     column) exactly as the second generation stages its mask bytes;
 //   * a visit's operands are requested a visit AHEAD (into the other of two register sets):
 //     the gathers need the NEXT visit's tip words and shape, so tip words are read two visits
-//     ahead (right after the gathers are issued) and shapes three.
+//     ahead (right after the gathers are issued) and shapes two (post-order: loaded at a
+//     visit's top, delivered behind its requests) or three (pre-order: at a visit's end).
 // Every other product, edge sum and reduction is the second generation's, in the same order;
 // a looked-up product is the very number the matrix instruction forms (one term; a gap's row
 // sum is added in index order by the table builder as by the instruction): results are
@@ -458,6 +459,21 @@ __device__ __forceinline__ void walk_lut_body(const LikArgs& a, double* wlds, co
   using Pre = std::true_type;
 #ifdef W3_STAMPS
   long long stamp_fetch = 0, stamp_visits = 0;
+  // Where the lgkmcnt time goes (never the product; s_memtime returns through lgkmcnt itself, so
+  // every interval below holds one round trip of the clock read: stamp_null measures that alone):
+  //   stamp_lds / stamp_lds_n: the stored vectors a visit reads first -- post-order: every stored
+  //     child and grandchild; pre-order: the node's own vector q -- from the ds_read's issue to its
+  //     data, waited for at once;
+  //   stamp_land: post-order -- the scalar loads of a visit's top, waited for behind its operand
+  //     requests (what of their round trip the request burst does not cover);
+  //   stamp_smem (-DW3_STAMPS=2): every visit's scalar loads waited for right where they are
+  //     issued (post-order: the visit's top, pre-order: its end) -- their whole round trip.
+  long long stamp_lds = 0, stamp_lds_n = 0, stamp_land = 0, stamp_smem = 0, stamp_null = 0;
+  auto stamped_lgkm_wait = [&](long long& acc) {
+    const long long c0 = __builtin_amdgcn_s_memtime();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    acc += __builtin_amdgcn_s_memtime() - c0;
+  };
 #endif
   auto fetch = [&](auto pre_tag, int m, int sh, const Tw& tw, auto& o0, auto& o1) {
 #ifdef W3_STAMPS
@@ -499,10 +515,30 @@ __device__ __forceinline__ void walk_lut_body(const LikArgs& a, double* wlds, co
     for (int i = 0; i < n; i++) asm volatile("" : "+v"(o1.x[i]));
   };
 
+  auto stamp_scalars_issued = [&]() {
+#if defined(W3_STAMPS) && W3_STAMPS >= 2
+    stamped_lgkm_wait(stamp_smem);
+#endif
+  };
+  // Post-order: a visit takes delivery of the scalars it loaded at its top BEHIND its operand
+  // requests: the compiler waits for scalar data where it is first used, and this is that use.
+  auto land = [&](Slots& x, int& shape) {
+#ifdef W3_STAMPS
+    stamped_lgkm_wait(stamp_land);
+#endif
+    asm volatile("" : "+s"(x.q), "+s"(x.c[0]), "+s"(x.c[1]), "+s"(x.g[0]), "+s"(x.g[1]), "+s"(x.g[2]), "+s"(x.g[3]), "+s"(shape));
+    if constexpr (ARENA) asm volatile("" : "+s"(x.dst));
+  };
+  // ... and of its tip words AHEAD of those scalar loads: the compiler's wait for the LDS data
+  // stands here (the visit index passes through the same asm, so that the loads, whose addresses
+  // are formed from it, cannot be moved above it).
+  auto take_tw = [&](Tw& t, int& idx) {
+    if constexpr (COMPACT) asm volatile("" : "+v"(t.w[0]), "+v"(t.w[1]), "+v"(t.w[2]), "+s"(idx));
+    else asm volatile("" : "+v"(t.w[0]), "+v"(t.w[1]), "+v"(t.w[2]), "+v"(t.w[3]), "+v"(t.w[4]), "+v"(t.w[5]), "+s"(idx));
+  };
   const int M1 = M - 1;  // the root's macro is the last one; visits 0 .. M1 - 1 are stored nodes
   // the first visits' scalars are on their way while the tip codes are staged
-  const int sh_a = load_shape(0), sh_b = load_shape(min(1, M1)), sh_c = load_shape(min(2, M1));
-  const Slots sl_a = load_slots(0);
+  const int sh_a = load_shape(0), sh_b = load_shape(min(1, M1));
 
   int pat[R], patc[R];
   double pw[R];
@@ -629,6 +665,19 @@ __device__ __forceinline__ void walk_lut_body(const LikArgs& a, double* wlds, co
 #pragma unroll
     for (int r = 0; r < R; r++) x.v[r] = c[r * kTile];
     return x;
+  };
+  auto load_slot_first = [&](int slot) {  // (load_slot; the W3_STAMPS build times it)
+#ifdef W3_STAMPS
+    const long long l0 = __builtin_amdgcn_s_memtime();
+    asm volatile("" ::: "memory");
+    const V x = load_slot(slot);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    stamp_lds += __builtin_amdgcn_s_memtime() - l0;
+    stamp_lds_n++;
+    return x;
+#else
+    return load_slot(slot);
+#endif
   };
   auto store_slot = [&](int slot, const V& x) {
     double* c = slot_ptr(slot);
@@ -773,14 +822,14 @@ __device__ __forceinline__ void walk_lut_body(const LikArgs& a, double* wlds, co
     }
     V L;
     if (kind == 1) {
-      L = load_slot(sl.c[J]);
+      L = load_slot_first(sl.c[J]);
     } else if (sh & (1 << (10 + 2 * J))) {
       if (sh & (1 << (11 + 2 * J))) L = mul(tip_p(Post{}, o, OA{}), tip_p(Post{}, o, OB{}));
-      else L = mul(tip_p(Post{}, o, OA{}), mm(o.x[R + 1], load_slot(sl.g[2 * J + 1])));
+      else L = mul(tip_p(Post{}, o, OA{}), mm(o.x[R + 1], load_slot_first(sl.g[2 * J + 1])));
     } else {
-      const V Ap = mm(o.x[1], load_slot(sl.g[2 * J]));
+      const V Ap = mm(o.x[1], load_slot_first(sl.g[2 * J]));
       if (sh & (1 << (11 + 2 * J))) L = mul(Ap, tip_p(Post{}, o, OB{}));
-      else L = mul(Ap, mm(o.x[R + 1], load_slot(sl.g[2 * J + 1])));
+      else L = mul(Ap, mm(o.x[R + 1], load_slot_first(sl.g[2 * J + 1])));
     }
     use(mm(o.x[0], L));
   };
@@ -855,51 +904,62 @@ __device__ __forceinline__ void walk_lut_body(const LikArgs& a, double* wlds, co
   using Inner = std::false_type;
   using Root = std::true_type;
   {
-    // Two visits per iteration, two operand sets (A, B), nothing copied.  At the top of visit
-    // m: shape (s0), slots and operands of m are there; shape (s1) and tip words of m + 1 too,
-    // so its operands are requested into the other set; then the tip words of m + 2 are read
-    // (LDS).  The visit ends with the scalar loads: slots of m + 1, shape of m + 3 (scalar
-    // loads return out of order: any wait for LDS data with one of them in flight is a wait
-    // for everything -- at the visit's top or in its middle they cost 12-14 %, round 4).
+    // Two visits per iteration, two operand sets (A, B).  At the top of visit m: shape (s0) and
+    // operands of m are there; shape (s1) and tip words of m + 1 too.  The visit takes delivery
+    // of those tip words (take_tw: the LDS wait stands here, with no scalar load in flight --
+    // scalar loads return out of order, so any wait for LDS data with one of them in flight is
+    // a wait for everything), THEN issues its scalar loads -- its own slots and the shape of
+    // m + 2 --, waits for its operands, requests those of m + 1 into the other set (the burst
+    // uses no LDS data but the tip words and no scalar younger than a visit) and takes delivery
+    // of the scalars behind the burst (land); then the tip words of m + 2 are read (LDS).
+    // Load and delivery stand in one straight line, no loop join between them: the slots
+    // arrive in aligned register tuples and are copied out of them, and such copies wait.
+    // ("The schedule words of a visit"; profiles/walk3_lgkm_waits.txt)
     Ops<false, R> a0, a1, b0, b1;
-    int s0 = sh_a, s1 = sh_b, s2 = sh_c;
-    Slots la = sl_a, lb;
+    int s0 = sh_a, s1 = sh_b, s2;
+    Slots sl;
     Tw tw = fetch_tw(0);
     fetch(Post{}, 0, s0, tw, a0, a1);
     tw = fetch_tw(min(1, M1));
     for (int m = 0; m < M1; m += 2) {
       // ---- visit m (set A) ----
+      int mv = m;
+      take_tw(tw, mv);
+      sl = load_slots(mv);
+      s2 = load_shape(min(mv + 2, M1));
+      stamp_scalars_issued();
       settle(a0, a1);
       fetch(Post{}, min(m + 1, M1), s1, tw, b0, b1);
+      land(sl, s2);
       tw = fetch_tw(min(m + 2, M1));
       flush_arena();
-      post_visit(Inner{}, s0, la, a0, a1, 0);
-      lb = load_slots(min(m + 1, M1));
-      const int s3 = load_shape(min(m + 3, M1));
+      post_visit(Inner{}, s0, sl, a0, a1, 0);
       s0 = s1;
       s1 = s2;
-      s2 = s3;
       if (m + 1 < M1) {
         // ---- visit m + 1 (set B) ----
+        mv = m + 1;
+        take_tw(tw, mv);
+        sl = load_slots(mv);
+        s2 = load_shape(min(mv + 2, M1));
+        stamp_scalars_issued();
         settle(b0, b1);
         fetch(Post{}, min(m + 2, M1), s1, tw, a0, a1);
+        land(sl, s2);
         tw = fetch_tw(min(m + 3, M1));
         flush_arena();
-        post_visit(Inner{}, s0, lb, b0, b1, 0);
-        la = load_slots(min(m + 2, M1));
-        const int s4 = load_shape(min(m + 4, M1));
+        post_visit(Inner{}, s0, sl, b0, b1, 0);
         s0 = s1;
         s1 = s2;
-        s2 = s4;
       } else {  // M1 odd: the root's operands arrived in set B
         a0 = b0;
         a1 = b1;
-        la = lb;
       }
     }
+    sl = load_slots(M1);
     settle(a0, a1);
     flush_arena();
-    post_visit(Root{}, s0, la, a0, a1, tile);
+    post_visit(Root{}, s0, sl, a0, a1, tile);
   }
 
   // ================= pre-order + edge derivatives =================
@@ -966,7 +1026,7 @@ __device__ __forceinline__ void walk_lut_body(const LikArgs& a, double* wlds, co
 #pragma unroll
       for (int r = 0; r < R; r++) qv.v[r] = qroot[r];
     } else {
-      qv = load_slot(sl.q);
+      qv = load_slot_first(sl.q);
       if (RESCALE) {
 #pragma unroll
         for (int r = 0; r < R; r++)
@@ -989,9 +1049,12 @@ __device__ __forceinline__ void walk_lut_body(const LikArgs& a, double* wlds, co
   };
   {
     // the root's visit first (set A), then the stored nodes downwards, B and A in turn; the
-    // same pipeline backwards: at the top of visit m the operands of m - 1 are requested,
-    // then the tip words of m - 2 are read; the visit ends with the slots of m - 1 and the
-    // shape of m - 3
+    // same pipeline backwards: at the top of visit m the operands of m - 1 are requested (the
+    // last visit, m = 0, requests nothing), then the tip words of m - 2 are read.  This walk
+    // ENDS a visit with its scalar loads -- the slots of m - 1 and the shape of m - 3 -- and
+    // waits for them there: with the slots known at the visit's top the node's own vector q is
+    // read from LDS ahead of the request burst, which is worth more than the scalar round trip
+    // (the post-order loop's form measured slower here)
     auto dn = [&](int m) { return max(m, 0); };
     Ops<true, R> a0, a1, b0, b1;
     int s0 = load_shape(M1), s1 = load_shape(dn(M1 - 1)), s2 = load_shape(dn(M1 - 2));
@@ -1001,11 +1064,12 @@ __device__ __forceinline__ void walk_lut_body(const LikArgs& a, double* wlds, co
     tw = fetch_tw(dn(M1 - 1));
     {  // ---- visit M1 (the root, set A) ----
       settle(a0, a1);
-      fetch(Pre{}, dn(M1 - 1), s1, tw, b0, b1);
+      if (M1 > 0) fetch(Pre{}, M1 - 1, s1, tw, b0, b1);
       tw = fetch_tw(dn(M1 - 2));
       pre_visit(Root{}, s0, la, a0, a1, M1);
       lb = load_slots(dn(M1 - 1));
       const int s3 = load_shape(dn(M1 - 3));
+      stamp_scalars_issued();
       s0 = s1;
       s1 = s2;
       s2 = s3;
@@ -1013,22 +1077,24 @@ __device__ __forceinline__ void walk_lut_body(const LikArgs& a, double* wlds, co
     for (int m = M1 - 1; m >= 0; m -= 2) {
       // ---- visit m (set B) ----
       settle(b0, b1);
-      fetch(Pre{}, dn(m - 1), s1, tw, a0, a1);
+      if (m > 0) fetch(Pre{}, m - 1, s1, tw, a0, a1);
       tw = fetch_tw(dn(m - 2));
       pre_visit(Inner{}, s0, lb, b0, b1, m);
       la = load_slots(dn(m - 1));
       const int s3 = load_shape(dn(m - 3));
+      stamp_scalars_issued();
       s0 = s1;
       s1 = s2;
       s2 = s3;
       if (m >= 1) {
         // ---- visit m - 1 (set A) ----
         settle(a0, a1);
-        fetch(Pre{}, dn(m - 2), s1, tw, b0, b1);
+        if (m > 1) fetch(Pre{}, m - 2, s1, tw, b0, b1);
         tw = fetch_tw(dn(m - 3));
         pre_visit(Inner{}, s0, la, a0, a1, m - 1);
         lb = load_slots(dn(m - 2));
         const int s4 = load_shape(dn(m - 4));
+        stamp_scalars_issued();
         s0 = s1;
         s1 = s2;
         s2 = s4;
@@ -1039,6 +1105,10 @@ __device__ __forceinline__ void walk_lut_body(const LikArgs& a, double* wlds, co
   if (lane == 0 && (job_eval % 250) == 3 && (tile % 39) == 5)
     printf("walk3 stamps eval %d tile %d: operand waits %lld, operand requests %lld (%lld visits) of %lld shader clocks\n", job_eval, tile,
            stamp_wait, stamp_fetch, stamp_visits, (long long)__builtin_amdgcn_s_memtime() - stamp_t0);
+  stamped_lgkm_wait(stamp_null);
+  if (lane == 0 && (job_eval % 250) == 3 && (tile % 39) == 5)
+    printf("walk3 lgkm stamps eval %d tile %d: first stored-vector reads %lld (%lld reads), scalar loads behind the requests %lld, where they are issued %lld (W3_STAMPS=%d), one empty stamp %lld\n",
+           job_eval, tile, stamp_lds, stamp_lds_n, stamp_land, stamp_smem, (int)W3_STAMPS, stamp_null);
 #endif
   __syncthreads();
   // positions that do not exist in a macro are never written nor read downstream
