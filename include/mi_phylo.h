@@ -560,6 +560,90 @@ int32_t mi_engine_starting_trees_unrooted(mi_engine* engine, int32_t replicate_c
                                           double* out_branch_lengths /* [B][2n-2] */,
                                           double* out_distances /* [B][n][n] or NULL */);
 
+/* ---- split tables of tree batches (an extension) ----
+ *
+ * Trees: n taxa, leaves 0..n-1, internal nodes in post-order, the root 2n-3 of degree 3 -- the
+ * form every unrooted call takes.  Edge v is the branch above node v, v < 2n-3.  The SPLIT of
+ * edge v is the set of leaves below v, minorised as the reference does (Bitset::Minorize,
+ * src/bitset.cpp:147-152): if it holds taxon 0, its complement is taken, so a split never holds
+ * taxon 0.  A split is stored as W = ceil(n/32) uint32 words, taxon i in bit i & 31 of word
+ * i >> 5; bits at and above n are 0, also after a complement.  The distinct splits of a batch
+ * are numbered BY FIRST OCCURRENCE in (t, v) order: the index of a split is the number of
+ * distinct splits whose first occurrence comes earlier.  So the trivial split of leaf v has
+ * index v (tree 0's leaves come first) and the nontrivial splits start at n; the indices of
+ * trees 0..t do not change when trees are appended; a tree put first has index v on its edge v.
+ * (The reference's own numbering is its unordered_map's iteration order and depends on the
+ * compiler, unrooted_sbn_instance.hpp:120-121: it is not reproduced.)  A split occurs at most
+ * once per tree.  A parent-id vector that is not a tree in that form, a root of degree 2
+ * included, is an error that names its tree ("... (tree t)").
+ *
+ * mi_engine_split_index: the table.  taxon_count is an argument: any engine serves, 4 or 20
+ * states (the alignment plays no part); a sharded handle lets its first shard do the work.
+ *   out_split_index [T][2n-1]      index of the split of edge v; -1 in entries 2n-3 and 2n-2:
+ *                                  the layout and the "negative = not a parameter" rule of
+ *                                  mi_engine_gradients_unrooted_reduced's branch_index
+ *   out_split_count [1]            S, the number of distinct splits
+ *   out_split_bits  [capacity][W]  the split
+ *   out_split_first [capacity]     entry number t (2n-1) + v of its first occurrence
+ *   out_split_trees [capacity]     number of trees that hold it
+ *   out_split_stats [capacity][3] or NULL: sum w_t, sum round(w_t l), sum round(w_t round(l l))
+ *                                  over the trees that hold it IN ASCENDING TREE ORDER, one
+ *                                  accumulator each, every operation rounded once (l: that
+ *                                  tree's length of the edge; columns 1 and 2 are 0 without
+ *                                  branch_lengths; w = 1 without tree_weights).  Support, mean
+ *                                  and variance of a split's length follow (what the reference's
+ *                                  PSPIndexer::SplitLengths is used for, src/psp_indexer.cpp:110-120)
+ * Rows at and above S are left untouched.  S > split_capacity is an error whose message carries
+ * S; T (2n-3) always suffices.  The workspace is (4 W + 16) bytes per occurrence (an edge of a
+ * tree) plus 12 bytes per slot of a table of the power of two at or above twice the occurrences,
+ * 16 more bytes per occurrence and a sort's temporary storage when statistics are asked for,
+ * and 512 (n-1) bytes per wave of trees beyond 128 taxa.  The call is NOT chunked: a batch whose
+ * workspace is over MI_PHYLO_PLV_BYTES is refused with the sizes in the message.
+ * mi_engine_last_call_path: "splits n=<n> W=<W> store=lds|global". */
+int32_t mi_engine_split_index(mi_engine* engine, int32_t tree_count, int32_t taxon_count,
+                              const int32_t* parent_ids /* [T][2n-3] */,
+                              const double* branch_lengths /* [T][2n-2] or NULL */,
+                              const double* tree_weights /* [T] or NULL */, int32_t split_capacity,
+                              int32_t* out_split_index /* [T][2n-1] */, int32_t* out_split_count /* [1] */,
+                              uint32_t* out_split_bits /* [capacity][W] */,
+                              int32_t* out_split_first /* [capacity] */,
+                              int32_t* out_split_trees /* [capacity] */,
+                              double* out_split_stats /* [capacity][3] or NULL */);
+
+/* Distances between the trees of a batch from their split indices (any array in the layout
+ * above: entries 0..2n-4 of a row are read, negative ones passed over; an index occurs at most
+ * once per tree).
+ *   out_rf           [T][T]  Robinson-Foulds distance |A| + |B| - 2 |A n B| over the NONTRIVIAL
+ *                            splits (index >= n) of the two trees; symmetric, zero diagonal
+ *   out_branch_score [T][T] or NULL: sum over the splits of either tree, trivial ones included,
+ *                            of (l_a - l_b)^2, an absent split counting as length 0: the SQUARED
+ *                            Kuhner-Felsenstein branch score.  Terms are added in ascending split
+ *                            index, one accumulator, every operation rounded once: the result
+ *                            depends neither on T nor on the pair's place in the launch.  Needs
+ *                            branch_lengths.
+ * At most 2049 taxa (a tree's sorted list is kept in LDS). */
+int32_t mi_engine_rf_distances(mi_engine* engine, int32_t tree_count, int32_t taxon_count,
+                               const int32_t* split_index /* [T][2n-1] */,
+                               const double* branch_lengths /* [T][2n-2] or NULL */,
+                               int32_t* out_rf /* [T][T] */, double* out_branch_score /* [T][T] or NULL */);
+
+/* The majority-rule consensus tree of a split table (host arithmetic only, like
+ * mi_nni_neighbour).  Every nontrivial split with split_weight > threshold * total_weight is
+ * kept (split_weight: column 0 of the statistics, or the tree counts); threshold is in
+ * [0.5, 1): below 0.5 is refused, because a strict majority is what makes the kept splits
+ * pairwise compatible (kept splits that are not are an error).  The result is the tree they
+ * form, in the reference's convention: leaves 0..n-1, internal nodes in post-order with the
+ * children ordered by largest leaf id, the root last -- it holds leaf 0, the maximal kept sets
+ * and the leaves none of them covers, so its degree is at least 3.
+ *   out_node_count [1]    m, n+1 <= m <= 2n-2
+ *   out_parent_ids [m-1]  (capacity 2n-3)
+ *   out_node_split [m]    table index of each node's edge (-1: the root, or a leaf whose
+ *                         trivial split the table lacks); capacity 2n-2
+ * A fully resolved result (m = 2n-2) is a valid input to every unrooted call. */
+int32_t mi_consensus_tree(int32_t taxon_count, int32_t split_count, const uint32_t* split_bits /* [S][W] */,
+                          const double* split_weight /* [S] */, double total_weight, double threshold,
+                          int32_t* out_node_count, int32_t* out_parent_ids, int32_t* out_node_split);
+
 /* Maximum-likelihood branch lengths of unrooted trees under box bounds (an extension: the
  * consumer of the Hessian call's outputs).  Every tree of the batch is
  * iterated on the device: an evaluation is one Hessian pass at a trial point, a step is a
@@ -1029,6 +1113,23 @@ int32_t mi_engine_starting_trees_unrooted_device(mi_engine* engine, void* stream
  * launch, as in every other call -- there too, one call before the capture.)  4-state engines
  * only; a sharded handle reserves on its first shard. */
 int32_t mi_engine_reserve_start_trees(mi_engine* engine, int32_t replicate_count);
+/* The device forms of mi_engine_split_index and mi_engine_rf_distances: every array a device
+ * pointer.  They only enqueue; after mi_engine_reserve_splits(engine, tree_count, taxon_count)
+ * a call of at most that many trees of that taxon count allocates nothing and synchronises
+ * nothing, so it can be captured in a hipGraph.  Input errors of a tree and a table larger than
+ * split_capacity (whose rows at and above the capacity are then not written; *out_split_count
+ * holds S) go to the status word (mi_engine_check_status).  A sharded handle reserves on its
+ * first shard. */
+int32_t mi_engine_split_index_device(mi_engine* engine, void* stream, int32_t tree_count, int32_t taxon_count,
+                                     const int32_t* parent_ids, const double* branch_lengths,
+                                     const double* tree_weights, int32_t split_capacity,
+                                     int32_t* out_split_index, int32_t* out_split_count,
+                                     uint32_t* out_split_bits, int32_t* out_split_first,
+                                     int32_t* out_split_trees, double* out_split_stats);
+int32_t mi_engine_rf_distances_device(mi_engine* engine, void* stream, int32_t tree_count, int32_t taxon_count,
+                                      const int32_t* split_index, const double* branch_lengths,
+                                      int32_t* out_rf, double* out_branch_score);
+int32_t mi_engine_reserve_splits(mi_engine* engine, int32_t tree_count, int32_t taxon_count);
 /* Synchronise `stream` and report the first per-tree error since the last check (the status
  * word is sticky and cleared when an error is reported: calls themselves never clear it). */
 int32_t mi_engine_check_status(mi_engine* engine, void* stream);

@@ -3,9 +3,9 @@ libsbn's Engine / FatBeagle API.  The compute path is libmi_phylo.so (hand-writt
 HIP for gfx950, C ABI in include/mi_phylo.h); this package is a thin ctypes mirror
 of the reference's Engine interface.  No CPU fallback exists."""
 from .engine import (AncestralStates, BranchOptResult, Engine, NniSearchResult, PairwiseDistances, PhyloGradient, Placement,  # noqa: F401
-                     PhyloModelSpecification, RellResult, SprSearchResult, SprScan, StartingTrees, nni_neighbour, rell_weights, site_pattern_compress_device,
-                     spr_neighbour)
+                     PhyloModelSpecification, RellResult, SplitTable, SprSearchResult, SprScan, StartingTrees, consensus_tree, nni_neighbour, rell_weights, site_pattern_compress_device,
+                     split_strings, spr_neighbour)
 from .instance import rooted_instance, unrooted_instance  # noqa: F401
 
-__all__ = ["AncestralStates", "BranchOptResult", "Engine", "NniSearchResult", "PairwiseDistances", "PhyloGradient", "Placement", "PhyloModelSpecification", "RellResult", "SprScan", "SprSearchResult", "StartingTrees", "unrooted_instance",
-           "rooted_instance", "nni_neighbour", "spr_neighbour", "rell_weights", "site_pattern_compress_device"]
+__all__ = ["AncestralStates", "BranchOptResult", "Engine", "NniSearchResult", "PairwiseDistances", "PhyloGradient", "Placement", "PhyloModelSpecification", "RellResult", "SplitTable", "SprScan", "SprSearchResult", "StartingTrees", "unrooted_instance",
+           "rooted_instance", "nni_neighbour", "spr_neighbour", "rell_weights", "site_pattern_compress_device", "consensus_tree", "split_strings"]

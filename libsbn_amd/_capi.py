@@ -161,6 +161,15 @@ SYMBOLS = {
     "mi_engine_starting_trees_unrooted_device":
         (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, _V, _V, _V]),
     "mi_engine_reserve_start_trees": (C.c_int32, [_V, C.c_int32]),
+    "mi_engine_split_index":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_split_index_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_rf_distances": (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, _V]),
+    "mi_engine_rf_distances_device": (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V]),
+    "mi_engine_reserve_splits": (C.c_int32, [_V, C.c_int32, C.c_int32]),
+    "mi_consensus_tree":
+        (C.c_int32, [C.c_int32, C.c_int32, _V, _V, C.c_double, C.c_double, I32P, _V, _V]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),
     "mi_engine_profile_begin": (C.c_int32, [_V, C.c_int32]),
     "mi_engine_profile_collect": (C.c_int32, [_V, F64P, C.c_int32, I32P]),

@@ -89,6 +89,28 @@ struct StartingTreeResult {
   std::vector<double> branch_lengths_, distances_;
 };
 
+// Engine::SplitIndex (an extension, include/mi_phylo.h): the distinct splits of a batch of unrooted
+// trees numbered by first occurrence; split_index_ [T][2n-1], and per split bits_ [S][W], first_ [S],
+// trees_ [S] and stats_ [S][3] (sum w, sum w l, sum w l^2 over the trees that hold it)
+struct SplitTable {
+  size_t taxon_count_ = 0, split_count_ = 0;
+  std::vector<int32_t> split_index_, first_, trees_;
+  std::vector<uint32_t> bits_;
+  std::vector<double> stats_;
+};
+
+// Engine::RfDistances: rf_ [T][T] and, with branch lengths, branch_score_ [T][T]
+struct TreeDistances {
+  std::vector<int32_t> rf_;
+  std::vector<double> branch_score_;
+};
+
+// ConsensusTree: parent_ids_ [m-1] and node_split_ [m] (the table index of each node's edge, -1
+// for the root) of the majority-rule consensus, m = n+1 .. 2n-2 nodes
+struct ConsensusTreeResult {
+  std::vector<int32_t> parent_ids_, node_split_;
+};
+
 // Engine::AncestralStates, per tree (an extension, include/mi_phylo.h), per pattern and
 // unweighted: state_posteriors_ [n-2][P][4] of the internal nodes n .. 2n-3 (row v - n) and, asked
 // for, map_states_ [n-2][P], category_posteriors_ [P][K] with pattern_rates_ [P], and
@@ -519,6 +541,57 @@ class Engine {
     return out;
   }
 
+  // The split table of a batch of unrooted trees (an extension; any engine serves: the taxon
+  // count is the trees'): mi_engine_split_index.  parent_ids [T][2n-3]; branch_lengths [T][2n-2]
+  // and tree_weights [T] may be empty (they enter the statistics only).
+  SplitTable SplitIndex(const size_t tree_count, const size_t taxon_count, const std::vector<int32_t>& parent_ids,
+                        const std::vector<double>& branch_lengths = {},
+                        const std::vector<double>& tree_weights = {}) const {
+    const size_t T = tree_count, n = taxon_count;
+    if (T < 1 || n < 3 || parent_ids.size() != T * (2 * n - 3) ||
+        (!branch_lengths.empty() && branch_lengths.size() != T * (2 * n - 2)) ||
+        (!tree_weights.empty() && tree_weights.size() != T))
+      Failwith("SplitIndex: parent ids must be [trees][2 taxa - 3], lengths [trees][2 taxa - 2], weights [trees].");
+    const size_t cap = T * (2 * n - 3), W = (n + 31) / 32;
+    SplitTable out;
+    out.taxon_count_ = n;
+    out.split_index_.resize(T * (2 * n - 1));
+    out.bits_.resize(cap * W);
+    out.first_.resize(cap);
+    out.trees_.resize(cap);
+    out.stats_.resize(cap * 3);
+    int32_t S = 0;
+    Check(mi_engine_split_index(handle_, static_cast<int32_t>(T), static_cast<int32_t>(n), parent_ids.data(),
+                                branch_lengths.empty() ? nullptr : branch_lengths.data(),
+                                tree_weights.empty() ? nullptr : tree_weights.data(), static_cast<int32_t>(cap),
+                                out.split_index_.data(), &S, out.bits_.data(), out.first_.data(),
+                                out.trees_.data(), out.stats_.data()));
+    out.split_count_ = static_cast<size_t>(S);
+    out.bits_.resize(out.split_count_ * W);
+    out.first_.resize(out.split_count_);
+    out.trees_.resize(out.split_count_);
+    out.stats_.resize(out.split_count_ * 3);
+    return out;
+  }
+
+  // Robinson-Foulds distances and (with branch lengths) squared branch scores between the trees
+  // of a split index [T][2n-1]: mi_engine_rf_distances.
+  TreeDistances RfDistances(const size_t tree_count, const size_t taxon_count,
+                            const std::vector<int32_t>& split_index,
+                            const std::vector<double>& branch_lengths = {}) const {
+    const size_t T = tree_count, n = taxon_count;
+    if (T < 1 || n < 3 || split_index.size() != T * (2 * n - 1) ||
+        (!branch_lengths.empty() && branch_lengths.size() != T * (2 * n - 2)))
+      Failwith("RfDistances: the split index must be [trees][2 taxa - 1], lengths [trees][2 taxa - 2].");
+    TreeDistances out;
+    out.rf_.resize(T * T);
+    if (!branch_lengths.empty()) out.branch_score_.resize(T * T);
+    Check(mi_engine_rf_distances(handle_, static_cast<int32_t>(T), static_cast<int32_t>(n), split_index.data(),
+                                 branch_lengths.empty() ? nullptr : branch_lengths.data(), out.rf_.data(),
+                                 branch_lengths.empty() ? nullptr : out.branch_score_.data()));
+    return out;
+  }
+
   // PairwiseDistances followed by NeighbourJoining in one call, nothing returning to the host in
   // between (an extension; 4-state engines): mi_engine_starting_trees_unrooted.
   StartingTreeResult StartingTrees(const size_t replicates, const std::vector<double>& replicate_weights,
@@ -803,5 +876,25 @@ class Engine {
     if (v->size() < count) v->resize(count);
   }
 };
+
+// The majority-rule consensus tree of a split table (host arithmetic only): mi_consensus_tree.
+inline ConsensusTreeResult ConsensusTree(const size_t taxon_count, const std::vector<uint32_t>& split_bits,
+                                         const std::vector<double>& split_weight, const double total_weight,
+                                         const double threshold = 0.5) {
+  const size_t n = taxon_count, W = (n + 31) / 32;
+  if (n < 3 || split_bits.size() != split_weight.size() * W)
+    Failwith("ConsensusTree: split bits must be [splits][ceil(taxa / 32)], weights [splits].");
+  ConsensusTreeResult out;
+  out.parent_ids_.resize(2 * n - 3);
+  out.node_split_.resize(2 * n - 2);
+  int32_t m = 0;
+  if (mi_consensus_tree(static_cast<int32_t>(n), static_cast<int32_t>(split_weight.size()), split_bits.data(),
+                        split_weight.data(), total_weight, threshold, &m, out.parent_ids_.data(),
+                        out.node_split_.data()) != 0)
+    Failwith(mi_last_error());
+  out.parent_ids_.resize(static_cast<size_t>(m) - 1);
+  out.node_split_.resize(static_cast<size_t>(m));
+  return out;
+}
 
 }  // namespace mihost

@@ -93,6 +93,7 @@ enum StatusCode : int32_t {
   kBadColumnPattern = 11,
   kBadPendantLength = 12,
   kBadSprMove = 13,
+  kSplitCapacity = 14,  // (its second status word carries S, not a tree)
 };
 
 }  // namespace miphylo

@@ -11,6 +11,7 @@
 //   mi_phylo_spr_search.cpp   SPR moves on the device, the SPR hill-climbing search
 //   mi_phylo_rell.cpp         per-pattern log-likelihoods (device form), RELL re-summation, tree mixtures
 //   mi_phylo_start_trees.cpp  pairwise distances, neighbour joining, starting trees (device forms, reservation)
+//   mi_phylo_splits.cpp       split tables, Robinson-Foulds distances (device and host forms, reservation), mi_consensus_tree
 //   mi_phylo_host_calls.cpp   what runs a host-pointer call (staging, status, shards), the plain entry points
 //   mi_phylo_engine_aa.cpp    20-state call sequence
 #pragma once
@@ -139,6 +140,7 @@ inline const char* status_message(int code) {
     case kBadPendantLength: return "placement: a pendant length is not finite or is negative";
     case kBadSprMove:
       return "SPR move is neither (-1, -1, -1) nor a triple (s, dir, f) that mi_spr_neighbour takes";
+    case kSplitCapacity: return "split index: the batch has more distinct splits than split_capacity";
     default: return "unknown device status";
   }
 }
@@ -215,6 +217,11 @@ struct mi_engine {
   // SPR moves and the SPR search (mi_engine_spr_{apply,search}_unrooted*)
   Buffer spr_apply_ws;   // the apply kernel's working arrays of trees too large for LDS
   Buffer spr_search_ws;  // the pair of tree buffers, a round's results, packed inputs, maps, counters
+  // split tables and Robinson-Foulds distances (mi_engine_split_index*, mi_engine_rf_distances*)
+  Buffer split_ws;     // occurrences: bitsets [O][W] | hashes, then flags and ranks [O] 8 bytes | slots [O] | the table: owner, first, trees [slots] each | the scan's temporary storage
+  Buffer split_store;  // tree_splits_kernel's working bitsets of trees too large for LDS
+  Buffer split_sort;   // the statistics' sort: keys, values, sorted keys, sorted values [O] each | rocPRIM's temporary storage
+  Buffer rf_ws;        // a batch's sorted lists: lengths [T][2n-3] | indices [T][2n-3] | counts [T]
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)
   std::vector<hipEvent_t> prof_events;  // kProfEvents per call: [begin, end, mark 0..4]
@@ -471,6 +478,24 @@ int run_nj_device(mi_engine* e, hipStream_t s, int B, int n, const double* dist,
                   int32_t* out_parent_ids, double* out_bl);
 int run_start_trees_device(mi_engine* e, hipStream_t s, const PairDistanceCall& c, int32_t* out_parent_ids,
                            double* out_bl);
+
+// ---- mi_phylo_splits.cpp ----
+// One split-table call with every pointer a device pointer.
+struct SplitIndexCall {
+  int T = 0, n = 0, capacity = 0;
+  const int32_t* parent_ids = nullptr;  // [T][2n-3]
+  const double* bl = nullptr;           // [T][2n-2] or nullptr
+  const double* weights = nullptr;      // [T] or nullptr
+  int32_t* out_index = nullptr;         // [T][2n-1]
+  int32_t* out_count = nullptr;         // [1]
+  uint32_t* out_bits = nullptr;         // [capacity][W]
+  int32_t* out_first = nullptr;         // [capacity]
+  int32_t* out_trees = nullptr;         // [capacity]
+  double* out_stats = nullptr;          // [capacity][3] or nullptr
+};
+int run_split_index_device(mi_engine* e, hipStream_t s, const SplitIndexCall& c);
+int run_rf_device(mi_engine* e, hipStream_t s, int T, int n, const int32_t* split_index, const double* bl,
+                  int32_t* out_rf, double* out_bs);
 
 // mi_phylo_engine_aa.cpp
 int aa_engine_init(mi_engine* e, const double* exchangeabilities, const double* frequencies);

@@ -546,6 +546,75 @@ struct NjArgs {
 // size, which must not happen inside a graph capture -- a reservation calls this beforehand
 void nj_prepare(int n);
 void launch_nj(const NjArgs& a, hipStream_t s);
+// kernels_splits.hip: the split table of a batch of unrooted trees and the Robinson-Foulds
+// distances from its indices.  An occurrence is an edge of a tree, numbered
+// o = t (2n-3) + v.  A wave of tree_splits_kernel owns 64 / split_lane_words(n) trees; a tree's
+// working bitsets ([2n-2 nodes][64 lanes] words per wave) are in LDS up to kSplitLdsTaxa taxa,
+// else in `store`.
+constexpr int kSplitLdsTaxa = 128;
+constexpr int kRfMaxTaxa = 2049;  // (a tree's sorted list, padded to a power of two, in 48 KiB of LDS)
+inline __host__ __device__ int split_words(int n) { return (n + 31) >> 5; }
+// words a tree's lanes take at once: the power of two at or above split_words(n), 64 at most
+inline __host__ __device__ int split_lane_words(int n) {
+  int w = 1;
+  while (w < split_words(n) && w < 64) w <<= 1;
+  return w;
+}
+inline __host__ __device__ size_t split_store_bytes_per_wave(int n) { return (2 * (size_t)n - 2) * 64 * 4; }
+inline size_t split_wave_count(int T, int n) {
+  const int per = 64 / split_lane_words(n);
+  return ((size_t)T + per - 1) / per;
+}
+inline size_t split_table_slots(size_t occurrences) {  // a power of two >= 2 x occurrences
+  size_t h = 2;
+  while (h < 2 * occurrences) h <<= 1;
+  return h;
+}
+struct SplitArgs {
+  int n, T, W, capacity;
+  int hash_bits;              // the hash is masked to that many bits before the first probe (32: all)
+  uint32_t slots;             // table slots, a power of two
+  const int32_t* parent_ids;  // [T][2n-3]
+  const double* bl;           // [T][2n-2] or nullptr
+  const double* weights;      // [T] or nullptr
+  int32_t* status;            // the engine's status word
+  // workspace
+  uint32_t* store;      // [waves][2n-2][64] working bitsets (n > kSplitLdsTaxa)
+  uint32_t* occ_bits;   // [O][W] the canonical split of every occurrence
+  uint64_t* occ_hash;   // [O]; after the insertion: uint32 flags [O] | uint32 ranks [O]
+  int32_t* occ_slot;    // [O] the table slot of the occurrence's split (between the word passes
+                        // of tree_splits_kernel: 1 where the leaf set held taxon 0)
+  void* scan_tmp;       // rocPRIM's temporary storage of the scan
+  size_t scan_tmp_bytes;
+  int32_t* slot_owner;  // [slots] -1, or the occurrence that claimed the slot
+  int32_t* slot_first;  // [slots] the lowest occurrence number of the slot's split
+  int32_t* slot_trees;  // [slots] occurrences of the slot's split
+  // the statistics' sort (out_stats only): keys = split index, values = occurrence
+  uint32_t *keys, *vals, *keys2, *vals2;
+  void* sort_tmp;
+  size_t sort_tmp_bytes;
+  // outputs
+  int32_t* out_index;   // [T][2n-1]
+  int32_t* out_count;   // [1]
+  uint32_t* out_bits;   // [capacity][W]
+  int32_t* out_first;   // [capacity]
+  int32_t* out_trees;   // [capacity]
+  double* out_stats;    // [capacity][3] or nullptr
+};
+size_t split_scan_tmp_bytes(size_t occurrences);
+size_t split_sort_tmp_bytes(size_t occurrences);
+int launch_split_index(const SplitArgs& a, hipStream_t s);  // nonzero: rocPRIM refused a launch
+struct RfArgs {
+  int n, T;
+  const int32_t* split_index;  // [T][2n-1]
+  const double* bl;            // [T][2n-2] or nullptr
+  int32_t* sorted_index;       // [T][2n-3] workspace: a tree's nonnegative indices, ascending
+  double* sorted_length;       // [T][2n-3] workspace: their lengths
+  int32_t* sorted_count;       // [T] workspace
+  int32_t* out_rf;             // [T][T]
+  double* out_bs;              // [T][T] or nullptr
+};
+void launch_rf(const RfArgs& a, hipStream_t s);
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
 // the first, gradient_mfma_kernel, was retired in round 6): all categories of a group of four
 // per instruction; they also write the log-likelihood partial sums, so no separate logL pass is

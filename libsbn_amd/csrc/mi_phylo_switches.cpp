@@ -93,6 +93,7 @@ bool parse_switches(Switches& out, std::string& error) {
   s.fused_debug_skip = (int)r.integer("MI_PHYLO_DEBUG_FUSED_SKIP", 0, INT_MAX, 0);
   s.plv_bytes = r.integer("MI_PHYLO_PLV_BYTES", 0, LLONG_MAX, -1);
   s.place_table_global = r.choice("MI_PHYLO_PLACE_TABLE", "lds|global", 0) == 1;
+  s.split_hash_bits = (int)r.integer("MI_PHYLO_SPLIT_HASH_BITS", 0, 32, 32);
   s.aa_jacobi_seq = r.choice("MI_PHYLO_AA_JACOBI", "wave|seq", 0) == 1;
   s.aa_post_wave = r.choice("MI_PHYLO_AA_POST", "wg|wave", 0) == 1;
   s.aa_pre_wave = r.choice("MI_PHYLO_AA_PRE", "wg|wave", 0) == 1;

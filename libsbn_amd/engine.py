@@ -256,6 +256,45 @@ def spr_neighbour(taxon_count, parent_ids, branch_lengths, s, direction, f):
     return out_pid, out_bl
 
 
+@dataclass
+class SplitTable:
+    """Engine.split_index: the distinct splits of a batch of unrooted trees, numbered by first
+    occurrence in (tree, edge) order (include/mi_phylo.h)."""
+    taxon_count: int
+    split_index: np.ndarray   # [T][2n-1] int32: index of edge v's split; -1 in entries 2n-3, 2n-2
+    bits: np.ndarray          # [S][W] uint32: taxon i is bit i & 31 of word i >> 5; never taxon 0
+    first: np.ndarray         # [S] entry number t (2n-1) + v of the first occurrence
+    trees: np.ndarray         # [S] number of trees that hold the split
+    stats: np.ndarray         # [S][3] sum w, sum w l, sum w l^2 over those trees, in tree order
+
+    @property
+    def split_count(self):
+        return int(self.bits.shape[0])
+
+
+def split_strings(bits, taxon_count):
+    """The reference's "01110" form of stored splits (Bitset::ToString: taxon 0 first)."""
+    n = int(taxon_count)
+    b = _np(bits, np.uint32).reshape(-1, (n + 31) // 32)
+    return ["".join("1" if (int(row[i >> 5]) >> (i & 31)) & 1 else "0" for i in range(n)) for row in b]
+
+
+def consensus_tree(taxon_count, split_bits, split_weight, total_weight, threshold=0.5):
+    """The majority-rule consensus tree of a split table (mi_consensus_tree: host arithmetic
+    only): every nontrivial split with weight > threshold * total_weight, threshold in
+    [0.5, 1).  Returns (parent ids [m-1], node split [m]: the table index of each node's edge,
+    -1 for the root), m = n+1 .. 2n-2 nodes in the reference's convention."""
+    n = int(taxon_count)
+    b = _np(split_bits, np.uint32).reshape(-1, (n + 31) // 32)
+    w = _np(split_weight, np.float64).reshape(b.shape[0])
+    m = C.c_int32()
+    pid, node_split = np.empty(2 * n - 3, np.int32), np.empty(2 * n - 2, np.int32)
+    if _capi.load().mi_consensus_tree(n, b.shape[0], _ptr(b), _ptr(w), float(total_weight), float(threshold),
+                                      C.byref(m), _ptr(pid), _ptr(node_split)):
+        raise RuntimeError(_capi.last_error())
+    return pid[:m.value - 1].copy(), node_split[:m.value].copy()
+
+
 def _parse_site(site):
     # src/site_model.cpp:10-25
     if site == "constant":
@@ -738,6 +777,60 @@ class Engine:
             _ptr(out.branch_lengths), _ptr(out.distances)))
         return out
 
+    def split_index(self, parent_ids, branch_lengths=None, tree_weights=None, split_capacity=None):
+        """The split table of a batch of unrooted trees [T][2n-3] (mi_engine_split_index; any
+        engine serves: n is the trees').  branch_lengths [T][2n-2] and tree_weights [T] enter
+        the statistics only.  split_capacity: rows of the table (default T (2n-3), which always
+        suffices).  Returns a SplitTable."""
+        pid = _np(parent_ids, np.int32)
+        if pid.ndim == 1:
+            pid = pid[None]
+        if pid.ndim != 2 or pid.shape[0] < 1 or pid.shape[1] < 3 or pid.shape[1] % 2 == 0:
+            raise RuntimeError(f"split_index takes parent ids [T][2n-3], n >= 3; got {pid.shape}")
+        T, E = pid.shape
+        n = (E + 3) // 2
+        bl = None if branch_lengths is None else _np(branch_lengths, np.float64).reshape(T, E + 1)
+        tw = None if tree_weights is None else _np(tree_weights, np.float64).reshape(T)
+        cap = T * E if split_capacity is None else int(split_capacity)
+        W = (n + 31) // 32
+        index, count = np.empty((T, E + 2), np.int32), np.zeros(1, np.int32)
+        bits, first, trees = np.zeros((cap, W), np.uint32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        stats = np.zeros((cap, 3))
+        self._check(self._lib.mi_engine_split_index(
+            self._h, T, n, _ptr(pid), _ptr(bl), _ptr(tw), cap, _ptr(index), _ptr(count), _ptr(bits),
+            _ptr(first), _ptr(trees), _ptr(stats)))
+        S = int(count[0])
+        return SplitTable(n, index, bits[:S].copy(), first[:S].copy(), trees[:S].copy(), stats[:S].copy())
+
+    def rf_distances(self, split_index, branch_lengths=None):
+        """Robinson-Foulds distances [T][T] between the trees of a split index [T][2n-1]
+        (mi_engine_rf_distances); with branch_lengths [T][2n-2] also the squared
+        Kuhner-Felsenstein branch scores [T][T]: returns rf, or (rf, branch_score)."""
+        idx = _np(split_index, np.int32)
+        if idx.ndim != 2 or idx.shape[0] < 1 or idx.shape[1] < 5 or idx.shape[1] % 2 == 0:
+            raise RuntimeError(f"rf_distances takes a split index [T][2n-1], n >= 3; got {idx.shape}")
+        T, n = idx.shape[0], (idx.shape[1] + 1) // 2
+        bl = None if branch_lengths is None else _np(branch_lengths, np.float64).reshape(T, 2 * n - 2)
+        rf = np.empty((T, T), np.int32)
+        bs = None if bl is None else np.empty((T, T))
+        self._check(self._lib.mi_engine_rf_distances(self._h, T, n, _ptr(idx), _ptr(bl), _ptr(rf), _ptr(bs)))
+        return rf if bs is None else (rf, bs)
+
+    def split_support(self, tree, trees, tree_weights=None):
+        """Support of every edge of `tree` [2n-3] among `trees` [T][2n-3]: the (weighted)
+        share of them that hold the edge's split, [2n-3].  `tree` is placed first in one
+        split_index call, so that its edge v has index v, and its own occurrence is taken off."""
+        one = _np(tree, np.int32).reshape(1, -1)
+        rest = _np(trees, np.int32).reshape(-1, one.shape[1])
+        E = one.shape[1]
+        if tree_weights is None:
+            table = self.split_index(np.concatenate([one, rest]))
+            return (table.trees[:E] - 1) / rest.shape[0]
+        w = _np(tree_weights, np.float64).reshape(rest.shape[0])
+        # (weight 0 for the tree itself: its splits come first and add nothing)
+        table = self.split_index(np.concatenate([one, rest]), tree_weights=np.concatenate([[0.0], w]))
+        return table.stats[:E, 0] / w.sum()
+
     def pattern_mixture(self, pattern_log_likelihoods, pattern_weights, tree_log_weights=None):
         """Marginal of a mixture of trees (mi_engine_pattern_mixture): s [T][P], pattern weights
         [P], log tree weights [T] (None: log(1/T) each) -> (logsumexp_t(s[t][p] + lw_t) [P], its
@@ -1129,6 +1222,26 @@ class Engine:
         """mi_engine_reserve_start_trees: workspace of the three calls above for that many
         replicates (their *_device forms then allocate nothing: graph capture)."""
         self._check(self._lib.mi_engine_reserve_start_trees(self._h, int(replicate_count)))
+
+    def split_index_device(self, stream, T, n, parent_ids, split_capacity, out_split_index, out_split_count,
+                           out_split_bits, out_split_first, out_split_trees, out_split_stats=None,
+                           branch_lengths=None, tree_weights=None):
+        """mi_engine_split_index_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_split_index_device(
+            self._h, stream, int(T), int(n), parent_ids, branch_lengths, tree_weights, int(split_capacity),
+            out_split_index, out_split_count, out_split_bits, out_split_first, out_split_trees,
+            out_split_stats))
+
+    def rf_distances_device(self, stream, T, n, split_index, out_rf, out_branch_score=None,
+                            branch_lengths=None):
+        """mi_engine_rf_distances_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_rf_distances_device(
+            self._h, stream, int(T), int(n), split_index, branch_lengths, out_rf, out_branch_score))
+
+    def reserve_splits(self, tree_count, taxon_count):
+        """mi_engine_reserve_splits: workspace of the two calls above for that many trees of
+        that taxon count (their *_device forms then allocate nothing: graph capture)."""
+        self._check(self._lib.mi_engine_reserve_splits(self._h, int(tree_count), int(taxon_count)))
 
     def pattern_mixture_device(self, stream, T, P, pattern_ll, pattern_weights, out_pattern_log_marginal,
                                out_log_marginal, tree_log_weights=None):
