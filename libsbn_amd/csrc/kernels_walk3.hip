@@ -1432,6 +1432,165 @@ __global__ __launch_bounds__(kTile) void setup_records_kernel(FusedSetupArgs f) 
   fused_setup_role(f, blockIdx.x, reinterpret_cast<char*>(wlds));
 }
 
+// ------------------------------------------------------------------------
+// Set-up and operand records of a large batch in ONE launch in front of the walk's: a workgroup
+// of four waves per tree (workgroup t is tree t: the walk's xcd_map runs the waves of tree t on
+// XCD t & 7, where workgroups dealt round-robin by id put workgroup t -- a speed matter only).
+//   * wave 0 builds the tree (small_tree_build) while wave 1 builds the model instance in LDS;
+//     wave 0 leaves slot_of[node] = macro * 6 + position and the tree's status in LDS;
+//   * ONE barrier;
+//   * every wave takes a quarter of the tree's (node, category) rows: lut_record into registers,
+//     then through LDS in passes of `pass_rows` rows (a quarter at once is 17 KB per wave for a
+//     DS1 tree: four of those, and four workgroups per CU, do not fit) and out in whole 16-byte
+//     pieces, consecutive lanes to consecutive bytes;
+//   * wave 0 also writes what small_tree_store writes, wave 1 the model instance.
+// The device functions are those of fused_setup_role / the two launches this replaces: the same
+// bits.  Plain stores throughout -- a kernel boundary follows; nobody polls, nothing is handed over.
+// Budget: four workgroups per CU (1000 trees resident at once on 256 CUs), i.e. at most 40 KB of
+// LDS and 128 vector registers.
+// ------------------------------------------------------------------------
+constexpr int kSetupWgWaves = 4, kSetupWgThreads = 64 * kSetupWgWaves;
+constexpr unsigned kSetupWgLdsMax = 40u * 1024u;
+constexpr unsigned kSetupWgRowBytes = 41u * 8u;
+// LDS of a set-up workgroup: staged rows [4][pass_rows][41] (the tree build's scratch overlays
+// them) | model instance | slot_of [64] | status word
+__host__ __device__ inline unsigned setup_wg_model_offset(int pass_rows) {
+  return (kSetupWgWaves * (unsigned)pass_rows * kSetupWgRowBytes + 127u) & ~127u;
+}
+__host__ __device__ inline unsigned setup_wg_lds(int pass_rows) {
+  return setup_wg_model_offset(pass_rows) + (unsigned)sizeof(DevModel) + 64u * 4u + 16u;
+}
+// rows of its quarter a wave stages at a time: the quarter in the fewest equal passes that fit
+inline int setup_wg_pass_rows(int n, int K) {
+  const int per_q = ((2 * n - 2) * K + kSetupWgWaves - 1) / kSetupWgWaves;
+  for (int passes = 1;; passes++) {
+    const int h = (per_q + passes - 1) / passes;
+    if (setup_wg_lds(h) <= kSetupWgLdsMax || h == 1) return h;
+  }
+}
+
+// (JC: the substitution model is JC69's constants -- the call's ModelSetupArgs::subst says so --,
+// and the kernel holds no eigensystem code; a GTR instance is one lane's Jacobi sweeps, which do
+// not fit 128 registers: that variant is compiled for two workgroups per CU.)
+template <bool JC>
+__global__ __launch_bounds__(kSetupWgThreads, JC ? 4 : 2) void setup_wg_kernel(FusedSetupArgs f, int pass_rows) {
+  extern __shared__ double wlds[];
+  char* lds = reinterpret_cast<char*>(wlds);
+  const TreeSetupArgs& a = f.ts;
+  const int t = blockIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int n = a.n, N = 2 * n - 1, K = f.ms.K;
+  const int per_q = ((N - 1) * K + kSetupWgWaves - 1) / kSetupWgWaves;
+  const int H = pass_rows;
+  double* stage = reinterpret_cast<double*>(lds) + wave * H * 41;
+  DevModel* md = reinterpret_cast<DevModel*>(lds + setup_wg_model_offset(H));
+  int* slot_of = reinterpret_cast<int*>(md + 1);
+  int* tree_ok = slot_of + 64;
+  static_assert(kSetupWgWaves * kSetupWgRowBytes >= kSmallTreeLdsInts * sizeof(int), "the tree build's scratch fits one staged row per wave");
+
+  // this lane's row of records: node * K + category; its branch length is asked for now, so that
+  // it arrives under the tree build (effective branch length as small_tree_store forms it)
+  const int idx = wave * per_q + lane;
+  const int node = idx / K, k = idx - node * K;
+  const bool live = lane < per_q && node < N - 1;
+  double bl = 0.0;
+  if (live) {
+    if (!a.rooted) {
+      bl = node < N - 2 ? a.bl[(size_t)t * (N - 1) + node] : 0.0;
+    } else {
+      bl = a.bl[(size_t)t * N + node];
+      if (a.rates) bl *= a.rates[(size_t)t * (N - 1) + node];
+    }
+  }
+
+  if (wave == 0) {
+    SmallTree<1> tree;
+    small_tree_build<1>(a, t, lane, tree, reinterpret_cast<int*>(lds));
+    const bool built = tree.status == kOk;
+    // node -> macro * 6 + position (the lane that owns a macro knows its children)
+    if (built && tree.is_macro[0]) {
+      const MacroEntry& me = tree.me[0];
+      const int base = tree.macro_rank[0] * 6;
+      slot_of[me.child[0]] = base;
+      slot_of[me.child[1]] = base + 1;
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+        if (((me.shape >> (2 * j)) & 3) == 2) {
+          slot_of[me.grand[2 * j]] = base + 2 + 2 * j;
+          slot_of[me.grand[2 * j + 1]] = base + 3 + 2 * j;
+        }
+    }
+    if (lane == 0) *tree_ok = built ? 1 : 0;
+    // schedule, macro list and count, effective branch lengths, status: whether or not it was built
+    small_tree_store<1>(a, t, lane, tree);
+  } else if (wave == 1) {
+    ModelSetupArgs ms = f.ms;  // (one model instance per tree in these calls)
+    if (JC) ms.subst = 0;
+    model_setup_wave(ms, t, lane, *md);
+  }
+  __syncthreads();
+  if (!__builtin_amdgcn_readfirstlane(*tree_ok)) return;  // (an error tree writes no records)
+
+  if (wave == 1) {  // the model instance: the walk reads frequencies, rates, weights
+    dbl2* dst = reinterpret_cast<dbl2*>(f.ms.models + t);
+    const dbl2* src = reinterpret_cast<const dbl2*>(md);
+    static_assert(sizeof(DevModel) % 16 == 0, "whole 16-byte pieces");
+    for (int i = lane; i < (int)(sizeof(DevModel) / 16); i += 64) dst[i] = src[i];
+  }
+  double st[40];
+  int rec = -1, len = 0;
+  if (live) {
+    const bool tip = node < n;
+    lut_record(*md, md->cat_rate[k] * bl, tip, st);
+    const int slot = slot_of[node], m = slot / 6, pos = slot - m * 6;
+    const int rec8 = (int)((((size_t)t * max_macros(n) + m) * 6 + pos) * (kPos / 8));
+    rec = rec8 + k * (tip ? (int)(kTipCat / 8) : 32);
+    len = tip ? 40 : 32;
+  }
+  const int part = lane & 7;
+  for (int base = 0; base < per_q; base += H) {
+    // the lanes of this pass stage their rows ...
+    if (live && lane >= base && lane < base + H) {
+      double* row = stage + (lane - base) * 41;
+#pragma unroll
+      for (int d = 0; d < 32; d++) row[d] = st[d];
+      if (len == 40) {
+#pragma unroll
+        for (int d = 32; d < 40; d++) row[d] = st[d];
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (one wave: its LDS operations are in order)
+    // ... and the wave writes them: eight lanes per record, up to three 16-byte pieces each.
+    // A record per lane at a time: its three LDS reads first, unconditionally (rows and offsets
+    // clamped), then the stores under their conditions -- left to itself the compiler puts each
+    // read and its wait inside its store's condition, a round trip apiece (as in
+    // fused_setup_role; more than three at once, beside the 80 registers the lanes of a later
+    // pass still hold their records in, do not fit the register budget).
+#pragma unroll
+    for (int x = 0; x < 4; x++) {
+      const int r = (lane >> 3) + 8 * x, owner = base + r;
+      const int rec_r = __shfl(rec, owner & 63, 64), len_r = __shfl(len, owner & 63, 64);
+      const bool have = r < H && owner < per_q && rec_r >= 0;
+      const double* row = stage + min(r, H - 1) * 41;
+      double va[3], vb[3];
+#pragma unroll
+      for (int p3 = 0; p3 < 3; p3++) {
+        const int d = 2 * (p3 * 8 + part);
+        va[p3] = row[min(d, 38)];
+        vb[p3] = row[min(d, 38) + 1];
+      }
+#pragma unroll
+      for (int p3 = 0; p3 < 3; p3++) asm volatile("" : "+v"(va[p3]), "+v"(vb[p3]));
+#pragma unroll
+      for (int p3 = 0; p3 < 3; p3++) {
+        const int d = 2 * (p3 * 8 + part);
+        if (have && d < len_r) *reinterpret_cast<dbl2*>(f.mmats + (size_t)rec_r + d) = dbl2{va[p3], vb[p3]};
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (read before the next pass overwrites it)
+  }
+}
+
 template <bool RESCALE, int KP>
 __global__ __launch_bounds__(kTile, kRegs == 2 ? 3 : 2) void gradient_walk_lut_fused_kernel(LikArgs a, FusedSetupArgs f) {
   extern __shared__ double wlds[];
@@ -1500,6 +1659,20 @@ void launch_setup_records(const FusedSetupArgs& f_in, int count, hipStream_t s) 
   const size_t lds = fused_setup_lds(f.ts.n, f.ms.K);
   allow_large_lds(reinterpret_cast<const void*>(setup_records_kernel), lds);
   hipLaunchKernelGGL(setup_records_kernel, dim3((unsigned)f.setup_blocks), dim3(kTile), lds, s, f);
+}
+
+void launch_setup_workgroups(const FusedSetupArgs& f_in, int count, hipStream_t s) {
+  if (count <= 0) return;
+  FusedSetupArgs f = f_in;
+  f.setup_blocks = count;
+  f.xcd_base = 0;
+  f.ready = nullptr;
+  f.fence = 0;
+  f.debug_skip = 0;
+  const int pass_rows = setup_wg_pass_rows(f.ts.n, f.ms.K);
+  const dim3 grid((unsigned)count), block(kSetupWgThreads);
+  if (f.ms.subst == 0) hipLaunchKernelGGL(setup_wg_kernel<true>, grid, block, setup_wg_lds(pass_rows), s, f, pass_rows);
+  else hipLaunchKernelGGL(setup_wg_kernel<false>, grid, block, setup_wg_lds(pass_rows), s, f, pass_rows);
 }
 
 void launch_transition_lut(const TransitionMacroArgs& a, hipStream_t s) {

@@ -238,9 +238,17 @@ CallPlan plan_call(const mi_engine* e, CallKind kind, int T, bool rescaling, int
   // Built, bit-identical (test), and not the default: the four quarter-waves of a tree each build
   // the tree, and 4 000 of them take what the two launches take -- the replayed headline step
   // 0.7826 against 0.7823 ms (tools/ab_kernels.py, four rounds), direct launches -1 %.
-  p.setup_records = p.walk3 && !p.fuse_setup && !arena && !p.tile_regs && !p.analytic && p.groups == 1 && e->fused_setup &&
-                    p.E == T && p.models_per_tree == 1 && !p.need_slots && T <= kMaxEvals &&
-                    gradient_walk_lut_fused_applies(n, e->K) && e->sw.setup_records;
+  const bool records_possible = p.walk3 && !p.fuse_setup && !arena && !p.tile_regs && !p.analytic && p.groups == 1 &&
+                                e->fused_setup && p.E == T && p.models_per_tree == 1 && !p.need_slots && T <= kMaxEvals &&
+                                gradient_walk_lut_fused_applies(n, e->K);
+  p.setup_records = records_possible && e->sw.setup_records == 1;
+  // The same in a four-wave workgroup per tree (launch_setup_workgroups): the tree and the model
+  // instance are built once, side by side, and all of a 1000-tree batch's workgroups are resident
+  // at once.  Taken where a tree has more rows of records than one wave has lanes -- below that,
+  // four waves per tree are three idle ones -- (MI_PHYLO_SETUP_RECORDS=wg: wherever it can be;
+  // =0, MI_PHYLO_FUSE_FINALIZE=0: the two launches).  DESIGN.md 4.7.
+  p.setup_wg = records_possible && (e->sw.setup_records == 2 ||
+                                    (e->sw.setup_records < 0 && e->sw.fuse_finalize && (e->N - 1) * e->K > 64));
   // The C ABI's outputs are optional, and work nobody reads is not done: without a
   // substitution-gradient output the 16 finite-difference log-likelihood passes of a GTR
   // call are skipped, without a site-gradient output the extra gradient pass under the
@@ -265,7 +273,10 @@ std::string plan_path(const mi_engine* e, const CallPlan& p) {
   std::string path = p.dominant;
   if (p.kind != kLogLikCall)
     path += p.store == kStoreHbm ? " store=hbm" : (p.store == kStoreArena ? " store=arena" : " store=lds");
-  path += p.fuse_setup ? " setup=in-walk" : (p.setup_records ? " setup=with-records" : " setup=own-launch");
+  path += p.fuse_setup      ? " setup=in-walk"
+          : p.setup_records ? " setup=with-records"
+          : p.setup_wg      ? " setup=workgroup-records"
+                            : " setup=own-launch";
   if (p.kind == kHessianCall) path += " hess";
   if (p.kind == kNniCall) path += " nni";
   if (p.kind == kAncestralCall) path += " ancestral";
@@ -572,7 +583,8 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d_in) {
 
   // set-up: tree schedules and model instances, one launch (or riding with the walk's records)
   if (p.setup_records) launch_setup_records(fused_setup_args(e, d, p), T, s);
-  const bool slots_done = !p.fuse_setup && !p.setup_records &&
+  if (p.setup_wg) launch_setup_workgroups(fused_setup_args(e, d, p), T, s);
+  const bool slots_done = !p.fuse_setup && !p.setup_records && !p.setup_wg &&
                           launch_setup(tree_setup_args(e, d, p), model_setup_args(e, d, p), e->sw, s);
   if (p.store == kStoreArena && !slots_done) macro_slots(e, T, s);
 
@@ -595,7 +607,7 @@ int run_device(mi_engine* e, hipStream_t s, const DeviceCall& d_in) {
     if (p.walk3) launch_transition_lut(tm, s);
     else launch_transition_macro(tm, s);
   };
-  if (p.mfma && !p.fuse_setup && !p.setup_records) {
+  if (p.mfma && !p.fuse_setup && !p.setup_records && !p.setup_wg) {
     macro_matrices(0, 0, T);
     if (p.site_pass) macro_matrices(17 * T, T, T);
   }

@@ -276,7 +276,8 @@ struct CallPlan {
   bool analytic;    // analytic substitution gradient (opt-in) instead of finite differences
   bool light;       // GTR gradient call nobody reads the substitution / site gradient of
   bool fuse_setup;     // set-up rides in the walk's launch (the one-launch call)
-  bool setup_records;  // set-up and operand records in one launch in front of the walk's
+  bool setup_records;  // set-up and operand records in one launch in front of the walk's (quarter-waves)
+  bool setup_wg;       // ... by a four-wave workgroup per tree (at most one of the three is set)
   bool need_slots;     // the schedule gets LDS slots: a log-likelihood (or HBM Hessian) kernel walks it
   bool fd_pass, site_pass;  // the 16 finite-difference passes / the perturbed-model site pass run
   bool loglik_runs;         // a log-likelihood kernel runs at all

@@ -679,6 +679,11 @@ void launch_gradient_walk_lut_fused(const LikArgs& a, const FusedSetupArgs& f, i
 // records in ONE launch in front of the walk's, for batches beyond the one-launch call's size
 // (instead of launch_setup + launch_transition_lut).  f.ready may be nullptr.
 void launch_setup_records(const FusedSetupArgs& f, int count, hipStream_t s);
+// The same work by a four-wave workgroup per tree: wave 0 builds the tree, wave 1 the model
+// instance, then each wave writes a quarter of the tree's operand records (plain stores; the
+// ts, ms and mmats members of `f` are read, nothing else).  Four workgroups fit a CU, so a batch
+// of 1000 trees is resident at once.  Same conditions as launch_setup_records.
+void launch_setup_workgroups(const FusedSetupArgs& f, int count, hipStream_t s);
 const char* gradient_walk_lut_kernel_name();
 const char* gradient_walk_lut_fused_kernel_name();
 // waves per CU the walks' LDS footprint allows for this tree size and category count

@@ -82,7 +82,7 @@ bool parse_switches(Switches& out, std::string& error) {
   s.loglik_evals_per_wave = r.listed("MI_PHYLO_LOGLIK_EVALS_PER_WAVE", "1|2|4|8", 0);
   s.tree_setup = r.choice("MI_PHYLO_TREE_SETUP", "small|wg|lds", -1) + 1;
   s.macro_slots = r.choice("MI_PHYLO_MACRO_SLOTS", "own|seq", -1) + 1;
-  s.setup_records = r.on_off("MI_PHYLO_SETUP_RECORDS", false);
+  s.setup_records = r.choice("MI_PHYLO_SETUP_RECORDS", "0|1|wg", -1);
   s.fused_setup = r.on_off("MI_PHYLO_FUSED_SETUP", true);
   s.fuse_finalize = r.on_off("MI_PHYLO_FUSE_FINALIZE", true);
   s.fused_max_trees = (int)r.integer("MI_PHYLO_FUSED_MAX_TREES", 0, INT_MAX, 512);

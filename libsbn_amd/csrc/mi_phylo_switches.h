@@ -26,7 +26,7 @@ struct Switches {
   // tree set-up
   int tree_setup = 0;          // TREE_SETUP: 0 by tree size, 1 small, 2 wg, 3 lds
   int macro_slots = 0;         // MACRO_SLOTS: 0 folded into the set-up launch where it can be, 1 own, 2 seq
-  bool setup_records = false;  // SETUP_RECORDS=1
+  int setup_records = -1;      // SETUP_RECORDS: -1 by rows of records per tree, 0 own launches, 1 quarter-waves, 2 wg
   // the one-launch call
   bool fused_setup = true;     // FUSED_SETUP=0: always the four-launch sequence
   bool fuse_finalize = true;   // FUSE_FINALIZE=0: likewise
