@@ -644,6 +644,126 @@ int32_t mi_consensus_tree(int32_t taxon_count, int32_t split_count, const uint32
                           const double* split_weight /* [S] */, double total_weight, double threshold,
                           int32_t* out_node_count, int32_t* out_parent_ids, int32_t* out_node_split);
 
+/* ---- subsplit Bayesian networks of unrooted trees (an extension) ----
+ * What the reference's UnrootedSBNMaps (src/sbn_maps.cpp) and SBNProbability
+ * (src/sbn_probability.cpp) compute on the host with bitset maps, for a batch of trees on the
+ * device.  Trees have the form every unrooted call takes: n taxa, E = 2n-3 edges, edge v the
+ * branch above node v, the root 2n-3 of degree 3.  The split table (above) names every clade by
+ * an integer, 2 split + side: side 0 is the stored split (never taxon 0), side 1 its complement.
+ *
+ * Directed edge d = 2v + s.  s = 0: the focal clade is the leaf set below v, the far node is
+ * parent(v), the focal node is v.  s = 1: the focal clade is everything else, the far node is v,
+ * the focal node is parent(v) and its two child clades are its other two neighbours'.
+ * Slot (d, k), k in {0, 1, 2}: it exists only if the focal clade has at least 2 taxa.
+ *   k = 0     the sister is the complement of the focal clade (the rooting on that very edge)
+ *   k = 1, 2  the sister is one of the far node's other two clades (far node internal only):
+ *             s = 0, parent(v) not the root: the sibling's clade, then the clade above parent(v);
+ *             s = 0 under the root: the two siblings in ascending node id;
+ *             s = 1: v's two children in ascending node id.
+ * The slot's PCSP is (sister | focal | child), the child being the one of the focal node's two
+ * child clades that does NOT hold the focal clade's lowest-numbered taxon (what std::min over the
+ * reference's bitsets picks, src/sbn_maps.cpp:78).  A tree has at most 6 (2n-3) slots; the
+ * reference's per-rooting lists (O(n^2) per tree) are never formed on the device.
+ *
+ * Parameters: a vector of length P = S + C.  Entries 0 .. S-1 are the rootsplits: every split of
+ * the support, with the split table's indices.  Entries S .. P-1 are the C distinct PCSPs in
+ * contiguous blocks per parent (sister | focal); blocks are ordered by the first occurrence of the
+ * parent in (tree, d, k) order, children within a block by their own first occurrence.  (The
+ * reference's numbering follows the iteration order of an unordered_map: it is not reproduced.)
+ * The support is that of trees 0 .. support_tree_count-1; the later trees are only looked up, and
+ * a rootsplit or PCSP they alone hold gets the sentinel P (the reference's out_of_sample_index).
+ *
+ * The rooting on edge v has  log p_v = theta[root(v)] + A(2v, 0) + A(2v+1, 0),
+ *   A(d, k) = theta[slot(d, k)] + B(d),  B(d) = sum over the two child directed edges c of d whose
+ *   focal clade is no leaf of A(c, k_c), k_c the slot of c whose sister is c's sibling
+ * (A = 0 for a leaf clade), and log q = logsumexp_v log p_v.  Orders of the sums: B adds the lower
+ * child (s = 0), resp. the sibling before the edge above or the lower sibling under the root
+ * (s = 1), first; log p_v adds from left to right as written; log q takes the maximum m, adds
+ * exp(log p_v - m) in ascending v and adds log of the sum to m.  A rooting that touches the
+ * sentinel or a -inf parameter has log p_v = -inf; a tree without a rooting in the support has
+ * log q = -inf.  There is no NaN.
+ *
+ * mi_engine_sbn_index: the support and every tree's slots.  Any engine serves.
+ *   out_root_index [T][2n-3]          parameter index of the rootsplit of edge v, or P
+ *   out_slot_index [T][2(2n-3)][3]    -1: no such slot; P: outside the support; else the index
+ *   out_counts [3]                    S, C, and the number of parents (blocks)
+ *   out_split_bits [rootsplit_capacity][W]  the rootsplits, as mi_engine_split_index stores them
+ *   out_pcsp_clades [pcsp_capacity][3]      sister, focal, child of PCSP S + i, each 2 split + side
+ *   out_parent_range [pcsp_capacity][2]     parameter range [begin, end) of block b
+ *   out_pcsp_parent [pcsp_capacity]         the block of PCSP S + i
+ * Rows at and above the counts stay untouched.  S > rootsplit_capacity or C > pcsp_capacity is an
+ * error whose message carries both counts (T0 (2n-3) and 6 T0 (2n-3) always suffice).  A refused
+ * tree is named as by mi_engine_split_index.  The call is not chunked: a batch whose workspace is
+ * over the arena budget (MI_PHYLO_PLV_BYTES) is refused with the sizes in the message.
+ * mi_engine_last_call_path of every SBN call: "sbn n=<n> store=lds|global". */
+int32_t mi_engine_sbn_index(mi_engine* engine, int32_t tree_count, int32_t taxon_count,
+                            const int32_t* parent_ids /* [T][2n-3] */, int32_t support_tree_count,
+                            int32_t rootsplit_capacity, int32_t pcsp_capacity,
+                            int32_t* out_root_index, int32_t* out_slot_index, int32_t* out_counts,
+                            uint32_t* out_split_bits, int32_t* out_pcsp_clades, int32_t* out_parent_range,
+                            int32_t* out_pcsp_parent);
+
+/* Probabilities of a batch under given parameters (SBNProbability::ProbabilityOfSingle in log
+ * space, and the E-step).  log_params [P]: entries may be -inf; NaN and +inf are refused.
+ * normalized = 0: the vector is log-normalised per block first (mi_engine_sbn_normalize).
+ *   out_rooting_log_prob [T][2n-3]  log p_v
+ *   out_log_q [T]
+ *   out_log_expected_counts [P] or NULL: log sum_t w_t usage_t[j], w = tree_weights (NULL: 1;
+ *       finite and >= 0).  usage: rho_v = exp(log p_v - log q) for the rootsplit of v and both
+ *       k = 0 slots of v; a slot (d, k != 0) whose sister lies toward neighbour w of the far node
+ *       x is used by the rootings on the edges beyond x's third neighbour u, the edge (x, u)
+ *       included.  These region sums are formed in log space, one ascending and one descending
+ *       pass: R(d) = log(exp(log rho of d's edge) + exp(R(c1)) + exp(R(c2))) over the child
+ *       directed edges in the order of B above.  Over the trees, a parameter's terms are added in
+ *       ascending (tree, entry) order, entry = edge for a rootsplit, else 2n-3 + 3 d + k: the
+ *       maximum m of the terms, then sum exp(x - m), then m + log.  A parameter no tree uses, and
+ *       a tree with log q = -inf, give -inf resp. add nothing.
+ * This is the E-step and the building block of the gradient with respect to unnormalised
+ * parameters phi (theta = log softmax per block): with G_j = sum_t w_t usage_t[j] and w_t the
+ * coefficients of sum_t w_t log q_t,  d/d phi_j = G_j - exp(theta_j) sum_{i in block(j)} G_i.
+ * Per-tree outputs depend on the tree alone: the same bits alone and inside any batch. */
+int32_t mi_engine_sbn_log_prob(mi_engine* engine, int32_t tree_count, int32_t taxon_count,
+                               const int32_t* parent_ids, const int32_t* root_index, const int32_t* slot_index,
+                               int32_t rootsplit_count, int32_t pcsp_count, int32_t parent_count,
+                               const int32_t* parent_range /* [parent_count][2] */,
+                               const double* log_params /* [P] */, int32_t normalized,
+                               const double* tree_weights /* [T] or NULL */, double* out_rooting_log_prob,
+                               double* out_log_q, double* out_log_expected_counts /* [P] or NULL */);
+
+/* SBNProbability::ProbabilityNormalizeParamsInLog: out[j] = in[j] - logsumexp of j's block, the
+ * rootsplits [0, S) and every parent's range.  A block of up to 16 entries: the maximum m, then
+ * the sum of exp(x - m) in ascending order.  A longer block is a wave's: lane l takes the maximum,
+ * then the sum of exp(x - m), of entries l, l + 64, ..., and the lanes meet in a butterfly (offsets
+ * 32, 16, .., 1).  A block that is all -inf stays -inf.  In place is allowed. */
+int32_t mi_engine_sbn_normalize(mi_engine* engine, int32_t rootsplit_count, int32_t pcsp_count,
+                                int32_t parent_count, const int32_t* parent_range, const double* log_params,
+                                double* out_log_params);
+
+/* Training on the batch (every tree must be in the support: a sentinel in a tree is an error that
+ * names the tree).  tree_weights: the topology counts (NULL: 1); a duplicate tree in the batch is
+ * the same as a larger weight, by linearity.
+ *   MI_SBN_SA  SimpleAverage: the log of the weighted rooting counts (the usage with rho = 1),
+ *              normalised.
+ *   MI_SBN_EM  ExpectationMaximization (src/sbn_probability.cpp:214-329) in its mathematics: start
+ *              from m~ = counts / (2n-3), normalised; per iteration the E-step (log m-bar = the
+ *              expected counts of mi_engine_sbn_log_prob), theta = normalise(log m-bar), with
+ *              alpha > 0 normalise(logaddexp(log m-bar, log alpha + log m~)); the score is
+ *              sum_t w_t log q_t (under the parameters BEFORE the update) plus, for alpha > 0,
+ *              sum_j alpha m~_j theta_j; stop when |score - previous| / |previous| < score_epsilon;
+ *              fail if that ratio falls below the reference's -1e-10.  The reference's replacement
+ *              of a log probability by DOUBLE_MINIMUM after a floating-point exception
+ *              (fetestexcept) is not reproduced: nothing here raises one.
+ *   out_log_params [P]          normalised
+ *   out_score_history [max_iter]  zero beyond out_iterations (EM; may be NULL for SA)
+ *   out_iterations [1]          EM iterations run (0 for SA) */
+enum { MI_SBN_SA = 0, MI_SBN_EM = 1 };
+int32_t mi_engine_sbn_train(mi_engine* engine, int32_t tree_count, int32_t taxon_count,
+                            const int32_t* parent_ids, const int32_t* root_index, const int32_t* slot_index,
+                            int32_t rootsplit_count, int32_t pcsp_count, int32_t parent_count,
+                            const int32_t* parent_range, const double* tree_weights /* [T] or NULL */,
+                            int32_t method, double alpha, int32_t max_iter, double score_epsilon,
+                            double* out_log_params, double* out_score_history, int32_t* out_iterations);
+
 /* Maximum-likelihood branch lengths of unrooted trees under box bounds (an extension: the
  * consumer of the Hessian call's outputs).  Every tree of the batch is
  * iterated on the device: an evaluation is one Hessian pass at a trial point, a step is a
@@ -1130,6 +1250,34 @@ int32_t mi_engine_rf_distances_device(mi_engine* engine, void* stream, int32_t t
                                       const int32_t* split_index, const double* branch_lengths,
                                       int32_t* out_rf, double* out_branch_score);
 int32_t mi_engine_reserve_splits(mi_engine* engine, int32_t tree_count, int32_t taxon_count);
+/* The device forms of the SBN calls: every array a device pointer.  index, log_prob and normalize
+ * only enqueue; errors of the inputs go to the status word (mi_engine_check_status).  After
+ * mi_engine_reserve_sbn(engine, tree_count, taxon_count), log_prob and normalize calls of at most
+ * that many trees of that taxon count, with at most 7 tree_count (2n-3) parameters, allocate
+ * nothing and synchronise nothing: they can be captured in a hipGraph.  mi_engine_sbn_train_device
+ * reads one double per EM iteration and so synchronises the stream: it cannot be captured.  A
+ * sharded handle reserves on its first shard. */
+int32_t mi_engine_sbn_index_device(mi_engine* engine, void* stream, int32_t tree_count, int32_t taxon_count,
+                                   const int32_t* parent_ids, int32_t support_tree_count,
+                                   int32_t rootsplit_capacity, int32_t pcsp_capacity, int32_t* out_root_index,
+                                   int32_t* out_slot_index, int32_t* out_counts, uint32_t* out_split_bits,
+                                   int32_t* out_pcsp_clades, int32_t* out_parent_range, int32_t* out_pcsp_parent);
+int32_t mi_engine_sbn_log_prob_device(mi_engine* engine, void* stream, int32_t tree_count, int32_t taxon_count,
+                                      const int32_t* parent_ids, const int32_t* root_index,
+                                      const int32_t* slot_index, int32_t rootsplit_count, int32_t pcsp_count,
+                                      int32_t parent_count, const int32_t* parent_range, const double* log_params,
+                                      int32_t normalized, const double* tree_weights, double* out_rooting_log_prob,
+                                      double* out_log_q, double* out_log_expected_counts);
+int32_t mi_engine_sbn_normalize_device(mi_engine* engine, void* stream, int32_t rootsplit_count, int32_t pcsp_count,
+                                       int32_t parent_count, const int32_t* parent_range, const double* log_params,
+                                       double* out_log_params);
+int32_t mi_engine_sbn_train_device(mi_engine* engine, void* stream, int32_t tree_count, int32_t taxon_count,
+                                   const int32_t* parent_ids, const int32_t* root_index, const int32_t* slot_index,
+                                   int32_t rootsplit_count, int32_t pcsp_count, int32_t parent_count,
+                                   const int32_t* parent_range, const double* tree_weights, int32_t method,
+                                   double alpha, int32_t max_iter, double score_epsilon, double* out_log_params,
+                                   double* out_score_history, int32_t* out_iterations);
+int32_t mi_engine_reserve_sbn(mi_engine* engine, int32_t tree_count, int32_t taxon_count);
 /* Synchronise `stream` and report the first per-tree error since the last check (the status
  * word is sticky and cleared when an error is reported: calls themselves never clear it). */
 int32_t mi_engine_check_status(mi_engine* engine, void* stream);

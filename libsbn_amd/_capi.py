@@ -168,6 +168,26 @@ SYMBOLS = {
     "mi_engine_rf_distances": (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, _V]),
     "mi_engine_rf_distances_device": (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V]),
     "mi_engine_reserve_splits": (C.c_int32, [_V, C.c_int32, C.c_int32]),
+    "mi_engine_sbn_index":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_sbn_index_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V,
+                     _V]),
+    "mi_engine_sbn_log_prob":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, C.c_int32,
+                     _V, _V, _V, _V]),
+    "mi_engine_sbn_log_prob_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V,
+                     C.c_int32, _V, _V, _V, _V]),
+    "mi_engine_sbn_normalize": (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V]),
+    "mi_engine_sbn_normalize_device": (C.c_int32, [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V]),
+    "mi_engine_sbn_train":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, C.c_int32,
+                     C.c_double, C.c_int32, C.c_double, _V, _V, _V]),
+    "mi_engine_sbn_train_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V,
+                     C.c_int32, C.c_double, C.c_int32, C.c_double, _V, _V, _V]),
+    "mi_engine_reserve_sbn": (C.c_int32, [_V, C.c_int32, C.c_int32]),
     "mi_consensus_tree":
         (C.c_int32, [C.c_int32, C.c_int32, _V, _V, C.c_double, C.c_double, I32P, _V, _V]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),

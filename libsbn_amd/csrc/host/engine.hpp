@@ -99,6 +99,29 @@ struct SplitTable {
   std::vector<double> stats_;
 };
 
+// Engine::SbnIndex (an extension, include/mi_phylo.h): the subsplit support of the first
+// support_tree_count_ trees of a batch and the slots of all its trees.  root_index_ [T][2n-3],
+// slot_index_ [T][2(2n-3)][3]; per rootsplit bits_ [S][W]; per PCSP pcsp_clades_ [C][3] (sister,
+// focal, child, each 2 split + side) and pcsp_parent_ [C]; per parent parent_range_ [parents][2]
+struct SbnSupport {
+  size_t taxon_count_ = 0, tree_count_ = 0, support_tree_count_ = 0;
+  size_t rootsplit_count_ = 0, pcsp_count_ = 0, parent_count_ = 0;
+  std::vector<int32_t> parent_ids_, root_index_, slot_index_, pcsp_clades_, parent_range_, pcsp_parent_;
+  std::vector<uint32_t> bits_;
+  size_t ParameterCount() const { return rootsplit_count_ + pcsp_count_; }
+};
+
+// Engine::SbnLogProb: rooting_log_prob_ [T][2n-3], log_q_ [T] and, asked for,
+// log_expected_counts_ [P]
+struct SbnProbabilities {
+  std::vector<double> rooting_log_prob_, log_q_, log_expected_counts_;
+};
+
+// Engine::SbnTrain: normalised log_params_ [P] and the EM score of every iteration run
+struct SbnTraining {
+  std::vector<double> log_params_, score_history_;
+};
+
 // Engine::RfDistances: rf_ [T][T] and, with branch lengths, branch_score_ [T][T]
 struct TreeDistances {
   std::vector<int32_t> rf_;
@@ -589,6 +612,84 @@ class Engine {
     Check(mi_engine_rf_distances(handle_, static_cast<int32_t>(T), static_cast<int32_t>(n), split_index.data(),
                                  branch_lengths.empty() ? nullptr : branch_lengths.data(), out.rf_.data(),
                                  branch_lengths.empty() ? nullptr : out.branch_score_.data()));
+    return out;
+  }
+
+  // The subsplit support of a batch of unrooted trees and every tree's slots (an extension; any
+  // engine serves): mi_engine_sbn_index.  support_tree_count 0: all trees.
+  SbnSupport SbnIndex(const size_t tree_count, const size_t taxon_count, const std::vector<int32_t>& parent_ids,
+                      const size_t support_tree_count = 0) const {
+    const size_t T = tree_count, n = taxon_count, T0 = support_tree_count ? support_tree_count : T;
+    if (T < 1 || n < 3 || T0 > T || parent_ids.size() != T * (2 * n - 3))
+      Failwith("SbnIndex: parent ids must be [trees][2 taxa - 3], the support trees at most all of them.");
+    const size_t E = 2 * n - 3, W = (n + 31) / 32, rcap = T0 * E, pcap = T0 * E * 6;
+    SbnSupport out;
+    out.taxon_count_ = n;
+    out.tree_count_ = T;
+    out.support_tree_count_ = T0;
+    out.parent_ids_ = parent_ids;
+    out.root_index_.resize(T * E);
+    out.slot_index_.resize(T * E * 6);
+    out.bits_.resize(rcap * W);
+    out.pcsp_clades_.resize(pcap * 3);
+    out.parent_range_.resize(pcap * 2);
+    out.pcsp_parent_.resize(pcap);
+    int32_t counts[3] = {0, 0, 0};
+    Check(mi_engine_sbn_index(handle_, static_cast<int32_t>(T), static_cast<int32_t>(n), parent_ids.data(),
+                              static_cast<int32_t>(T0), static_cast<int32_t>(rcap), static_cast<int32_t>(pcap),
+                              out.root_index_.data(), out.slot_index_.data(), counts, out.bits_.data(),
+                              out.pcsp_clades_.data(), out.parent_range_.data(), out.pcsp_parent_.data()));
+    out.rootsplit_count_ = static_cast<size_t>(counts[0]);
+    out.pcsp_count_ = static_cast<size_t>(counts[1]);
+    out.parent_count_ = static_cast<size_t>(counts[2]);
+    out.bits_.resize(out.rootsplit_count_ * W);
+    out.pcsp_clades_.resize(out.pcsp_count_ * 3);
+    out.parent_range_.resize(out.parent_count_ * 2);
+    out.pcsp_parent_.resize(out.pcsp_count_);
+    return out;
+  }
+
+  // log p of every rooting and log q of every tree of the support's batch under log_params [P],
+  // normalised or not; with tree_weights [T] or expected_counts also the E-step:
+  // mi_engine_sbn_log_prob.
+  SbnProbabilities SbnLogProb(const SbnSupport& support, const std::vector<double>& log_params,
+                              const bool normalized = false, const bool expected_counts = false,
+                              const std::vector<double>& tree_weights = {}) const {
+    const size_t T = support.tree_count_, E = 2 * support.taxon_count_ - 3, P = support.ParameterCount();
+    if (log_params.size() != P || (!tree_weights.empty() && tree_weights.size() != T))
+      Failwith("SbnLogProb: log parameters must be [rootsplits + PCSPs], weights [trees].");
+    SbnProbabilities out;
+    out.rooting_log_prob_.resize(T * E);
+    out.log_q_.resize(T);
+    if (expected_counts) out.log_expected_counts_.resize(P);
+    Check(mi_engine_sbn_log_prob(
+        handle_, static_cast<int32_t>(T), static_cast<int32_t>(support.taxon_count_), support.parent_ids_.data(),
+        support.root_index_.data(), support.slot_index_.data(), static_cast<int32_t>(support.rootsplit_count_),
+        static_cast<int32_t>(support.pcsp_count_), static_cast<int32_t>(support.parent_count_),
+        support.parent_range_.data(), log_params.data(), normalized ? 1 : 0,
+        tree_weights.empty() ? nullptr : tree_weights.data(), out.rooting_log_prob_.data(), out.log_q_.data(),
+        expected_counts ? out.log_expected_counts_.data() : nullptr));
+    return out;
+  }
+
+  // Simple-average (MI_SBN_SA) or EM (MI_SBN_EM) training on the support's own trees, which must
+  // be the first of its batch: mi_engine_sbn_train.  tree_weights [support trees] may be empty.
+  SbnTraining SbnTrain(const SbnSupport& support, const int32_t method, const std::vector<double>& tree_weights = {},
+                       const double alpha = 0.0, const size_t max_iter = 0, const double score_epsilon = 0.0) const {
+    const size_t T = support.support_tree_count_, P = support.ParameterCount();
+    if (!tree_weights.empty() && tree_weights.size() != T) Failwith("SbnTrain: weights must be [support trees].");
+    SbnTraining out;
+    out.log_params_.resize(P);
+    out.score_history_.resize(max_iter ? max_iter : 1);
+    int32_t iterations = 0;
+    Check(mi_engine_sbn_train(
+        handle_, static_cast<int32_t>(T), static_cast<int32_t>(support.taxon_count_), support.parent_ids_.data(),
+        support.root_index_.data(), support.slot_index_.data(), static_cast<int32_t>(support.rootsplit_count_),
+        static_cast<int32_t>(support.pcsp_count_), static_cast<int32_t>(support.parent_count_),
+        support.parent_range_.data(), tree_weights.empty() ? nullptr : tree_weights.data(), method, alpha,
+        static_cast<int32_t>(max_iter), score_epsilon, out.log_params_.data(), out.score_history_.data(),
+        &iterations));
+    out.score_history_.resize(static_cast<size_t>(iterations));
     return out;
   }
 

@@ -94,6 +94,10 @@ enum StatusCode : int32_t {
   kBadPendantLength = 12,
   kBadSprMove = 13,
   kSplitCapacity = 14,  // (its second status word carries S, not a tree)
+  kSbnCapacity = 15,    // (its second and fourth status words carry S and C)
+  kSbnBadParam = 16,    // (its second status word carries the parameter's index)
+  kSbnBadWeight = 17,
+  kSbnOutOfSupport = 18,
 };
 
 }  // namespace miphylo

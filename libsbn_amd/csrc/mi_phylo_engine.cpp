@@ -86,6 +86,10 @@ int check_status(mi_engine* e, hipStream_t s) {
                   std::to_string(st[1]) + ")");
     // (the split table's capacity: its second word is the number of distinct splits)
     if (st[0] == kSplitCapacity) return fail(std::string(status_message(st[0])) + " (S = " + std::to_string(st[1]) + ")");
+    // (the SBN support's capacities: both needed counts)
+    if (st[0] == kSbnCapacity)
+      return fail(std::string(status_message(st[0])) + " (S = " + std::to_string(st[1]) + ", C = " + std::to_string(st[3]) + ")");
+    if (st[0] == kSbnBadParam) return fail(std::string(status_message(st[0])) + " (parameter " + std::to_string(st[1]) + ")");
     return fail(std::string(status_message(st[0])) + (st[0] == kBadDistance ? " (matrix " : " (tree ") +
                 std::to_string(st[1] + e->status_tree_offset) + ")");
   }
@@ -456,7 +460,8 @@ void mi_engine_destroy(mi_engine* e) {
         &e->pattern_blank, &e->pattern_ll_out, &e->rell_ws, &e->rell_s, &e->dist_codes, &e->dist_model,
         &e->dist_counts, &e->dist_matrix, &e->nj_ws, &e->place_bl, &e->place_half, &e->place_pend,
         &e->place_table, &e->spr_bl, &e->spr_half, &e->spr_ws, &e->spr_path,
-        &e->spr_apply_ws, &e->spr_search_ws, &e->split_ws, &e->split_store, &e->split_sort, &e->rf_ws})
+        &e->spr_apply_ws, &e->spr_search_ws, &e->split_ws, &e->split_store, &e->split_sort, &e->rf_ws, &e->sbn_index_ws,
+        &e->sbn_prob_ws, &e->sbn_store})
     b->release();
   if (e->opt_word) (void)hipHostFree(e->opt_word);
   e->pinned.release();

@@ -12,6 +12,7 @@
 //   mi_phylo_rell.cpp         per-pattern log-likelihoods (device form), RELL re-summation, tree mixtures
 //   mi_phylo_start_trees.cpp  pairwise distances, neighbour joining, starting trees (device forms, reservation)
 //   mi_phylo_splits.cpp       split tables, Robinson-Foulds distances (device and host forms, reservation), mi_consensus_tree
+//   mi_phylo_sbn.cpp          subsplit Bayesian networks: support and slots, probabilities, normalisation, training
 //   mi_phylo_host_calls.cpp   what runs a host-pointer call (staging, status, shards), the plain entry points
 //   mi_phylo_engine_aa.cpp    20-state call sequence
 #pragma once
@@ -141,6 +142,10 @@ inline const char* status_message(int code) {
     case kBadSprMove:
       return "SPR move is neither (-1, -1, -1) nor a triple (s, dir, f) that mi_spr_neighbour takes";
     case kSplitCapacity: return "split index: the batch has more distinct splits than split_capacity";
+    case kSbnCapacity: return "SBN index: the support has more rootsplits or PCSPs than the capacities";
+    case kSbnBadParam: return "SBN log parameters must be finite or -inf";
+    case kSbnBadWeight: return "SBN tree weights must be finite and not negative";
+    case kSbnOutOfSupport: return "SBN training: a training tree has a rootsplit or PCSP outside the support";
     default: return "unknown device status";
   }
 }
@@ -221,6 +226,10 @@ struct mi_engine {
   Buffer split_ws;     // occurrences: bitsets [O][W] | hashes, then flags and ranks [O] 8 bytes | slots [O] | the table: owner, first, trees [slots] each | the scan's temporary storage
   Buffer split_store;  // tree_splits_kernel's working bitsets of trees too large for LDS
   Buffer split_sort;   // the statistics' sort: keys, values, sorted keys, sorted values [O] each | rocPRIM's temporary storage
+  // subsplit Bayesian networks (mi_engine_sbn_*)
+  Buffer sbn_index_ws;  // the index call: the batch's split table | PCSP occurrences, the two tables, the sort and the scan
+  Buffer sbn_prob_ws;   // log_prob / normalize / train: normalised parameters | usages | the accumulation's sort | training vectors
+  Buffer sbn_store;     // the per-tree kernels' node arrays of trees too large for LDS
   Buffer rf_ws;        // a batch's sorted lists: lengths [T][2n-3] | indices [T][2n-3] | counts [T]
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)

@@ -615,6 +615,87 @@ struct RfArgs {
   double* out_bs;              // [T][T] or nullptr
 };
 void launch_rf(const RfArgs& a, hipStream_t s);
+// kernels_sbn.hip: subsplit Bayesian networks over tree batches.  A tree has
+// E = 2n-3 edges, 2E directed edges d = 2v + s and 3 slots per directed edge; a PCSP occurrence
+// is numbered o = (t 2E + d) 3 + k.  The per-tree kernels give a tree to a LANE; a wave holds
+// `tpw` trees (MI_PHYLO_SBN_TREES_PER_WAVE) and the per-node arrays of its trees, six 32-bit
+// words per node laid out [word][node][tpw], are in LDS while they fit 160 KiB, else in `store`.
+constexpr int kSbnNodeWords = 6;  // child 0, child 1, two doubles (or four ints)
+constexpr int kSbnDefaultTreesPerWave = 16;
+inline __host__ __device__ size_t sbn_store_bytes_per_wave(int n, int tpw) {
+  return (2 * (size_t)n - 2) * kSbnNodeWords * 4 * tpw;
+}
+inline int sbn_lds_taxa(int tpw) { return (int)((160 * 1024 / (kSbnNodeWords * 4 * tpw) + 2) / 2); }
+inline size_t sbn_wave_count(int T, int tpw) { return ((size_t)T + tpw - 1) / tpw; }
+struct SbnIndexArgs {
+  int n, T, T0, W, tpw;
+  int root_capacity, pcsp_capacity;
+  int hash_bits;
+  uint32_t slots;               // table slots (each of the two tables), a power of two
+  const int32_t* parent_ids;    // [T][2n-3]
+  int32_t* status;
+  // workspace
+  char* store;                  // [waves][sbn_store_bytes_per_wave] (n > sbn_lds_taxa)
+  const int32_t* split_index;   // [T][2n-1] of the whole batch
+  const int32_t* split_first;   // [T (2n-3)] first occurrences of the batch's splits
+  const int32_t* split_count;   // [1]
+  const uint32_t* split_bits;   // [T (2n-3)][W]
+  int32_t* counts;              // [4] S, C, parents, spare
+  int32_t* occ_key;             // [O][3] sister, focal, child clades (2 split + side); sister -1: no such slot
+  int32_t* occ_slot;            // [O] slot in the PCSP table
+  int32_t* occ_pslot;           // [O] slot in the parent table
+  int32_t *slot_owner, *slot_first, *pslot_owner, *pslot_first;  // [slots] each
+  uint64_t *keys, *keys2;       // [O] (parent's first occurrence, own first occurrence); all ones: not a first occurrence
+  uint32_t *vals, *vals2;       // [O]
+  uint32_t *heads, *head_scan;  // [O] block heads in sorted order and their inclusive scan
+  int32_t* rank_of;             // [O] sorted position of a first occurrence
+  void *sort_tmp, *scan_tmp;
+  size_t sort_tmp_bytes, scan_tmp_bytes;
+  // outputs
+  int32_t* out_root_index;      // [T][2n-3]
+  int32_t* out_slot_index;      // [T][2(2n-3)][3]
+  int32_t* out_counts;          // [3]
+  uint32_t* out_split_bits;     // [root_capacity][W]
+  int32_t* out_pcsp_clades;     // [pcsp_capacity][3]
+  int32_t* out_parent_range;    // [pcsp_capacity][2]
+  int32_t* out_pcsp_parent;     // [pcsp_capacity]
+};
+size_t sbn_index_sort_tmp_bytes(size_t occurrences);
+size_t sbn_index_scan_tmp_bytes(size_t occurrences);
+int launch_sbn_index(const SbnIndexArgs& a, hipStream_t s);  // (after the split table; nonzero: rocPRIM refused)
+struct SbnProbArgs {
+  int n, T, tpw;
+  int P;                        // parameters: rootsplits + PCSPs (the sentinel)
+  int uniform;                  // 1: every rooting has weight 1 (the counts of simple-average training)
+  int require_support;          // 1: a sentinel in a tree is an error (training)
+  const int32_t* parent_ids;    // [T][2n-3]
+  const int32_t* root_index;    // [T][2n-3]
+  const int32_t* slot_index;    // [T][2(2n-3)][3]
+  const double* theta;          // [P] normalised log parameters
+  const double* weights;        // [T] or nullptr
+  int32_t* status;
+  char* store;
+  double* usage;                // [T][7 (2n-3)] log usage of every entry (roots, then slots), or nullptr
+  uint32_t *keys, *keys2, *vals, *vals2;  // [T 7 (2n-3)] the accumulation's sort
+  void* sort_tmp;
+  size_t sort_tmp_bytes;
+  double* out_rooting;          // [T][2n-3]
+  double* out_log_q;            // [T]
+  double* out_counts;           // [P] or nullptr
+};
+size_t sbn_prob_sort_tmp_bytes(size_t entries, int P);
+void sbn_prepare(int n, int tpw);  // the large-LDS opt-in (before a graph capture)
+int launch_sbn_log_prob(const SbnProbArgs& a, hipStream_t s);
+// out[j] = in[j] - logsumexp(block of j): block 0 is [0, S), block b > 0 is parent_range[b-1]
+void launch_sbn_normalize(int S, int parents, const int32_t* parent_range, const double* in, double* out,
+                          hipStream_t s);
+// status if an entry is NaN or +inf
+void launch_sbn_check_params(int P, const double* theta, int32_t* status, hipStream_t s);
+// out[j] = log(exp(a[j]) + exp(b[j] + shift)) (b nullptr: a[j] + shift)
+void launch_sbn_combine(int P, const double* a, const double* b, double shift, double* out, hipStream_t s);
+// *out = sum_t w_t log_q[t] (+ sum_j exp(log_m[j]) theta[j] if log_m), in ascending order by one wave
+void launch_sbn_score(int T, const double* weights, const double* log_q, int P, const double* log_m,
+                      const double* theta, double* out, hipStream_t s);
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
 // the first, gradient_mfma_kernel, was retired in round 6): all categories of a group of four
 // per instruction; they also write the log-likelihood partial sums, so no separate logL pass is

@@ -41,6 +41,8 @@ struct Switches {
   bool place_table_global = false;  // PLACE_TABLE=global: the scoring gathers from memory even where the table fits LDS
   // split tables
   int split_hash_bits = 32;  // SPLIT_HASH_BITS: bits of the hash that choose the first slot (testing: 0 sends every split to slot 0)
+  // subsplit Bayesian networks
+  int sbn_trees_per_wave = 16;  // SBN_TREES_PER_WAVE: trees (lanes at work) per wave of the per-tree kernels, 16 | 32 | 64
   // 20-state kernels
   bool aa_jacobi_seq = false;        // AA_JACOBI=seq
   bool aa_post_wave = false;         // AA_POST=wave

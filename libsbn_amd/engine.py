@@ -279,6 +279,102 @@ def split_strings(bits, taxon_count):
     return ["".join("1" if (int(row[i >> 5]) >> (i & 31)) & 1 else "0" for i in range(n)) for row in b]
 
 
+@dataclass
+class SbnSupport:
+    """Engine.sbn_index: the subsplit support of trees 0 .. support_tree_count-1 of a batch with
+    its parameter numbering, and the slots of every tree of the batch (include/mi_phylo.h)."""
+    taxon_count: int
+    parent_ids: np.ndarray     # [T][2n-3] the batch
+    support_tree_count: int
+    root_index: np.ndarray     # [T][2n-3] parameter index of edge v's rootsplit, or P
+    slot_index: np.ndarray     # [T][2(2n-3)][3] -1: no such slot; P: outside the support
+    split_bits: np.ndarray     # [S][W] the rootsplits, as SplitTable.bits
+    pcsp_clades: np.ndarray    # [C][3] sister, focal, child of PCSP S + i, each 2 split + side
+    parent_range: np.ndarray   # [parents][2] parameter range [begin, end) of every block
+    pcsp_parent: np.ndarray    # [C] block of PCSP S + i
+
+    @property
+    def rootsplit_count(self):
+        return int(self.split_bits.shape[0])
+
+    @property
+    def pcsp_count(self):
+        return int(self.pcsp_clades.shape[0])
+
+    @property
+    def parent_count(self):
+        return int(self.parent_range.shape[0])
+
+    @property
+    def parameter_count(self):
+        return self.rootsplit_count + self.pcsp_count
+
+
+def _clade_strings(support):
+    """"01110" of clade 2 split + side, for every clade the PCSPs name."""
+    n = support.taxon_count
+    plain = split_strings(support.split_bits, n)
+    flip = ["".join("1" if c == "0" else "0" for c in s) for s in plain]
+    return lambda clade: (flip if clade & 1 else plain)[clade >> 1]
+
+
+def sbn_strings(support):
+    """The reference's pretty indexer of a support (PrettyIndexer): "01110" for a rootsplit,
+    "00001|11110|01110" (sister|focal|child) for a PCSP, in parameter order."""
+    name = _clade_strings(support)
+    return split_strings(support.split_bits, support.taxon_count) + \
+        ["|".join(name(int(c)) for c in row) for row in support.pcsp_clades]
+
+
+def sbn_rooted_representations(support, t):
+    """Tree t's slots expanded to the reference's per-rooting index lists
+    (UnrootedSBNMaps::IndexerRepresentationOf): [2n-3] lists, the rootsplit first.  A host helper
+    for tests and small n: it walks the tree once per slot."""
+    pid = [int(p) for p in support.parent_ids[t]]
+    E = len(pid)
+    kids = [[] for _ in range(E + 1)]
+    for v in range(E):
+        kids[pid[v]].append(v)
+    slot = support.slot_index[t].reshape(2 * E, 3)
+    out = [[int(support.root_index[t][v])] for v in range(E)]
+
+    def below(v):  # the edges of the clade below v, its own included
+        edges, stack = [], [v]
+        while stack:
+            x = stack.pop()
+            edges.append(x)
+            stack.extend(kids[x])
+        return edges
+
+    def above(v):  # the edges on the other side of node pid[v], the edge above it included
+        p, edges = pid[v], []
+        for c in kids[p]:
+            if c != v:
+                edges += below(c)
+        return edges if p == E else edges + [p] + above(p)
+
+    for v in range(E):
+        p = pid[v]
+        # the two other neighbours of p: the regions beyond them
+        if p == E:
+            x, y = [c for c in kids[p] if c != v]
+            beyond = [below(x), below(y)]
+        else:
+            x = [c for c in kids[p] if c != v][0]
+            beyond = [below(x), [p] + above(p)]
+        for s in (0, 1):
+            d = 2 * v + s
+            if slot[d][0] >= 0:
+                out[v].append(int(slot[d][0]))
+            regions = beyond if s == 0 else ([below(c) for c in kids[v]] if kids[v] else [])
+            for k in (1, 2):
+                if slot[d][k] >= 0:
+                    # the sister lies toward region k-1: the rootings in the other region use it
+                    for edge in regions[2 - k]:
+                        out[edge].append(int(slot[d][k]))
+    return out
+
+
 def consensus_tree(taxon_count, split_bits, split_weight, total_weight, threshold=0.5):
     """The majority-rule consensus tree of a split table (mi_consensus_tree: host arithmetic
     only): every nontrivial split with weight > threshold * total_weight, threshold in
@@ -802,6 +898,92 @@ class Engine:
         S = int(count[0])
         return SplitTable(n, index, bits[:S].copy(), first[:S].copy(), trees[:S].copy(), stats[:S].copy())
 
+    def sbn_index(self, parent_ids, support_tree_count=None, rootsplit_capacity=None, pcsp_capacity=None):
+        """The subsplit support of a batch of unrooted trees [T][2n-3] and every tree's slots
+        (mi_engine_sbn_index; any engine serves).  The support is that of the first
+        support_tree_count trees (default: all); the later ones are only looked up and get the
+        sentinel P where they leave it.  Capacities default to what always suffices.  Returns an
+        SbnSupport."""
+        pid = _np(parent_ids, np.int32)
+        if pid.ndim == 1:
+            pid = pid[None]
+        if pid.ndim != 2 or pid.shape[0] < 1 or pid.shape[1] < 3 or pid.shape[1] % 2 == 0:
+            raise RuntimeError(f"sbn_index takes parent ids [T][2n-3], n >= 3; got {pid.shape}")
+        T, E = pid.shape
+        n = (E + 3) // 2
+        T0 = T if support_tree_count is None else int(support_tree_count)
+        rcap = max(T0, 1) * E if rootsplit_capacity is None else int(rootsplit_capacity)
+        pcap = max(T0, 1) * E * 6 if pcsp_capacity is None else int(pcsp_capacity)
+        W = (n + 31) // 32
+        root, slot = np.empty((T, E), np.int32), np.empty((T, 2 * E, 3), np.int32)
+        counts = np.zeros(3, np.int32)
+        bits, clades = np.zeros((rcap, W), np.uint32), np.zeros((pcap, 3), np.int32)
+        prange, parent = np.zeros((pcap, 2), np.int32), np.zeros(pcap, np.int32)
+        self._check(self._lib.mi_engine_sbn_index(
+            self._h, T, n, _ptr(pid), T0, rcap, pcap, _ptr(root), _ptr(slot), _ptr(counts), _ptr(bits),
+            _ptr(clades), _ptr(prange), _ptr(parent)))
+        S, Cn, parents = (int(x) for x in counts)
+        return SbnSupport(n, pid.copy(), T0, root, slot, bits[:S].copy(), clades[:Cn].copy(),
+                          prange[:parents].copy(), parent[:Cn].copy())
+
+    def _sbn_trees(self, support, trees):
+        """(parent ids, root index, slot index) of `trees`: None (the support's own batch), a
+        range / index array into it, or an SbnSupport indexed against the same support."""
+        if trees is None:
+            return support.parent_ids, support.root_index, support.slot_index
+        if isinstance(trees, SbnSupport):
+            return trees.parent_ids, trees.root_index, trees.slot_index
+        idx = np.arange(support.parent_ids.shape[0])[trees]
+        return (np.ascontiguousarray(support.parent_ids[idx]), np.ascontiguousarray(support.root_index[idx]),
+                np.ascontiguousarray(support.slot_index[idx]))
+
+    def sbn_log_prob(self, support, log_params, trees=None, normalized=False, tree_weights=None,
+                     expected_counts=False):
+        """log p of every rooting [T][2n-3] and log q [T] of trees of a support's batch under
+        log_params [P] (mi_engine_sbn_log_prob); with expected_counts also
+        log sum_t w_t usage_t [P] (the E-step).  trees: see _sbn_trees."""
+        pid, root, slot = self._sbn_trees(support, trees)
+        T, E = pid.shape
+        P = support.parameter_count
+        th = _np(log_params, np.float64).reshape(P)
+        tw = None if tree_weights is None else _np(tree_weights, np.float64).reshape(T)
+        lp, lq = np.empty((T, E)), np.empty(T)
+        counts = np.empty(P) if expected_counts else None
+        self._check(self._lib.mi_engine_sbn_log_prob(
+            self._h, T, support.taxon_count, _ptr(pid), _ptr(root), _ptr(slot), support.rootsplit_count,
+            support.pcsp_count, support.parent_count, _ptr(support.parent_range), _ptr(th), int(bool(normalized)),
+            _ptr(tw), _ptr(lp), _ptr(lq), _ptr(counts)))
+        return (lp, lq, counts) if expected_counts else (lp, lq)
+
+    def sbn_normalize(self, support, log_params):
+        """Log-normalise log_params [P] over the rootsplits and every parent's block
+        (mi_engine_sbn_normalize)."""
+        P = support.parameter_count
+        th, out = _np(log_params, np.float64).reshape(P), np.empty(P)
+        self._check(self._lib.mi_engine_sbn_normalize(
+            self._h, support.rootsplit_count, support.pcsp_count, support.parent_count,
+            _ptr(support.parent_range), _ptr(th), _ptr(out)))
+        return out
+
+    def sbn_train(self, support, method="sa", tree_weights=None, alpha=0.0, max_iter=0, score_epsilon=0.0,
+                  trees=None):
+        """Simple-average ("sa") or EM ("em") training on trees of a support's batch (default: its
+        support trees) with topology counts tree_weights (mi_engine_sbn_train).  Returns
+        (normalised log parameters [P], score history [iterations])."""
+        if method not in ("sa", "em"):
+            raise RuntimeError(f"sbn_train: method must be 'sa' or 'em', got {method!r}")
+        pid, root, slot = self._sbn_trees(support, slice(0, support.support_tree_count) if trees is None else trees)
+        T = pid.shape[0]
+        P = support.parameter_count
+        tw = None if tree_weights is None else _np(tree_weights, np.float64).reshape(T)
+        out, history, iters = np.empty(P), np.zeros(max(int(max_iter), 1)), np.zeros(1, np.int32)
+        self._check(self._lib.mi_engine_sbn_train(
+            self._h, T, support.taxon_count, _ptr(pid), _ptr(root), _ptr(slot), support.rootsplit_count,
+            support.pcsp_count, support.parent_count, _ptr(support.parent_range), _ptr(tw),
+            0 if method == "sa" else 1, float(alpha), int(max_iter), float(score_epsilon), _ptr(out),
+            _ptr(history), _ptr(iters)))
+        return out, history[:int(iters[0])].copy()
+
     def rf_distances(self, split_index, branch_lengths=None):
         """Robinson-Foulds distances [T][T] between the trees of a split index [T][2n-1]
         (mi_engine_rf_distances); with branch_lengths [T][2n-2] also the squared
@@ -1242,6 +1424,46 @@ class Engine:
         """mi_engine_reserve_splits: workspace of the two calls above for that many trees of
         that taxon count (their *_device forms then allocate nothing: graph capture)."""
         self._check(self._lib.mi_engine_reserve_splits(self._h, int(tree_count), int(taxon_count)))
+
+    def sbn_index_device(self, stream, T, n, parent_ids, support_tree_count, rootsplit_capacity, pcsp_capacity,
+                         out_root_index, out_slot_index, out_counts, out_split_bits, out_pcsp_clades,
+                         out_parent_range, out_pcsp_parent):
+        """mi_engine_sbn_index_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_sbn_index_device(
+            self._h, stream, int(T), int(n), parent_ids, int(support_tree_count), int(rootsplit_capacity),
+            int(pcsp_capacity), out_root_index, out_slot_index, out_counts, out_split_bits, out_pcsp_clades,
+            out_parent_range, out_pcsp_parent))
+
+    def sbn_log_prob_device(self, stream, T, n, parent_ids, root_index, slot_index, rootsplit_count, pcsp_count,
+                            parent_count, parent_range, log_params, normalized, out_rooting_log_prob, out_log_q,
+                            out_log_expected_counts=None, tree_weights=None):
+        """mi_engine_sbn_log_prob_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_sbn_log_prob_device(
+            self._h, stream, int(T), int(n), parent_ids, root_index, slot_index, int(rootsplit_count),
+            int(pcsp_count), int(parent_count), parent_range, log_params, int(bool(normalized)), tree_weights,
+            out_rooting_log_prob, out_log_q, out_log_expected_counts))
+
+    def sbn_normalize_device(self, stream, rootsplit_count, pcsp_count, parent_count, parent_range, log_params,
+                             out_log_params):
+        """mi_engine_sbn_normalize_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_sbn_normalize_device(
+            self._h, stream, int(rootsplit_count), int(pcsp_count), int(parent_count), parent_range, log_params,
+            out_log_params))
+
+    def sbn_train_device(self, stream, T, n, parent_ids, root_index, slot_index, rootsplit_count, pcsp_count,
+                         parent_count, parent_range, method, alpha, max_iter, score_epsilon, out_log_params,
+                         out_score_history, out_iterations, tree_weights=None):
+        """mi_engine_sbn_train_device: device pointers; synchronises `stream` (one double is read
+        per EM iteration), so it cannot be captured in a graph."""
+        self._check(self._lib.mi_engine_sbn_train_device(
+            self._h, stream, int(T), int(n), parent_ids, root_index, slot_index, int(rootsplit_count),
+            int(pcsp_count), int(parent_count), parent_range, tree_weights, 0 if method == "sa" else 1,
+            float(alpha), int(max_iter), float(score_epsilon), out_log_params, out_score_history, out_iterations))
+
+    def reserve_sbn(self, tree_count, taxon_count):
+        """mi_engine_reserve_sbn: workspace of the SBN calls for that many trees of that taxon
+        count (sbn_log_prob_device and sbn_normalize_device then allocate nothing: graph capture)."""
+        self._check(self._lib.mi_engine_reserve_sbn(self._h, int(tree_count), int(taxon_count)))
 
     def pattern_mixture_device(self, stream, T, P, pattern_ll, pattern_weights, out_pattern_log_marginal,
                                out_log_marginal, tree_log_weights=None):
