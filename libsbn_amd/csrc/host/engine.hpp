@@ -767,30 +767,7 @@ class Engine {
   std::vector<NniSearchEnd> NniSearch(const UnrootedTreeCollection& trees, const ParamMatrix& params,
                                       const bool rescaling,
                                       const mi_nni_search_options* options = nullptr) const {
-    const size_t T = trees.size(), N = 2 * site_pattern_.SequenceCount() - 1;
-    const size_t M = options ? static_cast<size_t>(std::max(options->max_moves, 0)) : 100;
-    std::vector<int32_t> parents;
-    std::vector<double> bl;
-    Flatten(trees, params, false, &parents, &bl);
-    if (trees.empty()) return {};
-    std::vector<int32_t> pid(T * (N - 2)), count(T), log(T * M + 1), status(T), opt_status(T);
-    std::vector<double> t(T * (N - 1)), ll(T), delta(T), gain(T * M + 1);
-    Check(mi_engine_nni_search_unrooted(
-        handle_, static_cast<int32_t>(T), parents.data(), bl.data(), params.data.data(), rescaling,
-        options, pid.data(), t.data(), ll.data(), delta.data(), count.data(), log.data(), gain.data(),
-        status.data(), opt_status.data()));
-    std::vector<NniSearchEnd> out(T);
-    for (size_t i = 0; i < T; i++) {
-      out[i].parent_ids_.assign(pid.begin() + i * (N - 2), pid.begin() + (i + 1) * (N - 2));
-      out[i].branch_lengths_.assign(t.begin() + i * (N - 1), t.begin() + (i + 1) * (N - 1));
-      out[i].log_likelihood_ = ll[i];
-      out[i].best_delta_ = delta[i];
-      out[i].moves_.assign(log.begin() + i * M, log.begin() + i * M + count[i]);
-      out[i].gains_.assign(gain.begin() + i * M, gain.begin() + i * M + count[i]);
-      out[i].status_ = status[i];
-      out[i].branch_opt_status_ = opt_status[i];
-    }
-    return out;
+    return Search<NniSearchEnd>(mi_engine_nni_search_unrooted, 1, trees, params, rescaling, options);
   }
 
   // One SPR move per tree on the device (an extension): mi_engine_spr_apply_unrooted.  moves
@@ -823,30 +800,7 @@ class Engine {
   std::vector<SprSearchEnd> SprSearch(const UnrootedTreeCollection& trees, const ParamMatrix& params,
                                       const bool rescaling,
                                       const mi_spr_search_options* options = nullptr) const {
-    const size_t T = trees.size(), N = 2 * site_pattern_.SequenceCount() - 1;
-    const size_t M = options ? static_cast<size_t>(std::max(options->max_moves, 0)) : 100;
-    std::vector<int32_t> parents;
-    std::vector<double> bl;
-    Flatten(trees, params, false, &parents, &bl);
-    if (trees.empty()) return {};
-    std::vector<int32_t> pid(T * (N - 2)), count(T), log(3 * T * M + 1), status(T), opt_status(T);
-    std::vector<double> t(T * (N - 1)), ll(T), delta(T), gain(T * M + 1);
-    Check(mi_engine_spr_search_unrooted(
-        handle_, static_cast<int32_t>(T), parents.data(), bl.data(), params.data.data(), rescaling,
-        options, pid.data(), t.data(), ll.data(), delta.data(), count.data(), log.data(), gain.data(),
-        status.data(), opt_status.data()));
-    std::vector<SprSearchEnd> out(T);
-    for (size_t i = 0; i < T; i++) {
-      out[i].parent_ids_.assign(pid.begin() + i * (N - 2), pid.begin() + (i + 1) * (N - 2));
-      out[i].branch_lengths_.assign(t.begin() + i * (N - 1), t.begin() + (i + 1) * (N - 1));
-      out[i].log_likelihood_ = ll[i];
-      out[i].best_delta_ = delta[i];
-      out[i].moves_.assign(log.begin() + 3 * i * M, log.begin() + 3 * (i * M + count[i]));
-      out[i].gains_.assign(gain.begin() + i * M, gain.begin() + i * M + count[i]);
-      out[i].status_ = status[i];
-      out[i].branch_opt_status_ = opt_status[i];
-    }
-    return out;
+    return Search<SprSearchEnd>(mi_engine_spr_search_unrooted, 3, trees, params, rescaling, options);
   }
 
   std::vector<PhyloGradient> Gradients(const RootedTreeCollection& trees,
@@ -935,6 +889,35 @@ class Engine {
       pp = std::copy(tree.parent_ids.begin(), tree.parent_ids.end(), pp);
       pb = std::copy(tree.branch_lengths.begin(), tree.branch_lengths.end(), pb);
     }
+  }
+
+  // NniSearch and SprSearch: the C function of the kind of move, the entries of moves_ per move
+  template <class End, class Fn, class Options>
+  std::vector<End> Search(Fn search, const size_t width, const UnrootedTreeCollection& trees,
+                          const ParamMatrix& params, const bool rescaling, const Options* options) const {
+    const size_t T = trees.size(), N = 2 * site_pattern_.SequenceCount() - 1;
+    const size_t M = options ? static_cast<size_t>(std::max(options->max_moves, 0)) : 100;
+    std::vector<int32_t> parents;
+    std::vector<double> bl;
+    Flatten(trees, params, false, &parents, &bl);
+    if (trees.empty()) return {};
+    std::vector<int32_t> pid(T * (N - 2)), count(T), log(width * T * M + 1), status(T), opt_status(T);
+    std::vector<double> t(T * (N - 1)), ll(T), delta(T), gain(T * M + 1);
+    Check(search(handle_, static_cast<int32_t>(T), parents.data(), bl.data(), params.data.data(), rescaling,
+                 options, pid.data(), t.data(), ll.data(), delta.data(), count.data(), log.data(), gain.data(),
+                 status.data(), opt_status.data()));
+    std::vector<End> out(T);
+    for (size_t i = 0; i < T; i++) {
+      out[i].parent_ids_.assign(pid.begin() + i * (N - 2), pid.begin() + (i + 1) * (N - 2));
+      out[i].branch_lengths_.assign(t.begin() + i * (N - 1), t.begin() + (i + 1) * (N - 1));
+      out[i].log_likelihood_ = ll[i];
+      out[i].best_delta_ = delta[i];
+      out[i].moves_.assign(log.begin() + width * i * M, log.begin() + width * (i * M + count[i]));
+      out[i].gains_.assign(gain.begin() + i * M, gain.begin() + i * M + count[i]);
+      out[i].status_ = status[i];
+      out[i].branch_opt_status_ = opt_status[i];
+    }
+    return out;
   }
 
   std::vector<double> RootedLogLikelihoods(const RootedTreeCollection& trees,

@@ -7,8 +7,7 @@
 //   mi_phylo_branch_opt.cpp   branch-length optimisation
 //   mi_phylo_nni.cpp          mi_nni_neighbour, the scan's best move on the host (no device code)
 //   mi_phylo_spr.cpp          mi_spr_neighbour (no device code)
-//   mi_phylo_nni_search.cpp   NNI moves on the device, the NNI hill-climbing search
-//   mi_phylo_spr_search.cpp   SPR moves on the device, the SPR hill-climbing search
+//   mi_phylo_search.cpp       NNI and SPR moves on the device, the two hill-climbing searches
 //   mi_phylo_rell.cpp         per-pattern log-likelihoods (device form), RELL re-summation, tree mixtures
 //   mi_phylo_start_trees.cpp  pairwise distances, neighbour joining, starting trees (device forms, reservation)
 //   mi_phylo_splits.cpp       split tables, Robinson-Foulds distances (device and host forms, reservation), mi_consensus_tree

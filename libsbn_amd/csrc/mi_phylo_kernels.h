@@ -376,85 +376,42 @@ void launch_branch_opt_init(const BranchOptArgs& a, const double* start, hipStre
 void launch_branch_opt_step(const BranchOptArgs& a, hipStream_t s);
 void launch_branch_opt_pack(const BranchOptPackArgs& a, int old_count, const int32_t* map_old,
                             const int32_t* status, hipStream_t s);
-// The NNI hill-climbing search (kernels_nni_search.hip): taking NNI moves on the
-// device in the reference's numbering, and the per-tree step between two rounds of the search.
-// A wave per tree; the working arrays of a tree (six of 2n-2 words and eight more) are in LDS
-// up to kNniApplyLdsNodes nodes, else in `ws`.
+// The hill-climbing searches (kernels_search.hip): taking NNI and SPR
+// moves on the device in the reference's numbering, and the per-tree step between two rounds of
+// a search.  A wave per tree; the working arrays of a tree (NNI: six of 2n-2 words and eight
+// more, SPR: seven) are in LDS up to k{Nni,Spr}ApplyLdsNodes nodes, else in `ws`.
 constexpr int kNniApplyLdsNodes = 512, kNniApplyArrays = 6, kNniApplyExtra = 8;
+constexpr int kSprApplyLdsNodes = 512, kSprApplyArrays = 7, kSprApplyExtra = 8;
 inline __host__ __device__ size_t nni_apply_ws_words(int n) {  // per tree; 0: the arrays are in LDS
   const size_t R = 2 * (size_t)n - 2;
   return R > kNniApplyLdsNodes ? kNniApplyArrays * R + kNniApplyExtra : 0;
 }
-struct NniApplyArgs {
-  int n, T;
-  const int32_t* parent_ids;  // [T][2n-3]
-  const double* bl;           // [T][2n-2]
-  const int32_t* moves;       // [T] 2 v + i, or -1: copy
-  int32_t* ws;                // [T][nni_apply_ws_words(n)]
-  int32_t* status;            // the engine's status word
-  int32_t* out_parent_ids;    // [T][2n-3]  (no output may overlap an input)
-  double* out_bl;             // [T][2n-2]
-};
-void launch_nni_apply(const NniApplyArgs& a, hipStream_t s);
-constexpr int kNniSearchActive = -1;  // internal; the rest are mi_phylo.h's MI_NNI_SEARCH_*
-struct NniSearchStepArgs {
-  int n, count, round, max_moves;  // count: trees of the packed set
-  double min_gain;
-  const int32_t* map;  // [count] packed position -> tree, or nullptr
-  // this round's results, by packed position
-  const double *opt_bl, *opt_ll;  // [count][2n-2], [count]
-  const int32_t* opt_status;      // [count]
-  const double* delta;            // [count][2n-1][2]
-  const int32_t* best;            // [count]
-  // the trees by tree index: this round's and the other half of the pair
-  const int32_t* cur_pid;  // [T][2n-3]
-  double* cur_bl;          // [T][2n-2]
-  int32_t* next_pid;
-  double* next_bl;
-  // the packed inputs of the next round (map != nullptr)
-  int32_t* pk_pid;  // [count][2n-3]
-  double* pk_bl;    // [count][2n-2]
-  int32_t* ws;      // [count][nni_apply_ws_words(n)]
-  int32_t* engine_status;
-  // the call's outputs, by tree
-  int32_t* out_pid;
-  double *out_bl, *out_ll, *out_best_delta;  // (out_best_delta may be nullptr)
-  int32_t *move_count, *move_log;            // [T], [T][max_moves] or nullptr
-  double* move_gain;                         // [T][max_moves] or nullptr
-  int32_t *status, *out_opt_status;          // [T] kNniSearchActive while searching; [T] or nullptr
-  int32_t* active;                           // this round's word: trees that moved
-};
-void launch_nni_search_step(const NniSearchStepArgs& a, hipStream_t s);
-// The SPR hill-climbing search (kernels_spr_search.hip): taking SPR moves on the
-// device in the reference's numbering, and the per-tree step between two rounds of the search.
-// A wave per tree; the working arrays of a tree (seven of 2n-2 words and eight more) are in LDS
-// up to kSprApplyLdsNodes nodes, else in `ws`.
-constexpr int kSprApplyLdsNodes = 512, kSprApplyArrays = 7, kSprApplyExtra = 8;
-inline __host__ __device__ size_t spr_apply_ws_words(int n) {  // per tree; 0: the arrays are in LDS
+inline __host__ __device__ size_t spr_apply_ws_words(int n) {
   const size_t R = 2 * (size_t)n - 2;
   return R > kSprApplyLdsNodes ? kSprApplyArrays * R + kSprApplyExtra : 0;
 }
-struct SprApplyArgs {
+struct MoveApplyArgs {
   int n, T;
   const int32_t* parent_ids;  // [T][2n-3]
   const double* bl;           // [T][2n-2]
-  const int32_t* moves;       // [T][3] (s, dir, f), or (-1, -1, -1): copy
-  int32_t* ws;                // [T][spr_apply_ws_words(n)]
+  const int32_t* moves;       // NNI [T]: 2 v + i, or -1: copy; SPR [T][3]: (s, dir, f), or (-1, -1, -1): copy
+  int32_t* ws;                // [T][{nni,spr}_apply_ws_words(n)]
   int32_t* status;            // the engine's status word
   int32_t* out_parent_ids;    // [T][2n-3]  (no output may overlap an input)
   double* out_bl;             // [T][2n-2]
 };
-void launch_spr_apply(const SprApplyArgs& a, hipStream_t s);
-constexpr int kSprSearchActive = -1;  // internal; the rest are mi_phylo.h's MI_SPR_SEARCH_*
-struct SprSearchStepArgs {
+void launch_nni_apply(const MoveApplyArgs& a, hipStream_t s);
+void launch_spr_apply(const MoveApplyArgs& a, hipStream_t s);
+constexpr int kSearchActive = -1;  // internal; the rest are mi_phylo.h's MI_{NNI,SPR}_SEARCH_*
+struct SearchStepArgs {
   int n, count, round, max_moves;  // count: trees of the packed set
   double min_gain;
   const int32_t* map;  // [count] packed position -> tree, or nullptr
   // this round's results, by packed position
   const double *opt_bl, *opt_ll;  // [count][2n-2], [count]
   const int32_t* opt_status;      // [count]
-  const double* delta;            // [count][2n-3][2] the scan's best_delta
-  const int32_t* best;            // [count][3] the scan's best_move
+  const double* delta;            // NNI [count][2n-1][2]; SPR [count][2n-3][2], the scan's best_delta
+  const int32_t* best;            // NNI [count]; SPR [count][3], the scan's best_move
   // the trees by tree index: this round's and the other half of the pair
   const int32_t* cur_pid;  // [T][2n-3]
   double* cur_bl;          // [T][2n-2]
@@ -463,17 +420,18 @@ struct SprSearchStepArgs {
   // the packed inputs of the next round (map != nullptr)
   int32_t* pk_pid;  // [count][2n-3]
   double* pk_bl;    // [count][2n-2]
-  int32_t* ws;      // [count][spr_apply_ws_words(n)]
+  int32_t* ws;      // [count][{nni,spr}_apply_ws_words(n)]
   int32_t* engine_status;
   // the call's outputs, by tree
   int32_t* out_pid;
   double *out_bl, *out_ll, *out_best_delta;  // (out_best_delta may be nullptr)
-  int32_t *move_count, *move_log;            // [T], [T][max_moves][3] or nullptr
+  int32_t *move_count, *move_log;            // [T], NNI [T][max_moves] / SPR [T][max_moves][3] or nullptr
   double* move_gain;                         // [T][max_moves] or nullptr
-  int32_t *status, *out_opt_status;          // [T] kSprSearchActive while searching; [T] or nullptr
+  int32_t *status, *out_opt_status;          // [T] kSearchActive while searching; [T] or nullptr
   int32_t* active;                           // this round's word: trees that moved
 };
-void launch_spr_search_step(const SprSearchStepArgs& a, hipStream_t s);
+void launch_nni_search_step(const SearchStepArgs& a, hipStream_t s);
+void launch_spr_search_step(const SearchStepArgs& a, hipStream_t s);
 // RELL re-summation and the tree-mixture marginal (kernels_rell.hip)
 struct RellArgs {
   int B, T, P;

@@ -1,7 +1,7 @@
 // Writing an unrooted tree in the reference's numbering by ONE wave, lanes over nodes, without a
 // stack: leaves keep their ids, internal nodes are numbered in post-order with the children
 // ordered by largest leaf id, the trifurcating root is 2n-3, every length goes with its subtree.
-// Shared by the NNI move (kernels_nni_search.hip: MOVE = true) and neighbour joining
+// Shared by the NNI move (kernels_search.hip: MOVE = true) and neighbour joining
 // (kernels_nj.hip: MOVE = false, the tree as it is); everything here is inline, each kernel file
 // gets its own copy.  A workgroup is one wave: the barriers order that wave's own loads and
 // stores.

@@ -1,6 +1,6 @@
 // One SPR move of one unrooted tree by ONE wave, lanes over nodes, without a stack: the result of
 // mi_spr_neighbour (mi_phylo_spr.cpp), bit for bit.  Shared by the apply kernel
-// and the step kernel of the SPR search (kernels_spr_search.hip).  A workgroup is one wave: the
+// and the step kernel of the SPR search (kernels_search.hip).  A workgroup is one wave: the
 // barriers order that wave's own loads and stores, nothing here waits on another wave.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -206,8 +206,8 @@ def rell_weights(weights, replicates, seed):
     return rng.multinomial(total, w / w.sum(), size=int(replicates)).astype(np.float64)
 
 
-def _nni_search_options(max_moves, pack_active, min_gain, branch_opt):
-    o = _capi.NniSearchOptions()
+def _search_options(o, max_moves, pack_active, min_gain, branch_opt):
+    """The fields that _capi.NniSearchOptions and _capi.SprSearchOptions share, into `o`."""
     o.max_moves, o.pack_active, o.min_gain = int(max_moves), int(bool(pack_active)), float(min_gain)
     if branch_opt:  # (left at zeros: the optimiser's defaults)
         keys = dict(max_iterations=100, check_interval=4, pack_active=True, tolerance=1e-6,
@@ -220,11 +220,13 @@ def _nni_search_options(max_moves, pack_active, min_gain, branch_opt):
     return o
 
 
+def _nni_search_options(max_moves, pack_active, min_gain, branch_opt):
+    return _search_options(_capi.NniSearchOptions(), max_moves, pack_active, min_gain, branch_opt)
+
+
 def _spr_search_options(max_moves, pack_active, min_gain, radius, branch_opt):
-    o = _capi.SprSearchOptions()
-    o.max_moves, o.pack_active, o.min_gain = int(max_moves), int(bool(pack_active)), float(min_gain)
+    o = _search_options(_capi.SprSearchOptions(), max_moves, pack_active, min_gain, branch_opt)
     o.radius = int(radius)
-    o.branch_opt = _nni_search_options(0, True, 0.0, branch_opt).branch_opt
     return o
 
 
@@ -1075,20 +1077,26 @@ class Engine:
         4-state engines): optimise the branch lengths, scan the neighbourhood, take the best move
         while its delta exceeds min_gain, at most max_moves times.  branch_opt: a dict of
         optimize_branch_lengths' keyword options for every round.  Returns an NniSearchResult."""
+        return self._search(self._lib.mi_engine_nni_search_unrooted,
+                            _nni_search_options(max_moves, pack_active, min_gain, branch_opt),
+                            NniSearchResult, 1, parent_ids, start_branch_lengths, params, rescaling)
+
+    def _search(self, fn, opts, result, width, parent_ids, start_branch_lengths, params, rescaling):
+        """The host-pointer search of either kind of move: the C function, its options object,
+        the result class and the words of a move in the log."""
         n = self.taxon_count
         pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
         T = pid.shape[0]
-        opts = _nni_search_options(max_moves, pack_active, min_gain, branch_opt)
-        M = max(int(max_moves), 0)
-        out = NniSearchResult(np.empty((T, 2 * n - 3), np.int32), np.empty((T, 2 * n - 2)),
-                              np.empty(T), np.empty(T), np.empty(T, np.int32),
-                              np.empty((T, M), np.int32), np.empty((T, M)), np.empty(T, np.int32),
-                              np.empty(T, np.int32))
+        M = max(opts.max_moves, 0)
+        out = result(np.empty((T, 2 * n - 3), np.int32), np.empty((T, 2 * n - 2)),
+                     np.empty(T), np.empty(T), np.empty(T, np.int32),
+                     np.empty((T, M) if width == 1 else (T, M, width), np.int32),
+                     np.empty((T, M)), np.empty(T, np.int32), np.empty(T, np.int32))
         if T == 0:
             return out
         bl = _np(start_branch_lengths, np.float64).reshape(T, 2 * n - 2)
         pr = self._params(params, T)
-        self._check(self._lib.mi_engine_nni_search_unrooted(
+        self._check(fn(
             self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), C.addressof(opts),
             _ptr(out.parent_ids), _ptr(out.branch_lengths), _ptr(out.log_likelihood),
             _ptr(out.best_delta), _ptr(out.move_count), _ptr(out.move_log), _ptr(out.move_gain),
@@ -1119,25 +1127,9 @@ class Engine:
         (0: every move), take the best move while its delta exceeds min_gain, at most max_moves
         times.  branch_opt: a dict of optimize_branch_lengths' keyword options for every round.
         Returns an SprSearchResult."""
-        n = self.taxon_count
-        pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
-        T = pid.shape[0]
-        opts = _spr_search_options(max_moves, pack_active, min_gain, radius, branch_opt)
-        M = max(int(max_moves), 0)
-        out = SprSearchResult(np.empty((T, 2 * n - 3), np.int32), np.empty((T, 2 * n - 2)),
-                              np.empty(T), np.empty(T), np.empty(T, np.int32),
-                              np.empty((T, M, 3), np.int32), np.empty((T, M)), np.empty(T, np.int32),
-                              np.empty(T, np.int32))
-        if T == 0:
-            return out
-        bl = _np(start_branch_lengths, np.float64).reshape(T, 2 * n - 2)
-        pr = self._params(params, T)
-        self._check(self._lib.mi_engine_spr_search_unrooted(
-            self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), C.addressof(opts),
-            _ptr(out.parent_ids), _ptr(out.branch_lengths), _ptr(out.log_likelihood),
-            _ptr(out.best_delta), _ptr(out.move_count), _ptr(out.move_log), _ptr(out.move_gain),
-            _ptr(out.status), _ptr(out.branch_opt_status)))
-        return out
+        return self._search(self._lib.mi_engine_spr_search_unrooted,
+                            _spr_search_options(max_moves, pack_active, min_gain, radius, branch_opt),
+                            SprSearchResult, 3, parent_ids, start_branch_lengths, params, rescaling)
 
     def _phylo_gradients(self, ll, blocks, site, subst):
         """Per-tree PhyloGradient objects over row views of the freshly allocated result

@@ -78,6 +78,10 @@ std::vector<Kind> kinds() {
       {"nni_search", tree_inputs(),
        {per_tree(I32, 2 * n - 3), per_tree(F64, 2 * n - 2), per_tree(F64, 1), per_tree(F64, 1), per_tree(I32, 1), per_tree(I32, kMaxMoves),
         per_tree(F64, kMaxMoves), per_tree(I32, 1), per_tree(I32, 1)}},
+      {"spr_apply", {per_tree(I32, 2 * n - 3), per_tree(F64, 2 * n - 2), per_tree(I32, 3)}, {per_tree(I32, 2 * n - 3), per_tree(F64, 2 * n - 2)}},
+      {"spr_search", tree_inputs(),
+       {per_tree(I32, 2 * n - 3), per_tree(F64, 2 * n - 2), per_tree(F64, 1), per_tree(F64, 1), per_tree(I32, 1), per_tree(I32, 3 * kMaxMoves),
+        per_tree(F64, kMaxMoves), per_tree(I32, 1), per_tree(I32, 1)}},
   };
 }
 // (not per tree throughout: these go to one engine whole, so only their packing is checked)

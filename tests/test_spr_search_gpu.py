@@ -319,6 +319,32 @@ def test_arena_store_36_taxa(monkeypatch):
     assert 1 <= max(len(m) for m in logs) <= 2
 
 
+def test_step_kernel_workspace_branch_after_a_pack():
+    """258 taxa (the regraft walk's LDS takes them: 3 x 514 + 3 x 258 + 1 words): 2n-2 = 514 nodes
+    do not fit the step kernel's LDS arrays (512), so a move is taken in the global workspace --
+    and, after a pack, in the piece of the tree's PACKED position.  min_gain is set between the
+    best deltas of the trees at their first optimum so that two of five move: round 0 of the
+    search runs the route and the numbers of the max_moves = 0 call, and a tree's numbers do
+    not depend on which others search."""
+    n, T, radius = 258, 5, 2
+    rng = np.random.default_rng(175)
+    pids, bls = TU.random_trees(n, T, rng)
+    tips, w = TU.random_alignment(n, 64, rng)
+    eng = _engine("JC69", "constant", tips, w)
+    top = eng.spr_search(pids, bls, None, max_moves=0, radius=radius).best_delta
+    rank = np.argsort(-top)
+    min_gain = 0.5 * (top[rank[1]] + top[rank[2]])
+    print("best deltas", top.tolist(), "min_gain", min_gain)
+    assert top[rank[1]] > min_gain > top[rank[2]]
+    order = rank[[2, 0, 3, 1, 4]]  # the two that will move at indices 1 and 3: packed positions 0 and 1
+    pids, bls = pids[order], bls[order]
+    res = eng.spr_search(pids, bls, None, max_moves=2, min_gain=min_gain, radius=radius)
+    path = _path(eng, radius)
+    assert "batches=5x1,2x" in path, path
+    assert np.array_equal(res.move_count >= 1, [False, True, False, True, False]), res.move_count
+    _matches_python_loop(eng, res, pids, bls, None, max_moves=2, min_gain=min_gain, radius=radius)
+
+
 # ---- 9. handles and refusals ----
 
 def test_tree_sharded_handle_gives_the_single_engines_results():
