@@ -78,6 +78,10 @@ int32_t mi_abi_version(void);
 const char* mi_last_error(void);
 /* visible HIP devices (0 without a GPU); what thread_count is capped by in the adapter */
 int32_t mi_device_count(void);
+/* bytes of device memory the library's own buffers hold in this process at the moment, engines'
+ * and calls' (not the arrays mi_site_pattern_compress_device hands to the caller): back where it
+ * was once every engine made since is destroyed, whatever other users of the device do */
+int64_t mi_device_bytes_held(void);
 
 /* Engine::Engine + FatBeagle::SetTipStates/SetTipPartials/SetPatternWeights.
  * tip_states[n*P]: 0..s-1, >= s means gap (src/site_pattern.cpp:16-46).

@@ -51,6 +51,7 @@ SYMBOLS = {
     "mi_abi_version": (C.c_int32, []),
     "mi_last_error": (C.c_char_p, []),
     "mi_device_count": (C.c_int32, []),
+    "mi_device_bytes_held": (C.c_int64, []),
     "mi_engine_create_sharded":
         (C.c_int32, [C.POINTER(EngineSpec), C.c_int32, I32P, C.c_int32, _V, _V, _V, _V, _V,
                      C.POINTER(_V)]),

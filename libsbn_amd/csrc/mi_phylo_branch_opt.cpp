@@ -53,7 +53,7 @@ const mi_branch_opt_options kBranchOptDefaults = {100, 4, 1, 1e-6, 1e-8, 10.0, {
 int reserve_branch_opt(mi_engine* e, int T) {
   if (reserve_hessian_calls(e, T)) return 1;
   if (e->opt_ws.ensure(BranchOptWorkspace(e, T, nullptr).bytes)) return 1;
-  if (!e->opt_word) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->opt_word), 256, hipHostMallocDefault));
+  if (!e->opt_word) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->opt_word.h), 256, hipHostMallocDefault));
   return 0;
 }
 

@@ -2,8 +2,10 @@
 // (device memory), error reporting, status, profiling and the device-pointer entry points (the
 // call sequences behind them: mi_phylo_call.cpp).  Compiled with hipcc; no torch.
 #include <map>
+#include <memory>
 
 #include "mi_phylo_engine.h"
+#include "mi_phylo_tip_forms.h"
 
 namespace {
 thread_local std::string g_error;
@@ -16,7 +18,16 @@ int fail(const std::string& msg) {
   return 1;
 }
 void set_last_error(const std::string& msg) { g_error = msg; }
+std::atomic<int64_t> device_bytes_held{0};
 }  // namespace miphylo
+
+// (what the members do after this body: mi_phylo_engine.h)
+mi_engine::~mi_engine() {
+  for (mi_engine* shard : shards) delete shard;
+  if (!stream) return;
+  (void)hipSetDevice(spec.device);
+  (void)hipStreamSynchronize(stream);
+}
 
 namespace {
 // (engine creation, tips in mask form on the device: the log-likelihood kernel's pre-tiled copy)
@@ -45,9 +56,265 @@ int upload(Buffer& b, const T* host, size_t count, hipStream_t s) {
   return 0;
 }
 
-void add_block(std::map<std::string, std::pair<int, int>>& m, const std::string& k, int start,
-               int len) {
-  m[k] = {start, len};
+// ---- engine creation: create_engine below, step by step ----
+
+// A new engine's tips and pattern weights: host arrays, or (on_device:
+// mi_engine_create_device_tips) states and weights already on the engine's device.
+struct TipSource {
+  const int32_t* states;
+  const double* partials;
+  const double* weights;
+  bool on_device = false;
+};
+// What prepare_tips uploads asynchronously: create_engine keeps it until its one synchronisation.
+struct TipStaging {
+  Buffer states;                       // the caller's host states, for tips_prepare_kernel
+  std::vector<int32_t> from_partials;  // 20 states: the compact states of the caller's partials
+  std::vector<uint8_t> masks, codes;   // 4 states: the forms of the caller's partials
+};
+
+// The switches of a new engine (or sharded handle), read before anything else is done.
+int32_t read_switches(Switches& sw) {
+  std::string error;
+  return parse_switches(sw, error) ? 0 : fail(error);
+}
+
+int check_spec(const mi_engine_spec* spec, const TipSource& t) {
+  if (spec->taxon_count < 3) return fail("need at least 3 taxa");
+  if (spec->pattern_count < 1) return fail("need at least one site pattern");
+  if (spec->state_count != kStates && spec->state_count != kAa)
+    return fail("state_count must be 4 (DNA, as in the reference: substitution_model.cpp:6-15) "
+                "or 20 (amino acids)");
+  const int states = spec->state_count;
+  if (states == kStates && spec->subst_model != MI_SUBST_JC69 && spec->subst_model != MI_SUBST_GTR)
+    return fail("Substitution model not known");
+  if (states == kAa && spec->subst_model != MI_SUBST_REVERSIBLE)
+    return fail("a 20-state engine takes subst_model MI_SUBST_REVERSIBLE (an empirical model "
+                "given as data; WAG when none is passed)");
+  if (spec->site_model != MI_SITE_CONSTANT && spec->site_model != MI_SITE_WEIBULL)
+    return fail("Site model not known");
+  if (spec->clock_model != MI_CLOCK_NONE && spec->clock_model != MI_CLOCK_STRICT)
+    return fail("Clock model not known");
+  if (spec->site_model == MI_SITE_CONSTANT && spec->category_count != 1)
+    return fail("the constant site model has exactly one rate category");
+  if (spec->category_count < 1 || spec->category_count > kMaxCategories)
+    return fail("category_count out of range (1..64)");
+  if (!t.states && !(spec->use_tip_states == 0 && t.partials)) return fail("tip_states is required");
+  if (!t.weights) return fail("pattern_weights is required");
+  const int count = mi_device_count();
+  if (count == 0) return fail("no HIP device available: the MI355X engine has no CPU fallback");
+  if (spec->device >= count) return fail("device ordinal out of range");
+  return 0;
+}
+
+// the engine's sizes (its device is current)
+void set_shape(mi_engine* e, const Switches& sw) {
+  const mi_engine_spec& spec = e->spec;
+  e->n = spec.taxon_count;
+  e->N = 2 * e->n - 1;
+  e->P = spec.pattern_count;
+  e->K = spec.category_count;
+  e->s = spec.state_count;
+  if (e->s == kAa) {
+    e->tiles = aa_tiles(e->P);
+    e->ll_stride = aa_ll_blocks(e->P);
+    // 32 MB per vector at 50 000 patterns x 4 categories, 16.4 GB per gradient tree of 512
+    // taxa: the arena gets half of what the device has free now (an MI355X has 288 GB; more
+    // trees per launch fill its 256 CUs better: 8 such trees in one launch instead of 3 + 3 + 2
+    // are 8 % quicker), never less than 8 GB; aa_reserve backs off if that cannot be had
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)96 << 30;
+    e->plv_budget = std::max<size_t>(free_b / 2, (size_t)8 << 30);
+  } else {
+    e->tiles = (e->P + kTile - 1) / kTile;
+    e->ll_stride =
+        std::max({e->tiles, loglik_mfma_tiles(e->P, e->K), gradient_mfma_tiles(e->P, e->K)});
+  }
+  int lg = 0;
+  while ((2 << lg) <= e->n) lg++;
+  e->max_slots = lg + 1;
+  e->sw = sw;
+  e->fused_setup = sw.fused_setup;
+  if (sw.plv_bytes >= 0) e->plv_budget = (size_t)sw.plv_bytes;
+}
+
+// BlockSpecification (block_specification.cpp:11-50, phylo_model.cpp:13-15): names in map order
+void set_blocks(mi_engine* e) {
+  std::map<std::string, std::pair<int, int>> bm;
+  int off = 0;
+  auto block = [&](const char* name, int length) {  // the next `length` parameters; returns their start
+    bm[name] = {off, length};
+    off += length;
+    return off - length;
+  };
+  e->rates_off = e->freqs_off = e->shape_off = e->clock_off = -1;
+  if (e->spec.subst_model == MI_SUBST_GTR) {
+    e->rates_off = block("GTR rates", 6);
+    e->freqs_off = block("frequencies", 4);
+  }
+  bm["entire substitution"] = {0, off};
+  const int site_start = off;
+  if (e->spec.site_model == MI_SITE_WEIBULL) e->shape_off = block("Weibull shape", 1);
+  bm["entire site"] = {site_start, off - site_start};
+  const int clock_start = off;
+  if (e->spec.clock_model == MI_CLOCK_STRICT) e->clock_off = block("clock rate", 1);
+  bm["entire clock"] = {clock_start, off - clock_start};
+  bm["entire"] = {0, off};
+  e->param_count = off;
+  for (const auto& kv : bm) e->blocks.push_back({kv.first, kv.second.first, kv.second.second});
+}
+
+int start_stream(mi_engine* e) {
+  if (hipStreamCreateWithFlags(&e->stream.h, hipStreamNonBlocking) != hipSuccess)
+    return fail("hipStreamCreate failed");
+  if (e->status.ensure(sizeof(int32_t) * kStatusWords) ||
+      hipMemsetAsync(e->status.ptr, 0, sizeof(int32_t) * kStatusWords, e->stream) != hipSuccess)
+    return fail("status word allocation failed");
+  if (e->spec.site_model == MI_SITE_WEIBULL) {
+    // what the Weibull site model needs of its quantiles, once per engine (kernels_setup.hip)
+    if (e->weibull_x.ensure(sizeof(double) * 2 * (size_t)e->K)) return 1;
+    launch_weibull_table(e->K, e->weibull_x.as<double>(), e->stream);
+  }
+  return 0;
+}
+
+// Everything engine creation derives from the compact tip states (mi_phylo_tip_forms.h), on the
+// device: the int8 states (rows padded with gaps to `stride`), and for 4-state engines the state
+// masks, the table offsets of the third-generation walk and (use_tip_states == 0) the 0/1
+// partial vectors of SitePattern::GetPartials (site_pattern.cpp:117-131).
+__global__ __launch_bounds__(256) void tips_prepare_kernel(const int32_t* in, int n, int P, int states,
+                                                           int stride, int8_t* st8, uint8_t* masks,
+                                                           uint8_t* codes, double* partials) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)n * stride) return;
+  const int x = (int)(idx / stride), p = (int)(idx - (size_t)x * stride);
+  const size_t i = (size_t)x * P + p;
+  const int c = p < P ? tip_state(in[i], states) : states;
+  st8[idx] = (int8_t)c;
+  if (p >= P) return;
+  if (masks) masks[i] = tip_mask(c);
+  if (codes) codes[i] = tip_code(c);
+  if (partials)
+    for (int k = 0; k < kStates; k++) partials[i * kStates + k] = tip_partial(c, k);
+}
+
+// Compact states, the caller's on either side or (20 states) those of the caller's partials, go
+// through the kernel; the host derives only the forms of caller-supplied 4-state partials.
+int prepare_tips(mi_engine* e, const TipSource& t, TipStaging& st) {
+  const int states = e->s, n = e->n, P = e->P;
+  const bool dna = states == kStates;
+  const size_t np = (size_t)n * P;
+  // (the two arrays must be device memory of THIS engine's device: a host pointer or another
+  // device's memory would fault inside the preparation kernel, or worse, not fault)
+  if (t.on_device)
+    for (const void* p : {static_cast<const void*>(t.states), static_cast<const void*>(t.weights)}) {
+      hipPointerAttribute_t at{};
+      if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice ||
+          at.device != e->spec.device) {
+        (void)hipGetLastError();
+        return fail("device_tip_states / device_pattern_weights must be device memory of "
+                    "the engine's device");
+      }
+    }
+  const double* partials = e->spec.use_tip_states ? nullptr : t.partials;
+  const int32_t* d_states = t.states;  // (on the host until uploaded)
+  if (partials && !dna) {
+    // the 20-state kernels read compact states only; tip partials are accepted in the form
+    // SitePattern::GetPartials produces (one-hot, or all ones for a gap: site_pattern.cpp:117-131)
+    st.from_partials.resize(np);
+    for (size_t i = 0; i < np; i++)
+      if ((st.from_partials[i] = tip_state_of_partials(partials + i * states, states)) < 0)
+        return fail("20-state engine: tip partials must be one-hot or all ones");
+    d_states = st.from_partials.data();
+  }
+  if (d_states && !t.on_device) {
+    if (upload(st.states, d_states, np, e->stream)) return 1;
+    d_states = st.states.as<int32_t>();
+  }
+  // 20 states: rows padded with gaps to whole 16-pattern tiles (the walk kernels read them
+  // unmasked), and a tile group of slack behind the last row (the workgroup kernels fetch the
+  // states of their whole pattern range, padding waves included, with one LDS-DMA)
+  const int stride = dna ? P : e->tiles * kAaTile;
+  const size_t rows = (size_t)n * stride, slack = dna ? 0 : kAaTipSlack;
+  // 4 states: masks, codes and (use_tip_states == 0) partial rows follow from the states unless
+  // the caller brought partials.  (codes + 16 bytes: the look-up walk reads 12-byte groups as
+  // three words.)
+  const bool derive = dna && !partials;
+  if (e->tip_states.ensure(rows + slack)) return 1;
+  if (derive && (e->tip_masks.ensure(np) || e->tip_codes.ensure(np + 16))) return 1;
+  if (derive && !e->spec.use_tip_states && e->tip_partials.ensure(sizeof(double) * np * kStates)) return 1;
+  // (gaps wherever the kernel does not write: the slack, every state of an engine made from partials alone)
+  HIP_TRY(hipMemsetAsync(e->tip_states.ptr, states, rows + slack, e->stream));
+  if (derive) HIP_TRY(hipMemsetAsync(e->tip_codes.ptr, 64, np + 16, e->stream));
+  if (d_states)
+    hipLaunchKernelGGL(tips_prepare_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, e->stream,
+                       d_states, n, P, states, stride, e->tip_states.as<int8_t>(),
+                       derive ? e->tip_masks.as<uint8_t>() : nullptr, derive ? e->tip_codes.as<uint8_t>() : nullptr,
+                       derive && !e->spec.use_tip_states ? e->tip_partials.as<double>() : nullptr);
+  e->have_tip_masks = e->have_tip_codes = derive;
+  if (!dna || derive) return 0;
+  // The caller's 4-state partials are kept as they are.  They have state masks (the matrix-core
+  // kernels) when every entry is exactly 0 or 1 -- real-valued partials take the HBM-streamed
+  // kernel -- and codes (the look-up walk, kernels_walk3.hip) when every vector is one of the
+  // five SitePattern produces; an engine with any other 0/1 vector keeps the mask kernels.
+  if (upload(e->tip_partials, partials, np * kStates, e->stream)) return 1;
+  st.masks.resize(np);
+  st.codes.assign(np + 16, 64);
+  e->have_tip_masks = e->have_tip_codes = true;
+  for (size_t i = 0; i < np && e->have_tip_masks; i++) {
+    st.masks[i] = tip_mask_of_partials(partials + i * kStates);
+    st.codes[i] = tip_code_of_mask(st.masks[i]);
+    e->have_tip_masks = st.masks[i] != kTipNoForm;
+    e->have_tip_codes &= st.codes[i] != kTipNoForm;  // (no mask: no code either)
+  }
+  if (e->have_tip_masks && upload(e->tip_masks, st.masks.data(), np, e->stream)) return 1;
+  if (e->have_tip_codes && upload(e->tip_codes, st.codes.data(), np + 16, e->stream)) return 1;
+  return 0;
+}
+
+// what follows the tip forms, whichever side they came from, and creation's one synchronisation
+int finish_tips(mi_engine* e, const TipSource& t, const double* exchangeabilities, const double* frequencies) {
+  if (build_tip_tiles(e)) return 1;
+  if (e->s == kAa && aa_engine_init(e, exchangeabilities, frequencies)) return 1;
+  const size_t bytes = sizeof(double) * (size_t)e->P;
+  if (e->weights.ensure(bytes) ||
+      hipMemcpyAsync(e->weights.ptr, t.weights, bytes,
+                     t.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream) != hipSuccess)
+    return fail("copy of the pattern weights failed");
+  if (hipStreamSynchronize(e->stream) != hipSuccess || hipGetLastError() != hipSuccess)
+    return fail("preparation of the tips failed");
+  return 0;
+}
+
+// A failed step returns at once: the engine, and with it whatever it had allocated, goes with `e`.
+int32_t create_engine(const mi_engine_spec* spec, const Switches& sw, const double* exchangeabilities,
+                      const double* frequencies, const TipSource& tips, mi_engine** out_engine) {
+  if (!spec || !out_engine) return fail("null spec / out_engine");
+  *out_engine = nullptr;
+  if (check_spec(spec, tips)) return 1;
+  if (spec->device >= 0) HIP_TRY(hipSetDevice(spec->device));
+  TipStaging staging;  // (before `e`: a failed engine synchronises its stream before the staging goes)
+  std::unique_ptr<mi_engine> e(new mi_engine());
+  e->spec = *spec;
+  if (spec->device < 0) HIP_TRY(hipGetDevice(&e->spec.device));
+  set_shape(e.get(), sw);
+  set_blocks(e.get());
+  if (start_stream(e.get()) || prepare_tips(e.get(), tips, staging) ||
+      finish_tips(e.get(), tips, exchangeabilities, frequencies))
+    return 1;
+  *out_engine = e.release();
+  return 0;
+}
+
+// columns [b, b + c) of a host array [taxon][pattern][width] (a pattern shard's tips)
+template <typename T>
+const T* slice_columns(const T* all, int n, int P, int b, int c, int width, std::vector<T>& store) {
+  if (!all) return nullptr;
+  store.resize((size_t)n * c * width);
+  for (int x = 0; x < n; x++)
+    std::copy(all + ((size_t)x * P + b) * width, all + ((size_t)x * P + b + c) * width,
+              store.begin() + (size_t)x * c * width);
+  return store.data();
 }
 
 }  // namespace
@@ -116,51 +383,14 @@ int32_t mi_device_count(void) {
   return count;
 }
 
-// (device_tips / device_weights: the tips already on the device, mi_engine_create_device_tips)
-static int32_t create_engine(const mi_engine_spec* spec, const Switches& sw,
-                             const double* exchangeabilities, const double* frequencies,
-                             const int32_t* tip_states, const double* tip_partials,
-                             const double* pattern_weights, mi_engine** out_engine,
-                             const int32_t* device_tips = nullptr,
-                             const double* device_weights = nullptr);
-// The switches of a new engine (or sharded handle), read before anything else is done.
-static int32_t read_switches(Switches& sw) {
-  std::string error;
-  return parse_switches(sw, error) ? 0 : fail(error);
-}
-
 int32_t mi_engine_create_device_tips(const mi_engine_spec* spec, const int32_t* device_tip_states,
                                      const double* device_pattern_weights,
                                      mi_engine** out_engine) {
   Switches sw;
   if (read_switches(sw)) return 1;
   if (!device_tip_states || !device_pattern_weights) return fail("null device pointer");
-  return create_engine(spec, sw, nullptr, nullptr, nullptr, nullptr, nullptr, out_engine,
-                       device_tip_states, device_pattern_weights);
-}
-
-// Everything engine creation derives from the compact tip states, on the device: the int8
-// states (rows padded with gaps to `stride`), and for 4-state engines the state masks, the
-// table offsets of the third-generation walk and (use_tip_states == 0) the 0/1 partial vectors
-// of SitePattern::GetPartials (site_pattern.cpp:117-131).
-__global__ __launch_bounds__(256) void tips_prepare_kernel(const int32_t* in, int n, int P, int states,
-                                                           int stride, int8_t* st8, uint8_t* masks,
-                                                           uint8_t* codes, double* partials) {
-  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (size_t)n * stride) return;
-  const int x = (int)(idx / stride), p = (int)(idx - (size_t)x * stride);
-  int c = states;
-  if (p < P) {
-    const int32_t v = in[(size_t)x * P + p];
-    c = (v >= 0 && v < states) ? v : states;
-  }
-  st8[idx] = (int8_t)c;
-  if (p >= P) return;
-  const size_t i = (size_t)x * P + p;
-  if (masks) masks[i] = c >= kStates ? 0xF : (uint8_t)(1u << c);
-  if (codes) codes[i] = c >= kStates ? 64 : (uint8_t)(16 * c);
-  if (partials)
-    for (int k = 0; k < kStates; k++) partials[i * kStates + k] = (c >= kStates || c == k) ? 1.0 : 0.0;
+  return create_engine(spec, sw, nullptr, nullptr, {device_tip_states, nullptr, device_pattern_weights, true},
+                       out_engine);
 }
 
 int32_t mi_engine_create(const mi_engine_spec* spec, const int32_t* tip_states,
@@ -168,8 +398,7 @@ int32_t mi_engine_create(const mi_engine_spec* spec, const int32_t* tip_states,
                          mi_engine** out_engine) {
   Switches sw;
   if (read_switches(sw)) return 1;
-  return create_engine(spec, sw, nullptr, nullptr, tip_states, tip_partials, pattern_weights,
-                       out_engine);
+  return create_engine(spec, sw, nullptr, nullptr, {tip_states, tip_partials, pattern_weights}, out_engine);
 }
 
 int32_t mi_engine_create_reversible(const mi_engine_spec* spec, const double* exchangeabilities,
@@ -182,293 +411,14 @@ int32_t mi_engine_create_reversible(const mi_engine_spec* spec, const double* ex
     return fail("mi_engine_create_reversible needs subst_model == MI_SUBST_REVERSIBLE");
   if ((exchangeabilities == nullptr) != (frequencies == nullptr))
     return fail("pass both exchangeabilities and frequencies, or neither (built-in WAG)");
-  return create_engine(spec, sw, exchangeabilities, frequencies, tip_states, tip_partials,
-                       pattern_weights, out_engine);
-}
-
-static int32_t create_engine(const mi_engine_spec* spec, const Switches& sw,
-                             const double* exchangeabilities, const double* frequencies,
-                             const int32_t* tip_states, const double* tip_partials,
-                             const double* pattern_weights, mi_engine** out_engine,
-                             const int32_t* device_tips, const double* device_weights) {
-  if (!spec || !out_engine) return fail("null spec / out_engine");
-  *out_engine = nullptr;
-  if (spec->taxon_count < 3) return fail("need at least 3 taxa");
-  if (spec->pattern_count < 1) return fail("need at least one site pattern");
-  if (spec->state_count != kStates && spec->state_count != kAa)
-    return fail("state_count must be 4 (DNA, as in the reference: substitution_model.cpp:6-15) "
-                "or 20 (amino acids)");
-  const int states = spec->state_count;
-  if (states == kStates && spec->subst_model != MI_SUBST_JC69 && spec->subst_model != MI_SUBST_GTR)
-    return fail("Substitution model not known");
-  if (states == kAa && spec->subst_model != MI_SUBST_REVERSIBLE)
-    return fail("a 20-state engine takes subst_model MI_SUBST_REVERSIBLE (an empirical model "
-                "given as data; WAG when none is passed)");
-  if (spec->site_model != MI_SITE_CONSTANT && spec->site_model != MI_SITE_WEIBULL)
-    return fail("Site model not known");
-  if (spec->clock_model != MI_CLOCK_NONE && spec->clock_model != MI_CLOCK_STRICT)
-    return fail("Clock model not known");
-  if (spec->site_model == MI_SITE_CONSTANT && spec->category_count != 1)
-    return fail("the constant site model has exactly one rate category");
-  if (spec->category_count < 1 || spec->category_count > kMaxCategories)
-    return fail("category_count out of range (1..64)");
-  if (!device_tips && !tip_states && !(spec->use_tip_states == 0 && tip_partials))
-    return fail("tip_states is required");
-  if (!device_tips && !pattern_weights) return fail("pattern_weights is required");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return fail("no HIP device available: the MI355X engine has no CPU fallback");
-  if (spec->device >= count) return fail("device ordinal out of range");
-  if (spec->device >= 0) HIP_TRY(hipSetDevice(spec->device));
-
-  mi_engine* e = new mi_engine();
-  e->spec = *spec;
-  if (spec->device < 0) HIP_TRY(hipGetDevice(&e->spec.device));
-  e->n = spec->taxon_count;
-  e->N = 2 * e->n - 1;
-  e->P = spec->pattern_count;
-  e->K = spec->category_count;
-  e->s = states;
-  if (states == kAa) {
-    e->tiles = aa_tiles(e->P);
-    e->ll_stride = aa_ll_blocks(e->P);
-    // 32 MB per vector at 50 000 patterns x 4 categories, 16.4 GB per gradient tree of 512
-    // taxa: the arena gets half of what the device has free now (an MI355X has 288 GB; more
-    // trees per launch fill its 256 CUs better: 8 such trees in one launch instead of 3 + 3 + 2
-    // are 8 % quicker), never less than 8 GB; aa_reserve backs off if that cannot be had
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)96 << 30;
-    e->plv_budget = std::max<size_t>(free_b / 2, (size_t)8 << 30);
-  } else {
-    e->tiles = (e->P + kTile - 1) / kTile;
-    e->ll_stride =
-        std::max({e->tiles, loglik_mfma_tiles(e->P, e->K), gradient_mfma_tiles(e->P, e->K)});
-  }
-  int lg = 0;
-  while ((2 << lg) <= e->n) lg++;
-  e->max_slots = lg + 1;
-  e->sw = sw;
-  e->fused_setup = sw.fused_setup;
-  if (sw.plv_bytes >= 0) e->plv_budget = (size_t)sw.plv_bytes;
-
-  // BlockSpecification (block_specification.cpp:11-50, phylo_model.cpp:13-15)
-  std::map<std::string, std::pair<int, int>> bm;
-  int off = 0;
-  e->rates_off = e->freqs_off = e->shape_off = e->clock_off = -1;
-  if (spec->subst_model == MI_SUBST_GTR) {
-    e->rates_off = off;
-    add_block(bm, "GTR rates", off, 6);
-    off += 6;
-    e->freqs_off = off;
-    add_block(bm, "frequencies", off, 4);
-    off += 4;
-  }
-  add_block(bm, "entire substitution", 0, off);
-  const int site_start = off;
-  if (spec->site_model == MI_SITE_WEIBULL) {
-    e->shape_off = off;
-    add_block(bm, "Weibull shape", off, 1);
-    off += 1;
-  }
-  add_block(bm, "entire site", site_start, off - site_start);
-  const int clock_start = off;
-  if (spec->clock_model == MI_CLOCK_STRICT) {
-    e->clock_off = off;
-    add_block(bm, "clock rate", off, 1);
-    off += 1;
-  }
-  add_block(bm, "entire clock", clock_start, off - clock_start);
-  add_block(bm, "entire", 0, off);
-  e->param_count = off;
-  for (const auto& kv : bm) e->blocks.push_back({kv.first, kv.second.first, kv.second.second});
-
-  auto cleanup_fail = [&](int) {
-    mi_engine_destroy(e);
-    return 1;
-  };
-  if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
-    return cleanup_fail(fail("hipStreamCreate failed"));
-  if (e->status.ensure(sizeof(int32_t) * kStatusWords) ||
-      hipMemsetAsync(e->status.ptr, 0, sizeof(int32_t) * kStatusWords, e->stream) != hipSuccess)
-    return cleanup_fail(fail("status word allocation failed"));
-  if (spec->site_model == MI_SITE_WEIBULL) {
-    // what the Weibull site model needs of its quantiles, once per engine (kernels_setup.hip)
-    if (e->weibull_x.ensure(sizeof(double) * 2 * (size_t)e->K)) return cleanup_fail(1);
-    launch_weibull_table(e->K, e->weibull_x.as<double>(), e->stream);
-  }
-  const size_t np = (size_t)e->n * e->P;
-  if (device_tips) {
-    // (the two arrays must be device memory of THIS engine's device: a host pointer or another
-    // device's memory would fault inside the preparation kernel, or worse, not fault)
-    for (const void* p : {static_cast<const void*>(device_tips), static_cast<const void*>(device_weights)}) {
-      hipPointerAttribute_t at{};
-      if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice ||
-          at.device != e->spec.device) {
-        (void)hipGetLastError();
-        return cleanup_fail(fail("device_tip_states / device_pattern_weights must be device memory of "
-                                 "the engine's device"));
-      }
-    }
-    // the tips are on the device already: one kernel derives what the host loops below derive
-    const int stride = states == kAa ? e->tiles * kAaTile : e->P;
-    const bool dna = states == kStates;
-    if (e->tip_states.ensure((size_t)e->n * stride + (states == kAa ? kAaTipSlack : 0))) return cleanup_fail(1);
-    if (states == kAa &&
-        hipMemsetAsync(e->tip_states.as<int8_t>() + (size_t)e->n * stride, states, kAaTipSlack, e->stream) != hipSuccess)
-      return cleanup_fail(fail("hipMemset failed"));
-    if (dna && (e->tip_masks.ensure(np) || e->tip_codes.ensure(np + 16))) return cleanup_fail(1);
-    if (dna && !spec->use_tip_states && e->tip_partials.ensure(sizeof(double) * np * kStates))
-      return cleanup_fail(1);
-    if (dna && hipMemsetAsync(e->tip_codes.ptr, 64, np + 16, e->stream) != hipSuccess)
-      return cleanup_fail(fail("hipMemset failed"));
-    const size_t total = (size_t)e->n * stride;
-    hipLaunchKernelGGL(tips_prepare_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       e->stream, device_tips, e->n, e->P, states, stride,
-                       e->tip_states.as<int8_t>(), dna ? e->tip_masks.as<uint8_t>() : nullptr,
-                       dna ? e->tip_codes.as<uint8_t>() : nullptr,
-                       dna && !spec->use_tip_states ? e->tip_partials.as<double>() : nullptr);
-    e->have_tip_masks = e->have_tip_codes = dna;
-    if (build_tip_tiles(e)) return cleanup_fail(1);
-    if (states == kAa && aa_engine_init(e, exchangeabilities, frequencies)) return cleanup_fail(1);
-    if (e->weights.ensure(sizeof(double) * (size_t)e->P) ||
-        hipMemcpyAsync(e->weights.ptr, device_weights, sizeof(double) * (size_t)e->P,
-                       hipMemcpyDeviceToDevice, e->stream) != hipSuccess)
-      return cleanup_fail(fail("copy of the pattern weights failed"));
-    if (hipStreamSynchronize(e->stream) != hipSuccess || hipGetLastError() != hipSuccess)
-      return cleanup_fail(fail("preparation of the device-resident tips failed"));
-    *out_engine = e;
-    return 0;
-  }
-  std::vector<int8_t> st8(np, (int8_t)states);
-  if (tip_states)
-    for (size_t i = 0; i < np; i++) {
-      const int32_t v = tip_states[i];
-      st8[i] = (v >= 0 && v < states) ? (int8_t)v : (int8_t)states;
-    }
-  if (states == kAa) {
-    // the 20-state kernels read compact states only; tip partials are accepted in the form
-    // SitePattern::GetPartials produces (one-hot, or all ones for a gap: site_pattern.cpp:117-131)
-    if (!spec->use_tip_states && tip_partials) {
-      for (size_t i = 0; i < np; i++) {
-        int ones = 0, last = 0;
-        for (int x = 0; x < states; x++) {
-          const double v = tip_partials[i * states + x];
-          if (v == 1.0) { ones++; last = x; }
-          else if (v != 0.0) ones = -states - 1;
-        }
-        if (ones == 1) st8[i] = (int8_t)last;
-        else if (ones == states) st8[i] = (int8_t)states;
-        else {
-          mi_engine_destroy(e);
-          return fail("20-state engine: tip partials must be one-hot or all ones");
-        }
-      }
-    }
-    {  // rows padded with gaps to whole 16-pattern tiles: the walk kernels read them unmasked
-      const size_t stride = (size_t)e->tiles * kAaTile;
-      // (+ a tile group of slack behind the last row: the workgroup kernels fetch the states of
-      // their whole pattern range, padding waves included, with one LDS-DMA)
-      std::vector<int8_t> padded((size_t)e->n * stride + kAaTipSlack, (int8_t)states);
-      for (int x = 0; x < e->n; x++)
-        std::copy(st8.begin() + (size_t)x * e->P, st8.begin() + (size_t)(x + 1) * e->P,
-                  padded.begin() + (size_t)x * stride);
-      if (upload(e->tip_states, padded.data(), padded.size(), e->stream)) return cleanup_fail(1);
-    }
-    if (aa_engine_init(e, exchangeabilities, frequencies)) return cleanup_fail(1);
-  } else {
-  if (upload(e->tip_states, st8.data(), np, e->stream)) return cleanup_fail(1);
-  if (!spec->use_tip_states) {
-    std::vector<double> tp(np * kStates);
-    if (tip_partials) {
-      std::copy(tip_partials, tip_partials + np * kStates, tp.begin());
-    } else {
-      for (size_t i = 0; i < np; i++)
-        for (int x = 0; x < kStates; x++)
-          tp[i * kStates + x] = (st8[i] >= kStates || st8[i] == x) ? 1.0 : 0.0;
-    }
-    if (upload(e->tip_partials, tp.data(), tp.size(), e->stream)) return cleanup_fail(1);
-  }
-  {
-    // Tip vectors as state masks (bit s = compatible with state s) for the matrix-core
-    // kernel: from the compact states, or from the partials when every entry is exactly 0
-    // or 1 (what SitePattern::GetPartials produces, site_pattern.cpp:117-131); real-valued
-    // partials have no mask form and take the HBM-streamed kernel.
-    std::vector<uint8_t> masks(np);
-    e->have_tip_masks = true;
-    if (spec->use_tip_states || !tip_partials) {
-      for (size_t i = 0; i < np; i++) masks[i] = st8[i] >= kStates ? 0xF : (uint8_t)(1u << st8[i]);
-    } else {
-      for (size_t i = 0; i < np && e->have_tip_masks; i++) {
-        uint8_t m = 0;
-        for (int x = 0; x < kStates; x++) {
-          const double v = tip_partials[i * kStates + x];
-          if (v == 1.0) m |= (uint8_t)(1u << x);
-          else if (v != 0.0) e->have_tip_masks = false;
-        }
-        masks[i] = m;
-      }
-    }
-    if (e->have_tip_masks && upload(e->tip_masks, masks.data(), np, e->stream)) return cleanup_fail(1);
-    // The same tips as byte offsets of a state's entry in the third-generation walk's tip
-    // tables (kernels_walk3.hip): 16 x state, 64 for the all-ones vector.  Only the five
-    // vectors SitePattern produces have that form (site_pattern.cpp:117-131); an engine with
-    // any other 0/1 vector keeps the mask kernels.  (+16 bytes: the kernel reads 12-byte
-    // groups as three words.)
-    if (e->have_tip_masks) {
-      std::vector<uint8_t> codes(np + 16, 64);
-      e->have_tip_codes = true;
-      for (size_t i = 0; i < np && e->have_tip_codes; i++) {
-        switch (masks[i]) {
-          case 1: codes[i] = 0; break;
-          case 2: codes[i] = 16; break;
-          case 4: codes[i] = 32; break;
-          case 8: codes[i] = 48; break;
-          case 15: codes[i] = 64; break;
-          default: e->have_tip_codes = false;
-        }
-      }
-      if (e->have_tip_codes && upload(e->tip_codes, codes.data(), codes.size(), e->stream))
-        return cleanup_fail(1);
-    }
-  }
-  }
-  if (build_tip_tiles(e)) return cleanup_fail(1);
-  if (upload(e->weights, pattern_weights, (size_t)e->P, e->stream)) return cleanup_fail(1);
-  if (hipStreamSynchronize(e->stream) != hipSuccess)
-    return cleanup_fail(fail("upload of tips failed"));
-  *out_engine = e;
-  return 0;
+  return create_engine(spec, sw, exchangeabilities, frequencies, {tip_states, tip_partials, pattern_weights},
+                       out_engine);
 }
 
 void mi_engine_destroy(mi_engine* e) {
-  if (!e) return;
-  for (mi_engine* shard : e->shards) mi_engine_destroy(shard);
-  e->shards.clear();
-  if (e->stream || e->tip_states.ptr) (void)hipSetDevice(e->spec.device);
-  if (e->stream) {
-    (void)hipStreamSynchronize(e->stream);
-  }
-  for (Buffer* b :
-       {&e->tip_states, &e->tip_partials, &e->tip_masks, &e->tip_tiles, &e->tip_code_tiles, &e->tip_codes, &e->weights, &e->tree_scratch, &e->sched, &e->macros,
-        &e->arena_macros, &e->slot_need,
-        &e->macro_count, &e->tip_tables, &e->mmats, &e->mphi, &e->x_sum, &e->bl_eff,
-        &e->models, &e->mats, &e->ll_part, &e->plv, &e->g_part, &e->site_lik, &e->site_exp, &e->fin_scratch,
-        &e->ll_sum, &e->g_sum, &e->status, &e->ready, &e->weibull_x, &e->aa_model, &e->aa_matP, &e->aa_matPT,
-        &e->aa_tipP, &e->aa_tipPQ, &e->aa_exp_cum, &e->aa_exp_loc, &e->aa_root_val,
-        &e->aa_root_exp, &e->aa_root_scale, &e->red_ll, &e->red_g, &e->red_site, &e->red_sort,
-        &e->in_pack, &e->out_pack, &e->opt_ws, &e->nni_apply_ws, &e->nni_search_ws,
-        &e->pattern_blank, &e->pattern_ll_out, &e->rell_ws, &e->rell_s, &e->dist_codes, &e->dist_model,
-        &e->dist_counts, &e->dist_matrix, &e->nj_ws, &e->place_bl, &e->place_half, &e->place_pend,
-        &e->place_table, &e->spr_bl, &e->spr_half, &e->spr_ws, &e->spr_path,
-        &e->spr_apply_ws, &e->spr_search_ws, &e->split_ws, &e->split_store, &e->split_sort, &e->rf_ws, &e->sbn_index_ws,
-        &e->sbn_prob_ws, &e->sbn_store})
-    b->release();
-  if (e->opt_word) (void)hipHostFree(e->opt_word);
-  e->pinned.release();
-  for (hipEvent_t ev : e->prof_events) (void)hipEventDestroy(ev);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
+  if (e) delete e;
 }
+int64_t mi_device_bytes_held(void) { return miphylo::device_bytes_held.load(); }
 
 int32_t mi_engine_param_count(const mi_engine* e) { return e ? e->param_count : -1; }
 int32_t mi_engine_block_count(const mi_engine* e) { return e ? (int32_t)e->blocks.size() : -1; }
@@ -538,9 +488,9 @@ static int32_t profile_begin(mi_engine* e, int32_t max_calls, bool phases) {
   if (max_calls < 0) return fail("max_calls must be >= 0");
   HIP_TRY(hipSetDevice(e->spec.device));
   while ((int)e->prof_events.size() < kProfEvents * max_calls) {
-    hipEvent_t ev;
-    HIP_TRY(hipEventCreate(&ev));
-    e->prof_events.push_back(ev);
+    Event ev;
+    HIP_TRY(hipEventCreate(&ev.h));
+    e->prof_events.push_back(std::move(ev));
   }
   e->prof_capacity = max_calls;
   e->prof_used = 0;
@@ -571,7 +521,7 @@ int32_t mi_engine_profile_collect_phases(mi_engine* e, double* out_ms, double* o
     return fail("phase times were not recorded: use mi_engine_profile_begin_phases");
   const int count = std::min(e->prof_used, capacity);
   for (int i = 0; i < count; i++) {
-    hipEvent_t* ev = &e->prof_events[(size_t)kProfEvents * i];
+    const Event* ev = &e->prof_events[(size_t)kProfEvents * i];
     HIP_TRY(hipEventSynchronize(ev[1]));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
@@ -994,12 +944,11 @@ int32_t mi_engine_create_sharded(const mi_engine_spec* spec, int32_t shard_count
     return fail("unknown shard mode");
   if (shard_mode == MI_SHARD_PATTERNS && shard_count > spec->pattern_count)
     return fail("more pattern shards than site patterns");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return fail("no HIP device available: the MI355X engine has no CPU fallback");
+  const int count = mi_device_count();
+  if (count == 0) return fail("no HIP device available: the MI355X engine has no CPU fallback");
   int current = 0;
   if (hipGetDevice(&current) != hipSuccess) current = 0;
-  mi_engine* front = new mi_engine();
+  std::unique_ptr<mi_engine> front(new mi_engine());
   front->spec = *spec;
   front->sw = sw;
   front->shard_mode = shard_mode;
@@ -1007,7 +956,7 @@ int32_t mi_engine_create_sharded(const mi_engine_spec* spec, int32_t shard_count
   front->N = 2 * front->n - 1;
   front->P = spec->pattern_count;
   front->K = spec->category_count;
-  const int n = spec->taxon_count, s = spec->state_count;
+  const int n = spec->taxon_count, P = spec->pattern_count;
   for (int i = 0; i < shard_count; i++) {
     mi_engine_spec sub = *spec;
     // NULL: round-robin over the visible devices STARTING AT THE CALLER'S CURRENT DEVICE (a
@@ -1016,43 +965,25 @@ int32_t mi_engine_create_sharded(const mi_engine_spec* spec, int32_t shard_count
     int want = devices ? devices[i] : -1 - i;
     if (want < 0) want = (current + (-1 - want)) % count;
     sub.device = want;
-    int32_t b = 0, c = spec->pattern_count;
-    if (shard_mode == MI_SHARD_PATTERNS) mi_shard_range(spec->pattern_count, shard_count, i, &b, &c);
-    sub.pattern_count = c;
-    std::vector<int32_t> tips;
-    std::vector<double> parts;
-    if (shard_mode == MI_SHARD_PATTERNS) {  // columns [b, b + c) of the [taxon][pattern] arrays
-      if (tip_states) {
-        tips.resize((size_t)n * c);
-        for (int x = 0; x < n; x++)
-          std::copy(tip_states + (size_t)x * spec->pattern_count + b,
-                    tip_states + (size_t)x * spec->pattern_count + b + c, tips.begin() + (size_t)x * c);
-      }
-      if (tip_partials) {
-        parts.resize((size_t)n * c * s);
-        for (int x = 0; x < n; x++)
-          std::copy(tip_partials + ((size_t)x * spec->pattern_count + b) * s,
-                    tip_partials + ((size_t)x * spec->pattern_count + b + c) * s,
-                    parts.begin() + (size_t)x * c * s);
-      }
+    TipSource tips{tip_states, tip_partials, pattern_weights};
+    std::vector<int32_t> states;
+    std::vector<double> partials;
+    if (shard_mode == MI_SHARD_PATTERNS) {
+      int32_t b = 0, c = P;
+      mi_shard_range(P, shard_count, i, &b, &c);
+      sub.pattern_count = c;
+      tips = {slice_columns(tip_states, n, P, b, c, 1, states),
+              slice_columns(tip_partials, n, P, b, c, spec->state_count, partials), pattern_weights + b};
     }
     mi_engine* shard = nullptr;
-    const int rc = create_engine(
-        &sub, sw, exchangeabilities, frequencies,
-        shard_mode == MI_SHARD_PATTERNS ? (tip_states ? tips.data() : nullptr) : tip_states,
-        shard_mode == MI_SHARD_PATTERNS ? (tip_partials ? parts.data() : nullptr) : tip_partials,
-        pattern_weights + b, &shard);
-    if (rc) {
-      mi_engine_destroy(front);
-      return 1;
-    }
+    if (create_engine(&sub, sw, exchangeabilities, frequencies, tips, &shard)) return 1;
     front->shards.push_back(shard);
   }
   const mi_engine* first = front->shards[0];
   front->param_count = first->param_count;
   front->blocks = first->blocks;
   front->s = first->s;
-  *out_engine = front;
+  *out_engine = front.release();
   return 0;
 }
 

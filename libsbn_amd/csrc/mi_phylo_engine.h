@@ -24,95 +24,15 @@
 #include <vector>
 
 #include "../../include/mi_phylo.h"
+#include "mi_phylo_buffer.h"
 #include "mi_phylo_host_arrays.h"
 #include "mi_phylo_kernels.h"
 
 namespace miphylo {
-int fail(const std::string& msg);  // sets mi_last_error()
 void set_last_error(const std::string& msg);
 }
 using miphylo::fail;
 using namespace miphylo;
-
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t err__ = (expr);                                                     \
-    if (err__ != hipSuccess)                                                       \
-      return fail(std::string("HIP error: ") + hipGetErrorString(err__) + " at " + \
-                  __FILE__ + ":" + std::to_string(__LINE__));                      \
-  } while (0)
-
-// A device buffer that only ever grows.
-struct Buffer {
-  void* ptr = nullptr;
-  size_t bytes = 0;
-  int ensure(size_t need) {
-    if (need <= bytes) return 0;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    bytes = 0;
-    HIP_TRY(hipMalloc(&ptr, need));
-    bytes = need;
-    return 0;
-  }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    bytes = 0;
-  }
-  template <typename T>
-  T* as() const { return static_cast<T*>(ptr); }
-};
-
-// Pinned host staging for the host-pointer entry points: inputs are copied into it and
-// DMA'd from there, outputs are DMA'd into it and copied out after the call's one
-// synchronisation.  (hipMemcpyAsync on pageable memory is staged by the runtime, copy by
-// copy and mostly synchronously: ~0.5 ms per call for 1000 DS1 trees, against ~0.1 ms.)
-struct PinnedArena {
-  char* ptr = nullptr;
-  size_t bytes = 0, used = 0;
-  struct Pending {
-    void* host;
-    const void* staged;
-    size_t bytes;
-  };
-  std::vector<Pending> pending;
-  // returns nullptr on failure; may synchronise `s` when it has to grow
-  void* alloc(size_t need, hipStream_t s) {
-    need = (need + 255) & ~(size_t)255;
-    if (used + need > bytes) {
-      // copies already issued from / into the old block must finish before it goes away;
-      // pending outputs are delivered first
-      if (hipStreamSynchronize(s) != hipSuccess) return nullptr;
-      flush();
-      if (ptr) (void)hipHostFree(ptr);
-      ptr = nullptr;
-      bytes = 0;
-      const size_t want = std::max<size_t>(2 * (used + need), 1 << 20);
-      if (hipHostMalloc(reinterpret_cast<void**>(&ptr), want, hipHostMallocDefault) != hipSuccess)
-        return nullptr;
-      bytes = want;
-      used = 0;
-    }
-    void* p = ptr + used;
-    used += need;
-    return p;
-  }
-  void flush() {  // after a synchronisation: hand the staged outputs to the caller
-    for (const Pending& q : pending) memcpy(q.host, q.staged, q.bytes);
-    pending.clear();
-  }
-  void reset() {
-    pending.clear();
-    used = 0;
-  }
-  void release() {
-    if (ptr) (void)hipHostFree(ptr);
-    ptr = nullptr;
-    bytes = used = 0;
-    pending.clear();
-  }
-};
 
 struct Block {
   std::string name;
@@ -151,13 +71,18 @@ inline const char* status_message(int code) {
 
 constexpr int kStatusWords = 4;  // code, tree, 1 + tree of a one-launch time-out, spare
 
+// Every resource below releases itself.  The order of an engine's end is the destructor's body
+// (mi_phylo_engine.cpp: shards before their front handle, the engine's device made current, its
+// stream synchronised) followed by the members in reverse order of declaration: `stream` is
+// declared before every buffer, the pinned memory and the events, so it goes last.
 struct mi_engine {
+  ~mi_engine();
   mi_engine_spec spec;
   int n, N, P, K, tiles, max_slots, ll_stride;
   int s = 4;  // states: 4 (kernels_{loglik,gradient}.hip) or 20 (kernels_aa.hip)
   int param_count, rates_off, freqs_off, shape_off, clock_off;
   std::vector<Block> blocks;
-  hipStream_t stream = nullptr;
+  Stream stream;
   // static device data
   Buffer tip_states, tip_partials, tip_masks, tip_codes, weights;
   Buffer tip_code_tiles;  // tip_codes by pattern tile of the look-up walk (launch_tip_code_tiles), if have_tip_codes and K <= 4
@@ -180,7 +105,7 @@ struct mi_engine {
   Switches sw;  // the MI_PHYLO_* switches as they were when the engine was created
   int tile_regs = 0;  // look-up walk: the engine's tile width (0: default, 4: wide -- engine_tile_regs, at creation)
   // a sharded handle (mi_engine_create_sharded): the per-device / per-shard engines it
-  // drives; such a handle owns no device memory itself
+  // drives (deleted by its destructor); such a handle owns no device memory itself
   std::vector<mi_engine*> shards;
   int shard_mode = 0;
   std::vector<double> shard_sums;  // per-shard partial results (pattern shards, fused sums)
@@ -193,7 +118,7 @@ struct mi_engine {
   Buffer in_pack, out_pack;
   // branch-length optimisation (mi_engine_optimize_branch_lengths_unrooted*)
   Buffer opt_ws;                // trial points, kept derivatives, packed inputs, maps, counters
-  int32_t* opt_word = nullptr;  // pinned: the active count read at a check point
+  PinnedWord opt_word;          // pinned: the active count read at a check point
   // NNI moves and the NNI search (mi_engine_nni_{apply,search}_unrooted*)
   Buffer nni_apply_ws;   // the apply kernel's working arrays of trees too large for LDS
   Buffer nni_search_ws;  // the pair of tree buffers, a round's results, packed inputs, maps, counters
@@ -232,7 +157,7 @@ struct mi_engine {
   Buffer rf_ws;        // a batch's sorted lists: lengths [T][2n-3] | indices [T][2n-3] | counts [T]
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)
-  std::vector<hipEvent_t> prof_events;  // kProfEvents per call: [begin, end, mark 0..4]
+  std::vector<Event> prof_events;  // kProfEvents per call: [begin, end, mark 0..4]
   int prof_capacity = 0, prof_used = 0;
   bool prof_phases = false;   // also record the phase marks (mi_engine_profile_begin_phases)
   int prof_first_launch_evals = 0;  // evaluations in the first walk launch of the last call

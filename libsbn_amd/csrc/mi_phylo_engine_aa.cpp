@@ -52,8 +52,6 @@ int aa_engine_init(mi_engine* e, const double* exchangeabilities, const double* 
   int32_t st[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(st, e->status.ptr, sizeof st, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  dex.release();
-  dfr.release();
   if (st[0] != 0) return fail("model frequencies do not sum to 1 +/- 0.001!");
   return 0;
 }

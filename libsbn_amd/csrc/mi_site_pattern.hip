@@ -29,10 +29,7 @@
 #include <vector>
 
 #include "../../include/mi_phylo.h"
-
-namespace miphylo {
-int fail(const std::string& message);  // mi_phylo_engine.cpp
-}
+#include "mi_phylo_buffer.h"
 
 namespace {
 
@@ -162,15 +159,6 @@ std::vector<int> replay_unordered_map_order(const std::vector<int32_t>& hashes) 
   return order;
 }
 
-struct DevMem {
-  void* p = nullptr;
-  ~DevMem() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T* as() { return static_cast<T*>(p); }
-};
-
 }  // namespace
 
 // keep != nullptr: the device-resident form -- the gathered pattern matrix and the weights stay
@@ -197,26 +185,15 @@ static int32_t compress_impl(int32_t device, int32_t taxon_count, int64_t site_c
                 "(libmi_phylo_host.so has the CPU implementation)");
   SP_TRY(hipSetDevice(device < 0 ? 0 : device));
 
-  DevMem d_codes, d_ref, d_key, d_key2, d_site, d_site2, d_head, d_scan, d_leader, d_start, d_gid,
+  Buffer d_codes, d_ref, d_key, d_key2, d_site, d_site2, d_head, d_scan, d_leader, d_start, d_gid,
       d_gid2, d_leader2, d_osite, d_ocount, d_ohash, d_flag, d_tmp;
-  SP_TRY(hipMalloc(&d_codes.p, (size_t)n * L));
-  SP_TRY(hipMalloc(&d_ref.p, sizeof(int32_t) * L));
-  SP_TRY(hipMalloc(&d_key.p, sizeof(uint64_t) * L));
-  SP_TRY(hipMalloc(&d_key2.p, sizeof(uint64_t) * L));
-  SP_TRY(hipMalloc(&d_site.p, sizeof(uint32_t) * L));
-  SP_TRY(hipMalloc(&d_site2.p, sizeof(uint32_t) * L));
-  SP_TRY(hipMalloc(&d_head.p, sizeof(uint32_t) * L));
-  SP_TRY(hipMalloc(&d_scan.p, sizeof(uint32_t) * L));
-  SP_TRY(hipMalloc(&d_leader.p, sizeof(uint32_t) * L));
-  SP_TRY(hipMalloc(&d_start.p, sizeof(uint32_t) * L));
-  SP_TRY(hipMalloc(&d_gid.p, sizeof(uint32_t) * L));
-  SP_TRY(hipMalloc(&d_gid2.p, sizeof(uint32_t) * L));
-  SP_TRY(hipMalloc(&d_leader2.p, sizeof(uint32_t) * L));
-  SP_TRY(hipMalloc(&d_osite.p, sizeof(uint32_t) * L));
-  SP_TRY(hipMalloc(&d_ocount.p, sizeof(uint32_t) * L));
-  SP_TRY(hipMalloc(&d_ohash.p, sizeof(int32_t) * L));
-  SP_TRY(hipMalloc(&d_flag.p, sizeof(int32_t)));
-  SP_TRY(hipMemcpy(d_codes.p, codes, (size_t)n * L, hipMemcpyHostToDevice));
+  if (d_codes.ensure((size_t)n * L) || d_key.ensure(sizeof(uint64_t) * L) ||
+      d_key2.ensure(sizeof(uint64_t) * L) || d_flag.ensure(sizeof(int32_t)))
+    return 1;
+  for (Buffer* b : {&d_ref, &d_site, &d_site2, &d_head, &d_scan, &d_leader, &d_start, &d_gid, &d_gid2,
+                    &d_leader2, &d_osite, &d_ocount, &d_ohash})  // a 32-bit word per site each
+    if (b->ensure(sizeof(uint32_t) * L)) return 1;
+  SP_TRY(hipMemcpy(d_codes.ptr, codes, (size_t)n * L, hipMemcpyHostToDevice));
   const unsigned blocks = (unsigned)((L + 255) / 256);
   // temporary storage of the rocPRIM calls (queried once)
   size_t tmp_bytes = 0, need = 0;
@@ -230,15 +207,15 @@ static int32_t compress_impl(int32_t device, int32_t taxon_count, int64_t site_c
                                    d_leader2.as<uint32_t>(), d_gid.as<uint32_t>(),
                                    d_gid2.as<uint32_t>(), (size_t)L));
   tmp_bytes = std::max(tmp_bytes, need);
-  SP_TRY(hipMalloc(&d_tmp.p, tmp_bytes));
+  if (d_tmp.ensure(tmp_bytes)) return 1;
 
   uint32_t P = 0;
-  hipEvent_t ev0, ev1;
-  SP_TRY(hipEventCreate(&ev0));
-  SP_TRY(hipEventCreate(&ev1));
+  Event ev0, ev1;
+  SP_TRY(hipEventCreate(&ev0.h));
+  SP_TRY(hipEventCreate(&ev1.h));
   bool grouped = false;
   for (uint64_t seed = 0; seed < 4 && !grouped; seed++) {
-    SP_TRY(hipMemset(d_flag.p, 0, sizeof(int32_t)));
+    SP_TRY(hipMemset(d_flag.ptr, 0, sizeof(int32_t)));
     SP_TRY(hipEventRecord(ev0, nullptr));
     hipLaunchKernelGGL(hash_columns_kernel, dim3(blocks), dim3(256), 0, nullptr, n, L,
                        seed * 0x9e3779b97f4a7c15ull, d_codes.as<int8_t>(), d_ref.as<int32_t>(),
@@ -246,23 +223,21 @@ static int32_t compress_impl(int32_t device, int32_t taxon_count, int64_t site_c
     SP_TRY(hipEventRecord(ev1, nullptr));
     // stable sort by the 64-bit hash, run heads, verification
     need = tmp_bytes;
-    SP_TRY(rocprim::radix_sort_pairs(d_tmp.p, need, d_key.as<uint64_t>(), d_key2.as<uint64_t>(),
+    SP_TRY(rocprim::radix_sort_pairs(d_tmp.ptr, need, d_key.as<uint64_t>(), d_key2.as<uint64_t>(),
                                      d_site.as<uint32_t>(), d_site2.as<uint32_t>(), (size_t)L));
     hipLaunchKernelGGL(mark_heads_kernel, dim3(blocks), dim3(256), 0, nullptr, n, L,
                        d_codes.as<int8_t>(), d_key2.as<uint64_t>(), d_site2.as<uint32_t>(),
                        d_head.as<uint32_t>(), d_flag.as<int32_t>());
     need = tmp_bytes;
-    SP_TRY(rocprim::inclusive_scan(d_tmp.p, need, d_head.as<uint32_t>(), d_scan.as<uint32_t>(),
+    SP_TRY(rocprim::inclusive_scan(d_tmp.ptr, need, d_head.as<uint32_t>(), d_scan.as<uint32_t>(),
                                    (size_t)L, rocprim::plus<uint32_t>()));
     int32_t collision = 0;
     SP_TRY(hipMemcpy(&P, d_scan.as<uint32_t>() + (L - 1), sizeof P, hipMemcpyDeviceToHost));
-    SP_TRY(hipMemcpy(&collision, d_flag.p, sizeof collision, hipMemcpyDeviceToHost));
+    SP_TRY(hipMemcpy(&collision, d_flag.ptr, sizeof collision, hipMemcpyDeviceToHost));
     grouped = collision == 0;  // two different columns with one 64-bit hash: other seed
   }
   float hash_ms = 0;
   SP_TRY(hipEventElapsedTime(&hash_ms, ev0, ev1));
-  (void)hipEventDestroy(ev0);
-  (void)hipEventDestroy(ev1);
   if (out_hash_kernel_ms) *out_hash_kernel_ms = hash_ms;
   if (!grouped) return fail("site patterns: the grouping hash collided under every seed");
 
@@ -272,7 +247,7 @@ static int32_t compress_impl(int32_t device, int32_t taxon_count, int64_t site_c
   const unsigned pblocks = (P + 255) / 256;
   hipLaunchKernelGGL(iota_kernel, dim3(pblocks), dim3(256), 0, nullptr, P, d_gid.as<uint32_t>());
   need = tmp_bytes;
-  SP_TRY(rocprim::radix_sort_pairs(d_tmp.p, need, d_leader.as<uint32_t>(),
+  SP_TRY(rocprim::radix_sort_pairs(d_tmp.ptr, need, d_leader.as<uint32_t>(),
                                    d_leader2.as<uint32_t>(), d_gid.as<uint32_t>(),
                                    d_gid2.as<uint32_t>(), (size_t)P));
   hipLaunchKernelGGL(gather_groups_kernel, dim3(pblocks), dim3(256), 0, nullptr, P, L,
@@ -281,9 +256,9 @@ static int32_t compress_impl(int32_t device, int32_t taxon_count, int64_t site_c
                      d_ohash.as<int32_t>());
   std::vector<uint32_t> first(P), count(P);
   std::vector<int32_t> hashes(P);
-  SP_TRY(hipMemcpy(first.data(), d_osite.p, sizeof(uint32_t) * P, hipMemcpyDeviceToHost));
-  SP_TRY(hipMemcpy(count.data(), d_ocount.p, sizeof(uint32_t) * P, hipMemcpyDeviceToHost));
-  SP_TRY(hipMemcpy(hashes.data(), d_ohash.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost));
+  SP_TRY(hipMemcpy(first.data(), d_osite.ptr, sizeof(uint32_t) * P, hipMemcpyDeviceToHost));
+  SP_TRY(hipMemcpy(count.data(), d_ocount.ptr, sizeof(uint32_t) * P, hipMemcpyDeviceToHost));
+  SP_TRY(hipMemcpy(hashes.data(), d_ohash.ptr, sizeof(int32_t) * P, hipMemcpyDeviceToHost));
   SP_TRY(hipGetLastError());
 
   const std::vector<int> order = replay_unordered_map_order(hashes);
@@ -296,22 +271,22 @@ static int32_t compress_impl(int32_t device, int32_t taxon_count, int64_t site_c
   }
   if (!keep) std::copy(weights_host.begin(), weights_host.end(), out_weights);
   // the pattern matrix is gathered on the device and comes back in one copy
-  DevMem d_pat;
-  SP_TRY(hipMalloc(&d_pat.p, sizeof(int32_t) * (size_t)n * P));
-  SP_TRY(hipMemcpy(d_osite.p, final_site.data(), sizeof(uint32_t) * P, hipMemcpyHostToDevice));
+  Buffer d_pat;
+  if (d_pat.ensure(sizeof(int32_t) * (size_t)n * P)) return 1;
+  SP_TRY(hipMemcpy(d_osite.ptr, final_site.data(), sizeof(uint32_t) * P, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(gather_patterns_kernel, dim3(pblocks, n), dim3(256), 0, nullptr, n, L, P,
                      d_codes.as<int8_t>(), d_osite.as<uint32_t>(), d_pat.as<int32_t>());
   if (keep) {
-    DevMem d_w;
-    SP_TRY(hipMalloc(&d_w.p, sizeof(double) * P));
-    SP_TRY(hipMemcpy(d_w.p, weights_host.data(), sizeof(double) * P, hipMemcpyHostToDevice));
+    Buffer d_w;
+    if (d_w.ensure(sizeof(double) * P)) return 1;
+    SP_TRY(hipMemcpy(d_w.ptr, weights_host.data(), sizeof(double) * P, hipMemcpyHostToDevice));
     SP_TRY(hipDeviceSynchronize());
-    keep->patterns = d_pat.as<int32_t>();
-    keep->weights = d_w.as<double>();
-    d_pat.p = d_w.p = nullptr;  // (ownership passes to the caller: mi_device_free)
+    // (ownership passes to the caller: mi_device_free)
+    keep->patterns = static_cast<int32_t*>(d_pat.detach());
+    keep->weights = static_cast<double*>(d_w.detach());
     return 0;
   }
-  SP_TRY(hipMemcpy(out_patterns, d_pat.p, sizeof(int32_t) * (size_t)n * P, hipMemcpyDeviceToHost));
+  SP_TRY(hipMemcpy(out_patterns, d_pat.ptr, sizeof(int32_t) * (size_t)n * P, hipMemcpyDeviceToHost));
   return 0;
 }
 

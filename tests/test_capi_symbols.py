@@ -55,6 +55,29 @@ def test_no_cpu_fallback():
         L.Engine(L.PhyloModelSpecification(), np.zeros((3, 4), np.int32), np.ones(4))
 
 
+def test_device_bytes_held_is_back_after_a_creation():
+    """mi_device_bytes_held: a creation that fails (here: no device) leaves nothing held -- 0 in a
+    process that never had a device --, one that succeeds holds something until the engine is
+    destroyed."""
+    import torch
+    from libsbn_amd import _capi
+    lib = _capi.load()
+    before = lib.mi_device_bytes_held()
+    spec = _capi.EngineSpec(3, 4, 4, 1, 0, 0, 0, 1, -1, 0)  # JC69, constant site model, no clock
+    tips, weights = np.zeros((3, 4), np.int32), np.ones(4)
+    handle = ctypes.c_void_p()
+    rc = lib.mi_engine_create(ctypes.byref(spec), tips.ctypes.data, None, weights.ctypes.data,
+                              ctypes.byref(handle))
+    if torch.cuda.is_available():
+        assert rc == 0, lib.mi_last_error()
+        assert lib.mi_device_bytes_held() > before
+        lib.mi_engine_destroy(handle)
+    else:
+        assert rc != 0 and b"no HIP device" in lib.mi_last_error()
+        assert before == 0
+    assert lib.mi_device_bytes_held() == before
+
+
 def test_product_does_not_reference_the_oracle():
     """The product path must never route through oracle/ (test infrastructure)."""
     pkg = os.path.join(REPO, "libsbn_amd")

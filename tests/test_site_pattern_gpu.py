@@ -99,6 +99,41 @@ def test_device_resident_patterns_feed_an_engine_without_the_round_trip():
     dp.release()
 
 
+@pytest.mark.parametrize("P", [45, 130])
+def test_host_states_and_device_states_make_the_same_engine(P):
+    """Both doors derive the tip forms by one rule (mi_phylo_tip_forms.h): on shapes with gaps whose
+    pattern count is no multiple of 16 (the 20-state tile) or 64 (the 4-state one), an engine made
+    from host states and one made from the same states on the device give bit-identical
+    log-likelihoods and gradients -- 4 states with and without use_tip_states, and 20 states."""
+    import torch
+    import libsbn_amd as L
+    import aa_utils as A
+    import tree_utils as TU
+    rng = np.random.default_rng(50 + P)
+    n, T = 7, 3
+    pids, bls = TU.random_trees(n, T, rng)
+    tips4, w4 = TU.random_alignment(n, P, rng, gap_fraction=0.2)
+    tips20, w20 = A.random_aa_alignment(n, P, rng, gap_fraction=0.2)
+    gtr = np.ones((T, 12))
+    gtr[:, :6], gtr[:, 6:10] = TU.random_gtr_params(T, rng)
+    for subst, tips, w, pr, kw in (("GTR", tips4, w4, gtr, {"use_tip_states": True}),
+                                   ("GTR", tips4, w4, gtr, {"use_tip_states": False}),
+                                   ("WAG", tips20, w20, A.params_for("weibull+4", T, rng), {})):
+        spec = L.PhyloModelSpecification(subst, "weibull+4", "strict")
+        d_t, d_w = torch.from_numpy(tips).to("cuda:0"), torch.from_numpy(w).to("cuda:0")
+        a = L.Engine(spec, tips, w, **kw)
+        b = L.Engine(spec, None, None, device_tips=(d_t.data_ptr(), d_w.data_ptr(), n, P), **kw)
+        assert np.array_equal(a.log_likelihoods(pids, bls, pr), b.log_likelihoods(pids, bls, pr))
+        ga, gb = a.gradients(pids, bls, pr), b.gradients(pids, bls, pr)
+        assert a.last_call_info() == b.last_call_info()
+        for x, y in zip(ga, gb):
+            assert x.log_likelihood == y.log_likelihood
+            for k in x.gradient:
+                assert np.array_equal(x.gradient[k], y.gradient[k]), (subst, kw, k)
+        a.close()
+        b.close()
+
+
 def test_device_tips_arguments_are_validated():
     """the device-resident door validates what it is given -- host arrays beside
     device_tips, a 20-state model table, a sharded handle and a HOST pointer passed as a device
