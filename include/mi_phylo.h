@@ -768,6 +768,83 @@ int32_t mi_engine_sbn_train(mi_engine* engine, int32_t tree_count, int32_t taxon
                             int32_t method, double alpha, int32_t max_iter, double score_epsilon,
                             double* out_log_params, double* out_score_history, int32_t* out_iterations);
 
+/* ---- sampling from an SBN and the gradient of the variational objective ----
+ * What the reference's SampleTrees (src/generic_sbn_instance.hpp:320-366) and TopologyGradients
+ * (src/unrooted_sbn_instance.cpp:128-198, src/generic_sbn_instance.hpp:398-431) do on the host.
+ *
+ * The descent table: every parameter j leads to two parent subsplits, which the sampler visits.
+ *   out_descent [P][2]   >= 0: a block (an index into parent_range); < 0: the leaf ~value
+ * Rootsplit j < S with the stored split s (never taxon 0): entry 0 is (focal s, sister ~s), entry 1
+ * (focal ~s, sister s).  PCSP (sister | focal | child): entry 0 is (focal child, sister
+ * focal \ child), entry 1 (focal focal \ child, sister child).  The pairs are taken from the
+ * support trees' own slots: the PCSP of slot (d, k) leads to the slots (c, k_c) of d's two child
+ * directed edges, k_c as in B(d) above; such a slot's entry is the block of its PCSP
+ * (pcsp_parent), or ~taxon where c's focal clade is a leaf.  Every occurrence of a parameter
+ * writes the same pair.  Only trees 0 .. support_tree_count-1 are read; a sentinel (or a refused
+ * tree) among them is an error that names the tree. */
+int32_t mi_engine_sbn_descent(mi_engine* engine, int32_t support_tree_count, int32_t taxon_count,
+                              const int32_t* parent_ids, const int32_t* root_index, const int32_t* slot_index,
+                              int32_t rootsplit_count, int32_t pcsp_count, const int32_t* pcsp_parent /* [C] */,
+                              int32_t* out_descent /* [P][2] */);
+
+/* sample_count topologies drawn from the SBN with parameters log_params [P] (unnormalised is fine;
+ * -inf allowed; NaN and +inf refused).
+ * The CDF, per block (the rootsplits [0, S) and every parent's range), m the block's maximum:
+ *   cdf[j] = sum over i <= j of the block of exp(log_params[i] - m)
+ * added in ascending order with one accumulator, whatever the block's length (a block of more than
+ * 16 entries is a wave's, which takes 64 exponentials side by side and adds them lane after lane:
+ * the same additions in the same order).  A -inf entry adds 0; a block that is all -inf has a CDF
+ * of zeros.  The CDF is non-decreasing within a block, and it is all the draws read.
+ * Random numbers: Philox4x32-10 (multipliers D2511F53, CD9E8D57; key increments 9E3779B9,
+ * BB67AE85).  Draw i of sample t = first_sample + k: key (seed lo, seed hi), counter
+ * (i, 0, t lo, t hi), u = ((w0 << 32 | w1) >> 11) 2^-53 from the first two output words.  A
+ * sample's bits depend on (seed, t) alone.
+ * A draw in block [b, e): x = u cdf[e-1] (one rounded product); the smallest j with cdf[j] > x; if
+ * there is none, the smallest j with cdf[j] == cdf[e-1].  Draw 0 is the rootsplit; then the two
+ * entries of the chosen parameter are descended depth first, entry 0's subtree before entry 1's;
+ * every visit of a block takes one draw.  A visited block whose total is 0 is an error that names
+ * the sample (its position k in the call) and the block; that sample's integer outputs are -1
+ * and its log probability NaN.
+ *   out_parent_ids [K][2n-3]   the sampled rooted tree, de-rooted as Node::Deroot does (the
+ *       trifurcation goes to the root child that holds taxon n-1 unless that child is a leaf, then
+ *       to the other one; the remaining root child becomes its third child) and numbered as every
+ *       unrooted call expects (leaves 0..n-1, internal nodes in post-order, children by largest
+ *       leaf id, the root 2n-3)
+ *   out_root_edge [K]          the new id of that third child: the sampled rooting is on its edge
+ *   out_sampled_params [K][n-1]  the drawn indices in the order of the draws
+ *   out_log_prob [K]           sum over them, in that order, one accumulator, of
+ *                              (log_params[j] - m_b) - log(cdf[e_b - 1])
+ *   out_cdf [P] or NULL        the CDF the draws read */
+int32_t mi_engine_sbn_sample(mi_engine* engine, int32_t sample_count, int32_t taxon_count,
+                             int32_t rootsplit_count, int32_t pcsp_count, int32_t parent_count,
+                             const int32_t* parent_range, const int32_t* descent /* [P][2] */,
+                             const double* log_params /* [P] */, uint64_t seed, int64_t first_sample,
+                             int32_t* out_parent_ids, int32_t* out_root_edge, int32_t* out_sampled_params,
+                             double* out_log_prob, double* out_cdf);
+
+/* The gradient of the multi-sample variational objective with respect to the unnormalised SBN
+ * parameters: out_gradient[j] = G_j - exp(theta_j) sum_{i in block(j)} G_i (the block's sum in
+ * ascending order), G_j = sum_t a_t usage_t[j] with the usage of mi_engine_sbn_log_prob.  Every
+ * usage is taken to the linear domain per term (each in [0, 1]), multiplied by a_t, and a
+ * parameter's terms are added signed in ascending (tree, entry) order with one accumulator.  A
+ * tree with log q = -inf adds nothing (the reference gives NaN there) and sentinel entries are
+ * skipped.  The factors a_t from log_f [K]:
+ *   MI_SBN_FACTORS_PLAIN  log F = logsumexp(log_f) (the maximum, then ascending);
+ *                         a_t = (log F - log K) - exp(log_f[t] - log F)
+ *   MI_SBN_FACTORS_VIMCO  the plain factor minus the per-sample signal: logsumexp over the K values
+ *                         with log_f[t] replaced by (sum log_f - log_f[t]) / (K - 1), minus log K;
+ *                         a fresh logsumexp per t.  K < 2 is refused.
+ *   MI_SBN_FACTORS_GIVEN  a_t = log_f[t]
+ *   out_gradient [P], out_factors [K], out_log_q [K] */
+enum { MI_SBN_FACTORS_PLAIN = 0, MI_SBN_FACTORS_VIMCO = 1, MI_SBN_FACTORS_GIVEN = 2 };
+int32_t mi_engine_sbn_topology_gradient(mi_engine* engine, int32_t tree_count, int32_t taxon_count,
+                                        const int32_t* parent_ids, const int32_t* root_index,
+                                        const int32_t* slot_index, int32_t rootsplit_count, int32_t pcsp_count,
+                                        int32_t parent_count, const int32_t* parent_range,
+                                        const double* log_params, int32_t normalized, const double* log_f,
+                                        int32_t estimator, double* out_gradient, double* out_factors,
+                                        double* out_log_q);
+
 /* Maximum-likelihood branch lengths of unrooted trees under box bounds (an extension: the
  * consumer of the Hessian call's outputs).  Every tree of the batch is
  * iterated on the device: an evaluation is one Hessian pass at a trial point, a step is a
@@ -1282,6 +1359,26 @@ int32_t mi_engine_sbn_train_device(mi_engine* engine, void* stream, int32_t tree
                                    double alpha, int32_t max_iter, double score_epsilon, double* out_log_params,
                                    double* out_score_history, int32_t* out_iterations);
 int32_t mi_engine_reserve_sbn(mi_engine* engine, int32_t tree_count, int32_t taxon_count);
+/* The device forms of the descent table, the sampler and the topology gradient: they only enqueue
+ * and report through the status word; after mi_engine_reserve_sbn as above they allocate nothing
+ * and read nothing back, so all three can be captured. */
+int32_t mi_engine_sbn_descent_device(mi_engine* engine, void* stream, int32_t support_tree_count,
+                                     int32_t taxon_count, const int32_t* parent_ids, const int32_t* root_index,
+                                     const int32_t* slot_index, int32_t rootsplit_count, int32_t pcsp_count,
+                                     const int32_t* pcsp_parent, int32_t* out_descent);
+int32_t mi_engine_sbn_sample_device(mi_engine* engine, void* stream, int32_t sample_count, int32_t taxon_count,
+                                    int32_t rootsplit_count, int32_t pcsp_count, int32_t parent_count,
+                                    const int32_t* parent_range, const int32_t* descent, const double* log_params,
+                                    uint64_t seed, int64_t first_sample, int32_t* out_parent_ids,
+                                    int32_t* out_root_edge, int32_t* out_sampled_params, double* out_log_prob,
+                                    double* out_cdf);
+int32_t mi_engine_sbn_topology_gradient_device(mi_engine* engine, void* stream, int32_t tree_count,
+                                               int32_t taxon_count, const int32_t* parent_ids,
+                                               const int32_t* root_index, const int32_t* slot_index,
+                                               int32_t rootsplit_count, int32_t pcsp_count, int32_t parent_count,
+                                               const int32_t* parent_range, const double* log_params,
+                                               int32_t normalized, const double* log_f, int32_t estimator,
+                                               double* out_gradient, double* out_factors, double* out_log_q);
 /* Synchronise `stream` and report the first per-tree error since the last check (the status
  * word is sticky and cleared when an error is reported: calls themselves never clear it). */
 int32_t mi_engine_check_status(mi_engine* engine, void* stream);

@@ -189,6 +189,22 @@ SYMBOLS = {
         (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V,
                      C.c_int32, C.c_double, C.c_int32, C.c_double, _V, _V, _V]),
     "mi_engine_reserve_sbn": (C.c_int32, [_V, C.c_int32, C.c_int32]),
+    "mi_engine_sbn_descent":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, _V, _V]),
+    "mi_engine_sbn_descent_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, _V, _V]),
+    "mi_engine_sbn_sample":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, C.c_uint64, C.c_int64,
+                     _V, _V, _V, _V, _V]),
+    "mi_engine_sbn_sample_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, C.c_uint64,
+                     C.c_int64, _V, _V, _V, _V, _V]),
+    "mi_engine_sbn_topology_gradient":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, C.c_int32,
+                     _V, C.c_int32, _V, _V, _V]),
+    "mi_engine_sbn_topology_gradient_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V,
+                     C.c_int32, _V, C.c_int32, _V, _V, _V]),
     "mi_consensus_tree":
         (C.c_int32, [C.c_int32, C.c_int32, _V, _V, C.c_double, C.c_double, I32P, _V, _V]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),

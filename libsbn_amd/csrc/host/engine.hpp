@@ -122,6 +122,19 @@ struct SbnTraining {
   std::vector<double> log_params_, score_history_;
 };
 
+// Engine::SbnSample: parent_ids_ [K][2n-3], root_edge_ [K], sampled_params_ [K][n-1] in the order
+// of the draws, log_prob_ [K] of the sampled rootings and the cdf_ [P] the draws read
+struct SbnSamples {
+  std::vector<int32_t> parent_ids_, root_edge_, sampled_params_;
+  std::vector<double> log_prob_, cdf_;
+};
+
+// Engine::SbnTopologyGradient: gradient_ [P] with respect to the unnormalised parameters, the
+// factors_ [K] it was formed with and log_q_ [K]
+struct SbnGradient {
+  std::vector<double> gradient_, factors_, log_q_;
+};
+
 // Engine::RfDistances: rf_ [T][T] and, with branch lengths, branch_score_ [T][T]
 struct TreeDistances {
   std::vector<int32_t> rf_;
@@ -690,6 +703,65 @@ class Engine {
         static_cast<int32_t>(max_iter), score_epsilon, out.log_params_.data(), out.score_history_.data(),
         &iterations));
     out.score_history_.resize(static_cast<size_t>(iterations));
+    return out;
+  }
+
+  // The descent table [P][2] of a support: the two parent subsplits every parameter leads to
+  // (>= 0 a block of parent_range_, < 0 the leaf ~value): mi_engine_sbn_descent.
+  std::vector<int32_t> SbnDescent(const SbnSupport& support) const {
+    std::vector<int32_t> out(support.ParameterCount() * 2);
+    Check(mi_engine_sbn_descent(
+        handle_, static_cast<int32_t>(support.support_tree_count_), static_cast<int32_t>(support.taxon_count_),
+        support.parent_ids_.data(), support.root_index_.data(), support.slot_index_.data(),
+        static_cast<int32_t>(support.rootsplit_count_), static_cast<int32_t>(support.pcsp_count_),
+        support.pcsp_parent_.data(), out.data()));
+    return out;
+  }
+
+  // sample_count topologies drawn from the SBN with (unnormalised) log_params [P]; sample k is the
+  // Philox stream (seed, first_sample + k): mi_engine_sbn_sample.
+  SbnSamples SbnSample(const SbnSupport& support, const std::vector<int32_t>& descent,
+                       const std::vector<double>& log_params, const size_t sample_count, const uint64_t seed,
+                       const int64_t first_sample = 0) const {
+    const size_t K = sample_count, n = support.taxon_count_, P = support.ParameterCount();
+    if (log_params.size() != P || descent.size() != 2 * P)
+      Failwith("SbnSample: log parameters must be [rootsplits + PCSPs], the descent table twice that.");
+    SbnSamples out;
+    out.parent_ids_.resize(K * (2 * n - 3));
+    out.root_edge_.resize(K);
+    out.sampled_params_.resize(K * (n - 1));
+    out.log_prob_.resize(K);
+    out.cdf_.resize(P);
+    Check(mi_engine_sbn_sample(
+        handle_, static_cast<int32_t>(K), static_cast<int32_t>(n), static_cast<int32_t>(support.rootsplit_count_),
+        static_cast<int32_t>(support.pcsp_count_), static_cast<int32_t>(support.parent_count_),
+        support.parent_range_.data(), descent.data(), log_params.data(), seed, first_sample, out.parent_ids_.data(),
+        out.root_edge_.data(), out.sampled_params_.data(), out.log_prob_.data(), out.cdf_.data()));
+    return out;
+  }
+
+  // The gradient of the multi-sample variational objective with respect to the unnormalised
+  // parameters over trees first_tree .. of the support's batch (the samples, indexed behind the
+  // support trees), log_f one value per such tree, estimator MI_SBN_FACTORS_PLAIN / _VIMCO /
+  // _GIVEN: mi_engine_sbn_topology_gradient.
+  SbnGradient SbnTopologyGradient(const SbnSupport& support, const std::vector<double>& log_params,
+                                  const std::vector<double>& log_f, const int32_t estimator = MI_SBN_FACTORS_VIMCO,
+                                  const size_t first_tree = 0, const bool normalized = false) const {
+    const size_t E = 2 * support.taxon_count_ - 3, P = support.ParameterCount();
+    if (first_tree >= support.tree_count_ || log_f.size() != support.tree_count_ - first_tree || log_params.size() != P)
+      Failwith("SbnTopologyGradient: log_f must be [trees from first_tree on], log parameters [rootsplits + PCSPs].");
+    const size_t K = log_f.size();
+    SbnGradient out;
+    out.gradient_.resize(P);
+    out.factors_.resize(K);
+    out.log_q_.resize(K);
+    Check(mi_engine_sbn_topology_gradient(
+        handle_, static_cast<int32_t>(K), static_cast<int32_t>(support.taxon_count_),
+        support.parent_ids_.data() + first_tree * E, support.root_index_.data() + first_tree * E,
+        support.slot_index_.data() + first_tree * E * 6, static_cast<int32_t>(support.rootsplit_count_),
+        static_cast<int32_t>(support.pcsp_count_), static_cast<int32_t>(support.parent_count_),
+        support.parent_range_.data(), log_params.data(), normalized ? 1 : 0, log_f.data(), estimator,
+        out.gradient_.data(), out.factors_.data(), out.log_q_.data()));
     return out;
   }
 

@@ -98,6 +98,9 @@ enum StatusCode : int32_t {
   kSbnBadParam = 16,    // (its second status word carries the parameter's index)
   kSbnBadWeight = 17,
   kSbnOutOfSupport = 18,
+  kSbnEmptyBlock = 19,   // (its second and fourth status words carry the sample and the block)
+  kSbnBadDescent = 20,   // (its second status word carries the sample)
+  kSbnSupportSentinel = 21,
 };
 
 }  // namespace miphylo

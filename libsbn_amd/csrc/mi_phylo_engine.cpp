@@ -356,6 +356,9 @@ int check_status(mi_engine* e, hipStream_t s) {
     // (the SBN support's capacities: both needed counts)
     if (st[0] == kSbnCapacity)
       return fail(std::string(status_message(st[0])) + " (S = " + std::to_string(st[1]) + ", C = " + std::to_string(st[3]) + ")");
+    if (st[0] == kSbnEmptyBlock)
+      return fail(std::string(status_message(st[0])) + " (sample " + std::to_string(st[1]) + ", block " + std::to_string(st[3]) + ")");
+    if (st[0] == kSbnBadDescent) return fail(std::string(status_message(st[0])) + " (sample " + std::to_string(st[1]) + ")");
     if (st[0] == kSbnBadParam) return fail(std::string(status_message(st[0])) + " (parameter " + std::to_string(st[1]) + ")");
     return fail(std::string(status_message(st[0])) + (st[0] == kBadDistance ? " (matrix " : " (tree ") +
                 std::to_string(st[1] + e->status_tree_offset) + ")");

@@ -65,6 +65,9 @@ inline const char* status_message(int code) {
     case kSbnBadParam: return "SBN log parameters must be finite or -inf";
     case kSbnBadWeight: return "SBN tree weights must be finite and not negative";
     case kSbnOutOfSupport: return "SBN training: a training tree has a rootsplit or PCSP outside the support";
+    case kSbnEmptyBlock: return "SBN sample: a sample reached a block whose parameters are all -inf";
+    case kSbnBadDescent: return "SBN sample: the descent table or parent_range does not describe a support of this taxon count";
+    case kSbnSupportSentinel: return "SBN descent: a support tree has a rootsplit or PCSP outside the support";
     default: return "unknown device status";
   }
 }

@@ -654,6 +654,58 @@ void launch_sbn_combine(int P, const double* a, const double* b, double shift, d
 // *out = sum_t w_t log_q[t] (+ sum_j exp(log_m[j]) theta[j] if log_m), in ascending order by one wave
 void launch_sbn_score(int T, const double* weights, const double* log_q, int P, const double* log_m,
                       const double* theta, double* out, hipStream_t s);
+// kernels_sbn_vi.hip: the descent table, the sampler and the topology gradient.
+// The per-tree kernels (descent: a lane per support tree; sample: a lane per sample) use the node
+// arrays above: the same six words per node, the same [word][node][tpw] layout, LDS or `store`.
+struct SbnDescentArgs {
+  int n, T0, tpw;
+  int S, C;
+  const int32_t* parent_ids;   // [T0][2n-3]
+  const int32_t* root_index;   // [T0][2n-3]
+  const int32_t* slot_index;   // [T0][2(2n-3)][3]
+  const int32_t* pcsp_parent;  // [C]
+  int32_t* status;
+  char* store;
+  int32_t* out_descent;        // [S + C][2]
+};
+void launch_sbn_descent(const SbnDescentArgs& a, hipStream_t s);
+struct SbnSampleArgs {
+  int n, K, tpw;
+  int S, C, parents;
+  const int32_t* parent_range;  // [parents][2]
+  const int32_t* descent;       // [S + C][2]
+  const double* phi;            // [S + C] log parameters, unnormalised
+  uint64_t seed;
+  int64_t first_sample;
+  int32_t* status;
+  char* store;
+  double* cdf;                  // [S + C]
+  double* block_max;            // [parents + 1] the rootsplits' maximum, then every parent's
+  int32_t* out_parent_ids;      // [K][2n-3]
+  int32_t* out_root_edge;       // [K]
+  int32_t* out_params;          // [K][n-1]
+  double* out_log_prob;         // [K]
+};
+void launch_sbn_sample(const SbnSampleArgs& a, hipStream_t s);  // the CDF, then the draws
+struct SbnGradientArgs {
+  int n, T, P, S, parents;
+  int estimator;                // MI_SBN_FACTORS_*
+  const int32_t* root_index;    // [T][2n-3]
+  const int32_t* slot_index;    // [T][2(2n-3)][3]
+  const int32_t* parent_range;  // [parents][2]
+  const double* theta;          // [P] normalised
+  const double* log_f;          // [T]
+  const double* usage;          // [T][7 (2n-3)] log usage, as sbn_walk_kernel leaves it
+  uint32_t *keys, *keys2, *vals, *vals2;  // [T 7 (2n-3)]
+  void* sort_tmp;
+  size_t sort_tmp_bytes;
+  double* G;                    // [P] workspace
+  double* sums;                 // [2] workspace: log F and sum log_f
+  double* out_factors;          // [T]
+  double* out_gradient;         // [P]
+};
+int launch_sbn_gradient(const SbnGradientArgs& a, hipStream_t s);  // (after the walk; nonzero: rocPRIM refused)
+void sbn_vi_prepare(int n, int tpw);  // the large-LDS opt-in of the two per-tree kernels
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
 // the first, gradient_mfma_kernel, was retired in round 6): all categories of a group of four
 // per instruction; they also write the log-likelihood partial sums, so no separate logL pass is

@@ -1,7 +1,9 @@
 // Subsplit Bayesian networks: the support of a tree batch with every tree's slots
 // (mi_engine_sbn_index*), the probabilities of all rootings with the expected usages
 // (mi_engine_sbn_log_prob*), the segmented log-normalisation (mi_engine_sbn_normalize*),
-// simple-average and EM training (mi_engine_sbn_train*) and their reservation.  The device forms
+// simple-average and EM training (mi_engine_sbn_train*), the descent table, the sampler and the
+// topology gradient (mi_engine_sbn_{descent,sample,topology_gradient}*) and their
+// reservation.  The device forms
 // of the first three only enqueue; training reads one double per iteration and synchronises.  Any
 // engine serves: the taxon count is an argument and the alignment plays no part; a sharded handle
 // lets its first shard do the work.
@@ -403,6 +405,169 @@ int run_sbn_train_device(mi_engine* e, hipStream_t s, const SbnTrainCall& c) {
   return 0;
 }
 
+// ---- the descent table, the sampler and the topology gradient ----
+struct SbnDescentCall {
+  int T0 = 0, n = 0, S = 0, C = 0;
+  const int32_t *parent_ids = nullptr, *root_index = nullptr, *slot_index = nullptr, *pcsp_parent = nullptr;
+  int32_t* out_descent = nullptr;
+};
+
+int check_descent_call(const mi_engine* e, const SbnDescentCall& c) {
+  if (check_sbn_shape(e, c.T0, c.n)) return 1;
+  if (c.S < 1 || c.C < 0) return fail("SBN: bad rootsplit or PCSP count");
+  if (!c.parent_ids || !c.root_index || !c.slot_index) return fail("null tree arrays");
+  if (c.C > 0 && !c.pcsp_parent) return fail("SBN descent: null pcsp_parent");
+  if (!c.out_descent) return fail("null output pointer");
+  return 0;
+}
+
+int run_sbn_descent_device(mi_engine* e, hipStream_t s, const SbnDescentCall& c) {
+  if (check_descent_call(e, c)) return 1;
+  HIP_TRY(hipSetDevice(e->spec.device));
+  const size_t store = sbn_store_bytes(e, c.T0, c.n);
+  if (store > e->plv_budget) return fail("SBN descent: " + sizes(c.T0, c.n, store, e));
+  if (store && e->sbn_store.ensure(store)) return 1;
+  if (e->status.ensure(sizeof(int32_t) * kStatusWords)) return 1;
+  SbnDescentArgs a{};
+  a.n = c.n;
+  a.T0 = c.T0;
+  a.tpw = sbn_tpw(e);
+  a.S = c.S;
+  a.C = c.C;
+  a.parent_ids = c.parent_ids;
+  a.root_index = c.root_index;
+  a.slot_index = c.slot_index;
+  a.pcsp_parent = c.pcsp_parent;
+  a.status = e->status.as<int32_t>();
+  a.store = e->sbn_store.as<char>();
+  a.out_descent = c.out_descent;
+  launch_sbn_descent(a, s);
+  HIP_TRY(hipGetLastError());
+  note_call(e, "sbn_descent_kernel", c.T0, c.n);
+  return 0;
+}
+
+struct SbnSampleCall {
+  int K = 0, n = 0, S = 0, C = 0, parents = 0;
+  const int32_t *parent_range = nullptr, *descent = nullptr;
+  const double* log_params = nullptr;
+  uint64_t seed = 0;
+  int64_t first_sample = 0;
+  int32_t *out_parent_ids = nullptr, *out_root_edge = nullptr, *out_params = nullptr;
+  double *out_log_prob = nullptr, *out_cdf = nullptr;
+};
+
+int check_sample_call(const mi_engine* e, const SbnSampleCall& c) {
+  if (check_sbn_shape(e, c.K, c.n)) return 1;
+  if (check_support(c.S, c.C, c.parents, c.parent_range)) return 1;
+  if (!c.descent) return fail("SBN sample: null descent table");
+  if (!c.log_params) return fail("null parameter vector");
+  if (!c.out_parent_ids || !c.out_root_edge || !c.out_params || !c.out_log_prob) return fail("null output pointer");
+  return 0;
+}
+
+int run_sbn_sample_device(mi_engine* e, hipStream_t s, const SbnSampleCall& c) {
+  if (check_sample_call(e, c)) return 1;
+  HIP_TRY(hipSetDevice(e->spec.device));
+  const int P = c.S + c.C;
+  const ProbLayout l = call_layout(c.K, c.n, P);
+  if (reserve_sbn_prob(e, c.K, c.n, P)) return 1;
+  char* ws = e->sbn_prob_ws.as<char>();
+  SbnSampleArgs a{};
+  a.n = c.n;
+  a.K = c.K;
+  a.tpw = sbn_tpw(e);
+  a.S = c.S;
+  a.C = c.C;
+  a.parents = c.parents;
+  a.parent_range = c.parent_range;
+  a.descent = c.descent;
+  a.phi = c.log_params;
+  a.seed = c.seed;
+  a.first_sample = c.first_sample;
+  a.status = e->status.as<int32_t>();
+  a.store = e->sbn_store.as<char>();
+  a.cdf = c.out_cdf ? c.out_cdf : reinterpret_cast<double*>(ws + l.log_m_tilde);
+  a.block_max = reinterpret_cast<double*>(ws + l.log_m_bar);  // (parents + 1 <= P)
+  a.out_parent_ids = c.out_parent_ids;
+  a.out_root_edge = c.out_root_edge;
+  a.out_params = c.out_params;
+  a.out_log_prob = c.out_log_prob;
+  launch_sbn_check_params(P, c.log_params, a.status, s);
+  launch_sbn_sample(a, s);
+  HIP_TRY(hipGetLastError());
+  note_call(e, "sbn_sample_kernel", c.K, c.n);
+  return 0;
+}
+
+struct SbnGradientCall {
+  SbnProbCall p;  // (weights and the rooting output unused; out_counts null)
+  const double* log_f = nullptr;
+  int estimator = 0;
+  double *out_gradient = nullptr, *out_factors = nullptr;
+};
+
+int check_gradient_call(const mi_engine* e, const SbnGradientCall& c) {
+  if (check_sbn_shape(e, c.p.T, c.p.n)) return 1;
+  if (check_support(c.p.S, c.p.C, c.p.parents, c.p.parent_range)) return 1;
+  if (!c.p.parent_ids || !c.p.root_index || !c.p.slot_index) return fail("null tree arrays");
+  if (!c.p.log_params) return fail("null parameter vector");
+  if (c.estimator != MI_SBN_FACTORS_PLAIN && c.estimator != MI_SBN_FACTORS_VIMCO && c.estimator != MI_SBN_FACTORS_GIVEN)
+    return fail("SBN topology gradient: estimator must be MI_SBN_FACTORS_PLAIN, _VIMCO or _GIVEN");
+  if (c.estimator == MI_SBN_FACTORS_VIMCO && c.p.T < 2)
+    return fail("SBN topology gradient: the VIMCO factors need at least 2 trees");
+  if (!c.log_f) return fail("SBN topology gradient: null log_f");
+  if (!c.out_gradient || !c.out_factors || !c.p.out_log_q) return fail("null output pointer");
+  return 0;
+}
+
+int run_sbn_gradient_device(mi_engine* e, hipStream_t s, const SbnGradientCall& c) {
+  if (check_gradient_call(e, c)) return 1;
+  HIP_TRY(hipSetDevice(e->spec.device));
+  const int T = c.p.T, n = c.p.n, P = c.p.S + c.p.C;
+  const ProbLayout l = call_layout(T, n, P);
+  if (reserve_sbn_prob(e, T, n, P)) return 1;
+  char* ws = e->sbn_prob_ws.as<char>();
+  // the walk of log_prob: log q and the log usage of every entry, every tree with weight 1
+  SbnProbArgs a = prob_args(e, c.p, l);
+  launch_sbn_check_params(P, c.p.log_params, a.status, s);
+  double* theta = reinterpret_cast<double*>(ws + l.theta);
+  if (!c.p.normalized) launch_sbn_normalize(c.p.S, c.p.parents, c.p.parent_range, c.p.log_params, theta, s);
+  a.theta = c.p.normalized ? c.p.log_params : theta;
+  a.weights = nullptr;
+  a.out_rooting = reinterpret_cast<double*>(ws + l.rooting);
+  a.out_log_q = c.p.out_log_q;
+  a.out_counts = nullptr;
+  if (launch_sbn_log_prob(a, s)) return fail("SBN topology gradient: the walk could not be enqueued");
+  SbnGradientArgs g{};
+  g.n = n;
+  g.T = T;
+  g.P = P;
+  g.S = c.p.S;
+  g.parents = c.p.parents;
+  g.estimator = c.estimator;
+  g.root_index = c.p.root_index;
+  g.slot_index = c.p.slot_index;
+  g.parent_range = c.p.parent_range;
+  g.theta = a.theta;
+  g.log_f = c.log_f;
+  g.usage = a.usage;
+  g.keys = a.keys;
+  g.keys2 = a.keys2;
+  g.vals = a.vals;
+  g.vals2 = a.vals2;
+  g.sort_tmp = a.sort_tmp;
+  g.sort_tmp_bytes = a.sort_tmp_bytes;
+  g.G = reinterpret_cast<double*>(ws + l.log_m_bar);
+  g.sums = reinterpret_cast<double*>(ws + l.log_q);  // (the gradient's log q is the caller's array)
+  g.out_factors = c.out_factors;
+  g.out_gradient = c.out_gradient;
+  if (launch_sbn_gradient(g, s)) return fail("SBN topology gradient: the sort could not be enqueued");
+  HIP_TRY(hipGetLastError());
+  note_call(e, "sbn_walk_kernel", T, n);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -651,6 +816,194 @@ int32_t mi_engine_sbn_train(mi_engine* e, int32_t T, int32_t n, const int32_t* p
   return run_on_engine(first_engine(e), h);
 }
 
+int32_t mi_engine_sbn_descent_device(mi_engine* e, void* stream, int32_t T0, int32_t n, const int32_t* parent_ids,
+                                     const int32_t* root_index, const int32_t* slot_index, int32_t S, int32_t C,
+                                     const int32_t* pcsp_parent, int32_t* out_descent) {
+  if (!e) return fail("null engine");
+  if (!e->shards.empty()) return fail(kShardedDeviceCall);
+  SbnDescentCall c;
+  c.T0 = T0;
+  c.n = n;
+  c.S = S;
+  c.C = C;
+  c.parent_ids = parent_ids;
+  c.root_index = root_index;
+  c.slot_index = slot_index;
+  c.pcsp_parent = pcsp_parent;
+  c.out_descent = out_descent;
+  return run_sbn_descent_device(e, pick_stream(e, stream), c);
+}
+
+int32_t mi_engine_sbn_descent(mi_engine* e, int32_t T0, int32_t n, const int32_t* parent_ids, const int32_t* root_index,
+                              const int32_t* slot_index, int32_t S, int32_t C, const int32_t* pcsp_parent,
+                              int32_t* out_descent) {
+  SbnDescentCall c;
+  c.T0 = T0;
+  c.n = n;
+  c.S = S;
+  c.C = C;
+  c.parent_ids = parent_ids;
+  c.root_index = root_index;
+  c.slot_index = slot_index;
+  c.pcsp_parent = pcsp_parent;
+  c.out_descent = out_descent;
+  if (check_descent_call(e, c)) return 1;
+  const size_t E = 2 * (size_t)n - 3, P = (size_t)S + C;
+  HostCall h;
+  h.in = {fixed(parent_ids, (size_t)T0 * E), fixed(root_index, (size_t)T0 * E), fixed(slot_index, (size_t)T0 * E * 6),
+          fixed(pcsp_parent, (size_t)C)};
+  h.out = {fixed(out_descent, P * 2)};
+  h.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    SbnDescentCall d = c;
+    d.parent_ids = in[0].at<const int32_t>();
+    d.root_index = in[1].at<const int32_t>();
+    d.slot_index = in[2].at<const int32_t>();
+    d.pcsp_parent = in[3].at<const int32_t>();
+    d.out_descent = out[0].at<int32_t>();
+    return run_sbn_descent_device(e, e->stream, d);
+  };
+  return run_on_engine(first_engine(e), h);
+}
+
+int32_t mi_engine_sbn_sample_device(mi_engine* e, void* stream, int32_t K, int32_t n, int32_t S, int32_t C,
+                                    int32_t parents, const int32_t* parent_range, const int32_t* descent,
+                                    const double* log_params, uint64_t seed, int64_t first_sample,
+                                    int32_t* out_parent_ids, int32_t* out_root_edge, int32_t* out_sampled_params,
+                                    double* out_log_prob, double* out_cdf) {
+  if (!e) return fail("null engine");
+  if (!e->shards.empty()) return fail(kShardedDeviceCall);
+  SbnSampleCall c;
+  c.K = K;
+  c.n = n;
+  c.S = S;
+  c.C = C;
+  c.parents = parents;
+  c.parent_range = parent_range;
+  c.descent = descent;
+  c.log_params = log_params;
+  c.seed = seed;
+  c.first_sample = first_sample;
+  c.out_parent_ids = out_parent_ids;
+  c.out_root_edge = out_root_edge;
+  c.out_params = out_sampled_params;
+  c.out_log_prob = out_log_prob;
+  c.out_cdf = out_cdf;
+  return run_sbn_sample_device(e, pick_stream(e, stream), c);
+}
+
+int32_t mi_engine_sbn_sample(mi_engine* e, int32_t K, int32_t n, int32_t S, int32_t C, int32_t parents,
+                             const int32_t* parent_range, const int32_t* descent, const double* log_params,
+                             uint64_t seed, int64_t first_sample, int32_t* out_parent_ids, int32_t* out_root_edge,
+                             int32_t* out_sampled_params, double* out_log_prob, double* out_cdf) {
+  SbnSampleCall c;
+  c.K = K;
+  c.n = n;
+  c.S = S;
+  c.C = C;
+  c.parents = parents;
+  c.parent_range = parent_range;
+  c.descent = descent;
+  c.log_params = log_params;
+  c.seed = seed;
+  c.first_sample = first_sample;
+  c.out_parent_ids = out_parent_ids;
+  c.out_root_edge = out_root_edge;
+  c.out_params = out_sampled_params;
+  c.out_log_prob = out_log_prob;
+  c.out_cdf = out_cdf;
+  if (check_sample_call(e, c)) return 1;
+  const size_t E = 2 * (size_t)n - 3, P = (size_t)S + C;
+  HostCall h;
+  h.in = {fixed(parent_range, (size_t)parents * 2), fixed(descent, P * 2), fixed(log_params, P)};
+  h.out = {fixed(out_parent_ids, (size_t)K * E), fixed(out_root_edge, (size_t)K),
+           fixed(out_sampled_params, (size_t)K * (n - 1)), fixed(out_log_prob, (size_t)K), fixed(out_cdf, P)};
+  h.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    SbnSampleCall d = c;
+    d.parent_range = in[0].at<const int32_t>();
+    d.descent = in[1].at<const int32_t>();
+    d.log_params = in[2].at<const double>();
+    d.out_parent_ids = out[0].at<int32_t>();
+    d.out_root_edge = out[1].at<int32_t>();
+    d.out_params = out[2].at<int32_t>();
+    d.out_log_prob = out[3].at<double>();
+    d.out_cdf = out[4].at<double>();
+    return run_sbn_sample_device(e, e->stream, d);
+  };
+  return run_on_engine(first_engine(e), h);
+}
+
+int32_t mi_engine_sbn_topology_gradient_device(mi_engine* e, void* stream, int32_t T, int32_t n,
+                                               const int32_t* parent_ids, const int32_t* root_index,
+                                               const int32_t* slot_index, int32_t S, int32_t C, int32_t parents,
+                                               const int32_t* parent_range, const double* log_params,
+                                               int32_t normalized, const double* log_f, int32_t estimator,
+                                               double* out_gradient, double* out_factors, double* out_log_q) {
+  if (!e) return fail("null engine");
+  if (!e->shards.empty()) return fail(kShardedDeviceCall);
+  SbnGradientCall c;
+  c.p.T = T;
+  c.p.n = n;
+  c.p.S = S;
+  c.p.C = C;
+  c.p.parents = parents;
+  c.p.normalized = normalized != 0;
+  c.p.parent_ids = parent_ids;
+  c.p.root_index = root_index;
+  c.p.slot_index = slot_index;
+  c.p.parent_range = parent_range;
+  c.p.log_params = log_params;
+  c.p.out_log_q = out_log_q;
+  c.log_f = log_f;
+  c.estimator = estimator;
+  c.out_gradient = out_gradient;
+  c.out_factors = out_factors;
+  return run_sbn_gradient_device(e, pick_stream(e, stream), c);
+}
+
+int32_t mi_engine_sbn_topology_gradient(mi_engine* e, int32_t T, int32_t n, const int32_t* parent_ids,
+                                        const int32_t* root_index, const int32_t* slot_index, int32_t S, int32_t C,
+                                        int32_t parents, const int32_t* parent_range, const double* log_params,
+                                        int32_t normalized, const double* log_f, int32_t estimator,
+                                        double* out_gradient, double* out_factors, double* out_log_q) {
+  SbnGradientCall c;
+  c.p.T = T;
+  c.p.n = n;
+  c.p.S = S;
+  c.p.C = C;
+  c.p.parents = parents;
+  c.p.normalized = normalized != 0;
+  c.p.parent_ids = parent_ids;
+  c.p.root_index = root_index;
+  c.p.slot_index = slot_index;
+  c.p.parent_range = parent_range;
+  c.p.log_params = log_params;
+  c.p.out_log_q = out_log_q;
+  c.log_f = log_f;
+  c.estimator = estimator;
+  c.out_gradient = out_gradient;
+  c.out_factors = out_factors;
+  if (check_gradient_call(e, c)) return 1;
+  const size_t E = 2 * (size_t)n - 3, P = (size_t)S + C;
+  HostCall h;
+  h.in = {fixed(parent_ids, (size_t)T * E), fixed(root_index, (size_t)T * E), fixed(slot_index, (size_t)T * E * 6),
+          fixed(parent_range, (size_t)parents * 2), fixed(log_params, P), fixed(log_f, (size_t)T)};
+  h.out = {fixed(out_gradient, P), fixed(out_factors, (size_t)T), fixed(out_log_q, (size_t)T)};
+  h.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    SbnGradientCall d = c;
+    d.p.parent_ids = in[0].at<const int32_t>();
+    d.p.root_index = in[1].at<const int32_t>();
+    d.p.slot_index = in[2].at<const int32_t>();
+    d.p.parent_range = in[3].at<const int32_t>();
+    d.p.log_params = in[4].at<const double>();
+    d.log_f = in[5].at<const double>();
+    d.out_gradient = out[0].at<double>();
+    d.out_factors = out[1].at<double>();
+    d.p.out_log_q = out[2].at<double>();
+    return run_sbn_gradient_device(e, e->stream, d);
+  };
+  return run_on_engine(first_engine(e), h);
+}
+
 int32_t mi_engine_reserve_sbn(mi_engine* e, int32_t T, int32_t n) {
   if (check_sbn_shape(e, T, n)) return 1;
   e = first_engine(e);
@@ -659,6 +1012,7 @@ int32_t mi_engine_reserve_sbn(mi_engine* e, int32_t T, int32_t n) {
   if (reserve_sbn_index(e, T, n)) return 1;
   if (reserve_sbn_prob(e, T, n, 0)) return 1;
   sbn_prepare(n, sbn_tpw(e));
+  sbn_vi_prepare(n, sbn_tpw(e));
   return 0;
 }
 

@@ -411,6 +411,15 @@ def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+_SBN_FACTORS = {"plain": 0, "vimco": 1, "given": 2}   # MI_SBN_FACTORS_*
+
+
+def _sbn_factors(estimator):
+    if estimator not in _SBN_FACTORS:
+        raise RuntimeError(f"sbn_topology_gradient: estimator must be 'plain', 'vimco' or 'given', got {estimator!r}")
+    return _SBN_FACTORS[estimator]
+
+
 class Engine:
     """One MI355X engine: tips + pattern weights resident in HBM."""
 
@@ -986,6 +995,52 @@ class Engine:
             _ptr(history), _ptr(iters)))
         return out, history[:int(iters[0])].copy()
 
+    def sbn_descent(self, support):
+        """The descent table [P][2] of a support (mi_engine_sbn_descent): the two parent subsplits
+        every parameter leads to, >= 0 a block of parent_range, < 0 the leaf ~value."""
+        T0 = support.support_tree_count
+        pid = np.ascontiguousarray(support.parent_ids[:T0])
+        root = np.ascontiguousarray(support.root_index[:T0])
+        slot = np.ascontiguousarray(support.slot_index[:T0])
+        out = np.empty((support.parameter_count, 2), np.int32)
+        self._check(self._lib.mi_engine_sbn_descent(
+            self._h, T0, support.taxon_count, _ptr(pid), _ptr(root), _ptr(slot), support.rootsplit_count,
+            support.pcsp_count, _ptr(support.pcsp_parent), _ptr(out)))
+        return out
+
+    def sbn_sample(self, support, descent, log_params, K, seed, first_sample=0, cdf=False):
+        """K topologies drawn from the SBN with (unnormalised) log_params [P] by the Philox stream
+        (seed, first_sample + k) (mi_engine_sbn_sample).  Returns (parent ids [K][2n-3], root edge
+        [K], sampled parameters [K][n-1], log probability [K]), with cdf=True also the CDF [P]."""
+        n, P, K = support.taxon_count, support.parameter_count, int(K)
+        th = _np(log_params, np.float64).reshape(P)
+        desc = _np(descent, np.int32).reshape(P, 2)
+        pid, edge = np.empty((K, 2 * n - 3), np.int32), np.empty(K, np.int32)
+        params, lp = np.empty((K, n - 1), np.int32), np.empty(K)
+        out_cdf = np.empty(P) if cdf else None
+        self._check(self._lib.mi_engine_sbn_sample(
+            self._h, K, n, support.rootsplit_count, support.pcsp_count, support.parent_count,
+            _ptr(support.parent_range), _ptr(desc), _ptr(th), int(seed) & (2 ** 64 - 1), int(first_sample),
+            _ptr(pid), _ptr(edge), _ptr(params), _ptr(lp), _ptr(out_cdf)))
+        return (pid, edge, params, lp, out_cdf) if cdf else (pid, edge, params, lp)
+
+    def sbn_topology_gradient(self, support, log_params, log_f, estimator="vimco", trees=None, normalized=False):
+        """The gradient of the multi-sample variational objective with respect to the unnormalised
+        SBN parameters (mi_engine_sbn_topology_gradient) for trees of a support's batch (see
+        _sbn_trees) with log_f [K]; estimator "plain", "vimco" or "given" (log_f holds the
+        factors).  Returns (gradient [P], factors [K], log q [K])."""
+        code = _sbn_factors(estimator)
+        pid, root, slot = self._sbn_trees(support, trees)
+        T = pid.shape[0]
+        P = support.parameter_count
+        th, f = _np(log_params, np.float64).reshape(P), _np(log_f, np.float64).reshape(T)
+        grad, factors, lq = np.empty(P), np.empty(T), np.empty(T)
+        self._check(self._lib.mi_engine_sbn_topology_gradient(
+            self._h, T, support.taxon_count, _ptr(pid), _ptr(root), _ptr(slot), support.rootsplit_count,
+            support.pcsp_count, support.parent_count, _ptr(support.parent_range), _ptr(th), int(bool(normalized)),
+            _ptr(f), code, _ptr(grad), _ptr(factors), _ptr(lq)))
+        return grad, factors, lq
+
     def rf_distances(self, split_index, branch_lengths=None):
         """Robinson-Foulds distances [T][T] between the trees of a split index [T][2n-1]
         (mi_engine_rf_distances); with branch_lengths [T][2n-2] also the squared
@@ -1451,6 +1506,31 @@ class Engine:
             self._h, stream, int(T), int(n), parent_ids, root_index, slot_index, int(rootsplit_count),
             int(pcsp_count), int(parent_count), parent_range, tree_weights, 0 if method == "sa" else 1,
             float(alpha), int(max_iter), float(score_epsilon), out_log_params, out_score_history, out_iterations))
+
+    def sbn_descent_device(self, stream, support_tree_count, n, parent_ids, root_index, slot_index,
+                           rootsplit_count, pcsp_count, pcsp_parent, out_descent):
+        """mi_engine_sbn_descent_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_sbn_descent_device(
+            self._h, stream, int(support_tree_count), int(n), parent_ids, root_index, slot_index,
+            int(rootsplit_count), int(pcsp_count), pcsp_parent, out_descent))
+
+    def sbn_sample_device(self, stream, K, n, rootsplit_count, pcsp_count, parent_count, parent_range, descent,
+                          log_params, seed, first_sample, out_parent_ids, out_root_edge, out_sampled_params,
+                          out_log_prob, out_cdf=None):
+        """mi_engine_sbn_sample_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_sbn_sample_device(
+            self._h, stream, int(K), int(n), int(rootsplit_count), int(pcsp_count), int(parent_count),
+            parent_range, descent, log_params, int(seed) & (2 ** 64 - 1), int(first_sample), out_parent_ids,
+            out_root_edge, out_sampled_params, out_log_prob, out_cdf))
+
+    def sbn_topology_gradient_device(self, stream, T, n, parent_ids, root_index, slot_index, rootsplit_count,
+                                     pcsp_count, parent_count, parent_range, log_params, normalized, log_f,
+                                     estimator, out_gradient, out_factors, out_log_q):
+        """mi_engine_sbn_topology_gradient_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_sbn_topology_gradient_device(
+            self._h, stream, int(T), int(n), parent_ids, root_index, slot_index, int(rootsplit_count),
+            int(pcsp_count), int(parent_count), parent_range, log_params, int(bool(normalized)), log_f,
+            _sbn_factors(estimator), out_gradient, out_factors, out_log_q))
 
     def reserve_sbn(self, tree_count, taxon_count):
         """mi_engine_reserve_sbn: workspace of the SBN calls for that many trees of that taxon
