@@ -845,6 +845,93 @@ int32_t mi_engine_sbn_topology_gradient(mi_engine* engine, int32_t tree_count, i
                                         int32_t estimator, double* out_gradient, double* out_factors,
                                         double* out_log_q);
 
+/* ---- PSP indexing and the log-normal branch-length models (an extension) ----
+ * The branch-length side of a variational step: every tree's edges are indexed by split or by
+ * primary subsplit pair (PSP), every particle's branch lengths are drawn from a log-normal q whose
+ * (mu, sigma) are sums over those indices, and the gradient with respect to the (mu, sigma) tables
+ * comes by the reparametrisation trick (the reference's vip/branch_model.py and
+ * vip/scalar_model.py).  Any engine serves, 4 or 20 states: the taxon count is an argument and
+ * the alignment plays no part; a sharded handle lets its first shard do the work.  FP64
+ * throughout, no floating-point atomics, every sum in the one order stated here.
+ *
+ * A PSP is a PCSP of the support whose sister is the complement of its focal clade:
+ * pcsp_clades[i][0] == pcsp_clades[i][1] ^ 1 (the reference's PCSPIsRootsplit); its name is
+ * "focal|child" (PCSPWithoutParent).  In a tree these are the k = 0 slots: the "up" PSP of edge v
+ * is slot (2v+1, 0), the "down" PSP is slot (2v, 0) (absent for a pendant edge).
+ *
+ * mi_engine_psp_table: the PSP numbering of a support.
+ *   out_psp_of_pcsp [C]  S + the rank of PCSP i among the PSPs in ascending parameter order, or -1
+ *   out_counts [2]       S and V = S + the number of PSPs (the reference's first_empty_index)
+ * The variables are 0 .. V-1: the rootsplits, then the PSPs.  The reference numbers its PSPs in the
+ * iteration order of an unordered_map, which is not reproduced: the SETS of names agree. */
+int32_t mi_engine_psp_table(mi_engine* engine, int32_t rootsplit_count, int32_t pcsp_count,
+                            const int32_t* pcsp_clades /* [C][3] */, int32_t* out_psp_of_pcsp, int32_t* out_counts);
+
+/* The index rows of trees that mi_engine_sbn_index has given their root_index and slot_index
+ * (support trees or trees behind them): out_index [T][rows][2n-3], rows 1 (the split model) or 3.
+ *   row 0  root_index[t][v]                          (the reference's rootsplit_position)
+ *   row 1  psp_of_pcsp of slot (2v, 0)               (subsplit_down_position)
+ *   row 2  psp_of_pcsp of slot (2v + 1, 0)           (subsplit_up_position)
+ * Whatever is not a variable becomes variable_count (V): a slot that does not exist (-1), an entry
+ * outside the support (P) and a rootsplit outside the support.  This is the reference's "not
+ * present" index; the calls below skip it.  rows = 1 reads neither slot_index nor psp_of_pcsp. */
+int32_t mi_engine_psp_index(mi_engine* engine, int32_t tree_count, int32_t taxon_count, const int32_t* root_index,
+                            const int32_t* slot_index, int32_t rootsplit_count, int32_t pcsp_count,
+                            const int32_t* psp_of_pcsp /* [C] */, int32_t variable_count, int32_t rows,
+                            int32_t* out_index);
+
+/* Branch lengths of tree_count particles drawn from the log-normal q, with log q and the
+ * exponential prior.  index [T][rows][2n-3] (rows 1 or 3), q_params [V][2] = (mu, sigma) per
+ * variable.  An index outside [0, V) is not a variable and adds nothing.  Per tree t and edge v:
+ *   mu = 0 + q[index[t][0][v]][0] + q[index[t][1][v]][0] + ..., rows in ascending order; sigma
+ *   likewise from q[.][1].  sigma <= 0 or not finite, or a NaN mu, is an error that names the tree
+ *   and the edge (a row of sentinels alone gives sigma = 0).
+ *   eps = epsilon_in[t][v] if epsilon_in is given (the reference's prebaked_sample; antithetic
+ *   draws), else a standard normal from Philox4x32-10 (constants as mi_engine_sbn_sample): key
+ *   (seed lo, seed hi), counter (v, 1, s lo, s hi), s = first_sample + t -- the second counter
+ *   word is 1, so the stream is disjoint from mi_engine_sbn_sample's under the same seed;
+ *   u1 = (((w0 << 32 | w1) >> 11) + 1) 2^-53 in (0, 1], u2 = ((w2 << 32 | w3) >> 11) 2^-53,
+ *   eps = sqrt(-2 log u1) cos((2 pi) u2).  An edge's bits depend on (seed, s, v) alone.
+ *   x = mu + sigma eps (a rounded product, a rounded sum), theta = exp(x).
+ *   out_branch_lengths [T][2n-2]  theta; entry 2n-3 is 0: the layout the likelihood calls take
+ *   out_epsilon [T][2n-3]
+ *   out_log_q [T]     -sum_v (((x + log sigma) + log(2 pi)/2) + 0.5 (eps eps)), with x itself, the
+ *                     terms added in ascending v with one accumulator from 0
+ *   out_log_prior [T] (2n-3) log(prior_rate) - prior_rate sum_v theta, the sum in the same order
+ * prior_rate must be finite and positive (the reference's is 10). */
+int32_t mi_engine_branch_model_sample(mi_engine* engine, int32_t tree_count, int32_t taxon_count, int32_t rows,
+                                      const int32_t* index, int32_t variable_count, const double* q_params,
+                                      uint64_t seed, int64_t first_sample, double prior_rate,
+                                      const double* epsilon_in /* [T][2n-3] or NULL */, double* out_branch_lengths,
+                                      double* out_epsilon, double* out_log_q, double* out_log_prior);
+
+/* The gradient of sum_t w_t (log p_t - log q_t) with respect to q_params by the reparametrisation
+ * trick, and the log_f vector mi_engine_sbn_topology_gradient takes.  branch_lengths, epsilon,
+ * log_q_branch and log_prior are the sample call's outputs for the same index and q_params;
+ * branch_gradient [T][2n-1] and log_likelihoods [T] are mi_engine_gradients_unrooted's.
+ * Per tree t and edge v, with d = branch_gradient[t][v] - prior_rate and w = tree_weights[t] (1 if
+ * NULL), sigma as in the sample call (checked the same way):
+ *   c0 = w ((d theta) + 1)
+ *   c1 = w ((((d theta) eps) + eps) + (1 / sigma))
+ * every operation rounded once, in the order the parentheses give.
+ *   out_gradient [V][2]  row j: the sum of c0 resp. c1 over every entry (t, r, v) with
+ *       index[t][r][v] == j, in ascending entry number of the [T][rows][2n-3] array, one
+ *       accumulator per component from 0 (a run of more than 16 entries is a wave's, 64 entries
+ *       side by side and added lane after lane: the same additions in the same order).  A variable
+ *       no entry names gets 0.  This is SplitModel.scalar_grad for rows = 1 and what
+ *       PSPModel.scalar_grad computes for every real variable for rows = 3 (its sentinel row, zero
+ *       by decree, does not exist here).
+ *   out_log_f [T]  ((beta log_likelihoods[t] + log_prior[t]) - log_q_topology[t]) - log_q_branch[t]
+ *       (log_q_topology NULL: 0).  As in the reference, beta scales the likelihood in log_f only. */
+int32_t mi_engine_branch_model_gradient(mi_engine* engine, int32_t tree_count, int32_t taxon_count, int32_t rows,
+                                        const int32_t* index, int32_t variable_count, const double* q_params,
+                                        const double* branch_lengths, const double* epsilon,
+                                        const double* log_q_branch, const double* log_prior,
+                                        const double* branch_gradient, const double* log_likelihoods,
+                                        const double* log_q_topology /* [T] or NULL */,
+                                        const double* tree_weights /* [T] or NULL */, double beta, double prior_rate,
+                                        double* out_gradient, double* out_log_f);
+
 /* Maximum-likelihood branch lengths of unrooted trees under box bounds (an extension: the
  * consumer of the Hessian call's outputs).  Every tree of the batch is
  * iterated on the device: an evaluation is one Hessian pass at a trial point, a step is a
@@ -1379,6 +1466,35 @@ int32_t mi_engine_sbn_topology_gradient_device(mi_engine* engine, void* stream, 
                                                const int32_t* parent_range, const double* log_params,
                                                int32_t normalized, const double* log_f, int32_t estimator,
                                                double* out_gradient, double* out_factors, double* out_log_q);
+/* The device forms of PSP indexing and the branch-length models: every pointer a
+ * device pointer; they only enqueue and report through the status word.  The table, the index and
+ * the sample call need no workspace; after mi_engine_reserve_branch_model(engine, tree_count,
+ * taxon_count, rows) the gradient call of at most that many trees and rows of that taxon count
+ * allocates nothing either (its keys, its sort's workspace, the status word), and none of them
+ * reads anything back: a whole step can be captured in a hipGraph.  A sharded handle reserves on
+ * its first shard. */
+int32_t mi_engine_psp_table_device(mi_engine* engine, void* stream, int32_t rootsplit_count, int32_t pcsp_count,
+                                   const int32_t* pcsp_clades, int32_t* out_psp_of_pcsp, int32_t* out_counts);
+int32_t mi_engine_psp_index_device(mi_engine* engine, void* stream, int32_t tree_count, int32_t taxon_count,
+                                   const int32_t* root_index, const int32_t* slot_index, int32_t rootsplit_count,
+                                   int32_t pcsp_count, const int32_t* psp_of_pcsp, int32_t variable_count,
+                                   int32_t rows, int32_t* out_index);
+int32_t mi_engine_branch_model_sample_device(mi_engine* engine, void* stream, int32_t tree_count,
+                                             int32_t taxon_count, int32_t rows, const int32_t* index,
+                                             int32_t variable_count, const double* q_params, uint64_t seed,
+                                             int64_t first_sample, double prior_rate, const double* epsilon_in,
+                                             double* out_branch_lengths, double* out_epsilon, double* out_log_q,
+                                             double* out_log_prior);
+int32_t mi_engine_branch_model_gradient_device(mi_engine* engine, void* stream, int32_t tree_count,
+                                               int32_t taxon_count, int32_t rows, const int32_t* index,
+                                               int32_t variable_count, const double* q_params,
+                                               const double* branch_lengths, const double* epsilon,
+                                               const double* log_q_branch, const double* log_prior,
+                                               const double* branch_gradient, const double* log_likelihoods,
+                                               const double* log_q_topology, const double* tree_weights,
+                                               double beta, double prior_rate, double* out_gradient,
+                                               double* out_log_f);
+int32_t mi_engine_reserve_branch_model(mi_engine* engine, int32_t tree_count, int32_t taxon_count, int32_t rows);
 /* Synchronise `stream` and report the first per-tree error since the last check (the status
  * word is sticky and cleared when an error is reported: calls themselves never clear it). */
 int32_t mi_engine_check_status(mi_engine* engine, void* stream);

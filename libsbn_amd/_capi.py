@@ -205,6 +205,25 @@ SYMBOLS = {
     "mi_engine_sbn_topology_gradient_device":
         (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V,
                      C.c_int32, _V, C.c_int32, _V, _V, _V]),
+    "mi_engine_psp_table": (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V]),
+    "mi_engine_psp_table_device": (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V]),
+    "mi_engine_psp_index":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, _V]),
+    "mi_engine_psp_index_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, _V]),
+    "mi_engine_branch_model_sample":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, _V, C.c_uint64, C.c_int64, C.c_double,
+                     _V, _V, _V, _V, _V]),
+    "mi_engine_branch_model_sample_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, _V, C.c_uint64, C.c_int64, C.c_double,
+                     _V, _V, _V, _V, _V]),
+    "mi_engine_branch_model_gradient":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V,
+                     C.c_double, C.c_double, _V, _V]),
+    "mi_engine_branch_model_gradient_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V,
+                     C.c_double, C.c_double, _V, _V]),
+    "mi_engine_reserve_branch_model": (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32]),
     "mi_consensus_tree":
         (C.c_int32, [C.c_int32, C.c_int32, _V, _V, C.c_double, C.c_double, I32P, _V, _V]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),

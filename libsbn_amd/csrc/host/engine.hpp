@@ -135,6 +135,25 @@ struct SbnGradient {
   std::vector<double> gradient_, factors_, log_q_;
 };
 
+// Engine::PspTable (an extension, include/mi_phylo.h): psp_of_pcsp_ [C] the variable of every PCSP
+// that is a PSP (else -1); the variables are the rootsplits, then the PSPs; variable_count_ is also
+// the "not present" index.  Engine::PspIndex: [T][rows][2n-3] variable indices
+struct PspNumbering {
+  size_t rootsplit_count_ = 0, variable_count_ = 0;
+  std::vector<int32_t> psp_of_pcsp_;
+};
+
+// Engine::BranchModelSample: branch_lengths_ [T][2n-2] (entry 2n-3 is 0), epsilon_ [T][2n-3],
+// log_q_ [T], log_prior_ [T]
+struct BranchModelDraw {
+  std::vector<double> branch_lengths_, epsilon_, log_q_, log_prior_;
+};
+
+// Engine::BranchModelGradient: gradient_ [V][2] with respect to (mu, sigma), log_f_ [T]
+struct BranchModelGradientResult {
+  std::vector<double> gradient_, log_f_;
+};
+
 // Engine::RfDistances: rf_ [T][T] and, with branch lengths, branch_score_ [T][T]
 struct TreeDistances {
   std::vector<int32_t> rf_;
@@ -762,6 +781,87 @@ class Engine {
         static_cast<int32_t>(support.pcsp_count_), static_cast<int32_t>(support.parent_count_),
         support.parent_range_.data(), log_params.data(), normalized ? 1 : 0, log_f.data(), estimator,
         out.gradient_.data(), out.factors_.data(), out.log_q_.data()));
+    return out;
+  }
+
+  // The PSP numbering of a support: mi_engine_psp_table.
+  PspNumbering PspTable(const SbnSupport& support) const {
+    PspNumbering out;
+    out.psp_of_pcsp_.resize(support.pcsp_count_);
+    int32_t counts[2] = {0, 0};
+    Check(mi_engine_psp_table(handle_, static_cast<int32_t>(support.rootsplit_count_),
+                              static_cast<int32_t>(support.pcsp_count_), support.pcsp_clades_.data(),
+                              out.psp_of_pcsp_.data(), counts));
+    out.rootsplit_count_ = static_cast<size_t>(counts[0]);
+    out.variable_count_ = static_cast<size_t>(counts[1]);
+    return out;
+  }
+
+  // The index rows [trees from first_tree on][rows][2n-3] of a support's batch, rows 1 (splits) or
+  // 3 (split, down PSP, up PSP): mi_engine_psp_index.
+  std::vector<int32_t> PspIndex(const SbnSupport& support, const PspNumbering& table, const size_t rows = 3,
+                                const size_t first_tree = 0) const {
+    const size_t E = 2 * support.taxon_count_ - 3;
+    if (first_tree >= support.tree_count_ || table.psp_of_pcsp_.size() != support.pcsp_count_)
+      Failwith("PspIndex: the table must be the support's, first_tree one of its trees.");
+    const size_t T = support.tree_count_ - first_tree;
+    std::vector<int32_t> out(T * rows * E);
+    Check(mi_engine_psp_index(handle_, static_cast<int32_t>(T), static_cast<int32_t>(support.taxon_count_),
+                              support.root_index_.data() + first_tree * E,
+                              support.slot_index_.data() + first_tree * E * 6,
+                              static_cast<int32_t>(support.rootsplit_count_), static_cast<int32_t>(support.pcsp_count_),
+                              table.psp_of_pcsp_.data(), static_cast<int32_t>(table.variable_count_),
+                              static_cast<int32_t>(rows), out.data()));
+    return out;
+  }
+
+  // Branch lengths of tree_count particles from the log-normal q with q_params [V][2] summed over
+  // index [T][rows][2n-3]; particle t is the Philox stream (seed, first_sample + t), or takes
+  // epsilon [T][2n-3] if given: mi_engine_branch_model_sample.
+  BranchModelDraw BranchModelSample(const size_t tree_count, const size_t taxon_count, const size_t rows,
+                                    const std::vector<int32_t>& index, const std::vector<double>& q_params,
+                                    const uint64_t seed, const int64_t first_sample = 0, const double prior_rate = 10.0,
+                                    const std::vector<double>& epsilon = {}) const {
+    const size_t T = tree_count, E = 2 * taxon_count - 3;
+    if (index.size() != T * rows * E || q_params.size() % 2 || (!epsilon.empty() && epsilon.size() != T * E))
+      Failwith("BranchModelSample: index must be [trees][rows][2 taxa - 3], q_params [V][2], epsilon [trees][2 taxa - 3].");
+    BranchModelDraw out;
+    out.branch_lengths_.resize(T * (E + 1));
+    out.epsilon_.resize(T * E);
+    out.log_q_.resize(T);
+    out.log_prior_.resize(T);
+    Check(mi_engine_branch_model_sample(
+        handle_, static_cast<int32_t>(T), static_cast<int32_t>(taxon_count), static_cast<int32_t>(rows), index.data(),
+        static_cast<int32_t>(q_params.size() / 2), q_params.data(), seed, first_sample, prior_rate,
+        epsilon.empty() ? nullptr : epsilon.data(), out.branch_lengths_.data(), out.epsilon_.data(), out.log_q_.data(),
+        out.log_prior_.data()));
+    return out;
+  }
+
+  // The gradient with respect to q_params and log_f for a draw of the same index and q_params,
+  // from the likelihood call's branch gradients [T][2n-1] and log-likelihoods [T];
+  // log_q_topology and tree_weights may be empty: mi_engine_branch_model_gradient.
+  BranchModelGradientResult BranchModelGradient(const size_t tree_count, const size_t taxon_count, const size_t rows,
+                                                const std::vector<int32_t>& index, const std::vector<double>& q_params,
+                                                const BranchModelDraw& draw, const std::vector<double>& branch_gradient,
+                                                const std::vector<double>& log_likelihoods,
+                                                const std::vector<double>& log_q_topology = {},
+                                                const std::vector<double>& tree_weights = {}, const double beta = 1.0,
+                                                const double prior_rate = 10.0) const {
+    const size_t T = tree_count, E = 2 * taxon_count - 3;
+    if (index.size() != T * rows * E || q_params.size() % 2 || draw.epsilon_.size() != T * E ||
+        branch_gradient.size() != T * (E + 2) || log_likelihoods.size() != T ||
+        (!log_q_topology.empty() && log_q_topology.size() != T) || (!tree_weights.empty() && tree_weights.size() != T))
+      Failwith("BranchModelGradient: the arrays must be those of one batch of trees.");
+    BranchModelGradientResult out;
+    out.gradient_.resize(q_params.size());
+    out.log_f_.resize(T);
+    Check(mi_engine_branch_model_gradient(
+        handle_, static_cast<int32_t>(T), static_cast<int32_t>(taxon_count), static_cast<int32_t>(rows), index.data(),
+        static_cast<int32_t>(q_params.size() / 2), q_params.data(), draw.branch_lengths_.data(), draw.epsilon_.data(),
+        draw.log_q_.data(), draw.log_prior_.data(), branch_gradient.data(), log_likelihoods.data(),
+        log_q_topology.empty() ? nullptr : log_q_topology.data(), tree_weights.empty() ? nullptr : tree_weights.data(),
+        beta, prior_rate, out.gradient_.data(), out.log_f_.data()));
     return out;
   }
 

@@ -27,6 +27,7 @@
 #include "../../include/mi_phylo.h"
 #include "mi_phylo_device_utils.h"
 #include "mi_phylo_kernels.h"
+#include "mi_phylo_philox_device.h"
 
 namespace miphylo {
 
@@ -258,24 +259,10 @@ __global__ __launch_bounds__(64) void sbn_cdf_kernel(SbnSampleArgs a) {
 }
 
 // ---- the sampler ----
-__device__ __forceinline__ void philox_round(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  c[1] = (uint32_t)p1;
-  c[3] = (uint32_t)p0;
-  c[0] = n0;
-  c[2] = n2;
-}
-// u in [0, 1) of draw i of sample t
+// u in [0, 1) of draw i of sample t (the rounds: mi_phylo_philox_device.h)
 __device__ __forceinline__ double philox_uniform(uint64_t seed, uint64_t t, uint32_t i) {
   uint32_t c[4] = {i, 0u, (uint32_t)t, (uint32_t)(t >> 32)};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
+  philox4x32_10(c, seed);
   const uint64_t bits = ((uint64_t)c[0] << 32) | c[1];
   return (double)(bits >> 11) * 0x1.0p-53;
 }

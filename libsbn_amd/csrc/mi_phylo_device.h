@@ -101,6 +101,7 @@ enum StatusCode : int32_t {
   kSbnEmptyBlock = 19,   // (its second and fourth status words carry the sample and the block)
   kSbnBadDescent = 20,   // (its second status word carries the sample)
   kSbnSupportSentinel = 21,
+  kBranchModelBadParam = 22,  // (its second and fourth status words carry the tree and the edge)
 };
 
 }  // namespace miphylo

@@ -12,6 +12,7 @@
 //   mi_phylo_start_trees.cpp  pairwise distances, neighbour joining, starting trees (device forms, reservation)
 //   mi_phylo_splits.cpp       split tables, Robinson-Foulds distances (device and host forms, reservation), mi_consensus_tree
 //   mi_phylo_sbn.cpp          subsplit Bayesian networks: support and slots, probabilities, normalisation, training
+//   mi_phylo_branch_model.cpp PSP indexing and the log-normal branch-length models of a variational step
 //   mi_phylo_host_calls.cpp   what runs a host-pointer call (staging, status, shards), the plain entry points
 //   mi_phylo_engine_aa.cpp    20-state call sequence
 #pragma once
@@ -68,6 +69,8 @@ inline const char* status_message(int code) {
     case kSbnEmptyBlock: return "SBN sample: a sample reached a block whose parameters are all -inf";
     case kSbnBadDescent: return "SBN sample: the descent table or parent_range does not describe a support of this taxon count";
     case kSbnSupportSentinel: return "SBN descent: a support tree has a rootsplit or PCSP outside the support";
+    case kBranchModelBadParam:
+      return "branch model: an edge's summed sigma must be finite and positive and its summed mu not NaN";
     default: return "unknown device status";
   }
 }
@@ -157,6 +160,8 @@ struct mi_engine {
   Buffer sbn_index_ws;  // the index call: the batch's split table | PCSP occurrences, the two tables, the sort and the scan
   Buffer sbn_prob_ws;   // log_prob / normalize / train: normalised parameters | usages | the accumulation's sort | training vectors
   Buffer sbn_store;     // the per-tree kernels' node arrays of trees too large for LDS
+  // PSP indexing and the branch-length models (mi_engine_psp_*, mi_engine_branch_model_*)
+  Buffer branch_ws;     // the gradient call: every edge's two terms | the accumulation's sort
   Buffer rf_ws;        // a batch's sorted lists: lengths [T][2n-3] | indices [T][2n-3] | counts [T]
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)

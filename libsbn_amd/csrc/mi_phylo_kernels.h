@@ -706,6 +706,62 @@ struct SbnGradientArgs {
 };
 int launch_sbn_gradient(const SbnGradientArgs& a, hipStream_t s);  // (after the walk; nonzero: rocPRIM refused)
 void sbn_vi_prepare(int n, int tpw);  // the large-LDS opt-in of the two per-tree kernels
+// kernels_branch_model.hip: PSP indexing and the log-normal branch-length models.
+// E = 2n-3 edges; an index array is [T][R][E], R = 1 (splits) or 3 (rootsplit, down PSP, up PSP);
+// an entry outside [0, V) names no variable.
+struct PspTableArgs {
+  int S, C;
+  const int32_t* pcsp_clades;   // [C][3]
+  int32_t* out_psp_of_pcsp;     // [C]
+  int32_t* out_counts;          // [2] S, V
+};
+void launch_psp_table(const PspTableArgs& a, hipStream_t s);
+struct PspIndexArgs {
+  int n, T, S, C, V, R;
+  const int32_t* root_index;    // [T][2n-3]
+  const int32_t* slot_index;    // [T][2(2n-3)][3]
+  const int32_t* psp_of_pcsp;   // [C]
+  int32_t* out_index;           // [T][R][2n-3]
+};
+void launch_psp_index(const PspIndexArgs& a, hipStream_t s);
+struct BranchSampleArgs {
+  int n, T, R, V;
+  const int32_t* index;         // [T][R][2n-3]
+  const double* q_params;       // [V][2] mu, sigma
+  uint64_t seed;
+  int64_t first_sample;
+  double prior_rate;
+  const double* epsilon_in;     // [T][2n-3] or nullptr
+  int32_t* status;
+  double* out_bl;               // [T][2n-2]
+  double* out_epsilon;          // [T][2n-3]
+  double* out_log_q;            // [T]
+  double* out_log_prior;        // [T]
+};
+void launch_branch_sample(const BranchSampleArgs& a, hipStream_t s);
+struct BranchGradientArgs {
+  int n, T, R, V;
+  const int32_t* index;         // [T][R][2n-3]
+  const double* q_params;       // [V][2]
+  const double* bl;             // [T][2n-2] theta, as the sample call left it
+  const double* epsilon;        // [T][2n-3]
+  const double* log_q_branch;   // [T]
+  const double* log_prior;      // [T]
+  const double* branch_gradient;  // [T][2n-1]
+  const double* log_likelihoods;  // [T]
+  const double* log_q_topology;   // [T] or nullptr
+  const double* weights;          // [T] or nullptr
+  double beta, prior_rate;
+  int32_t* status;
+  double* terms;                // [T][2n-3][2] workspace: c0, c1 of every edge
+  uint32_t *keys, *keys2, *vals, *vals2;  // [T R (2n-3)]
+  void* sort_tmp;
+  size_t sort_tmp_bytes;
+  double* out_gradient;         // [V][2]
+  double* out_log_f;            // [T]
+};
+size_t branch_model_sort_tmp_bytes(size_t entries);
+int launch_branch_gradient(const BranchGradientArgs& a, hipStream_t s);  // (nonzero: rocPRIM refused)
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
 // the first, gradient_mfma_kernel, was retired in round 6): all categories of a group of four
 // per instruction; they also write the log-likelihood partial sums, so no separate logL pass is

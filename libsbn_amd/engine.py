@@ -377,6 +377,48 @@ def sbn_rooted_representations(support, t):
     return out
 
 
+@dataclass
+class PspTable:
+    """Engine.psp_table: the PSP numbering of a support (include/mi_phylo.h).  The variables of a
+    branch-length model are 0 .. variable_count-1: the rootsplits, then the PSPs."""
+    psp_of_pcsp: np.ndarray    # [C] the variable of PCSP S + i if it is a PSP, else -1
+    rootsplit_count: int       # S (the reference's after_rootsplits_index)
+    variable_count: int        # V (the reference's first_empty_index): also the "not present" index
+
+
+@dataclass
+class BranchModelSample:
+    """Engine.branch_model_sample: one draw of every particle's branch lengths."""
+    branch_lengths: np.ndarray  # [T][2n-2] theta; entry 2n-3 is 0 (what the likelihood calls take)
+    epsilon: np.ndarray         # [T][2n-3] the standard normals behind them
+    log_q: np.ndarray           # [T] log q of the lengths
+    log_prior: np.ndarray       # [T] the exponential prior
+
+
+def psp_strings(support, table):
+    """The reference's PSPIndexer::ToStringVector in this numbering: "01110" for a rootsplit,
+    "focal|child" for a PSP, "" for the "not present" index variable_count (the last entry)."""
+    name = _clade_strings(support)
+    out = split_strings(support.split_bits, support.taxon_count) + [""] * (table.variable_count - table.rootsplit_count + 1)
+    for row, j in zip(support.pcsp_clades, table.psp_of_pcsp):
+        if j >= 0:
+            out[int(j)] = name(int(row[1])) + "|" + name(int(row[2]))
+    return out
+
+
+def lognormal_mode_match(split_modes, table):
+    """The reference's mode-matching heuristic (LogNormalModel.mode_match, PSPModel.mode_match) as
+    q_params [V][2]: for split j with mode m_j, sigma = -0.1 log(clip(m, 1e-6, 1 - 1e-6)) and
+    mu = sigma^2 + log(max(m, 1e-6)); the PSP rows are zero.  split_modes [S]: for instance the mean
+    lengths stats[:, 1] / stats[:, 0] of Engine.split_index over the support's trees, whose
+    numbering is the rootsplits'."""
+    modes = _np(split_modes, np.float64).reshape(table.rootsplit_count)
+    q = np.zeros((table.variable_count, 2))
+    q[:table.rootsplit_count, 1] = -0.1 * np.log(np.clip(modes, 1e-6, 1 - 1e-6))
+    q[:table.rootsplit_count, 0] = np.square(q[:table.rootsplit_count, 1]) + np.log(np.clip(modes, 1e-6, None))
+    return q
+
+
 def consensus_tree(taxon_count, split_bits, split_weight, total_weight, threshold=0.5):
     """The majority-rule consensus tree of a split table (mi_consensus_tree: host arithmetic
     only): every nontrivial split with weight > threshold * total_weight, threshold in
@@ -1041,6 +1083,70 @@ class Engine:
             _ptr(f), code, _ptr(grad), _ptr(factors), _ptr(lq)))
         return grad, factors, lq
 
+    def psp_table(self, support):
+        """The PSP numbering of a support (mi_engine_psp_table).  Returns a PspTable."""
+        S, Cn = support.rootsplit_count, support.pcsp_count
+        clades = _np(support.pcsp_clades, np.int32).reshape(Cn, 3)
+        out, counts = np.empty(Cn, np.int32), np.zeros(2, np.int32)
+        self._check(self._lib.mi_engine_psp_table(self._h, S, Cn, _ptr(clades) if Cn else None,
+                                                  _ptr(out) if Cn else None, _ptr(counts)))
+        return PspTable(out, int(counts[0]), int(counts[1]))
+
+    def psp_index(self, support, table, rows=3, trees=None):
+        """The index rows [T][rows][2n-3] of trees of a support's batch (mi_engine_psp_index; trees
+        as _sbn_trees): row 0 the split of every edge, with rows=3 also its down and its up PSP;
+        table.variable_count where there is none."""
+        _, root, slot = self._sbn_trees(support, trees)
+        T, E = root.shape
+        out = np.empty((T, int(rows), E), np.int32)
+        Cn = support.pcsp_count
+        psp = _np(table.psp_of_pcsp, np.int32).reshape(Cn)
+        self._check(self._lib.mi_engine_psp_index(
+            self._h, T, support.taxon_count, _ptr(root), _ptr(slot), support.rootsplit_count, Cn,
+            _ptr(psp) if Cn else None, table.variable_count, int(rows), _ptr(out)))
+        return out
+
+    @staticmethod
+    def _branch_model_shape(index, q_params):
+        idx = _np(index, np.int32)
+        if idx.ndim != 3 or idx.shape[2] < 3 or idx.shape[2] % 2 == 0:
+            raise RuntimeError(f"the branch-length models take an index [T][rows][2n-3]; got {idx.shape}")
+        q = _np(q_params, np.float64)
+        if q.ndim != 2 or q.shape[1] != 2:
+            raise RuntimeError(f"the branch-length models take q_params [V][2]; got {q.shape}")
+        return idx, q, idx.shape[0], idx.shape[1], idx.shape[2]
+
+    def branch_model_sample(self, index, q_params, seed, first_sample=0, prior_rate=10.0, epsilon=None):
+        """Branch lengths of T particles drawn from the log-normal q with (mu, sigma) tables
+        q_params [V][2] summed over index [T][rows][2n-3] (Engine.psp_index), log q and the
+        exponential prior (mi_engine_branch_model_sample).  Particle t takes the Philox stream
+        (seed, first_sample + t), or epsilon [T][2n-3] if given.  Returns a BranchModelSample."""
+        idx, q, T, R, E = self._branch_model_shape(index, q_params)
+        eps_in = None if epsilon is None else _np(epsilon, np.float64).reshape(T, E)
+        bl, eps, lq, lp = np.empty((T, E + 1)), np.empty((T, E)), np.empty(T), np.empty(T)
+        self._check(self._lib.mi_engine_branch_model_sample(
+            self._h, T, (E + 3) // 2, R, _ptr(idx), q.shape[0], _ptr(q), int(seed) & (2 ** 64 - 1), int(first_sample),
+            float(prior_rate), _ptr(eps_in), _ptr(bl), _ptr(eps), _ptr(lq), _ptr(lp)))
+        return BranchModelSample(bl, eps, lq, lp)
+
+    def branch_model_gradient(self, index, q_params, sample, branch_gradient, log_likelihoods, log_q_topology=None,
+                              tree_weights=None, beta=1.0, prior_rate=10.0):
+        """The gradient [V][2] of sum_t w_t (log p_t - log q_t) with respect to q_params for a
+        BranchModelSample of the same index and q_params, from the likelihood call's
+        branch_gradient [T][2n-1] and log_likelihoods [T], and log_f [T] for
+        sbn_topology_gradient (mi_engine_branch_model_gradient).  Returns (gradient, log_f)."""
+        idx, q, T, R, E = self._branch_model_shape(index, q_params)
+        bl, eps = _np(sample.branch_lengths, np.float64).reshape(T, E + 1), _np(sample.epsilon, np.float64).reshape(T, E)
+        lqb, lp = _np(sample.log_q, np.float64).reshape(T), _np(sample.log_prior, np.float64).reshape(T)
+        g, ll = _np(branch_gradient, np.float64).reshape(T, E + 2), _np(log_likelihoods, np.float64).reshape(T)
+        lqt = None if log_q_topology is None else _np(log_q_topology, np.float64).reshape(T)
+        tw = None if tree_weights is None else _np(tree_weights, np.float64).reshape(T)
+        grad, log_f = np.empty((q.shape[0], 2)), np.empty(T)
+        self._check(self._lib.mi_engine_branch_model_gradient(
+            self._h, T, (E + 3) // 2, R, _ptr(idx), q.shape[0], _ptr(q), _ptr(bl), _ptr(eps), _ptr(lqb), _ptr(lp),
+            _ptr(g), _ptr(ll), _ptr(lqt), _ptr(tw), float(beta), float(prior_rate), _ptr(grad), _ptr(log_f)))
+        return grad, log_f
+
     def rf_distances(self, split_index, branch_lengths=None):
         """Robinson-Foulds distances [T][T] between the trees of a split index [T][2n-1]
         (mi_engine_rf_distances); with branch_lengths [T][2n-2] also the squared
@@ -1536,6 +1642,41 @@ class Engine:
         """mi_engine_reserve_sbn: workspace of the SBN calls for that many trees of that taxon
         count (sbn_log_prob_device and sbn_normalize_device then allocate nothing: graph capture)."""
         self._check(self._lib.mi_engine_reserve_sbn(self._h, int(tree_count), int(taxon_count)))
+
+    def psp_table_device(self, stream, rootsplit_count, pcsp_count, pcsp_clades, out_psp_of_pcsp, out_counts):
+        """mi_engine_psp_table_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_psp_table_device(
+            self._h, stream, int(rootsplit_count), int(pcsp_count), pcsp_clades, out_psp_of_pcsp, out_counts))
+
+    def psp_index_device(self, stream, T, n, root_index, slot_index, rootsplit_count, pcsp_count, psp_of_pcsp,
+                         variable_count, rows, out_index):
+        """mi_engine_psp_index_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_psp_index_device(
+            self._h, stream, int(T), int(n), root_index, slot_index, int(rootsplit_count), int(pcsp_count),
+            psp_of_pcsp, int(variable_count), int(rows), out_index))
+
+    def branch_model_sample_device(self, stream, T, n, rows, index, variable_count, q_params, seed, first_sample,
+                                   prior_rate, out_branch_lengths, out_epsilon, out_log_q, out_log_prior,
+                                   epsilon_in=None):
+        """mi_engine_branch_model_sample_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_branch_model_sample_device(
+            self._h, stream, int(T), int(n), int(rows), index, int(variable_count), q_params,
+            int(seed) & (2 ** 64 - 1), int(first_sample), float(prior_rate), epsilon_in, out_branch_lengths,
+            out_epsilon, out_log_q, out_log_prior))
+
+    def branch_model_gradient_device(self, stream, T, n, rows, index, variable_count, q_params, branch_lengths,
+                                     epsilon, log_q_branch, log_prior, branch_gradient, log_likelihoods, beta,
+                                     prior_rate, out_gradient, out_log_f, log_q_topology=None, tree_weights=None):
+        """mi_engine_branch_model_gradient_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_branch_model_gradient_device(
+            self._h, stream, int(T), int(n), int(rows), index, int(variable_count), q_params, branch_lengths,
+            epsilon, log_q_branch, log_prior, branch_gradient, log_likelihoods, log_q_topology, tree_weights,
+            float(beta), float(prior_rate), out_gradient, out_log_f))
+
+    def reserve_branch_model(self, tree_count, taxon_count, rows=3):
+        """mi_engine_reserve_branch_model: workspace of branch_model_gradient_device for that many
+        trees and rows of that taxon count (it then allocates nothing: graph capture)."""
+        self._check(self._lib.mi_engine_reserve_branch_model(self._h, int(tree_count), int(taxon_count), int(rows)))
 
     def pattern_mixture_device(self, stream, T, P, pattern_ll, pattern_weights, out_pattern_log_marginal,
                                out_log_marginal, tree_log_weights=None):
