@@ -1495,6 +1495,136 @@ int32_t mi_engine_branch_model_gradient_device(mi_engine* engine, void* stream, 
                                                double beta, double prior_rate, double* out_gradient,
                                                double* out_log_f);
 int32_t mi_engine_reserve_branch_model(mi_engine* engine, int32_t tree_count, int32_t taxon_count, int32_t rows);
+
+/* ---- a device-resident variational fit (an extension) ----
+ * What the reference's Burrito.gradient_steps does with vip/optimizers.py (SimpleOptimizer) and
+ * vip/sgd_server.py (adam): the state of a fit lives in device memory, one step is one chain of
+ * launches that reads and advances it, the optimiser is a kernel and a whole fit is one call.
+ *
+ * The state: the two tables (log_params [P] of the SBN, unnormalised; q_params [V][2]), Adam's
+ * first and second moments of both, and the scalars
+ *   t   steps so far, failed ones included      a   successful steps
+ *   b0 = adam_beta0^a, b1 = adam_beta1^a: one rounded multiply per successful step, from 1
+ *   step_size[2] (the mu and the sigma column of q_params), sbn_step_size, first_sample
+ * Step t draws the samples s = first_sample + t K + k, k = 0 .. K-1, with the Philox layout of
+ * mi_engine_sbn_sample and mi_engine_branch_model_sample under `seed`: its particles are bit for
+ * bit what those calls give for (seed, first_sample + t K).  Its beta is 1 if anneal_steps is 0,
+ * else max(min((t + 1) / anneal_steps, 1), 0.001) with one rounded division (burrito.py:119-121).
+ *
+ * One step (mi_vi_step_device) enqueues on one stream: sbn_sample, sbn_index (the support trees
+ * and the samples behind them), psp_index, branch_model_sample, the unrooted gradient call,
+ * sbn_log_prob, branch_model_gradient (which scales log L by beta in log_f), sbn_topology_gradient
+ * with the fit's estimator, and the update below.  It allocates nothing, synchronises nothing and
+ * reads nothing back: a caller may capture it in a hipGraph, and every replay is the NEXT step.
+ *
+ * The update (mi_vi_update*; elements are the P SBN parameters with step sbn_step_size, then
+ * q_params with its column's step).  The step FAILS if any entry of either gradient is not finite
+ * (the reference checks the q gradient only) or if the sigma of any split variable j < S would be
+ * <= 0 or not finite after it (the reference lets that through).  Every edge's sigma is one split
+ * variable's plus, with rows = 3, two PSP variables' corrections, which start at zero
+ * (lognormal_mode_match) and may take either sign: they are not checked, and an edge whose SUM
+ * leaves the positive numbers is reported by the next step's draw (kBranchModelBadParam).  A fit
+ * of the tables alone (below) checks every variable.  A failed step changes no table and no moment and halves
+ * step_size[0] and step_size[1].  Otherwise b0 and b1 are advanced first and, per element, every
+ * operation rounded once in the order of the parentheses (sgd_server.py:51-67, decay 0, ascent):
+ *   m = (beta0 m) + ((1 - beta0) g)
+ *   v = (beta1 v) + ((1 - beta1) (g g))
+ *   param = param + ((step (m / (1 - b0))) / (root + epsilon)),  root = sqrt(v / (1 - b1))
+ * Where |g| > 2^500 the square g g may overflow: v is then +inf and is stored so (as the reference's
+ * grad ** 2 gives it; that element's later steps are zero), while this step's root is taken of the
+ * same sum in a scaled range, c = 2^-600:  v' = (beta1 ((v c) c)) + ((1 - beta1) ((g c) (g c))),
+ * root = sqrt(v' / (1 - b1)) / c.  The products with c are exact (but for the underflow of
+ * (v c) c, a term then 2^800 times smaller than the other), so this root is the plain one wherever
+ * the plain one is finite, and a first step from zero moments is step g / (|g| + epsilon) at any g.
+ * then step_size[.] *= step_decay (sbn_step_size stays, as in the reference).  Either way t += 1.
+ * The step writes trace row [t] of [max_steps][6] (nothing beyond the capacity):
+ *   0 beta of the step
+ *   1 elbo   (sum_k f_k) / K, f_k = ((logL_k + log prior_k) - log q_topology_k) - log q_branch_k
+ *            (at beta = 1 whatever the annealing), added in ascending k with one accumulator
+ *   2 bound  (m + log(sum_k exp(f_k - m))) - log K, m the maximum, the sum in ascending k
+ *            (the reference's marginal_likelihood_estimate); -inf if every f_k is
+ *   3, 4     step_size[0], step_size[1] after the step      5  1 if the step succeeded, else 0
+ *
+ * mi_vi_default_options fills the reference's values: rows 3, estimator VIMCO, prior_rate 10,
+ * sbn_step_size 0.001, step_decay 0.99, adam 0.9 / 0.999 / 1e-8, particle_count 10, max_steps
+ * 1000, step_size {0.001, 0.001}, the rest 0.  mi_engine_vi_create takes the struct as it is. */
+typedef struct mi_vi mi_vi;
+typedef struct {
+  int32_t particle_count;  /* K >= 1 (VIMCO: >= 2) */
+  int32_t rows;            /* 1 (the split model) or 3 (the PSP model) */
+  int32_t estimator;       /* MI_SBN_FACTORS_PLAIN or MI_SBN_FACTORS_VIMCO */
+  int32_t anneal_steps;    /* >= 0 */
+  int32_t max_steps;       /* >= 1: rows of the trace buffer */
+  int32_t reserved0;
+  double prior_rate;       /* finite, > 0 */
+  double step_size[2];     /* finite, > 0 */
+  double sbn_step_size;    /* finite, >= 0 */
+  double step_decay;       /* in (0, 1] */
+  double adam_beta0, adam_beta1; /* in [0, 1) */
+  double adam_epsilon;     /* finite, >= 0 */
+  uint64_t seed;
+  int64_t first_sample;
+  int32_t reserved[4];
+} mi_vi_options;
+int32_t mi_vi_default_options(mi_vi_options* out_options);
+/* A fit on a single-device engine of 4 or 20 states (a handle of several shards is refused, one
+ * of a single shard serves as its one engine: the fit's calls then report there).  The support
+ * is that of parent_ids [support_tree_count][2n-3]; creation runs mi_engine_sbn_index,
+ * mi_engine_sbn_descent and mi_engine_psp_table on it once, reserves what a step needs
+ * (mi_engine_reserve_sbn for support_tree_count + K trees, mi_engine_reserve for K gradient
+ * evaluations, mi_engine_reserve_branch_model) and allocates every buffer of a step.
+ * parameter_count and variable_count must be the support's P and V (rows = 1: V = S).
+ * model_params [param_count] or NULL: the one model parameter row every particle takes.
+ * support_tree_count 0 (parent_ids NULL) makes a fit of the two tables alone, of any sizes
+ * parameter_count + 2 variable_count >= 1: it takes mi_vi_update*, the state calls and nothing else.
+ * mi_vi_destroy releases everything the fit holds (mi_device_bytes_held); the engine must outlive
+ * the fit. */
+int32_t mi_engine_vi_create(mi_engine* engine, int32_t support_tree_count, const int32_t* parent_ids,
+                            const double* model_params, int32_t parameter_count, const double* log_params,
+                            int32_t variable_count, const double* q_params, const mi_vi_options* options,
+                            mi_vi** out_fit);
+void mi_vi_destroy(mi_vi* fit);
+/* out_sizes [9]: n, K, rows, S, C, parent_count, V, max_steps, P */
+int32_t mi_vi_sizes(const mi_vi* fit, int32_t* out_sizes);
+/* Enqueue one step on `stream` (NULL: the engine's).  Errors of the inputs go to the engine's
+ * status word (mi_engine_check_status). */
+int32_t mi_vi_step_device(mi_vi* fit, void* stream);
+/* `steps` steps on the engine's stream with mi_engine_check_status after every check_interval
+ * of them (<= 0: only at the end), then the trace rows of these steps into out_trace [steps][6].
+ * Refused if the fit's t + steps exceeds max_steps.  The bits of a fit depend on the options, the
+ * initial state, the support and the alignment alone: not on check_interval, not on how the steps
+ * are split over calls, not on whether steps were replayed from a graph.
+ * mi_engine_last_call_path: "vi_fit n=<n> K=<K> rows=<R> steps=<s> | <the gradient call's path>". */
+int32_t mi_vi_fit(mi_vi* fit, int32_t steps, int32_t check_interval, double* out_trace);
+/* Trace rows [first_step, first_step + count) into out_trace [count][6]; they must lie below both
+ * the fit's t and max_steps (the rows of steps a caller's graph replayed are read this way).
+ * Synchronises the engine's stream. */
+int32_t mi_vi_trace(mi_vi* fit, int32_t first_step, int32_t count, double* out_trace);
+/* One update of the fit's state from given gradients and per-particle terms (what the last three
+ * launches of a step do): sbn_gradient [P], q_gradient [V][2], and log_likelihoods, log_prior,
+ * log_q_topology, log_q_branch [K] each.  out_trace_row [6] or NULL.  The device form only
+ * enqueues; every pointer a device pointer. */
+int32_t mi_vi_update(mi_vi* fit, const double* sbn_gradient, const double* q_gradient, const double* log_likelihoods,
+                     const double* log_prior, const double* log_q_topology, const double* log_q_branch,
+                     double* out_trace_row);
+int32_t mi_vi_update_device(mi_vi* fit, void* stream, const double* sbn_gradient, const double* q_gradient,
+                            const double* log_likelihoods, const double* log_prior, const double* log_q_topology,
+                            const double* log_q_branch, double* out_trace_row);
+/* The whole state, for a checkpoint: a fit resumed from it goes on bit for bit.
+ *   log_params [P], q_params [V][2], sbn_moments [2][P] (m, then v), q_moments [2][V][2]
+ *   scalars [5]: b0, b1, step_size[0], step_size[1], sbn_step_size
+ *   counters [3]: t, a, first_sample
+ * Both synchronise the engine's stream. */
+int32_t mi_vi_get_state(mi_vi* fit, double* out_log_params, double* out_q_params, double* out_sbn_moments,
+                        double* out_q_moments, double* out_scalars, int64_t* out_counters);
+int32_t mi_vi_set_state(mi_vi* fit, const double* log_params, const double* q_params, const double* sbn_moments,
+                        const double* q_moments, const double* scalars, const int64_t* counters);
+/* The last step's particles: out_parent_ids [K][2n-3] is required, the others may be NULL:
+ * out_branch_lengths [K][2n-2], and out_log_likelihoods, out_log_q_topology, out_log_q_branch,
+ * out_log_prior [K] each.  Synchronises the engine's stream. */
+int32_t mi_vi_particles(mi_vi* fit, int32_t* out_parent_ids, double* out_branch_lengths, double* out_log_likelihoods,
+                        double* out_log_q_topology, double* out_log_q_branch, double* out_log_prior);
+
 /* Synchronise `stream` and report the first per-tree error since the last check (the status
  * word is sticky and cleared when an error is reported: calls themselves never clear it). */
 int32_t mi_engine_check_status(mi_engine* engine, void* stream);

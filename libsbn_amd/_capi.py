@@ -45,6 +45,16 @@ class DistanceOptions(C.Structure):
                 ("min_length", C.c_double), ("max_length", C.c_double), ("reserved", C.c_int32 * 4)]
 
 
+class ViOptions(C.Structure):
+    """mi_vi_options (include/mi_phylo.h)."""
+    _fields_ = [("particle_count", C.c_int32), ("rows", C.c_int32), ("estimator", C.c_int32),
+                ("anneal_steps", C.c_int32), ("max_steps", C.c_int32), ("reserved0", C.c_int32),
+                ("prior_rate", C.c_double), ("step_size", C.c_double * 2), ("sbn_step_size", C.c_double),
+                ("step_decay", C.c_double), ("adam_beta0", C.c_double), ("adam_beta1", C.c_double),
+                ("adam_epsilon", C.c_double), ("seed", C.c_uint64), ("first_sample", C.c_int64),
+                ("reserved", C.c_int32 * 4)]
+
+
 # Every symbol include/mi_phylo.h declares: (restype, argtypes)
 _V = C.c_void_p
 SYMBOLS = {
@@ -224,6 +234,19 @@ SYMBOLS = {
         (C.c_int32, [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V,
                      C.c_double, C.c_double, _V, _V]),
     "mi_engine_reserve_branch_model": (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32]),
+    "mi_vi_default_options": (C.c_int32, [C.POINTER(ViOptions)]),
+    "mi_engine_vi_create":
+        (C.c_int32, [_V, C.c_int32, _V, _V, C.c_int32, _V, C.c_int32, _V, C.POINTER(ViOptions), C.POINTER(_V)]),
+    "mi_vi_destroy": (None, [_V]),
+    "mi_vi_sizes": (C.c_int32, [_V, I32P]),
+    "mi_vi_step_device": (C.c_int32, [_V, _V]),
+    "mi_vi_fit": (C.c_int32, [_V, C.c_int32, C.c_int32, _V]),
+    "mi_vi_trace": (C.c_int32, [_V, C.c_int32, C.c_int32, _V]),
+    "mi_vi_update": (C.c_int32, [_V, _V, _V, _V, _V, _V, _V, _V]),
+    "mi_vi_update_device": (C.c_int32, [_V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "mi_vi_get_state": (C.c_int32, [_V, _V, _V, _V, _V, _V, _V]),
+    "mi_vi_set_state": (C.c_int32, [_V, _V, _V, _V, _V, _V, _V]),
+    "mi_vi_particles": (C.c_int32, [_V, _V, _V, _V, _V, _V, _V]),
     "mi_consensus_tree":
         (C.c_int32, [C.c_int32, C.c_int32, _V, _V, C.c_double, C.c_double, I32P, _V, _V]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),

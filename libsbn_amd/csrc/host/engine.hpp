@@ -11,6 +11,7 @@
 // Errors are std::runtime_error, like Failwith (src/sugar.hpp:67-78).
 #pragma once
 #include <algorithm>
+#include <array>
 #include <map>
 #include <string>
 #include <tuple>
@@ -152,6 +153,37 @@ struct BranchModelDraw {
 // Engine::BranchModelGradient: gradient_ [V][2] with respect to (mu, sigma), log_f_ [T]
 struct BranchModelGradientResult {
   std::vector<double> gradient_, log_f_;
+};
+
+// Engine::ViCreate: a device-resident variational fit (mi_vi, include/mi_phylo.h); it releases
+// itself and must not outlive its engine.  ViStateResult: Engine::ViState, the whole state.
+class VariationalFit {
+ public:
+  VariationalFit() = default;
+  explicit VariationalFit(mi_vi* handle) : handle_(handle) {}
+  VariationalFit(VariationalFit&& o) noexcept : handle_(o.handle_) { o.handle_ = nullptr; }
+  VariationalFit& operator=(VariationalFit&& o) noexcept {
+    std::swap(handle_, o.handle_);
+    return *this;
+  }
+  VariationalFit(const VariationalFit&) = delete;
+  VariationalFit& operator=(const VariationalFit&) = delete;
+  ~VariationalFit() { mi_vi_destroy(handle_); }
+  mi_vi* Handle() const { return handle_; }
+  // n, K, rows, S, C, parent count, V, max_steps, P
+  std::array<int32_t, 9> Sizes() const {
+    std::array<int32_t, 9> out{};
+    if (mi_vi_sizes(handle_, out.data()) != 0) Failwith(mi_last_error());
+    return out;
+  }
+
+ private:
+  mi_vi* handle_ = nullptr;
+};
+struct ViStateResult {
+  std::vector<double> log_params_, q_params_, sbn_moments_, q_moments_;
+  std::array<double, 5> scalars_{};    // b0, b1, step_size[0], step_size[1], sbn_step_size
+  std::array<int64_t, 3> counters_{};  // t, a, first_sample
 };
 
 // Engine::RfDistances: rf_ [T][T] and, with branch lengths, branch_score_ [T][T]
@@ -862,6 +894,69 @@ class Engine {
         draw.log_q_.data(), draw.log_prior_.data(), branch_gradient.data(), log_likelihoods.data(),
         log_q_topology.empty() ? nullptr : log_q_topology.data(), tree_weights.empty() ? nullptr : tree_weights.data(),
         beta, prior_rate, out.gradient_.data(), out.log_f_.data()));
+    return out;
+  }
+
+  // A device-resident variational fit over the support of support_parent_ids [T0][2n-3] on this
+  // engine's alignment, from log_params [P] and q_params [V][2]; options as
+  // mi_vi_default_options leaves them unless given; model_param_row: the one row every particle
+  // takes: mi_engine_vi_create.
+  static mi_vi_options ViDefaultOptions() {
+    mi_vi_options o;
+    Check(mi_vi_default_options(&o));
+    return o;
+  }
+  VariationalFit ViCreate(const size_t support_tree_count, const std::vector<int32_t>& support_parent_ids,
+                          const std::vector<double>& log_params, const std::vector<double>& q_params,
+                          const mi_vi_options& options, const std::vector<double>& model_param_row = {}) const {
+    if (support_parent_ids.size() != support_tree_count * (2 * taxon_count_ - 3) || q_params.size() % 2)
+      Failwith("ViCreate: the support is [trees][2n-3] on the engine's taxa, q_params [V][2].");
+    if (!model_param_row.empty() && model_param_row.size() != static_cast<size_t>(ParameterCount()))
+      Failwith("ViCreate takes ONE parameter row.");
+    mi_vi* handle = nullptr;
+    Check(mi_engine_vi_create(handle_, static_cast<int32_t>(support_tree_count),
+                              support_tree_count ? support_parent_ids.data() : nullptr,
+                              model_param_row.empty() ? nullptr : model_param_row.data(),
+                              static_cast<int32_t>(log_params.size()), log_params.data(),
+                              static_cast<int32_t>(q_params.size() / 2), q_params.data(), &options, &handle));
+    return VariationalFit(handle);
+  }
+
+  // `steps` steps of a fit; their trace rows [steps][6]: mi_vi_fit.
+  std::vector<double> ViFit(const VariationalFit& fit, const size_t steps, const int check_interval = 0) const {
+    std::vector<double> trace(6 * steps);
+    Check(mi_vi_fit(fit.Handle(), static_cast<int32_t>(steps), check_interval, trace.data()));
+    return trace;
+  }
+
+  // One update of a fit's state from given gradients [P], [V][2] and the particles' terms [K]
+  // each; the trace row: mi_vi_update.
+  std::array<double, 6> ViUpdate(const VariationalFit& fit, const std::vector<double>& sbn_gradient,
+                                 const std::vector<double>& q_gradient, const std::vector<double>& log_likelihoods,
+                                 const std::vector<double>& log_prior, const std::vector<double>& log_q_topology,
+                                 const std::vector<double>& log_q_branch) const {
+    const auto sizes = fit.Sizes();
+    const size_t K = sizes[1], V = sizes[6], P = sizes[8];
+    if (sbn_gradient.size() != P || q_gradient.size() != 2 * V || log_likelihoods.size() != K ||
+        log_prior.size() != K || log_q_topology.size() != K || log_q_branch.size() != K)
+      Failwith("ViUpdate: gradients [P] and [V][2], the particles' terms [K] each.");
+    std::array<double, 6> row{};
+    Check(mi_vi_update(fit.Handle(), sbn_gradient.data(), q_gradient.data(), log_likelihoods.data(), log_prior.data(),
+                       log_q_topology.data(), log_q_branch.data(), row.data()));
+    return row;
+  }
+
+  // The whole state of a fit: mi_vi_get_state.
+  ViStateResult ViState(const VariationalFit& fit) const {
+    const auto sizes = fit.Sizes();
+    const size_t V = sizes[6], P = sizes[8];
+    ViStateResult out;
+    out.log_params_.resize(P);
+    out.q_params_.resize(2 * V);
+    out.sbn_moments_.resize(2 * P);
+    out.q_moments_.resize(4 * V);
+    Check(mi_vi_get_state(fit.Handle(), out.log_params_.data(), out.q_params_.data(), out.sbn_moments_.data(),
+                          out.q_moments_.data(), out.scalars_.data(), out.counters_.data()));
     return out;
   }
 

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void branch_sample_kernel(BranchSampleArgs a) 
   const int lane = threadIdx.x & 63, E = 2 * a.n - 3;
   const size_t t = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= (size_t)a.T) return;  // (the whole wave)
-  const uint64_t s = (uint64_t)(a.first_sample + (int64_t)t);
+  const uint64_t s = (uint64_t)((a.vi ? vi_sample_base(*a.vi) : a.first_sample) + (int64_t)t);
   double sum_q = 0.0, sum_theta = 0.0;
   for (int v0 = 0; v0 < E; v0 += 64) {
     const int v = v0 + lane;
@@ -152,9 +152,11 @@ __global__ __launch_bounds__(256) void branch_sample_kernel(BranchSampleArgs a) 
 __global__ __launch_bounds__(256) void branch_terms_kernel(BranchGradientArgs a) {
   const int E = 2 * a.n - 3;
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < (size_t)a.T)
-    a.out_log_f[i] = ((a.beta * a.log_likelihoods[i] + a.log_prior[i]) - (a.log_q_topology ? a.log_q_topology[i] : 0.0)) -
+  if (i < (size_t)a.T) {
+    const double beta = a.vi ? vi_beta(a.vi->t, a.vi->anneal_steps) : a.beta;
+    a.out_log_f[i] = ((beta * a.log_likelihoods[i] + a.log_prior[i]) - (a.log_q_topology ? a.log_q_topology[i] : 0.0)) -
                      a.log_q_branch[i];
+  }
   if (i >= (size_t)a.T * E) return;
   const size_t t = i / E;
   const int v = (int)(i - t * E);

@@ -284,7 +284,7 @@ __device__ __forceinline__ void sbn_sample(const SbnSampleArgs& a, char* store) 
   const NodeStore s = node_store(store, n, a.tpw, lane);
   int32_t* par = a.out_parent_ids + (size_t)k * E;
   int32_t* chosen = a.out_params + (size_t)k * (n - 1);
-  const uint64_t t = (uint64_t)(a.first_sample + (int64_t)k);
+  const uint64_t t = (uint64_t)((a.vi ? vi_sample_base(*a.vi) : a.first_sample) + (int64_t)k);
   int code = kOk, where = 0;
   double lp = 0.0;
   int count = 0, sp = 0, block = -1, slot = -1;  // block -1: the rootsplits

@@ -172,6 +172,7 @@ int run_branch_sample_device(mi_engine* e, hipStream_t s, const BranchSampleCall
   a.q_params = c.q_params;
   a.seed = c.seed;
   a.first_sample = c.first_sample;
+  a.vi = e->vi_state;
   a.prior_rate = c.prior_rate;
   a.epsilon_in = c.epsilon_in;
   a.status = e->status.as<int32_t>();
@@ -229,6 +230,7 @@ int run_branch_gradient_device(mi_engine* e, hipStream_t s, const BranchGradient
   a.weights = c.weights;
   a.beta = c.beta;
   a.prior_rate = c.prior_rate;
+  a.vi = e->vi_state;
   a.status = e->status.as<int32_t>();
   a.terms = reinterpret_cast<double*>(ws + l.terms);
   a.keys = reinterpret_cast<uint32_t*>(ws + l.keys);

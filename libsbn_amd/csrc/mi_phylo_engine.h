@@ -13,6 +13,7 @@
 //   mi_phylo_splits.cpp       split tables, Robinson-Foulds distances (device and host forms, reservation), mi_consensus_tree
 //   mi_phylo_sbn.cpp          subsplit Bayesian networks: support and slots, probabilities, normalisation, training
 //   mi_phylo_branch_model.cpp PSP indexing and the log-normal branch-length models of a variational step
+//   mi_phylo_vi.cpp           the variational fit: its device state, one step, the fit, the optimiser call
 //   mi_phylo_host_calls.cpp   what runs a host-pointer call (staging, status, shards), the plain entry points
 //   mi_phylo_engine_aa.cpp    20-state call sequence
 #pragma once
@@ -162,6 +163,9 @@ struct mi_engine {
   Buffer sbn_store;     // the per-tree kernels' node arrays of trees too large for LDS
   // PSP indexing and the branch-length models (mi_engine_psp_*, mi_engine_branch_model_*)
   Buffer branch_ws;     // the gradient call: every edge's two terms | the accumulation's sort
+  // a variational fit (mi_vi, mi_phylo_vi.cpp): set while mi_vi_step_device enqueues, so that the
+  // sampler, the branch-length draw and its gradient read first_sample and beta from the fit's state
+  const ViState* vi_state = nullptr;
   Buffer rf_ws;        // a batch's sorted lists: lengths [T][2n-3] | indices [T][2n-3] | counts [T]
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)

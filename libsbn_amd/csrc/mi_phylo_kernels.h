@@ -669,6 +669,23 @@ struct SbnDescentArgs {
   int32_t* out_descent;        // [S + C][2]
 };
 void launch_sbn_descent(const SbnDescentArgs& a, hipStream_t s);
+// The state of a variational fit (mi_vi): one struct in device memory that the
+// sampler, the branch-length draw, the branch-length gradient and the optimiser read where a plain
+// call takes seed-side arguments by value.  Only vi_finish_kernel writes it.
+struct ViState {
+  int64_t t, a;            // steps enqueued so far (failed ones included); successful ones
+  int64_t first_sample;    // the sample base: sample k of step t is first_sample + t K + k
+  int64_t K, anneal_steps; // (constants of the fit)
+  double b0, b1;           // beta0^a, beta1^a: one rounded multiply per successful step, from 1
+  double step[2], sbn_step;
+};
+__host__ __device__ inline int64_t vi_sample_base(const ViState& s) { return s.first_sample + s.t * s.K; }
+// beta of step t: 1 without annealing, else max(min((t+1) / anneal_steps, 1), 0.001)
+__host__ __device__ inline double vi_beta(int64_t t, int64_t anneal_steps) {
+  if (anneal_steps <= 0) return 1.0;
+  const double b = (double)(t + 1) / (double)anneal_steps;
+  return b < 1.0 ? (b > 0.001 ? b : 0.001) : 1.0;
+}
 struct SbnSampleArgs {
   int n, K, tpw;
   int S, C, parents;
@@ -677,6 +694,7 @@ struct SbnSampleArgs {
   const double* phi;            // [S + C] log parameters, unnormalised
   uint64_t seed;
   int64_t first_sample;
+  const ViState* vi;            // a fit's step: first_sample is the state's (else nullptr)
   int32_t* status;
   char* store;
   double* cdf;                  // [S + C]
@@ -730,6 +748,7 @@ struct BranchSampleArgs {
   const double* q_params;       // [V][2] mu, sigma
   uint64_t seed;
   int64_t first_sample;
+  const ViState* vi;            // a fit's step: first_sample is the state's (else nullptr)
   double prior_rate;
   const double* epsilon_in;     // [T][2n-3] or nullptr
   int32_t* status;
@@ -752,6 +771,7 @@ struct BranchGradientArgs {
   const double* log_q_topology;   // [T] or nullptr
   const double* weights;          // [T] or nullptr
   double beta, prior_rate;
+  const ViState* vi;            // a fit's step: beta is the state's (else nullptr)
   int32_t* status;
   double* terms;                // [T][2n-3][2] workspace: c0, c1 of every edge
   uint32_t *keys, *keys2, *vals, *vals2;  // [T R (2n-3)]
@@ -762,6 +782,27 @@ struct BranchGradientArgs {
 };
 size_t branch_model_sort_tmp_bytes(size_t entries);
 int launch_branch_gradient(const BranchGradientArgs& a, hipStream_t s);  // (nonzero: rocPRIM refused)
+// kernels_vi_fit.hip: the optimiser of a variational fit and its trace row.
+// Element i of the update: 0 .. P-1 the SBN parameters, then the 2 V entries of q_params.
+struct ViUpdateArgs {
+  int P, V, K;
+  int S;                        // variables 0 .. S-1 stand alone on an edge: their sigma must stay positive
+  double beta0, beta1, epsilon, decay;
+  ViState* state;
+  const double* g_sbn;          // [P]
+  const double* g_q;            // [V][2]
+  const double *log_lik, *log_prior, *log_q_top, *log_q_branch;  // [K]
+  double* phi;                  // [P]
+  double* q_params;             // [V][2]
+  double *m_sbn, *v_sbn;        // [P]
+  double *m_q, *v_q;            // [V][2]
+  int32_t* block_flags;         // [blocks of 256 elements] workspace
+  double* trace;                // [max_steps][6]: the step's row is [t], or nullptr
+  int64_t max_steps;
+  double* out_row;              // [6] or nullptr: the row once more (mi_vi_update)
+};
+int vi_update_blocks(int P, int V);
+void launch_vi_update(const ViUpdateArgs& a, hipStream_t s);  // check, apply, finish
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
 // the first, gradient_mfma_kernel, was retired in round 6): all categories of a group of four
 // per instruction; they also write the log-likelihood partial sums, so no separate logL pass is

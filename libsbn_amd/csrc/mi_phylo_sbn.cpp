@@ -485,6 +485,7 @@ int run_sbn_sample_device(mi_engine* e, hipStream_t s, const SbnSampleCall& c) {
   a.phi = c.log_params;
   a.seed = c.seed;
   a.first_sample = c.first_sample;
+  a.vi = e->vi_state;
   a.status = e->status.as<int32_t>();
   a.store = e->sbn_store.as<char>();
   a.cdf = c.out_cdf ? c.out_cdf : reinterpret_cast<double*>(ws + l.log_m_tilde);

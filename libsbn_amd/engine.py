@@ -1689,6 +1689,34 @@ class Engine:
         """mi_engine_reserve_reduced: workspace of a fused-reduction call (graph capture)."""
         self._check(self._lib.mi_engine_reserve_reduced(self._h, int(tree_count), int(index_count)))
 
+    def vi_create(self, support_parent_ids, log_params, q_params, particle_count=10, rows=3, estimator="vimco",
+                  anneal_steps=0, max_steps=1000, prior_rate=10.0, step_size=(0.001, 0.001), sbn_step_size=0.001,
+                  step_decay=0.99, adam_beta0=0.9, adam_beta1=0.999, adam_epsilon=1e-8, seed=0, first_sample=0,
+                  model_params=None):
+        """A device-resident variational fit over the support of support_parent_ids [T0][2n-3]
+        (mi_engine_vi_create), from log_params [P] and q_params [V][2] (for instance
+        lognormal_mode_match's); model_params: the one parameter row every particle takes.
+        Returns a VariationalFit."""
+        if estimator not in ("plain", "vimco"):
+            raise RuntimeError(f"vi_create: estimator must be 'plain' or 'vimco', got {estimator!r}")
+        pid = np.empty((0, 2 * self.taxon_count - 3), np.int32)   # (None: the two tables alone, for update())
+        if support_parent_ids is not None:
+            pid = _np(support_parent_ids, np.int32).reshape(-1, 2 * self.taxon_count - 3)
+        phi, q = _np(log_params, np.float64).reshape(-1), _np(q_params, np.float64).reshape(-1, 2)
+        mp = None if model_params is None or self.param_count == 0 else _np(model_params, np.float64).reshape(self.param_count)
+        o = _capi.ViOptions()
+        self._check(self._lib.mi_vi_default_options(C.byref(o)))
+        o.particle_count, o.rows, o.estimator = int(particle_count), int(rows), _SBN_FACTORS[estimator]
+        o.anneal_steps, o.max_steps, o.prior_rate = int(anneal_steps), int(max_steps), float(prior_rate)
+        o.step_size[0], o.step_size[1] = (float(x) for x in np.broadcast_to(step_size, 2))
+        o.sbn_step_size, o.step_decay = float(sbn_step_size), float(step_decay)
+        o.adam_beta0, o.adam_beta1, o.adam_epsilon = float(adam_beta0), float(adam_beta1), float(adam_epsilon)
+        o.seed, o.first_sample = int(seed) & (2 ** 64 - 1), int(first_sample)
+        h = C.c_void_p()
+        self._check(self._lib.mi_engine_vi_create(self._h, pid.shape[0], _ptr(pid) if len(pid) else None, _ptr(mp), phi.shape[0], _ptr(phi),
+                                                  q.shape[0], _ptr(q), C.byref(o), C.byref(h)))
+        return VariationalFit(self, h, pid, mp, o)
+
     def check_status(self, stream=None):
         self._check(self._lib.mi_engine_check_status(self._h, stream))
 
@@ -1735,6 +1763,138 @@ class Engine:
         a, b = C.c_int32(), C.c_int32()
         self._check(self._lib.mi_engine_last_call_launches(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+
+@dataclass
+class ViState:
+    """VariationalFit.state: the whole state of a fit (include/mi_phylo.h, mi_vi_get_state)."""
+    log_params: np.ndarray    # [P] the SBN's unnormalised log parameters
+    q_params: np.ndarray      # [V][2] mu, sigma
+    sbn_moments: np.ndarray   # [2][P] Adam's m, then v
+    q_moments: np.ndarray     # [2][V][2]
+    b0: float                 # adam_beta0 ** successes, by repeated rounded multiplication
+    b1: float
+    step_size: np.ndarray     # [2] the mu and the sigma column's
+    sbn_step_size: float
+    steps: int                # t: steps so far, failed ones included
+    successes: int            # a
+    first_sample: int         # the sample base: step t draws first_sample + t K + k
+
+
+TRACE_COLUMNS = ("beta", "elbo", "bound", "step_size_mu", "step_size_sigma", "success")
+
+
+class VariationalFit:
+    """A device-resident variational fit (mi_vi, include/mi_phylo.h), made by
+    Engine.vi_create.  The engine must outlive it."""
+
+    def __init__(self, engine, handle, support_ids, model_params, options):
+        self.engine, self._h, self._lib = engine, handle, engine._lib
+        self.support_ids, self.model_params, self.options = support_ids, model_params, options
+        sizes = np.zeros(9, np.int32)
+        self._check(self._lib.mi_vi_sizes(self._h, sizes.ctypes.data_as(_capi.I32P)))
+        (self.taxon_count, self.particle_count, self.rows, self.rootsplit_count, self.pcsp_count,
+         self.parent_count, self.variable_count, self.max_steps, self.parameter_count) = (int(x) for x in sizes)
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RuntimeError(_capi.last_error())
+
+    def close(self):
+        if self._h is not None:
+            if self.engine._h is not None:   # (a fit whose engine is gone already cannot be synchronised: left alone)
+                self._lib.mi_vi_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step_device(self, stream=None):
+        """Enqueue one step on `stream` (mi_vi_step_device): nothing is read back, so a caller may
+        capture it in a graph on one stream; every replay is the next step."""
+        self._check(self._lib.mi_vi_step_device(self._h, stream))
+
+    def fit(self, steps, check_interval=0):
+        """`steps` steps (mi_vi_fit); returns their trace rows [steps][6] (TRACE_COLUMNS)."""
+        out = np.empty((int(steps), 6))
+        self._check(self._lib.mi_vi_fit(self._h, int(steps), int(check_interval), _ptr(out)))
+        return out
+
+    def trace(self, first_step=0, count=None):
+        """Trace rows [first_step, first_step + count) of the steps so far (mi_vi_trace); count
+        None: up to the last step."""
+        if count is None:
+            count = min(self.state().steps, self.max_steps) - int(first_step)
+        out = np.empty((int(count), 6))
+        self._check(self._lib.mi_vi_trace(self._h, int(first_step), int(count), _ptr(out)))
+        return out
+
+    def update(self, sbn_gradient, q_gradient, log_likelihoods, log_prior, log_q_topology, log_q_branch):
+        """One update of the state from given gradients [P], [V][2] and the particles' terms [K]
+        each (mi_vi_update).  Returns the trace row [6]."""
+        P, V, K = self.parameter_count, self.variable_count, self.particle_count
+        arrays = [_np(sbn_gradient, np.float64).reshape(P), _np(q_gradient, np.float64).reshape(V, 2)]
+        arrays += [_np(x, np.float64).reshape(K) for x in (log_likelihoods, log_prior, log_q_topology, log_q_branch)]
+        row = np.empty(6)
+        self._check(self._lib.mi_vi_update(self._h, *[_ptr(x) for x in arrays], _ptr(row)))
+        return row
+
+    def update_device(self, stream, sbn_gradient, q_gradient, log_likelihoods, log_prior, log_q_topology,
+                      log_q_branch, out_trace_row=None):
+        """mi_vi_update_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_vi_update_device(self._h, stream, sbn_gradient, q_gradient, log_likelihoods,
+                                                  log_prior, log_q_topology, log_q_branch, out_trace_row))
+
+    def state(self):
+        """The whole state (mi_vi_get_state): a ViState."""
+        P, V = self.parameter_count, self.variable_count
+        phi, q, ms, mq = np.empty(P), np.empty((V, 2)), np.empty((2, P)), np.empty((2, V, 2))
+        scalars, counters = np.empty(5), np.empty(3, np.int64)
+        self._check(self._lib.mi_vi_get_state(self._h, _ptr(phi), _ptr(q), _ptr(ms), _ptr(mq), _ptr(scalars),
+                                              _ptr(counters)))
+        return ViState(phi, q, ms, mq, float(scalars[0]), float(scalars[1]), scalars[2:4].copy(), float(scalars[4]),
+                       int(counters[0]), int(counters[1]), int(counters[2]))
+
+    def set_state(self, state):
+        """Load a ViState (mi_vi_set_state): the fit goes on from it bit for bit."""
+        P, V = self.parameter_count, self.variable_count
+        phi, q = _np(state.log_params, np.float64).reshape(P), _np(state.q_params, np.float64).reshape(V, 2)
+        ms, mq = _np(state.sbn_moments, np.float64).reshape(2, P), _np(state.q_moments, np.float64).reshape(2, V, 2)
+        scalars = np.array([state.b0, state.b1, state.step_size[0], state.step_size[1], state.sbn_step_size])
+        counters = np.array([state.steps, state.successes, state.first_sample], np.int64)
+        self._check(self._lib.mi_vi_set_state(self._h, _ptr(phi), _ptr(q), _ptr(ms), _ptr(mq), _ptr(scalars),
+                                              _ptr(counters)))
+
+    def particles(self):
+        """The last step's particles (mi_vi_particles): (parent ids [K][2n-3], branch lengths
+        [K][2n-2], logL [K], log q of the topology [K], log q of the lengths [K], log prior [K])."""
+        K, E = self.particle_count, 2 * self.taxon_count - 3
+        pid, bl = np.empty((K, E), np.int32), np.empty((K, E + 1))
+        ll, lqt, lqb, lp = np.empty(K), np.empty(K), np.empty(K), np.empty(K)
+        self._check(self._lib.mi_vi_particles(self._h, _ptr(pid), _ptr(bl), _ptr(ll), _ptr(lqt), _ptr(lqb), _ptr(lp)))
+        return pid, bl, ll, lqt, lqb, lp
+
+    def estimate(self, particle_count, seed, first_sample=0):
+        """The reference's estimate_elbo and marginal_likelihood_estimate (burrito.py:127-183) of
+        the current state on fresh particles, composed from the engine's existing calls: returns
+        (elbo, marginal likelihood estimate)."""
+        e, K, T0 = self.engine, int(particle_count), self.support_ids.shape[0]
+        st = self.state()
+        sup = e.sbn_index(self.support_ids)
+        pid, _, _, _ = e.sbn_sample(sup, e.sbn_descent(sup), st.log_params, K, seed, first_sample=first_sample)
+        both = e.sbn_index(np.concatenate([self.support_ids, pid]), support_tree_count=T0)
+        index = e.psp_index(both, e.psp_table(sup), rows=self.rows, trees=slice(T0, None))
+        draw = e.branch_model_sample(index, st.q_params, seed, first_sample=first_sample,
+                                     prior_rate=self.options.prior_rate)
+        params = None if self.model_params is None else np.tile(self.model_params, (K, 1))
+        ll = e.log_likelihoods(pid, draw.branch_lengths, params)
+        _, lqt = e.sbn_log_prob(both, st.log_params, trees=slice(T0, None))
+        f = ll + draw.log_prior - lqt - draw.log_q
+        top = np.max(f)
+        return float(np.mean(f)), float(top + np.log(np.sum(np.exp(f - top))) - np.log(K))
 
 
 class DevicePatterns:
