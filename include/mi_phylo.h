@@ -1625,6 +1625,116 @@ int32_t mi_vi_set_state(mi_vi* fit, const double* log_params, const double* q_pa
 int32_t mi_vi_particles(mi_vi* fit, int32_t* out_parent_ids, double* out_branch_lengths, double* out_log_likelihoods,
                         double* out_log_q_topology, double* out_log_q_branch, double* out_log_prior);
 
+/* ---- generalized pruning: the marginal likelihood over a subsplit DAG ----
+ *
+ * What the reference's GPInstance / GPEngine / SubsplitDAG do (src/gp_instance.*, gp_engine.*,
+ * gp_dag.*, subsplit_dag.*): the likelihood marginalised over EVERY tree of the subsplit DAG of a
+ * batch of rooted topologies, in two sweeps over the DAG; per entry (GPCSP) the marginal
+ * restricted to the trees that use it; the SBN parameters that follow; branch lengths per entry.
+ * Hybrid (quartet) marginals are not provided.
+ *
+ * A mi_gp is bound to a single-device 4-state engine with ONE rate category (20 states, K > 1 and
+ * a handle of several shards are refused with a message; a handle of one shard serves as its one
+ * engine).  It keeps the DAG, its vectors, b[G] and q[G] in device memory, counted by
+ * mi_device_bytes_held; mi_gp_destroy releases them; the engine must outlive it.
+ *
+ * The DAG and its numbering (the reference numbers by unordered_map iteration; this rule is the
+ * project's own and is deterministic):
+ *   nodes    0..n-1 the leaves; then every distinct subsplit of the batch, numbered by first
+ *            occurrence scanning the trees in order and, within a tree, the nodes in id order.
+ *            A subsplit has two clades: clade 0 holds its lowest taxon (the reference's "sorted"
+ *            side), clade 1 is the other ("rotated").
+ *   entries  0..R-1 the rootsplits in order of first occurrence (as in the reference, a rootsplit
+ *            is an entry); then one contiguous block per (node, clade), blocks by node id then
+ *            clade, inside a block by child node id.  The entries of a block are the union over
+ *            the trees of the parent -> child pairs, leaves included, so the DAG spans every
+ *            combination of its entries: more trees than were given.
+ *   level    of a node: its clade size (children have smaller, parents larger levels).
+ *
+ * Initial values: q is SubsplitDAG::BuildUniformOnTopologicalSupportPrior; b is 0.1 on every
+ * entry (GPEngine's default_branch_length_), or with branch_lengths [T][2n-1] given
+ * HotStartBranchLengths: the mean over the trees that hold the entry; 0 on rootsplit entries, always.
+ *
+ * The vectors carry one integer exponent per pattern (true value = stored x 2^e); sums align their
+ * terms to the least-scaled one and a vector whose largest entry falls below rescaling_threshold
+ * is scaled by a power of two.  All of that is exact, so results do not depend on the threshold
+ * beyond where underflow would otherwise set in.  rescaling_threshold 0: the default 2^-256.
+ *
+ * Every sum over a block's entries or the entries into a node runs in entry order; every sum over
+ * patterns runs tile by tile of 64 (within a tile a fixed butterfly, then the tiles ascending).
+ * No float atomics: results are bit-identical however calls are batched or replayed. */
+typedef struct mi_gp mi_gp;
+int32_t mi_engine_gp_create(mi_engine* engine, int32_t tree_count, int32_t taxon_count,
+                            const int32_t* parent_ids /* [T][2n-2] */,
+                            const double* branch_lengths /* [T][2n-1] or NULL */,
+                            const double* model_params /* [param_count] or NULL */, double rescaling_threshold,
+                            mi_gp** out_gp);
+void mi_gp_destroy(mi_gp* gp);
+/* out_sizes [8]: n, node_count, rootsplit_count R, G, P, W = words of a clade bitset, levels,
+ * the kernels' pattern tile width */
+int32_t mi_gp_sizes(const mi_gp* gp, int32_t* out_sizes);
+/* Any pointer may be NULL.  out_entries [G][3] (parent node, clade, child node; a rootsplit entry
+ * is (-1, -1, its node)); out_block_range [node_count][2][2] (begin, end; a leaf: 0, 0);
+ * out_clades [node_count][2][W] (bit x of word x / 32; a leaf: its bit in clade 0);
+ * out_levels [node_count]; *out_topology_count = SubsplitDAG::TopologyCount. */
+int32_t mi_gp_structure(const mi_gp* gp, int32_t* out_entries, int32_t* out_block_range, uint32_t* out_clades,
+                        int32_t* out_levels, double* out_topology_count);
+/* The entries' names as GPInstance::PrettyIndexer gives them, separated by '\n': a rootsplit is its
+ * smaller chunk's bit string (taxon 0 first), a PCSP "<sister>|<focal>|<the child's smaller chunk>"
+ * (zeros for a leaf child).  *out_needed (or NULL): bytes with the final 0; buffer NULL only asks. */
+int32_t mi_gp_strings(const mi_gp* gp, char* buffer, int64_t capacity, int64_t* out_needed);
+/* b and q, [G] each (count must be G).  Rootsplit entries of b are stored as 0.  q is taken as
+ * given: normalised per block and over the rootsplits by the caller.  All four synchronise. */
+int32_t mi_gp_set_branch_lengths(mi_gp* gp, const double* branch_lengths, int32_t count);
+int32_t mi_gp_get_branch_lengths(mi_gp* gp, double* out_branch_lengths);
+int32_t mi_gp_set_sbn_parameters(mi_gp* gp, const double* q, int32_t count);
+int32_t mi_gp_get_sbn_parameters(mi_gp* gp, double* out_q);
+/* SubsplitDAG::UnconditionalNodeProbabilities [node_count] and InvertedGPCSPProbabilities [G] of a
+ * normalised q given in host memory (host code). */
+int32_t mi_gp_node_probabilities(const mi_gp* gp, const double* q, int32_t count, double* out);
+int32_t mi_gp_inverted_probabilities(const mi_gp* gp, const double* q, int32_t count, double* out);
+/* Both sweeps (GPInstance::PopulatePLVs) at the object's b and q, and with them the sums every call
+ * below reads.  The device form only enqueues: one launch per level and sweep, nothing allocated
+ * or synchronised, so it can be captured in a hipGraph.
+ * mi_engine_last_call_path: "gp_populate n=<n> nodes=<nodes> G=<G> levels=<levels> tiles=<tiles>". */
+int32_t mi_gp_populate(mi_gp* gp);
+int32_t mi_gp_populate_device(mi_gp* gp, void* stream);
+/* out_per_gpcsp_log_likelihood [G] (GPEngine::GetPerGPCSPLogLikelihoods): sum_p w_p log l_e, the
+ * likelihood restricted to the trees through e WITHOUT the factor q_e; a rootsplit row is the value
+ * conditional on the rootsplit, sum_p w_p log(pi . p(root node)).  *out_log_marginal
+ * (GetLogMarginalLikelihood): sum_p w_p log M_p.  Optional: out_pattern_log_marginal [P] = log M_p
+ * and out_matrix [G][P] = log l_e per pattern.  The host form populates first when b or q changed
+ * since the last populate (always when the matrix is asked for); the device form reads the last
+ * populate's sums and takes device pointers, either may be NULL. */
+int32_t mi_gp_likelihoods(mi_gp* gp, double* out_per_gpcsp_log_likelihood, double* out_log_marginal,
+                          double* out_pattern_log_marginal, double* out_matrix);
+int32_t mi_gp_likelihoods_device(mi_gp* gp, void* stream, double* out_per_gpcsp_log_likelihood,
+                                 double* out_log_marginal);
+/* Per entry, any pointer may be NULL: out_ll_derivative [G][2] = (sum_p w_p log l_e,
+ * sum_p w_p l'_e / l_e), GPEngine's LogLikelihoodAndDerivative pair; and of the MARGINAL
+ *   out_gradient [G]  g_e = sum_p w_p q_e l'_e / M_p   (the exact gradient of log_marginal in b_e)
+ *   out_hessian  [G]  H_e = sum_p w_p [q_e l''_e / M_p - (q_e l'_e / M_p)^2]
+ *   out_gsq      [G]  S_e = sum_p w_p (q_e l'_e / M_p)^2
+ * with the exponents accounted for; rootsplit rows are 0.  Host form: as above. */
+int32_t mi_gp_branch_derivatives(mi_gp* gp, double* out_ll_derivative, double* out_gradient, double* out_hessian,
+                                 double* out_gsq);
+int32_t mi_gp_branch_derivatives_device(mi_gp* gp, void* stream, double* out_ll_derivative, double* out_gradient,
+                                        double* out_hessian, double* out_gsq);
+/* GPInstance::EstimateSBNParameters: populate, likelihoods, then for the rootsplits and per block
+ * q <- softmax(per_gpcsp_log_likelihood + log q), one logsumexp per block with the entries in
+ * order; a block of one entry gets 1.  out_q [G] or NULL. */
+int32_t mi_gp_estimate_sbn_parameters(mi_gp* gp, double* out_q);
+/* Maximise log_marginal over all of b at once with the rule of
+ * mi_engine_optimize_branch_lengths_unrooted (accept / halve alpha, Newton step on c = -H or S,
+ * step limits, projected-gradient criterion): the DAG takes the part of one tree of G - R branches,
+ * an evaluation is one populate at the trial point.  Rootsplit entries stay 0.  options NULL: that
+ * call's defaults with min_length e^-13.9 and max_length e^1.1 (the reference's bounds);
+ * pack_active is ignored.  out_trace [max_iterations] or NULL: the accepted log_marginal after each
+ * evaluation (*out_evaluations of them); *out_status: MI_BRANCH_OPT_CONVERGED, _ITERATION_LIMIT or
+ * _STALLED.  This is not the reference's sequential Brent sweep over one entry at a time. */
+int32_t mi_gp_optimize_branch_lengths(mi_gp* gp, const mi_branch_opt_options* options, double* out_trace,
+                                      int32_t* out_evaluations, int32_t* out_status);
+
 /* Synchronise `stream` and report the first per-tree error since the last check (the status
  * word is sticky and cleared when an error is reported: calls themselves never clear it). */
 int32_t mi_engine_check_status(mi_engine* engine, void* stream);

@@ -247,6 +247,27 @@ SYMBOLS = {
     "mi_vi_get_state": (C.c_int32, [_V, _V, _V, _V, _V, _V, _V]),
     "mi_vi_set_state": (C.c_int32, [_V, _V, _V, _V, _V, _V, _V]),
     "mi_vi_particles": (C.c_int32, [_V, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_gp_create":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, C.c_double, C.POINTER(_V)]),
+    "mi_gp_destroy": (None, [_V]),
+    "mi_gp_sizes": (C.c_int32, [_V, I32P]),
+    "mi_gp_structure": (C.c_int32, [_V, _V, _V, _V, _V, F64P]),
+    "mi_gp_strings": (C.c_int32, [_V, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "mi_gp_set_branch_lengths": (C.c_int32, [_V, _V, C.c_int32]),
+    "mi_gp_get_branch_lengths": (C.c_int32, [_V, _V]),
+    "mi_gp_set_sbn_parameters": (C.c_int32, [_V, _V, C.c_int32]),
+    "mi_gp_get_sbn_parameters": (C.c_int32, [_V, _V]),
+    "mi_gp_node_probabilities": (C.c_int32, [_V, _V, C.c_int32, _V]),
+    "mi_gp_inverted_probabilities": (C.c_int32, [_V, _V, C.c_int32, _V]),
+    "mi_gp_populate": (C.c_int32, [_V]),
+    "mi_gp_populate_device": (C.c_int32, [_V, _V]),
+    "mi_gp_likelihoods": (C.c_int32, [_V, _V, _V, _V, _V]),
+    "mi_gp_likelihoods_device": (C.c_int32, [_V, _V, _V, _V]),
+    "mi_gp_branch_derivatives": (C.c_int32, [_V, _V, _V, _V, _V]),
+    "mi_gp_branch_derivatives_device": (C.c_int32, [_V, _V, _V, _V, _V, _V]),
+    "mi_gp_estimate_sbn_parameters": (C.c_int32, [_V, _V]),
+    "mi_gp_optimize_branch_lengths":
+        (C.c_int32, [_V, C.POINTER(BranchOptOptions), _V, I32P, I32P]),
     "mi_consensus_tree":
         (C.c_int32, [C.c_int32, C.c_int32, _V, _V, C.c_double, C.c_double, I32P, _V, _V]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),

@@ -186,6 +186,96 @@ struct ViStateResult {
   std::array<int64_t, 3> counters_{};  // t, a, first_sample
 };
 
+// Engine::GpCreate: generalized pruning over a subsplit DAG (mi_gp, include/mi_phylo.h); it releases
+// itself and must not outlive its engine.
+struct GpLikelihoodResult {
+  std::vector<double> per_gpcsp_log_likelihood_;  // [G]
+  double log_marginal_ = 0.0;
+};
+struct GpDerivativeResult {
+  std::vector<double> ll_derivative_;  // [G][2]
+  std::vector<double> gradient_, hessian_, gsq_;  // [G] each
+};
+struct GpOptimizeResult {
+  std::vector<double> branch_lengths_, trace_;
+  int32_t evaluations_ = 0, status_ = 0;
+};
+class GeneralizedPruning {
+ public:
+  GeneralizedPruning() = default;
+  explicit GeneralizedPruning(mi_gp* handle) : handle_(handle) {}
+  GeneralizedPruning(GeneralizedPruning&& o) noexcept : handle_(o.handle_) { o.handle_ = nullptr; }
+  GeneralizedPruning& operator=(GeneralizedPruning&& o) noexcept {
+    std::swap(handle_, o.handle_);
+    return *this;
+  }
+  GeneralizedPruning(const GeneralizedPruning&) = delete;
+  GeneralizedPruning& operator=(const GeneralizedPruning&) = delete;
+  ~GeneralizedPruning() { mi_gp_destroy(handle_); }
+  mi_gp* Handle() const { return handle_; }
+  // n, node count, rootsplit count, G, P, words of a clade bitset, levels, tile width
+  std::array<int32_t, 8> Sizes() const {
+    std::array<int32_t, 8> out{};
+    Try(mi_gp_sizes(handle_, out.data()));
+    return out;
+  }
+  size_t EntryCount() const { return static_cast<size_t>(Sizes()[3]); }
+  std::vector<double> BranchLengths() const {
+    std::vector<double> out(EntryCount());
+    Try(mi_gp_get_branch_lengths(handle_, out.data()));
+    return out;
+  }
+  void SetBranchLengths(const std::vector<double>& b) const {
+    Try(mi_gp_set_branch_lengths(handle_, b.data(), static_cast<int32_t>(b.size())));
+  }
+  std::vector<double> SbnParameters() const {
+    std::vector<double> out(EntryCount());
+    Try(mi_gp_get_sbn_parameters(handle_, out.data()));
+    return out;
+  }
+  void SetSbnParameters(const std::vector<double>& q) const {
+    Try(mi_gp_set_sbn_parameters(handle_, q.data(), static_cast<int32_t>(q.size())));
+  }
+  void Populate() const { Try(mi_gp_populate(handle_)); }
+  GpLikelihoodResult Likelihoods() const {
+    GpLikelihoodResult out;
+    out.per_gpcsp_log_likelihood_.resize(EntryCount());
+    Try(mi_gp_likelihoods(handle_, out.per_gpcsp_log_likelihood_.data(), &out.log_marginal_, nullptr, nullptr));
+    return out;
+  }
+  GpDerivativeResult BranchDerivatives() const {
+    const size_t G = EntryCount();
+    GpDerivativeResult out;
+    out.ll_derivative_.resize(2 * G);
+    out.gradient_.resize(G);
+    out.hessian_.resize(G);
+    out.gsq_.resize(G);
+    Try(mi_gp_branch_derivatives(handle_, out.ll_derivative_.data(), out.gradient_.data(), out.hessian_.data(),
+                                 out.gsq_.data()));
+    return out;
+  }
+  std::vector<double> EstimateSbnParameters() const {
+    std::vector<double> out(EntryCount());
+    Try(mi_gp_estimate_sbn_parameters(handle_, out.data()));
+    return out;
+  }
+  // options nullptr: tolerance 1e-6, 100 iterations, lengths in [e^-13.9, e^1.1]
+  GpOptimizeResult OptimizeBranchLengths(const mi_branch_opt_options* options = nullptr) const {
+    GpOptimizeResult out;
+    out.trace_.resize(options ? static_cast<size_t>(std::max(options->max_iterations, 1)) : 100);
+    Try(mi_gp_optimize_branch_lengths(handle_, options, out.trace_.data(), &out.evaluations_, &out.status_));
+    out.trace_.resize(static_cast<size_t>(out.evaluations_));
+    out.branch_lengths_ = BranchLengths();
+    return out;
+  }
+
+ private:
+  static void Try(const int32_t rc) {
+    if (rc != 0) Failwith(mi_last_error());
+  }
+  mi_gp* handle_ = nullptr;
+};
+
 // Engine::RfDistances: rf_ [T][T] and, with branch lengths, branch_score_ [T][T]
 struct TreeDistances {
   std::vector<int32_t> rf_;
@@ -920,6 +1010,25 @@ class Engine {
                               static_cast<int32_t>(log_params.size()), log_params.data(),
                               static_cast<int32_t>(q_params.size() / 2), q_params.data(), &options, &handle));
     return VariationalFit(handle);
+  }
+
+  // Generalized pruning over the subsplit DAG of rooted topologies parent_ids [T][2n-2] on this
+  // engine's alignment; branch_lengths [T][2n-1] or empty (0.1 everywhere); model_param_row: the
+  // one parameter row; rescaling_threshold 0: the default: mi_engine_gp_create.
+  GeneralizedPruning GpCreate(const size_t tree_count, const std::vector<int32_t>& parent_ids,
+                              const std::vector<double>& branch_lengths = {},
+                              const std::vector<double>& model_param_row = {},
+                              const double rescaling_threshold = 0.0) const {
+    if (parent_ids.size() != tree_count * (2 * taxon_count_ - 2) ||
+        (!branch_lengths.empty() && branch_lengths.size() != tree_count * (2 * taxon_count_ - 1)))
+      Failwith("GpCreate: parent_ids is [trees][2n-2] on the engine's taxa, branch_lengths [trees][2n-1] or empty.");
+    if (!model_param_row.empty() && model_param_row.size() != static_cast<size_t>(ParameterCount()))
+      Failwith("GpCreate takes ONE parameter row.");
+    mi_gp* handle = nullptr;
+    Check(mi_engine_gp_create(handle_, static_cast<int32_t>(tree_count), static_cast<int32_t>(taxon_count_),
+                              parent_ids.data(), branch_lengths.empty() ? nullptr : branch_lengths.data(),
+                              model_param_row.empty() ? nullptr : model_param_row.data(), rescaling_threshold, &handle));
+    return GeneralizedPruning(handle);
   }
 
   // `steps` steps of a fit; their trace rows [steps][6]: mi_vi_fit.

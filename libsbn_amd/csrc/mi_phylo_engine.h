@@ -14,6 +14,7 @@
 //   mi_phylo_sbn.cpp          subsplit Bayesian networks: support and slots, probabilities, normalisation, training
 //   mi_phylo_branch_model.cpp PSP indexing and the log-normal branch-length models of a variational step
 //   mi_phylo_vi.cpp           the variational fit: its device state, one step, the fit, the optimiser call
+//   mi_phylo_gp.cpp           generalized pruning: the subsplit DAG (host), its device object, the sweeps, the optimiser
 //   mi_phylo_host_calls.cpp   what runs a host-pointer call (staging, status, shards), the plain entry points
 //   mi_phylo_engine_aa.cpp    20-state call sequence
 #pragma once

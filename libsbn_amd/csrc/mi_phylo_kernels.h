@@ -803,6 +803,46 @@ struct ViUpdateArgs {
 };
 int vi_update_blocks(int P, int V);
 void launch_vi_update(const ViUpdateArgs& a, hipStream_t s);  // check, apply, finish
+// kernels_gp.hip: generalized pruning over a subsplit DAG.  A workgroup is one
+// wave over a tile of kGpTile patterns; a launch takes the nodes of one level (equal clade size).
+// Vectors are [internal node][4][Pp] (Pp: P rounded up to whole tiles), their exponents [..][Pp]:
+// true value = stored value x 2^exponent.
+constexpr int kGpTile = 64;
+constexpr int kGpSums = 5;  // per entry: sum w log l | sum w l'/l | g | H | S
+struct GpArgs {
+  int n, P, Pp, tiles, G, R, I;          // taxa, patterns, padded patterns, tiles, entries, rootsplits, internal nodes
+  double threshold;                      // a vector whose largest entry is below it is rescaled
+  const DevModel* model;
+  int Cp;                                // row stride of `codes` (distance_code_stride)
+  const uint8_t* codes;                  // [distance_code_rows(n)][Cp] tip codes 0..3, 4: all ones (launch_distance_codes)
+  const double* weights;                 // [P]
+  const double* b;                       // [G]
+  const double* q;                       // [G]
+  const int32_t* edge;                   // [G][3] parent node, clade, child node (rootsplits: -1, -1, node)
+  const int32_t* block_range;            // [nodes][2][2] begin, end
+  const int32_t* in_range;               // [nodes][2] begin, end into in_edges
+  const int32_t* in_edges;               // entries into a node, ascending
+  const int32_t* order;                  // internal nodes by (level, id)
+  double* mats;                          // [G][16] P(b_e), row-major
+  double* expl;                          // [G][8] e^{lambda_i b_e}, lambda_i (rate included)
+  double *phat, *p, *r;                  // [I][2][4][Pp], [I][4][Pp], [I][2][4][Pp]
+  int32_t *ephat, *ep, *er;              // [I][2][Pp], [I][Pp], [I][2][Pp]
+  double* marg;                          // [Pp] M_p's stored value
+  int32_t* emarg;                        // [Pp] its exponent
+  double* log_marg;                      // [Pp] log M_p
+  double* partial;                       // [G+1][tiles][kGpSums]; row G: the marginal's
+  double* sums;                          // [G+1][kGpSums]
+  double* matrix;                        // [G][P] log l_e per pattern, or nullptr
+};
+void launch_gp_matrices(const GpArgs& a, hipStream_t s);
+void launch_gp_rootward(const GpArgs& a, int first, int count, hipStream_t s);   // a level of `order`
+void launch_gp_marginal(const GpArgs& a, hipStream_t s);
+void launch_gp_leafward(const GpArgs& a, int first, int count, hipStream_t s);   // a level of `order`
+void launch_gp_leaves(const GpArgs& a, hipStream_t s);                           // the entries into leaves
+void launch_gp_finalize(const GpArgs& a, hipStream_t s);
+// scatter of the sums: what the calls hand out (any pointer may be nullptr)
+void launch_gp_outputs(const GpArgs& a, double* per_gpcsp, double* log_marginal, double* ll_deriv, double* g, double* h,
+                       double* s_out, hipStream_t s);
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
 // the first, gradient_mfma_kernel, was retired in round 6): all categories of a group of four
 // per instruction; they also write the log-likelihood partial sums, so no separate logL pass is

@@ -1717,6 +1717,29 @@ class Engine:
                                                   q.shape[0], _ptr(q), C.byref(o), C.byref(h)))
         return VariationalFit(self, h, pid, mp, o)
 
+    def gp_create(self, parent_ids, branch_lengths=None, params=None, rescaling_threshold=None):
+        """Generalized pruning over the subsplit DAG of the rooted topologies parent_ids [T][2n-2]
+        (mi_engine_gp_create).  branch_lengths [T][2n-1]: a hot start (the mean
+        over the trees that hold an entry), else 0.1 everywhere; params: the one model parameter
+        row; rescaling_threshold None: the default 2^-256.  Returns a GeneralizedPruning."""
+        pid = _np(parent_ids, np.int32)
+        if pid.ndim == 1:
+            pid = pid[None, :]
+        if pid.ndim != 2 or pid.shape[1] < 4 or pid.shape[1] % 2:
+            raise RuntimeError("gp_create: parent_ids must be [T][2n-2]")
+        n = pid.shape[1] // 2 + 1
+        bl = None
+        if branch_lengths is not None:
+            bl = _np(branch_lengths, np.float64).reshape(-1, 2 * n - 1)
+            if bl.shape[0] != pid.shape[0]:
+                raise RuntimeError("gp_create: branch_lengths must be [T][2n-1]")
+        mp = None if params is None or self.param_count == 0 else _np(params, np.float64).reshape(self.param_count)
+        h = C.c_void_p()
+        self._check(self._lib.mi_engine_gp_create(self._h, pid.shape[0], n, _ptr(pid), _ptr(bl), _ptr(mp),
+                                                  0.0 if rescaling_threshold is None else float(rescaling_threshold),
+                                                  C.byref(h)))
+        return GeneralizedPruning(self, h)
+
     def check_status(self, stream=None):
         self._check(self._lib.mi_engine_check_status(self._h, stream))
 
@@ -1895,6 +1918,176 @@ class VariationalFit:
         f = ll + draw.log_prior - lqt - draw.log_q
         top = np.max(f)
         return float(np.mean(f)), float(top + np.log(np.sum(np.exp(f - top))) - np.log(K))
+
+
+@dataclass
+class GpStructure:
+    """GeneralizedPruning.structure(): the subsplit DAG (include/mi_phylo.h, mi_gp_structure)."""
+    taxon_count: int
+    node_count: int
+    rootsplit_count: int
+    entry_count: int          # G
+    pattern_count: int
+    entries: np.ndarray       # [G][3] parent node, clade, child node; a rootsplit: (-1, -1, its node)
+    block_range: np.ndarray   # [node_count][2][2] begin, end
+    clades: np.ndarray        # [node_count][2][W] uint32 bitsets
+    levels: np.ndarray        # [node_count] clade sizes
+    topology_count: float
+
+
+@dataclass
+class GpLikelihoods:
+    per_gpcsp_log_likelihood: np.ndarray   # [G]
+    log_marginal: float
+    pattern_log_marginal: np.ndarray = None  # [P] log M_p
+    matrix: np.ndarray = None                # [G][P] log l_e per pattern
+
+
+@dataclass
+class GpBranchDerivatives:
+    log_likelihood: np.ndarray   # [G] sum_p w_p log l_e
+    derivative: np.ndarray       # [G] sum_p w_p l'_e / l_e
+    gradient: np.ndarray         # [G] of log_marginal
+    hessian: np.ndarray          # [G] its diagonal Hessian
+    gsq: np.ndarray              # [G] S_e
+
+
+@dataclass
+class GpOptimizeResult:
+    branch_lengths: np.ndarray   # [G] the last accepted point
+    trace: np.ndarray            # the accepted log_marginal after each evaluation
+    evaluations: int
+    status: int                  # MI_BRANCH_OPT_*: 0 converged, 1 iteration limit, 2 stalled
+
+
+class GeneralizedPruning:
+    """Generalized pruning over a subsplit DAG (mi_gp, include/mi_phylo.h), made by
+    Engine.gp_create.  The engine must outlive it."""
+
+    def __init__(self, engine, handle):
+        self.engine, self._h, self._lib = engine, handle, engine._lib
+        sizes = np.zeros(8, np.int32)
+        self._check(self._lib.mi_gp_sizes(self._h, sizes.ctypes.data_as(_capi.I32P)))
+        (self.taxon_count, self.node_count, self.rootsplit_count, self.entry_count, self.pattern_count,
+         self._words, self.level_count, self.tile_width) = (int(x) for x in sizes)
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RuntimeError(_capi.last_error())
+
+    def close(self):
+        if self._h is not None:
+            if self.engine._h is not None:
+                self._lib.mi_gp_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def structure(self):
+        G, nodes = self.entry_count, self.node_count
+        entries, block = np.empty((G, 3), np.int32), np.empty((nodes, 2, 2), np.int32)
+        clades, levels = np.empty((nodes, 2, self._words), np.uint32), np.empty(nodes, np.int32)
+        count = C.c_double()
+        self._check(self._lib.mi_gp_structure(self._h, _ptr(entries), _ptr(block), _ptr(clades), _ptr(levels),
+                                              C.byref(count)))
+        return GpStructure(self.taxon_count, nodes, self.rootsplit_count, G, self.pattern_count, entries, block,
+                           clades, levels, count.value)
+
+    def strings(self):
+        """The entries' names as GPInstance::PrettyIndexer gives them (mi_gp_strings)."""
+        need = C.c_int64()
+        self._check(self._lib.mi_gp_strings(self._h, None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        self._check(self._lib.mi_gp_strings(self._h, buf, need.value, None))
+        return buf.value.decode().split("\n")
+
+    def set_branch_lengths(self, branch_lengths):
+        b = _np(branch_lengths, np.float64).reshape(-1)
+        self._check(self._lib.mi_gp_set_branch_lengths(self._h, _ptr(b), b.shape[0]))
+
+    def get_branch_lengths(self):
+        out = np.empty(self.entry_count)
+        self._check(self._lib.mi_gp_get_branch_lengths(self._h, _ptr(out)))
+        return out
+
+    def set_sbn_parameters(self, q):
+        q = _np(q, np.float64).reshape(-1)
+        self._check(self._lib.mi_gp_set_sbn_parameters(self._h, _ptr(q), q.shape[0]))
+
+    def get_sbn_parameters(self):
+        out = np.empty(self.entry_count)
+        self._check(self._lib.mi_gp_get_sbn_parameters(self._h, _ptr(out)))
+        return out
+
+    def node_probabilities(self, q):
+        q, out = _np(q, np.float64).reshape(-1), np.empty(self.node_count)
+        self._check(self._lib.mi_gp_node_probabilities(self._h, _ptr(q), q.shape[0], _ptr(out)))
+        return out
+
+    def inverted_probabilities(self, q):
+        q, out = _np(q, np.float64).reshape(-1), np.empty(self.entry_count)
+        self._check(self._lib.mi_gp_inverted_probabilities(self._h, _ptr(q), q.shape[0], _ptr(out)))
+        return out
+
+    def populate(self):
+        """Both sweeps (mi_gp_populate: the reference's PopulatePLVs)."""
+        self._check(self._lib.mi_gp_populate(self._h))
+
+    def populate_device(self, stream=None):
+        self._check(self._lib.mi_gp_populate_device(self._h, stream))
+
+    def likelihoods(self, matrix=False, per_pattern=False):
+        """mi_gp_likelihoods: a GpLikelihoods."""
+        G, P = self.entry_count, self.pattern_count
+        per, marg = np.empty(G), C.c_double()
+        pat = np.empty(P) if per_pattern else None
+        mat = np.empty((G, P)) if matrix else None
+        self._check(self._lib.mi_gp_likelihoods(self._h, _ptr(per), C.byref(marg), _ptr(pat), _ptr(mat)))
+        return GpLikelihoods(per, marg.value, pat, mat)
+
+    def likelihoods_device(self, stream, out_per_gpcsp, out_log_marginal):
+        """mi_gp_likelihoods_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_gp_likelihoods_device(self._h, stream, out_per_gpcsp, out_log_marginal))
+
+    def components_of_full_log_marginal(self):
+        """per_gpcsp_log_likelihood + site_count log q (GPEngine's components of the full marginal)."""
+        w = self.engine._weights
+        if w is None:
+            raise RuntimeError("components_of_full_log_marginal needs the engine's pattern weights on the host")
+        with np.errstate(divide="ignore"):
+            return self.likelihoods().per_gpcsp_log_likelihood + float(np.sum(w)) * np.log(self.get_sbn_parameters())
+
+    def branch_derivatives(self):
+        """mi_gp_branch_derivatives: a GpBranchDerivatives."""
+        G = self.entry_count
+        pair, g, h, s = np.empty((G, 2)), np.empty(G), np.empty(G), np.empty(G)
+        self._check(self._lib.mi_gp_branch_derivatives(self._h, _ptr(pair), _ptr(g), _ptr(h), _ptr(s)))
+        return GpBranchDerivatives(pair[:, 0].copy(), pair[:, 1].copy(), g, h, s)
+
+    def branch_derivatives_device(self, stream, out_ll_derivative, out_gradient, out_hessian, out_gsq):
+        self._check(self._lib.mi_gp_branch_derivatives_device(self._h, stream, out_ll_derivative, out_gradient,
+                                                              out_hessian, out_gsq))
+
+    def estimate_sbn_parameters(self):
+        """mi_gp_estimate_sbn_parameters (the reference's EstimateSBNParameters); returns the new q."""
+        out = np.empty(self.entry_count)
+        self._check(self._lib.mi_gp_estimate_sbn_parameters(self._h, _ptr(out)))
+        return out
+
+    def optimize_branch_lengths(self, tolerance=1e-6, max_iterations=100, min_length=np.exp(-13.9),
+                                max_length=np.exp(1.1), check_interval=4):
+        """Maximise log_marginal over all branch lengths (mi_gp_optimize_branch_lengths): a
+        GpOptimizeResult."""
+        o = _branch_opt_options(max_iterations, check_interval, 0, tolerance, min_length, max_length)
+        trace = np.empty(max(int(max_iterations), 1))
+        evals, status = C.c_int32(), C.c_int32()
+        self._check(self._lib.mi_gp_optimize_branch_lengths(self._h, C.byref(o), _ptr(trace), C.byref(evals),
+                                                            C.byref(status)))
+        return GpOptimizeResult(self.get_branch_lengths(), trace[:evals.value].copy(), evals.value, status.value)
 
 
 class DevicePatterns:
