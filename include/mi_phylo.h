@@ -1630,8 +1630,8 @@ int32_t mi_vi_particles(mi_vi* fit, int32_t* out_parent_ids, double* out_branch_
  * What the reference's GPInstance / GPEngine / SubsplitDAG do (src/gp_instance.*, gp_engine.*,
  * gp_dag.*, subsplit_dag.*): the likelihood marginalised over EVERY tree of the subsplit DAG of a
  * batch of rooted topologies, in two sweeps over the DAG; per entry (GPCSP) the marginal
- * restricted to the trees that use it; the SBN parameters that follow; branch lengths per entry.
- * Hybrid (quartet) marginals are not provided.
+ * restricted to the trees that use it; the SBN parameters that follow; branch lengths per entry;
+ * and the quartet hybrid marginals (mi_gp_hybrid_marginals below).
  *
  * A mi_gp is bound to a single-device 4-state engine with ONE rate category (20 states, K > 1 and
  * a handle of several shards are refused with a message; a handle of one shard serves as its one
@@ -1724,6 +1724,62 @@ int32_t mi_gp_branch_derivatives_device(mi_gp* gp, void* stream, double* out_ll_
  * q <- softmax(per_gpcsp_log_likelihood + log q), one logsumexp per block with the entries in
  * order; a block of one entry gets 1.  out_q [G] or NULL. */
 int32_t mi_gp_estimate_sbn_parameters(mi_gp* gp, double* out_q);
+/* Quartet hybrid marginals (GPInstance::CalculateHybridMarginals, GPDAG::QuartetHybridRequestOf,
+ * GPEngine::CalculateQuartetHybridLikelihoods).  A central entry e = (t,c) -> s has
+ * four lists of entries:
+ *   rootward  the entries g = (u,cu) -> t into t, rootsplit entries excluded, ascending
+ *   sister    the entries sigma of block(t, 1-c)
+ *   rotated   the entries rho of block(s, 1)
+ *   sorted    the entries o of block(s, 0)
+ * and is FULLY FORMED iff none is empty (t is no rootsplit node and s no leaf; a rootsplit entry is
+ * never central).  One summand per (g, sigma, rho, o), numbered with g outermost and o innermost;
+ * per pattern, with P transposed on the two leafward steps,
+ *   A = P(b_g)^T r(u,cu)   B = P(b_sigma) p(child_sigma)   C = P(b_e)^T (A o B)
+ *   D = P(b_rho) p(child_rho)   E = P(b_o) p(child_o)      l_p = sum_i C_i D_i E_i
+ *   summand = log(inv[g] q_sigma q_rho q_o) + sum_p w_p (log l_p - log Pr(u))
+ *   hybrid[e] = logsumexp of e's summands in that order
+ * with Pr = UnconditionalNodeProbabilities and inv = InvertedGPCSPProbabilities of the object's q,
+ * computed on the device.  An entry that is not fully formed gets -inf; a summand whose l_p is 0 at
+ * a pattern of positive weight is -inf and drops out of the logsumexp (all of them: -inf, never
+ * NaN).  The vectors' exponents are accounted for, so, unlike the reference, rescaled DAGs are
+ * served.  Sums over patterns run tile by tile as everywhere in mi_gp; no float atomics.
+ *
+ * mi_gp_hybrid_requests (host tables, any pointer may be NULL): out_requests [G][3] = (formed,
+ * first summand, summand count) per entry; out_summand_entries [S][4] = the entries (g, sigma, rho,
+ * o) of every summand in summand order (written on demand from the lists: the object keeps nothing
+ * of size S before mi_gp_reserve_hybrid); *out_summand_count = S.
+ * mi_gp_reserve_hybrid allocates what the kernels need beyond the object's vectors: per entry the
+ * evolved vectors P(b_e) p(child_e) and P(b_e)^T r(t,c), the partial sums [S][tiles] and the
+ * summands [S]; counted by mi_device_bytes_held, refused when over MI_PHYLO_PLV_BYTES.
+ * Limits.  S grows with the product of four list lengths.  A DAG whose requests have more than
+ * 2^28 summands in all is still created and serves every other call, at no cost that grows with
+ * S, but mi_gp_hybrid_requests, mi_gp_reserve_hybrid, both forms of mi_gp_hybrid_marginals and
+ * mi_gp_estimate_sbn_parameters_hybrid refuse it with a message; so does mi_gp_reserve_hybrid a
+ * DAG of more than 65535 entries (the kernels take an entry per workgroup row).
+ * mi_gp_hybrid_request_count is host code that needs no engine and no device: the number of fully
+ * formed requests and S of the DAG that mi_engine_gp_create would build from the batch, refused
+ * with the same message when S exceeds max_summands (0: 2^28; at most 2^28).
+ * Concurrency.  A hybrid call recomputes Pr and inv from the q on the device each time (q may have
+ * been written there since, and the device form may not look) and, like populate, writes scratch
+ * that belongs to the object: calls of ONE object must not run concurrently on different streams.
+ * mi_gp_hybrid_marginals_device only enqueues (device pointers out_hybrid [G], out_summands [S] or
+ * NULL); it reads the vectors and matrices of the LAST populate and is refused before
+ * mi_gp_reserve_hybrid.  mi_gp_hybrid_marginals is the host form: it reserves on first use,
+ * populates first when b or q changed since (after mi_gp_optimize_branch_lengths too), synchronises.
+ * mi_engine_last_call_path: "gp_hybrid formed=<formed entries> summands=<S> tiles=<tiles> z=<z>"
+ * (z: over how many workgroups the summand kernel deals a request's (rootward, sister) pairs;
+ * MI_PHYLO_GP_HYBRID_Z; no result depends on it). */
+int32_t mi_gp_hybrid_requests(const mi_gp* gp, int32_t* out_requests, int32_t* out_summand_entries,
+                              int32_t* out_summand_count);
+int32_t mi_gp_hybrid_request_count(int32_t tree_count, int32_t taxon_count, const int32_t* parent_ids /* [T][2n-2] */,
+                                   int64_t max_summands, int32_t* out_formed, int64_t* out_summand_count);
+int32_t mi_gp_reserve_hybrid(mi_gp* gp);
+int32_t mi_gp_hybrid_marginals(mi_gp* gp, double* out_hybrid, double* out_summands);
+int32_t mi_gp_hybrid_marginals_device(mi_gp* gp, void* stream, double* out_hybrid, double* out_summands);
+/* mi_gp_estimate_sbn_parameters with the reference's rule for hybrid marginals
+ * (UpdateSBNProbabilities): a block whose entries ALL have a finite hybrid marginal takes
+ * q <- softmax(hybrid + log q); any other block, and the rootsplits always, the per-entry form. */
+int32_t mi_gp_estimate_sbn_parameters_hybrid(mi_gp* gp, double* out_q);
 /* Maximise log_marginal over all of b at once with the rule of
  * mi_engine_optimize_branch_lengths_unrooted (accept / halve alpha, Newton step on c = -H or S,
  * step limits, projected-gradient criterion): the DAG takes the part of one tree of G - R branches,

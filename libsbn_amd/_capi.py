@@ -266,6 +266,12 @@ SYMBOLS = {
     "mi_gp_branch_derivatives": (C.c_int32, [_V, _V, _V, _V, _V]),
     "mi_gp_branch_derivatives_device": (C.c_int32, [_V, _V, _V, _V, _V, _V]),
     "mi_gp_estimate_sbn_parameters": (C.c_int32, [_V, _V]),
+    "mi_gp_hybrid_requests": (C.c_int32, [_V, _V, _V, I32P]),
+    "mi_gp_hybrid_request_count": (C.c_int32, [C.c_int32, C.c_int32, _V, C.c_int64, I32P, C.POINTER(C.c_int64)]),
+    "mi_gp_reserve_hybrid": (C.c_int32, [_V]),
+    "mi_gp_hybrid_marginals": (C.c_int32, [_V, _V, _V]),
+    "mi_gp_hybrid_marginals_device": (C.c_int32, [_V, _V, _V, _V]),
+    "mi_gp_estimate_sbn_parameters_hybrid": (C.c_int32, [_V, _V]),
     "mi_gp_optimize_branch_lengths":
         (C.c_int32, [_V, C.POINTER(BranchOptOptions), _V, I32P, I32P]),
     "mi_consensus_tree":

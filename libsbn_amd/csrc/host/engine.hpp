@@ -200,6 +200,15 @@ struct GpOptimizeResult {
   std::vector<double> branch_lengths_, trace_;
   int32_t evaluations_ = 0, status_ = 0;
 };
+struct GpHybridRequests {
+  std::vector<int32_t> requests_;  // [G][3] formed, first summand, summand count
+  std::vector<int32_t> summands_;  // [S][4] the entries (rootward, sister, rotated, sorted) of every summand
+  size_t SummandCount() const { return summands_.size() / 4; }
+};
+struct GpHybridResult {
+  std::vector<double> hybrid_;    // [G]
+  std::vector<double> summands_;  // [S]
+};
 class GeneralizedPruning {
  public:
   GeneralizedPruning() = default;
@@ -254,9 +263,31 @@ class GeneralizedPruning {
                                  out.gsq_.data()));
     return out;
   }
-  std::vector<double> EstimateSbnParameters() const {
+  // hybrid: a block whose entries all have a finite hybrid marginal takes softmax(hybrid + log q)
+  std::vector<double> EstimateSbnParameters(const bool hybrid = false) const {
     std::vector<double> out(EntryCount());
-    Try(mi_gp_estimate_sbn_parameters(handle_, out.data()));
+    Try(hybrid ? mi_gp_estimate_sbn_parameters_hybrid(handle_, out.data())
+               : mi_gp_estimate_sbn_parameters(handle_, out.data()));
+    return out;
+  }
+  // the quartet hybrid request of every entry (mi_gp_hybrid_requests)
+  GpHybridRequests HybridRequests() const {
+    GpHybridRequests out;
+    int32_t count = 0;
+    Try(mi_gp_hybrid_requests(handle_, nullptr, nullptr, &count));
+    out.requests_.resize(3 * EntryCount());
+    out.summands_.resize(4 * static_cast<size_t>(count));
+    Try(mi_gp_hybrid_requests(handle_, out.requests_.data(), out.summands_.data(), nullptr));
+    return out;
+  }
+  // hybrid [G] (-inf where the request is not fully formed) and every summand [S]
+  GpHybridResult HybridMarginals() const {
+    GpHybridResult out;
+    int32_t count = 0;
+    Try(mi_gp_hybrid_requests(handle_, nullptr, nullptr, &count));
+    out.hybrid_.resize(EntryCount());
+    out.summands_.resize(static_cast<size_t>(count));
+    Try(mi_gp_hybrid_marginals(handle_, out.hybrid_.data(), out.summands_.data()));
     return out;
   }
   // options nullptr: tolerance 1e-6, 100 iterations, lengths in [e^-13.9, e^1.1]

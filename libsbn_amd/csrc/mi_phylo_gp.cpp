@@ -17,6 +17,11 @@ namespace {
 constexpr double kGpDefaultLength = 0.1;        // the reference's default_branch_length_
 constexpr double kGpDefaultThreshold = 0x1p-256;
 constexpr int kGpMaxIterations = 1000;          // (the step kernel's counter array)
+// The summand kernel deals an entry's (rootward, sister) pairs over blockIdx.z: as many as the widest entry has,
+// at most this (MI_PHYLO_GP_HYBRID_Z sets another number)
+constexpr int kGpHybridMaxZ = 16;
+// The summands of all requests of one DAG, at most (they are indexed by int32 together with the pattern tiles)
+constexpr int64_t kGpHybridMaxSummands = (int64_t)1 << 28;
 
 // The DAG on the host.  Node ids: leaves 0..n-1, then the subsplits by first occurrence.  Clade 0
 // of a subsplit is the one that holds its lowest taxon (the reference's "sorted" side: the larger
@@ -192,6 +197,76 @@ int build_dag(int n, int T, const int32_t* parent_ids, const double* bl, GpDag& 
   return 0;
 }
 
+// The quartet hybrid requests (GPDAG::QuartetHybridRequestOf).  The central entry e = (t,c) -> s
+// has four lists: rootward, the entries into t with the rootsplits skipped (a range of in_edges); sister,
+// block(t,1-c); rotated, block(s,1); sorted, block(s,0).  It is fully formed iff none is empty.  Its summands are
+// numbered from `first` with the rootward index outermost, then sister, rotated, and sorted innermost.
+// A DAG whose requests have more than `cap` summands in all (kGpHybridMaxSummands unless a caller gives another)
+// gets no request tables: too_large, nothing marked formed, F = S = 0, and every hybrid call refuses; whatever
+// else the object does is untouched by it.  Nothing here grows with S.
+struct HybridTables {
+  int F = 0, S = 0, Z = 1, widest = 0;  // formed entries, summands, gridDim.z, the largest summand count of an entry
+  bool too_large = false;
+  int64_t cap = 0;
+  std::vector<int32_t> desc;       // [G][kGpHybridDesc]
+  std::vector<int32_t> formed;     // [F]
+  std::vector<int32_t> levels;     // [levels][2]
+};
+
+void build_hybrid_tables(const GpDag& d, int64_t cap, HybridTables& h) {
+  h = HybridTables{};
+  h.cap = cap;
+  h.desc.assign((size_t)d.G * kGpHybridDesc, 0);
+  for (const auto& l : d.levels) h.levels.insert(h.levels.end(), {l.first, l.second});
+  // the lists and every request's summand count first: nothing is marked formed unless the total is under the cap
+  std::vector<int64_t> counts(d.G, 0);
+  int64_t total = 0;
+  for (int e = d.R; e < d.G; e++) {
+    const int t = d.edge[3 * e], c = d.edge[3 * e + 1], s = d.edge[3 * e + 2];
+    int32_t* row = &h.desc[(size_t)e * kGpHybridDesc];
+    int gb = d.in_range[2 * t];
+    const int ge = d.in_range[2 * t + 1];
+    while (gb < ge && d.in_edges[gb] < d.R) gb++;
+    row[4] = gb;
+    row[5] = ge;
+    const int32_t* lists[3] = {&d.block_range[(t * 2 + (1 - c)) * 2], &d.block_range[(s * 2 + 1) * 2],
+                               &d.block_range[(s * 2 + 0) * 2]};
+    int64_t count = ge - gb;
+    for (int k = 0; k < 3; k++) {
+      row[6 + 2 * k] = lists[k][0];
+      row[7 + 2 * k] = lists[k][1];
+      count = std::min(count * (lists[k][1] - lists[k][0]), cap + 1);  // (saturated: four factors of up to G each)
+    }
+    counts[e] = count;
+    total = std::min(total + count, cap + 1);
+  }
+  if (total > cap) {
+    h.too_large = true;
+    return;
+  }
+  int pairs = 1;
+  total = 0;
+  for (int e = d.R; e < d.G; e++) {
+    if (counts[e] == 0) continue;
+    int32_t* row = &h.desc[(size_t)e * kGpHybridDesc];
+    row[0] = 1;
+    row[1] = (int32_t)total;
+    row[2] = (int32_t)counts[e];
+    total += counts[e];
+    pairs = std::max(pairs, (row[5] - row[4]) * (row[7] - row[6]));
+    h.widest = std::max(h.widest, row[2]);
+    h.formed.push_back(e);
+  }
+  h.F = (int)h.formed.size();
+  h.S = (int)total;
+  h.Z = std::min(pairs, kGpHybridMaxZ);
+}
+
+int refuse_too_large(const HybridTables& t) {
+  return fail("generalized pruning: this DAG's hybrid requests have more than " + std::to_string(t.cap) +
+              " summands in all; hybrid marginals are not served for it");
+}
+
 // SubsplitDAG::BuildUniformOnTopologicalSupportPrior
 std::vector<double> uniform_prior(const GpDag& d) {
   std::vector<double> q(d.G, 1.0);
@@ -239,6 +314,14 @@ struct mi_gp {
   double *start = nullptr, *trial = nullptr, *tr_ll = nullptr, *tr_g = nullptr, *tr_h = nullptr, *tr_s = nullptr,
          *k_g = nullptr, *k_h = nullptr, *k_s = nullptr, *alpha = nullptr, *ll = nullptr, *trace = nullptr;
   int32_t *evals = nullptr, *status = nullptr, *active = nullptr;
+  // hybrid marginals: the request tables and their device copies (made at creation), the outputs
+  // of the host form, and what mi_gp_reserve_hybrid allocates: the evolve arrays and the partial sums
+  HybridTables ht;
+  int32_t *d_hdesc = nullptr, *d_hformed = nullptr, *d_hlevels = nullptr;
+  double *o_hybrid = nullptr, *o_summands = nullptr;  // (o_summands [S]: part of the reservation)
+  Buffer hybrid;
+  bool hybrid_reserved = false;
+  GpHybridArgs h{};
 };
 
 namespace {
@@ -301,6 +384,10 @@ size_t cut(mi_gp* g, char* base) {
   c.take(g->evals, 1);
   c.take(g->status, 1);
   c.take(g->active, (size_t)kGpMaxIterations);
+  c.take(g->d_hdesc, G * kGpHybridDesc);
+  c.take(g->d_hformed, g->ht.formed.size());
+  c.take(g->d_hlevels, g->ht.levels.size());
+  c.take(g->o_hybrid, G);
   return c.at;
 }
 
@@ -386,6 +473,7 @@ int32_t mi_engine_gp_create(mi_engine* e, int32_t T, int32_t n, const int32_t* p
   auto make = [&]() -> int {
     if (build_dag(n, T, parent_ids, branch_lengths, g->d, b)) return 1;
     const GpDag& d = g->d;
+    build_hybrid_tables(d, kGpHybridMaxSummands, g->ht);
     // (a launch takes a level's nodes, or the leaves, in its second grid dimension)
     size_t widest = (size_t)n;
     for (const auto& l : d.levels) widest = std::max(widest, (size_t)l.second);
@@ -408,7 +496,10 @@ int32_t mi_engine_gp_create(mi_engine* e, int32_t T, int32_t n, const int32_t* p
         upload(g->d_block, d.block_range.data(), sizeof(int32_t) * d.block_range.size()) ||
         upload(g->d_in_range, d.in_range.data(), sizeof(int32_t) * d.in_range.size()) ||
         upload(g->d_in_edges, d.in_edges.data(), sizeof(int32_t) * d.in_edges.size()) ||
-        upload(g->d_order, d.order.data(), sizeof(int32_t) * d.order.size()))
+        upload(g->d_order, d.order.data(), sizeof(int32_t) * d.order.size()) ||
+        upload(g->d_hdesc, g->ht.desc.data(), sizeof(int32_t) * g->ht.desc.size()) ||
+        upload(g->d_hformed, g->ht.formed.data(), sizeof(int32_t) * g->ht.formed.size()) ||
+        upload(g->d_hlevels, g->ht.levels.data(), sizeof(int32_t) * g->ht.levels.size()))
       return 1;
     // the model instance, by the set-up every other call uses (no trees in this launch), and the tip codes
     hipStream_t s = e->stream;
@@ -625,17 +716,21 @@ int32_t mi_gp_branch_derivatives(mi_gp* g, double* out_ll_derivative, double* ou
 
 // GPEngine / GPInstance::EstimateSBNParameters: populate, likelihoods, then per block and for the rootsplits
 // q <- softmax(per_gpcsp_log_likelihood + log q); a block of one entry gets 1.  One logsumexp per block, in order.
-int32_t mi_gp_estimate_sbn_parameters(mi_gp* g, double* out_q) {
-  if (!g) return fail("null object");
+// With hybrid [G] (UpdateSBNProbabilities' other branch): a block whose entries all have a finite hybrid marginal
+// takes softmax(hybrid + log q) instead; the rootsplits never do.
+static int estimate_sbn(mi_gp* g, const double* hybrid, double* out_q) {
   const GpDag& d = g->d;
   std::vector<double> ll(d.G), q(d.G);
   if (mi_gp_likelihoods(g, ll.data(), nullptr, nullptr, nullptr)) return 1;
   if (download(q.data(), g->q, sizeof(double) * d.G)) return 1;
-  auto block = [&](int begin, int end) {
+  auto block = [&](int begin, int end, bool may_be_hybrid) {
     if (end - begin == 1) {
       q[begin] = 1.0;
       return;
     }
+    bool use = may_be_hybrid && hybrid;
+    for (int i = begin; use && i < end; i++) use = std::isfinite(hybrid[i]);
+    if (use) std::copy(hybrid + begin, hybrid + end, ll.begin() + begin);
     double m = -INFINITY;
     for (int i = begin; i < end; i++) {
       ll[i] += std::log(q[i]);
@@ -646,14 +741,143 @@ int32_t mi_gp_estimate_sbn_parameters(mi_gp* g, double* out_q) {
     const double lse = m + std::log(sum);
     for (int i = begin; i < end; i++) q[i] = std::exp(ll[i] - lse);
   };
-  block(0, d.R);
+  block(0, d.R, false);
   for (int v = d.n; v < d.nodes; v++)
-    for (int c = 0; c < 2; c++) block(d.block_range[(v * 2 + c) * 2], d.block_range[(v * 2 + c) * 2 + 1]);
+    for (int c = 0; c < 2; c++) block(d.block_range[(v * 2 + c) * 2], d.block_range[(v * 2 + c) * 2 + 1], true);
   for (double x : q)
     if (!(x >= 0.0)) return fail("generalized pruning: the SBN estimate is not finite (a likelihood of zero?)");
   g->stale = true;
   if (upload(g->q, q.data(), sizeof(double) * d.G)) return 1;
   if (out_q) std::copy(q.begin(), q.end(), out_q);
+  return 0;
+}
+int32_t mi_gp_estimate_sbn_parameters(mi_gp* g, double* out_q) {
+  if (!g) return fail("null object");
+  return estimate_sbn(g, nullptr, out_q);
+}
+int32_t mi_gp_estimate_sbn_parameters_hybrid(mi_gp* g, double* out_q) {
+  if (!g) return fail("null object");
+  std::vector<double> hybrid(g->d.G);
+  if (mi_gp_hybrid_marginals(g, hybrid.data(), nullptr)) return 1;
+  return estimate_sbn(g, hybrid.data(), out_q);
+}
+
+// ---- quartet hybrid marginals ----
+int32_t mi_gp_hybrid_requests(const mi_gp* g, int32_t* out_requests, int32_t* out_summand_entries,
+                              int32_t* out_summand_count) {
+  if (!g) return fail("null object");
+  const HybridTables& t = g->ht;
+  if (t.too_large) return refuse_too_large(t);
+  for (int e = 0; e < g->d.G; e++) {
+    const int32_t* row = &t.desc[(size_t)e * kGpHybridDesc];
+    // (formed, first summand, summand count: a row's first three words)
+    if (out_requests) std::copy(row, row + 3, out_requests + 3 * (size_t)e);
+    if (!out_summand_entries || !row[0]) continue;
+    int32_t* out = out_summand_entries + 4 * (size_t)row[1];  // (written on demand: the object keeps no [S][4] table)
+    for (int ig = row[4]; ig < row[5]; ig++)
+      for (int a = row[6]; a < row[7]; a++)
+        for (int b = row[8]; b < row[9]; b++)
+          for (int o = row[10]; o < row[11]; o++, out += 4) {
+            out[0] = g->d.in_edges[ig];
+            out[1] = a;
+            out[2] = b;
+            out[3] = o;
+          }
+  }
+  if (out_summand_count) *out_summand_count = t.S;
+  return 0;
+}
+
+// Host code only, no engine and no device: the DAG of the batch and its requests, counted.
+int32_t mi_gp_hybrid_request_count(int32_t T, int32_t n, const int32_t* parent_ids, int64_t max_summands,
+                                   int32_t* out_formed, int64_t* out_summands) {
+  if (n < 3) return fail("generalized pruning needs at least 3 taxa");
+  if (T < 1) return fail("tree_count must be positive");
+  if (!parent_ids) return fail("null tree arrays");
+  if (max_summands < 0 || max_summands > kGpHybridMaxSummands)
+    return fail("generalized pruning: max_summands must be in [0, 2^28] (0: 2^28, the library's limit)");
+  GpDag d;
+  std::vector<double> b;
+  if (build_dag(n, T, parent_ids, nullptr, d, b)) return 1;
+  HybridTables t;
+  build_hybrid_tables(d, max_summands ? max_summands : kGpHybridMaxSummands, t);
+  if (t.too_large) return refuse_too_large(t);
+  if (out_formed) *out_formed = t.F;
+  if (out_summands) *out_summands = t.S;
+  return 0;
+}
+
+int32_t mi_gp_reserve_hybrid(mi_gp* g) {
+  if (!g) return fail("null object");
+  if (g->hybrid_reserved) return 0;
+  const HybridTables& t = g->ht;
+  if (t.too_large) return refuse_too_large(t);
+  const size_t G = g->d.G, Pp = g->Pp, nodes = g->d.nodes;
+  if (G > 65535) return fail("generalized pruning: hybrid marginals take at most 65535 entries");
+  GpHybridArgs& h = g->h;
+  auto lay = [&](char* base, size_t& evolve, size_t& partial) {
+    Cutter c{base};
+    c.take(h.z, G * 4 * Pp);
+    c.take(h.a, G * 4 * Pp);
+    c.take(h.ez, G * Pp);
+    c.take(h.ea, G * Pp);
+    evolve = c.at;
+    c.take(h.partial, (size_t)t.S * g->tiles);
+    c.take(h.summ, (size_t)t.S);
+    c.take(g->o_summands, (size_t)t.S);
+    partial = c.at - evolve;
+    c.take(h.pr, nodes);
+    c.take(h.log_pr, nodes);
+    c.take(h.inv, G);
+    return c.at;
+  };
+  size_t evolve = 0, partial = 0;
+  const size_t bytes = lay(nullptr, evolve, partial);
+  if (evolve + partial > g->e->plv_budget)
+    return fail("generalized pruning: hybrid marginals need " + std::to_string(evolve) + " bytes of evolved vectors and " +
+                std::to_string(partial) + " bytes of partial sums and summands (" + std::to_string(t.S) +
+                " summands), over the budget of " + std::to_string(g->e->plv_budget) + " bytes (MI_PHYLO_PLV_BYTES)");
+  HIP_TRY(hipSetDevice(g->e->spec.device));
+  if (g->hybrid.ensure(bytes)) return 1;
+  HIP_TRY(hipMemset(g->hybrid.ptr, 0, bytes));
+  lay(g->hybrid.as<char>(), evolve, partial);
+  h.L = (int)g->d.levels.size();
+  h.F = t.F;
+  h.S = t.S;
+  h.Z = g->e->sw.gp_hybrid_z > 0 ? g->e->sw.gp_hybrid_z : t.Z;
+  h.level_range = g->d_hlevels;
+  h.desc = g->d_hdesc;
+  h.formed = g->d_hformed;
+  h.widest = t.widest;
+  g->hybrid_reserved = true;
+  return 0;
+}
+
+int32_t mi_gp_hybrid_marginals_device(mi_gp* g, void* stream, double* out_hybrid, double* out_summands) {
+  if (!g) return fail("null object");
+  if (!out_hybrid) return fail("null output pointer");
+  if (!g->hybrid_reserved)
+    return fail("generalized pruning: mi_gp_hybrid_marginals_device before mi_gp_reserve_hybrid (the device form allocates nothing)");
+  HIP_TRY(hipSetDevice(g->e->spec.device));
+  launch_gp_hybrid(g->a, g->h, out_hybrid, out_summands, pick_stream(g->e, stream));
+  HIP_TRY(hipGetLastError());
+  mi_engine* e = g->e;
+  e->dominant = "gp_hybrid_summand_kernel";
+  e->last_path = "gp_hybrid formed=" + std::to_string(g->ht.F) + " summands=" + std::to_string(g->ht.S) +
+                 " tiles=" + std::to_string(g->tiles) + " z=" + std::to_string(g->h.Z);
+  return 0;
+}
+
+int32_t mi_gp_hybrid_marginals(mi_gp* g, double* out_hybrid, double* out_summands) {
+  if (!g) return fail("null object");
+  HIP_TRY(hipSetDevice(g->e->spec.device));
+  if (mi_gp_reserve_hybrid(g)) return 1;
+  if (fresh(g)) return 1;
+  if (mi_gp_hybrid_marginals_device(g, nullptr, g->o_hybrid, out_summands ? g->o_summands : nullptr)) return 1;
+  HIP_TRY(hipStreamSynchronize(g->e->stream));
+  if (download(out_hybrid, g->o_hybrid, sizeof(double) * g->d.G) ||
+      download(out_summands, g->o_summands, sizeof(double) * g->ht.S))
+    return 1;
   return 0;
 }
 

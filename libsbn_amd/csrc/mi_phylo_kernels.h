@@ -843,6 +843,25 @@ void launch_gp_finalize(const GpArgs& a, hipStream_t s);
 // scatter of the sums: what the calls hand out (any pointer may be nullptr)
 void launch_gp_outputs(const GpArgs& a, double* per_gpcsp, double* log_marginal, double* ll_deriv, double* g, double* h,
                        double* s_out, hipStream_t s);
+// kernels_gp_hybrid.hip: quartet hybrid marginals over the last populate's vectors.
+// desc, per entry: formed | first summand | summands | 0 | then (begin, end) of the rootward list
+// (into in_edges, rootsplits skipped) and of the sister, rotated and sorted blocks (entries).
+constexpr int kGpHybridDesc = 12;
+struct GpHybridArgs {
+  int L, F, S, Z;                        // levels, formed entries, summands, gridDim.z of the summand kernel
+  int widest;                            // the largest summand count of one entry
+  const int32_t* level_range;            // [L][2] first, count into GpArgs::order, ascending level
+  const int32_t* desc;                   // [G][kGpHybridDesc]
+  const int32_t* formed;                 // [F] the formed entries, ascending
+  double *pr, *log_pr;                   // [nodes] Pr(node) and its log
+  double* inv;                           // [G] Pr(t) q_e / Pr(s)
+  double *z, *a;                         // [G][4][Pp] P(b_e) p(child_e); P(b_e)^T r(t,c) (internal children)
+  int32_t *ez, *ea;                      // [G][Pp] their exponents
+  double* partial;                       // [S][tiles]
+  double* summ;                          // [S]
+};
+// node probabilities, evolve pass, summands, finalize: hybrid [G], summands [S] or nullptr
+void launch_gp_hybrid(const GpArgs& a, const GpHybridArgs& h, double* out_hybrid, double* out_summands, hipStream_t s);
 // The matrix-core gradient walks (kernels_walk.hip: second generation, kernels_walk3.hip: third;
 // the first, gradient_mfma_kernel, was retired in round 6): all categories of a group of four
 // per instruction; they also write the log-likelihood partial sums, so no separate logL pass is

@@ -43,6 +43,7 @@ struct Switches {
   int split_hash_bits = 32;  // SPLIT_HASH_BITS: bits of the hash that choose the first slot (testing: 0 sends every split to slot 0)
   // subsplit Bayesian networks
   int sbn_trees_per_wave = 16;  // SBN_TREES_PER_WAVE: trees (lanes at work) per wave of the per-tree kernels, 16 | 32 | 64
+  int gp_hybrid_z = 0;         // GP_HYBRID_Z: gridDim.z of the hybrid summand kernel (0: by the widest request, at most 16)
   // 20-state kernels
   bool aa_jacobi_seq = false;        // AA_JACOBI=seq
   bool aa_post_wave = false;         // AA_POST=wave

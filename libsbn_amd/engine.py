@@ -1953,11 +1953,40 @@ class GpBranchDerivatives:
 
 
 @dataclass
+class GpHybridRequests:
+    formed: np.ndarray          # [G] bool: all four lists of the entry's request are non-empty
+    first_summand: np.ndarray   # [G]
+    summand_count: np.ndarray   # [G]
+    summands: np.ndarray        # [S][4] the entries (rootward, sister, rotated, sorted) of every summand
+
+
+@dataclass
+class GpHybridMarginals:
+    hybrid: np.ndarray     # [G]
+    summands: np.ndarray   # [S]
+
+
+@dataclass
 class GpOptimizeResult:
     branch_lengths: np.ndarray   # [G] the last accepted point
     trace: np.ndarray            # the accepted log_marginal after each evaluation
     evaluations: int
     status: int                  # MI_BRANCH_OPT_*: 0 converged, 1 iteration limit, 2 stalled
+
+
+def gp_hybrid_request_count(parent_ids, max_summands=0):
+    """(fully formed quartet hybrid requests, summands S) of the subsplit DAG that Engine.gp_create
+    would build from rooted topologies parent_ids [T][2n-2] (mi_gp_hybrid_request_count).  Host
+    arithmetic only, no engine.  Raises when S exceeds max_summands (0: the library's limit, 2^28,
+    above which an object serves no hybrid call)."""
+    pid = _np(parent_ids, np.int32)
+    if pid.ndim != 2 or pid.shape[1] % 2:
+        raise RuntimeError("gp_hybrid_request_count: parent_ids must be [T][2n-2]")
+    formed, count = C.c_int32(), C.c_int64()
+    if _capi.load().mi_gp_hybrid_request_count(pid.shape[0], pid.shape[1] // 2 + 1, _ptr(pid), int(max_summands),
+                                               C.byref(formed), C.byref(count)):
+        raise RuntimeError(_capi.last_error())
+    return formed.value, count.value
 
 
 class GeneralizedPruning:
@@ -2072,11 +2101,44 @@ class GeneralizedPruning:
         self._check(self._lib.mi_gp_branch_derivatives_device(self._h, stream, out_ll_derivative, out_gradient,
                                                               out_hessian, out_gsq))
 
-    def estimate_sbn_parameters(self):
-        """mi_gp_estimate_sbn_parameters (the reference's EstimateSBNParameters); returns the new q."""
+    def estimate_sbn_parameters(self, hybrid=False):
+        """mi_gp_estimate_sbn_parameters (the reference's EstimateSBNParameters); returns the new q.
+        hybrid: mi_gp_estimate_sbn_parameters_hybrid, where a block whose entries all have a finite
+        hybrid marginal takes softmax(hybrid + log q)."""
         out = np.empty(self.entry_count)
-        self._check(self._lib.mi_gp_estimate_sbn_parameters(self._h, _ptr(out)))
+        call = self._lib.mi_gp_estimate_sbn_parameters_hybrid if hybrid else self._lib.mi_gp_estimate_sbn_parameters
+        self._check(call(self._h, _ptr(out)))
         return out
+
+    def hybrid_requests(self):
+        """mi_gp_hybrid_requests: a GpHybridRequests (the quartet hybrid request of every entry)."""
+        G, count = self.entry_count, C.c_int32()
+        self._check(self._lib.mi_gp_hybrid_requests(self._h, None, None, C.byref(count)))
+        req, summands = np.empty((G, 3), np.int32), np.empty((count.value, 4), np.int32)
+        self._check(self._lib.mi_gp_hybrid_requests(self._h, _ptr(req), _ptr(summands), None))
+        return GpHybridRequests(req[:, 0].astype(bool), req[:, 1].copy(), req[:, 2].copy(), summands)
+
+    def reserve_hybrid(self):
+        """mi_gp_reserve_hybrid: allocate what hybrid_marginals_device needs."""
+        self._check(self._lib.mi_gp_reserve_hybrid(self._h))
+
+    def hybrid_marginals(self, summands=False):
+        """mi_gp_hybrid_marginals: hybrid [G] (-inf where the request is not fully formed); with
+        summands=True a GpHybridMarginals that also holds every summand [S]."""
+        out = np.empty(self.entry_count)
+        if not summands:
+            self._check(self._lib.mi_gp_hybrid_marginals(self._h, _ptr(out), None))
+            return out
+        count = C.c_int32()
+        self._check(self._lib.mi_gp_hybrid_requests(self._h, None, None, C.byref(count)))
+        each = np.empty(count.value)
+        self._check(self._lib.mi_gp_hybrid_marginals(self._h, _ptr(out), _ptr(each)))
+        return GpHybridMarginals(out, each)
+
+    def hybrid_marginals_device(self, stream, out_hybrid, out_summands=None):
+        """mi_gp_hybrid_marginals_device: device pointers, enqueued on `stream`; reads the last
+        populate; needs reserve_hybrid() first."""
+        self._check(self._lib.mi_gp_hybrid_marginals_device(self._h, stream, out_hybrid, out_summands))
 
     def optimize_branch_lengths(self, tolerance=1e-6, max_iterations=100, min_length=np.exp(-13.9),
                                 max_length=np.exp(1.1), check_interval=4):
