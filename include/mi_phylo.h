@@ -1791,6 +1791,132 @@ int32_t mi_gp_estimate_sbn_parameters_hybrid(mi_gp* gp, double* out_q);
 int32_t mi_gp_optimize_branch_lengths(mi_gp* gp, const mi_branch_opt_options* options, double* out_trace,
                                       int32_t* out_evaluations, int32_t* out_status);
 
+/* ---- trees of the subsplit DAG: index, log q, training, sampling, enumeration ----
+ *
+ * With its q a mi_gp is a ROOTED subsplit Bayesian network (the reference's RootedSBNInstance and
+ * the tree side of GPInstance: TrainSimpleAverage, GenerateCompleteRootedTreeCollection,
+ * CurrentlyLoadedTreesWithGPBranchLengths).  A rooted tree is in the form mi_engine_gp_create
+ * takes: parent_ids [2n-2], leaves 0..n-1, every parent id above its children's, the root 2n-2,
+ * with the same checks; a refused tree is named in the engine's status word (a host form returns
+ * the error; mi_engine_check_status reports it after a device form), its entries are G and its
+ * nodes -1.  A tree the library BUILDS (sampled or enumerated) is numbered by one rule -- leaves
+ * 0..n-1 by taxon, internal nodes in post-order, children ordered by largest leaf id, the root
+ * 2n-2 --, under which a topology has exactly one id vector.
+ *
+ * mi_engine_gp_create_dag makes a DAG-ONLY object on ANY engine (4 or 20 states, any number of
+ * rate categories; a handle of several shards serves with its first shard): the same DAG,
+ * numbering, initial q and b as mi_engine_gp_create, and no model, tip codes or vectors.  The
+ * structure, string, b / q, probability and hybrid-request table calls and every call of this
+ * section serve it; populate, likelihoods, branch_derivatives, estimate_sbn_parameters, the hybrid
+ * marginals and optimize_branch_lengths refuse it with a message that says so.
+ *
+ * mi_gp_reserve_trees uploads what the tree calls read -- the clade words, a table from subsplit
+ * to node (open addressing, keyed by a hash of the two clades' W words; a candidate is CONFIRMED by
+ * comparing the clade words, so identification is exact), the rootsplit entry of every node and,
+ * as uint64 saturated at 2^62, the number of topologies below every node -- and allocates the
+ * workspace and staging for tree_capacity trees, counted by mi_device_bytes_held and refused with
+ * the sizes in the message when over MI_PHYLO_PLV_BYTES (a batch is not chunked).  After it the
+ * *_device forms of at most tree_capacity trees allocate nothing, synchronise nothing and can be
+ * captured in a hipGraph; before it, or with more trees, they are refused.  Reserving MORE
+ * reallocates: re-capture.  The host forms reserve on first use.  Calls of one object must not
+ * run concurrently on different streams.  Device forms take device pointers.
+ *
+ * mi_gp_tree_index: out_nodes [T][2n-1] (or NULL) the DAG node of every tree node (a leaf: its
+ * taxon; a subsplit the DAG does not hold: -1); out_entries [T][2n-1]: for v < 2n-2 the entry
+ * (node(parent v), clade, node(v)), found by bisection of the block (parent, clade), which is
+ * sorted by child node; for v = 2n-2 the rootsplit entry of the root's node.  Whatever is not in
+ * the DAG is the sentinel G: an unknown node at either end, a pair missing from its block, a root
+ * that is no rootsplit.
+ * mi_engine_last_call_path: "gp_trees n=<n> T=<T> store=lds|global" (a lane per tree; the tree's
+ * node words are in LDS while at least 8 trees' fit into 64 KiB, else in the workspace;
+ * MI_PHYLO_GP_TREES_STORE=global, read when the engine is created, keeps them in the workspace at
+ * every size: same bits).
+ *
+ * mi_gp_tree_log_prob: out_log_q[t] = sum over v = 0 .. 2n-2 ascending, one accumulator, of
+ * log q[entries[t][v]] at the object's q (taken as given).  A sentinel (anything outside [0, G))
+ * or a zero parameter gives -inf, never NaN.
+ * mi_gp_tree_branch_lengths (TreesWithGPBranchLengthsOfTopologies): b[entries[t][v]] per node,
+ * missing_length at a sentinel, 0 at the root.
+ *
+ * mi_gp_train_simple_average (the rooted TrainSimpleAverage; host pointers): per entry the sum of
+ * the weights (NULL: 1 each; finite, not negative) of the trees that use it, in ascending tree
+ * order (a stable sort by entry; the head of a run adds its run); then q = count / (the sum over
+ * the rootsplits, or over the entry's block, in entry order); a block whose total is 0 gets zeros.
+ * A tree with a sentinel is an error that names the tree, and q stays as it was.  The result is
+ * set as the object's q and copied to out_q [G] (or NULL).
+ *
+ * mi_gp_sample_trees: K rooted trees drawn from q.  cdf[j] = sum_{i <= j} q_i per block and over
+ * the rootsplits, ascending, one accumulator (out_cdf [G] or NULL); a negative, NaN or infinite q
+ * is refused.  Philox4x32-10 keyed and countered exactly as mi_engine_sbn_sample states: draw i of
+ * sample t = first_sample + k has key seed and counter (i, 0, t lo, t hi), u = (the first two
+ * output words as one 64-bit number >> 11) 2^-53, and picks the smallest j with
+ * cdf[j] > u cdf[e-1] (if there is none, the smallest j with cdf[j] == cdf[e-1]).  Draw 0 picks
+ * the rootsplit; at a node clade 0's block is drawn, then that child's subtree is descended depth
+ * first, then clade 1's block; every visited block takes one draw, blocks of one entry included.
+ * A visited block with total 0 is an error that names the sample (its position k in the call, as
+ * mi_engine_sbn_sample does, not first_sample + k) and the block; that sample's integer outputs
+ * are -1, its log q and lengths NaN.  out_parent_ids [K][2n-2] by the numbering
+ * rule; out_entries [K][2n-1] and out_log_q [K] are bit for bit what mi_gp_tree_index and
+ * mi_gp_tree_log_prob give for the tree; out_branch_lengths [K][2n-1] (or NULL) what
+ * mi_gp_tree_branch_lengths gives.  A sample's bits depend on (seed, t) alone.
+ *
+ * mi_gp_enumerate_trees: trees first .. first + count - 1 of the DAG by unranking in uint64 (the
+ * order of tests/gp_ref.py: enumerate_trees): the rootsplits in entry order by the running sum of
+ * the counts below them; at a node clade 0 is the slow digit and clade 1 the fast one; inside a
+ * clade the entries in order by the running sum of the counts below their children, the remainder
+ * passing down to the child.  Same outputs as the sampler (one tree-building kernel body, two ways
+ * to pick an entry).  Refused, before anything is reserved: first + count beyond the topology
+ * count, or a DAG of 2^62 topologies or more.  Sampling serves a DAG of any size.
+ * mi_gp_topology_count: *out_count = SubsplitDAG::TopologyCount as an integer, saturated at 2^62
+ * (mi_gp_structure gives it as a double).  Host arithmetic on the DAG, done once per object; it
+ * reserves and uploads nothing.
+ *
+ * mi_engine_deroot_trees (any engine, any n >= 3): Node::Deroot as mi_engine_sbn_sample words it.
+ * The trifurcation goes to the root child that holds taxon n-1 unless that child is a leaf, then to
+ * the other one; the remaining root child y becomes its third child; ids are renumbered in the
+ * unrooted convention (leaves, post-order, children by largest leaf id, root 2n-3).
+ * out_parent_ids [T][2n-3]; out_root_edge [T] the new id of y; with branch_lengths [T][2n-1],
+ * out_branch_lengths [T][2n-2] (or NULL): every edge's length under its new id, the two root
+ * edges' lengths added onto out_root_edge, 0 in the root's slot.  mi_engine_reserve_deroot
+ * allocates the device form's workspace. */
+int32_t mi_engine_gp_create_dag(mi_engine* engine, int32_t tree_count, int32_t taxon_count,
+                                const int32_t* parent_ids /* [T][2n-2] */,
+                                const double* branch_lengths /* [T][2n-1] or NULL */, mi_gp** out_gp);
+int32_t mi_gp_reserve_trees(mi_gp* gp, int32_t tree_capacity);
+int32_t mi_gp_topology_count(mi_gp* gp, uint64_t* out_count);
+int32_t mi_gp_tree_index(mi_gp* gp, int32_t tree_count, const int32_t* parent_ids, int32_t* out_entries,
+                         int32_t* out_nodes);
+int32_t mi_gp_tree_index_device(mi_gp* gp, void* stream, int32_t tree_count, const int32_t* parent_ids,
+                                int32_t* out_entries, int32_t* out_nodes);
+int32_t mi_gp_tree_log_prob(mi_gp* gp, int32_t tree_count, const int32_t* entries, double* out_log_q);
+int32_t mi_gp_tree_log_prob_device(mi_gp* gp, void* stream, int32_t tree_count, const int32_t* entries,
+                                   double* out_log_q);
+int32_t mi_gp_tree_branch_lengths(mi_gp* gp, int32_t tree_count, const int32_t* entries, double missing_length,
+                                  double* out_branch_lengths);
+int32_t mi_gp_tree_branch_lengths_device(mi_gp* gp, void* stream, int32_t tree_count, const int32_t* entries,
+                                         double missing_length, double* out_branch_lengths);
+int32_t mi_gp_train_simple_average(mi_gp* gp, int32_t tree_count, const int32_t* entries,
+                                   const double* tree_weights /* [T] or NULL */, double* out_q);
+int32_t mi_gp_sample_trees(mi_gp* gp, int32_t sample_count, uint64_t seed, int64_t first_sample,
+                           int32_t* out_parent_ids, int32_t* out_entries, double* out_log_q,
+                           double* out_branch_lengths, double* out_cdf);
+int32_t mi_gp_sample_trees_device(mi_gp* gp, void* stream, int32_t sample_count, uint64_t seed, int64_t first_sample,
+                                  int32_t* out_parent_ids, int32_t* out_entries, double* out_log_q,
+                                  double* out_branch_lengths, double* out_cdf);
+int32_t mi_gp_enumerate_trees(mi_gp* gp, int64_t first, int32_t count, int32_t* out_parent_ids, int32_t* out_entries,
+                              double* out_log_q, double* out_branch_lengths);
+int32_t mi_gp_enumerate_trees_device(mi_gp* gp, void* stream, int64_t first, int32_t count, int32_t* out_parent_ids,
+                                     int32_t* out_entries, double* out_log_q, double* out_branch_lengths);
+int32_t mi_engine_reserve_deroot(mi_engine* engine, int32_t tree_count, int32_t taxon_count);
+int32_t mi_engine_deroot_trees(mi_engine* engine, int32_t tree_count, int32_t taxon_count,
+                               const int32_t* parent_ids /* [T][2n-2] */,
+                               const double* branch_lengths /* [T][2n-1] or NULL */,
+                               int32_t* out_parent_ids /* [T][2n-3] */,
+                               double* out_branch_lengths /* [T][2n-2] or NULL */, int32_t* out_root_edge /* [T] */);
+int32_t mi_engine_deroot_trees_device(mi_engine* engine, void* stream, int32_t tree_count, int32_t taxon_count,
+                                      const int32_t* parent_ids, const double* branch_lengths,
+                                      int32_t* out_parent_ids, double* out_branch_lengths, int32_t* out_root_edge);
+
 /* Synchronise `stream` and report the first per-tree error since the last check (the status
  * word is sticky and cleared when an error is reported: calls themselves never clear it). */
 int32_t mi_engine_check_status(mi_engine* engine, void* stream);

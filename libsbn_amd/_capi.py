@@ -274,6 +274,23 @@ SYMBOLS = {
     "mi_gp_estimate_sbn_parameters_hybrid": (C.c_int32, [_V, _V]),
     "mi_gp_optimize_branch_lengths":
         (C.c_int32, [_V, C.POINTER(BranchOptOptions), _V, I32P, I32P]),
+    "mi_engine_gp_create_dag": (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, C.POINTER(_V)]),
+    "mi_gp_reserve_trees": (C.c_int32, [_V, C.c_int32]),
+    "mi_gp_topology_count": (C.c_int32, [_V, C.POINTER(C.c_uint64)]),
+    "mi_gp_tree_index": (C.c_int32, [_V, C.c_int32, _V, _V, _V]),
+    "mi_gp_tree_index_device": (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V]),
+    "mi_gp_tree_log_prob": (C.c_int32, [_V, C.c_int32, _V, _V]),
+    "mi_gp_tree_log_prob_device": (C.c_int32, [_V, _V, C.c_int32, _V, _V]),
+    "mi_gp_tree_branch_lengths": (C.c_int32, [_V, C.c_int32, _V, C.c_double, _V]),
+    "mi_gp_tree_branch_lengths_device": (C.c_int32, [_V, _V, C.c_int32, _V, C.c_double, _V]),
+    "mi_gp_train_simple_average": (C.c_int32, [_V, C.c_int32, _V, _V, _V]),
+    "mi_gp_sample_trees": (C.c_int32, [_V, C.c_int32, C.c_uint64, C.c_int64, _V, _V, _V, _V, _V]),
+    "mi_gp_sample_trees_device": (C.c_int32, [_V, _V, C.c_int32, C.c_uint64, C.c_int64, _V, _V, _V, _V, _V]),
+    "mi_gp_enumerate_trees": (C.c_int32, [_V, C.c_int64, C.c_int32, _V, _V, _V, _V]),
+    "mi_gp_enumerate_trees_device": (C.c_int32, [_V, _V, C.c_int64, C.c_int32, _V, _V, _V, _V]),
+    "mi_engine_reserve_deroot": (C.c_int32, [_V, C.c_int32, C.c_int32]),
+    "mi_engine_deroot_trees": (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),
+    "mi_engine_deroot_trees_device": (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),
     "mi_consensus_tree":
         (C.c_int32, [C.c_int32, C.c_int32, _V, _V, C.c_double, C.c_double, I32P, _V, _V]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),

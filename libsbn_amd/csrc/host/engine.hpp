@@ -209,6 +209,21 @@ struct GpHybridResult {
   std::vector<double> hybrid_;    // [G]
   std::vector<double> summands_;  // [S]
 };
+// the tree side
+struct GpTreeIndexResult {
+  std::vector<int32_t> entries_, nodes_;  // [T][2n-1] each; G and -1 mark what the DAG does not hold
+};
+struct GpTreesResult {  // sampled or enumerated rooted trees
+  std::vector<int32_t> parent_ids_;     // [K][2n-2]
+  std::vector<int32_t> entries_;        // [K][2n-1]
+  std::vector<double> log_q_;           // [K]
+  std::vector<double> branch_lengths_;  // [K][2n-1] the GP lengths, 0 at the root
+};
+struct DerootedTrees {
+  std::vector<int32_t> parent_ids_;     // [T][2n-3]
+  std::vector<double> branch_lengths_;  // [T][2n-2], empty without input lengths
+  std::vector<int32_t> root_edge_;      // [T]
+};
 class GeneralizedPruning {
  public:
   GeneralizedPruning() = default;
@@ -290,6 +305,63 @@ class GeneralizedPruning {
     Try(mi_gp_hybrid_marginals(handle_, out.hybrid_.data(), out.summands_.data()));
     return out;
   }
+  // ---- trees of the DAG (include/mi_phylo.h) ----
+  size_t NodesPerTree() const { return 2 * static_cast<size_t>(Sizes()[0]) - 1; }
+  void ReserveTrees(const size_t tree_capacity) const {
+    Try(mi_gp_reserve_trees(handle_, static_cast<int32_t>(tree_capacity)));
+  }
+  uint64_t TopologyCount() const {
+    uint64_t out = 0;
+    Try(mi_gp_topology_count(handle_, &out));
+    return out;
+  }
+  // rooted trees parent_ids [T][2n-2]: per tree node its entry and its DAG node
+  GpTreeIndexResult TreeIndex(const size_t tree_count, const std::vector<int32_t>& parent_ids) const {
+    const size_t N = NodesPerTree();
+    if (parent_ids.size() != tree_count * (N - 1)) Failwith("TreeIndex: parent_ids is [trees][2n-2].");
+    GpTreeIndexResult out;
+    out.entries_.resize(tree_count * N);
+    out.nodes_.resize(tree_count * N);
+    Try(mi_gp_tree_index(handle_, static_cast<int32_t>(tree_count), parent_ids.data(), out.entries_.data(), out.nodes_.data()));
+    return out;
+  }
+  // log q [T] of indexed trees, entries [T][2n-1]
+  std::vector<double> TreeLogProb(const std::vector<int32_t>& entries) const {
+    const size_t T = entries.size() / NodesPerTree();
+    std::vector<double> out(T);
+    Try(mi_gp_tree_log_prob(handle_, static_cast<int32_t>(T), entries.data(), out.data()));
+    return out;
+  }
+  std::vector<double> TreeBranchLengths(const std::vector<int32_t>& entries, const double missing_length = 0.0) const {
+    const size_t T = entries.size() / NodesPerTree();
+    std::vector<double> out(entries.size());
+    Try(mi_gp_tree_branch_lengths(handle_, static_cast<int32_t>(T), entries.data(), missing_length, out.data()));
+    return out;
+  }
+  // the rooted TrainSimpleAverage: sets and returns q [G]; tree_weights [T] or empty (1 each)
+  std::vector<double> TrainSimpleAverage(const std::vector<int32_t>& entries, const std::vector<double>& tree_weights = {}) const {
+    const size_t T = entries.size() / NodesPerTree();
+    if (!tree_weights.empty() && tree_weights.size() != T) Failwith("TrainSimpleAverage: tree_weights is [trees] or empty.");
+    std::vector<double> out(EntryCount());
+    Try(mi_gp_train_simple_average(handle_, static_cast<int32_t>(T), entries.data(),
+                                   tree_weights.empty() ? nullptr : tree_weights.data(), out.data()));
+    return out;
+  }
+  // K rooted trees drawn from q: sample k is the Philox stream (seed, first_sample + k)
+  GpTreesResult SampleTrees(const size_t sample_count, const uint64_t seed, const int64_t first_sample = 0) const {
+    GpTreesResult out = Built(sample_count);
+    Try(mi_gp_sample_trees(handle_, static_cast<int32_t>(sample_count), seed, first_sample, out.parent_ids_.data(),
+                           out.entries_.data(), out.log_q_.data(), out.branch_lengths_.data(), nullptr));
+    return out;
+  }
+  // trees first .. first + count - 1 of the DAG
+  GpTreesResult EnumerateTrees(const int64_t first, const size_t count) const {
+    GpTreesResult out = Built(count);
+    Try(mi_gp_enumerate_trees(handle_, first, static_cast<int32_t>(count), out.parent_ids_.data(), out.entries_.data(),
+                              out.log_q_.data(), out.branch_lengths_.data()));
+    return out;
+  }
+
   // options nullptr: tolerance 1e-6, 100 iterations, lengths in [e^-13.9, e^1.1]
   GpOptimizeResult OptimizeBranchLengths(const mi_branch_opt_options* options = nullptr) const {
     GpOptimizeResult out;
@@ -303,6 +375,15 @@ class GeneralizedPruning {
  private:
   static void Try(const int32_t rc) {
     if (rc != 0) Failwith(mi_last_error());
+  }
+  GpTreesResult Built(const size_t count) const {
+    const size_t N = NodesPerTree();
+    GpTreesResult out;
+    out.parent_ids_.resize(count * (N - 1));
+    out.entries_.resize(count * N);
+    out.log_q_.resize(count);
+    out.branch_lengths_.resize(count * N);
+    return out;
   }
   mi_gp* handle_ = nullptr;
 };
@@ -1060,6 +1141,36 @@ class Engine {
                               parent_ids.data(), branch_lengths.empty() ? nullptr : branch_lengths.data(),
                               model_param_row.empty() ? nullptr : model_param_row.data(), rescaling_threshold, &handle));
     return GeneralizedPruning(handle);
+  }
+
+  // A DAG-only GeneralizedPruning on any engine (mi_engine_gp_create_dag): the DAG, numbering, initial
+  // q and b of GpCreate, no vectors; it serves the structure, b / q and tree calls.
+  GeneralizedPruning GpCreateDag(const size_t tree_count, const std::vector<int32_t>& parent_ids,
+                                 const std::vector<double>& branch_lengths = {}) const {
+    if (parent_ids.size() != tree_count * (2 * taxon_count_ - 2) ||
+        (!branch_lengths.empty() && branch_lengths.size() != tree_count * (2 * taxon_count_ - 1)))
+      Failwith("GpCreateDag: parent_ids is [trees][2n-2] on the engine's taxa, branch_lengths [trees][2n-1] or empty.");
+    mi_gp* handle = nullptr;
+    Check(mi_engine_gp_create_dag(handle_, static_cast<int32_t>(tree_count), static_cast<int32_t>(taxon_count_),
+                                  parent_ids.data(), branch_lengths.empty() ? nullptr : branch_lengths.data(), &handle));
+    return GeneralizedPruning(handle);
+  }
+
+  // Rooted trees parent_ids [T][2n-2] of taxon_count taxa (root 2n-2; branch_lengths [T][2n-1] or empty),
+  // de-rooted as Node::Deroot does and renumbered in the unrooted convention: mi_engine_deroot_trees.
+  DerootedTrees DerootTrees(const size_t tree_count, const size_t taxon_count, const std::vector<int32_t>& parent_ids,
+                            const std::vector<double>& branch_lengths = {}) const {
+    if (parent_ids.size() != tree_count * (2 * taxon_count - 2) ||
+        (!branch_lengths.empty() && branch_lengths.size() != tree_count * (2 * taxon_count - 1)))
+      Failwith("DerootTrees: parent_ids is [trees][2n-2], branch_lengths [trees][2n-1] or empty.");
+    DerootedTrees out;
+    out.parent_ids_.resize(tree_count * (2 * taxon_count - 3));
+    out.root_edge_.resize(tree_count);
+    if (!branch_lengths.empty()) out.branch_lengths_.resize(tree_count * (2 * taxon_count - 2));
+    Check(mi_engine_deroot_trees(handle_, static_cast<int32_t>(tree_count), static_cast<int32_t>(taxon_count), parent_ids.data(),
+                                 branch_lengths.empty() ? nullptr : branch_lengths.data(), out.parent_ids_.data(),
+                                 branch_lengths.empty() ? nullptr : out.branch_lengths_.data(), out.root_edge_.data()));
+    return out;
   }
 
   // `steps` steps of a fit; their trace rows [steps][6]: mi_vi_fit.

@@ -102,6 +102,9 @@ enum StatusCode : int32_t {
   kSbnBadDescent = 20,   // (its second status word carries the sample)
   kSbnSupportSentinel = 21,
   kBranchModelBadParam = 22,  // (its second and fourth status words carry the tree and the edge)
+  kGpTreeBadParam = 23,       // (its second status word carries the entry)
+  kGpTreeEmptyBlock = 24,     // (its second and fourth status words carry the sample and 2 node + clade, -1: the rootsplits)
+  kGpTreeOutOfDag = 25,
 };
 
 }  // namespace miphylo

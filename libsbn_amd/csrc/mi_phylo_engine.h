@@ -73,6 +73,9 @@ inline const char* status_message(int code) {
     case kSbnSupportSentinel: return "SBN descent: a support tree has a rootsplit or PCSP outside the support";
     case kBranchModelBadParam:
       return "branch model: an edge's summed sigma must be finite and positive and its summed mu not NaN";
+    case kGpTreeBadParam: return "generalized pruning: SBN parameters must be finite and not negative to be sampled from";
+    case kGpTreeOutOfDag: return "generalized pruning: a training tree has a subsplit or an entry outside the DAG";
+    case kGpTreeEmptyBlock: return "generalized pruning: a sample reached a block whose parameters are all 0";
     default: return "unknown device status";
   }
 }
@@ -167,6 +170,7 @@ struct mi_engine {
   // a variational fit (mi_vi, mi_phylo_vi.cpp): set while mi_vi_step_device enqueues, so that the
   // sampler, the branch-length draw and its gradient read first_sample and beta from the fit's state
   const ViState* vi_state = nullptr;
+  Buffer deroot_ws;    // de-rooting (mi_engine_reserve_deroot): per-tree node words | staging of the host form
   Buffer rf_ws;        // a batch's sorted lists: lengths [T][2n-3] | indices [T][2n-3] | counts [T]
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)

@@ -11,36 +11,17 @@
 #include <vector>
 
 #include "mi_phylo_engine.h"
+#include "mi_phylo_gp_host.h"
 
 namespace {
 
 constexpr double kGpDefaultLength = 0.1;        // the reference's default_branch_length_
-constexpr double kGpDefaultThreshold = 0x1p-256;
 constexpr int kGpMaxIterations = 1000;          // (the step kernel's counter array)
 // The summand kernel deals an entry's (rootward, sister) pairs over blockIdx.z: as many as the widest entry has,
 // at most this (MI_PHYLO_GP_HYBRID_Z sets another number)
 constexpr int kGpHybridMaxZ = 16;
 // The summands of all requests of one DAG, at most (they are indexed by int32 together with the pattern tiles)
 constexpr int64_t kGpHybridMaxSummands = (int64_t)1 << 28;
-
-// The DAG on the host.  Node ids: leaves 0..n-1, then the subsplits by first occurrence.  Clade 0
-// of a subsplit is the one that holds its lowest taxon (the reference's "sorted" side: the larger
-// chunk of the bitset order), clade 1 the other ("rotated").
-struct GpDag {
-  int n = 0, W = 0, nodes = 0, R = 0, G = 0;
-  std::vector<uint32_t> clades;      // [nodes][2][W]; a leaf: its own bit in clade 0
-  std::vector<int32_t> level;        // [nodes] clade size
-  std::vector<int32_t> edge;         // [G][3]
-  std::vector<int32_t> block_range;  // [nodes][2][2]
-  std::vector<int32_t> in_range;     // [nodes][2]
-  std::vector<int32_t> in_edges;
-  std::vector<int32_t> order;        // internal nodes by (level, id)
-  std::vector<std::pair<int, int>> levels;  // (first, count) into order, ascending level
-  std::vector<double> below;         // [nodes] topologies below
-  double topology_count = 0.0;
-  std::map<std::tuple<int, int, int>, int> index;  // (parent, clade, child) -> entry
-  std::map<int, int> root_index;                   // root node -> entry
-};
 
 int popcount_words(const uint32_t* w, int W) {
   int c = 0;
@@ -204,15 +185,7 @@ int build_dag(int n, int T, const int32_t* parent_ids, const double* bl, GpDag& 
 // A DAG whose requests have more than `cap` summands in all (kGpHybridMaxSummands unless a caller gives another)
 // gets no request tables: too_large, nothing marked formed, F = S = 0, and every hybrid call refuses; whatever
 // else the object does is untouched by it.  Nothing here grows with S.
-struct HybridTables {
-  int F = 0, S = 0, Z = 1, widest = 0;  // formed entries, summands, gridDim.z, the largest summand count of an entry
-  bool too_large = false;
-  int64_t cap = 0;
-  std::vector<int32_t> desc;       // [G][kGpHybridDesc]
-  std::vector<int32_t> formed;     // [F]
-  std::vector<int32_t> levels;     // [levels][2]
-};
-
+// (struct HybridTables: mi_phylo_gp_host.h)
 void build_hybrid_tables(const GpDag& d, int64_t cap, HybridTables& h) {
   h = HybridTables{};
   h.cap = cap;
@@ -295,34 +268,7 @@ void node_probabilities(const GpDag& d, const double* q, double* out) {
 
 }  // namespace
 
-struct mi_gp {
-  mi_engine* e = nullptr;
-  GpDag d;
-  int P = 0, Pp = 0, tiles = 0, I = 0;
-  double threshold = kGpDefaultThreshold;
-  bool stale = true;  // the vectors are not those of the current b and q
-  Buffer pool, matrix;
-  GpArgs a{};         // the device pointers (b, q: the object's)
-  double *b = nullptr, *q = nullptr, *params = nullptr;
-  DevModel* model = nullptr;
-  uint8_t* codes = nullptr;
-  int32_t *d_edge = nullptr, *d_block = nullptr, *d_in_range = nullptr, *d_in_edges = nullptr, *d_order = nullptr;
-  // outputs of the host forms
-  double *o_gpcsp = nullptr, *o_marg = nullptr, *o_deriv = nullptr, *o_g = nullptr, *o_h = nullptr, *o_s = nullptr;
-  // the optimiser: trial point and its values, kept derivatives, counters (each G + 2 entries where the step kernel
-  // takes a tree's row)
-  double *start = nullptr, *trial = nullptr, *tr_ll = nullptr, *tr_g = nullptr, *tr_h = nullptr, *tr_s = nullptr,
-         *k_g = nullptr, *k_h = nullptr, *k_s = nullptr, *alpha = nullptr, *ll = nullptr, *trace = nullptr;
-  int32_t *evals = nullptr, *status = nullptr, *active = nullptr;
-  // hybrid marginals: the request tables and their device copies (made at creation), the outputs
-  // of the host form, and what mi_gp_reserve_hybrid allocates: the evolve arrays and the partial sums
-  HybridTables ht;
-  int32_t *d_hdesc = nullptr, *d_hformed = nullptr, *d_hlevels = nullptr;
-  double *o_hybrid = nullptr, *o_summands = nullptr;  // (o_summands [S]: part of the reservation)
-  Buffer hybrid;
-  bool hybrid_reserved = false;
-  GpHybridArgs h{};
-};
+// (struct mi_gp: mi_phylo_gp_host.h)
 
 namespace {
 
@@ -340,9 +286,6 @@ size_t cut(mi_gp* g, char* base) {
   const size_t G = g->d.G, I = g->I, Pp = g->Pp, nodes = g->d.nodes, n = g->d.n;
   GpArgs& a = g->a;
   Cutter c{base};
-  c.take(g->model, 1);
-  c.take(g->params, (size_t)g->e->param_count);
-  c.take(g->codes, (size_t)distance_code_rows((int)n) * distance_code_stride(g->P));
   c.take(g->b, G + 2);
   c.take(g->q, G);
   c.take(g->d_edge, 3 * G);
@@ -350,6 +293,10 @@ size_t cut(mi_gp* g, char* base) {
   c.take(g->d_in_range, 2 * nodes);
   c.take(g->d_in_edges, G);
   c.take(g->d_order, I);
+  if (g->dag_only) return c.at;  // (no model, no codes, no vectors, no outputs: DESIGN.md 4.27)
+  c.take(g->model, 1);
+  c.take(g->params, (size_t)g->e->param_count);
+  c.take(g->codes, (size_t)distance_code_rows((int)n) * distance_code_stride(g->P));
   c.take(a.mats, 16 * G);
   c.take(a.expl, 8 * G);
   c.take(a.phat, I * 2 * 4 * Pp);
@@ -424,7 +371,15 @@ int enqueue_populate(mi_gp* g, hipStream_t s, const double* b, double* matrix) {
   return 0;
 }
 
+// a DAG-only object (mi_engine_gp_create_dag) has no vectors: whatever reads or writes them refuses it
+int refuse_dag_only(const mi_gp* g, const char* call) {
+  if (!g->dag_only) return 0;
+  return fail(std::string("generalized pruning: ") + call +
+              " needs the vectors, and this object is DAG-only (mi_engine_gp_create_dag); create it with mi_engine_gp_create");
+}
+
 int populate(mi_gp* g, hipStream_t s) {
+  if (refuse_dag_only(g, "populate")) return 1;
   HIP_TRY(hipSetDevice(g->e->spec.device));
   if (enqueue_populate(g, s, g->b, nullptr)) return 1;
   g->stale = false;
@@ -447,27 +402,32 @@ int check_vector(const mi_gp* g, const double* v, int32_t count, const char* wha
 
 }  // namespace
 
-extern "C" {
-
-int32_t mi_engine_gp_create(mi_engine* e, int32_t T, int32_t n, const int32_t* parent_ids, const double* branch_lengths,
-                            const double* model_params, double rescaling_threshold, mi_gp** out) {
+// mi_engine_gp_create and mi_engine_gp_create_dag: the same DAG, numbering, initial q and b; the DAG-only object
+// takes any engine, and nothing that depends on the model or the patterns is allocated or launched for it
+static int gp_create(mi_engine* e, int32_t T, int32_t n, const int32_t* parent_ids, const double* branch_lengths,
+                     const double* model_params, double rescaling_threshold, bool dag_only, mi_gp** out) {
   if (!e) return fail("null engine");
   if (!out) return fail("null output pointer");
   *out = nullptr;
-  if (e->shards.size() == 1) e = e->shards[0];  // (a handle of one shard is its one engine)
-  if (!e->shards.empty()) return fail("generalized pruning runs on a single engine, not on a sharded handle");
-  if (e->s != 4) return fail("generalized pruning is 4-state only");
-  if (e->K != 1) return fail("generalized pruning takes one rate category (this engine has " + std::to_string(e->K) + ")");
+  if (dag_only) {
+    if (!e->shards.empty()) e = e->shards[0];  // (a handle of several shards: its first)
+  } else {
+    if (e->shards.size() == 1) e = e->shards[0];  // (a handle of one shard is its one engine)
+    if (!e->shards.empty()) return fail("generalized pruning runs on a single engine, not on a sharded handle");
+    if (e->s != 4) return fail("generalized pruning is 4-state only");
+    if (e->K != 1) return fail("generalized pruning takes one rate category (this engine has " + std::to_string(e->K) + ")");
+  }
   if (n != e->n) return fail("generalized pruning: trees of " + std::to_string(n) + " taxa, the engine has " + std::to_string(e->n));
   if (n < 3) return fail("generalized pruning needs at least 3 taxa");
   if (T < 1) return fail("tree_count must be positive");
   if (!parent_ids) return fail("null tree arrays");
-  if (e->param_count > 0 && !model_params) return fail("generalized pruning: this engine's model takes parameters");
+  if (!dag_only && e->param_count > 0 && !model_params) return fail("generalized pruning: this engine's model takes parameters");
   if (rescaling_threshold == 0.0) rescaling_threshold = kGpDefaultThreshold;
   if (!(rescaling_threshold > 0x1p-500 && rescaling_threshold <= 1.0))
     return fail("generalized pruning: rescaling_threshold must be in (2^-500, 1]");
   mi_gp* g = new mi_gp;
   g->e = e;
+  g->dag_only = dag_only;
   g->threshold = rescaling_threshold;
   std::vector<double> b;
   auto make = [&]() -> int {
@@ -491,13 +451,15 @@ int32_t mi_engine_gp_create(mi_engine* e, int32_t T, int32_t n, const int32_t* p
     cut(g, g->pool.as<char>());
     b.resize((size_t)d.G + 2, 0.0);
     const std::vector<double> q = uniform_prior(d);
-    if (upload(g->params, model_params, sizeof(double) * e->param_count) || upload(g->b, b.data(), sizeof(double) * b.size()) ||
+    if ((!dag_only && upload(g->params, model_params, sizeof(double) * e->param_count)) || upload(g->b, b.data(), sizeof(double) * b.size()) ||
         upload(g->q, q.data(), sizeof(double) * q.size()) || upload(g->d_edge, d.edge.data(), sizeof(int32_t) * d.edge.size()) ||
         upload(g->d_block, d.block_range.data(), sizeof(int32_t) * d.block_range.size()) ||
         upload(g->d_in_range, d.in_range.data(), sizeof(int32_t) * d.in_range.size()) ||
         upload(g->d_in_edges, d.in_edges.data(), sizeof(int32_t) * d.in_edges.size()) ||
-        upload(g->d_order, d.order.data(), sizeof(int32_t) * d.order.size()) ||
-        upload(g->d_hdesc, g->ht.desc.data(), sizeof(int32_t) * g->ht.desc.size()) ||
+        upload(g->d_order, d.order.data(), sizeof(int32_t) * d.order.size()))
+      return 1;
+    if (dag_only) return 0;  // (everything below belongs to the vectors)
+    if (upload(g->d_hdesc, g->ht.desc.data(), sizeof(int32_t) * g->ht.desc.size()) ||
         upload(g->d_hformed, g->ht.formed.data(), sizeof(int32_t) * g->ht.formed.size()) ||
         upload(g->d_hlevels, g->ht.levels.data(), sizeof(int32_t) * g->ht.levels.size()))
       return 1;
@@ -546,6 +508,17 @@ int32_t mi_engine_gp_create(mi_engine* e, int32_t T, int32_t n, const int32_t* p
   }
   *out = g;
   return 0;
+}
+
+extern "C" {
+
+int32_t mi_engine_gp_create(mi_engine* e, int32_t T, int32_t n, const int32_t* parent_ids, const double* branch_lengths,
+                            const double* model_params, double rescaling_threshold, mi_gp** out) {
+  return gp_create(e, T, n, parent_ids, branch_lengths, model_params, rescaling_threshold, false, out);
+}
+int32_t mi_engine_gp_create_dag(mi_engine* e, int32_t T, int32_t n, const int32_t* parent_ids, const double* branch_lengths,
+                                mi_gp** out) {
+  return gp_create(e, T, n, parent_ids, branch_lengths, nullptr, 0.0, true, out);
 }
 
 void mi_gp_destroy(mi_gp* g) {
@@ -666,6 +639,7 @@ int32_t mi_gp_populate(mi_gp* g) {
 
 int32_t mi_gp_likelihoods_device(mi_gp* g, void* stream, double* out_per_gpcsp, double* out_log_marginal) {
   if (!g) return fail("null object");
+  if (refuse_dag_only(g, "likelihoods")) return 1;
   HIP_TRY(hipSetDevice(g->e->spec.device));
   launch_gp_outputs(g->a, out_per_gpcsp, out_log_marginal, nullptr, nullptr, nullptr, nullptr, pick_stream(g->e, stream));
   HIP_TRY(hipGetLastError());
@@ -673,6 +647,7 @@ int32_t mi_gp_likelihoods_device(mi_gp* g, void* stream, double* out_per_gpcsp, 
 }
 int32_t mi_gp_likelihoods(mi_gp* g, double* out_per_gpcsp, double* out_log_marginal, double* out_pattern, double* out_matrix) {
   if (!g) return fail("null object");
+  if (refuse_dag_only(g, "likelihoods")) return 1;
   mi_engine* e = g->e;
   HIP_TRY(hipSetDevice(e->spec.device));
   const size_t G = g->d.G, P = g->P;
@@ -695,6 +670,7 @@ int32_t mi_gp_likelihoods(mi_gp* g, double* out_per_gpcsp, double* out_log_margi
 int32_t mi_gp_branch_derivatives_device(mi_gp* g, void* stream, double* out_ll_derivative, double* out_gradient,
                                         double* out_hessian, double* out_gsq) {
   if (!g) return fail("null object");
+  if (refuse_dag_only(g, "branch_derivatives")) return 1;
   HIP_TRY(hipSetDevice(g->e->spec.device));
   launch_gp_outputs(g->a, nullptr, nullptr, out_ll_derivative, out_gradient, out_hessian, out_gsq, pick_stream(g->e, stream));
   HIP_TRY(hipGetLastError());
@@ -703,6 +679,7 @@ int32_t mi_gp_branch_derivatives_device(mi_gp* g, void* stream, double* out_ll_d
 int32_t mi_gp_branch_derivatives(mi_gp* g, double* out_ll_derivative, double* out_gradient, double* out_hessian,
                                  double* out_gsq) {
   if (!g) return fail("null object");
+  if (refuse_dag_only(g, "branch_derivatives")) return 1;
   HIP_TRY(hipSetDevice(g->e->spec.device));
   if (fresh(g)) return 1;
   if (mi_gp_branch_derivatives_device(g, nullptr, g->o_deriv, g->o_g, g->o_h, g->o_s)) return 1;
@@ -753,10 +730,12 @@ static int estimate_sbn(mi_gp* g, const double* hybrid, double* out_q) {
 }
 int32_t mi_gp_estimate_sbn_parameters(mi_gp* g, double* out_q) {
   if (!g) return fail("null object");
+  if (refuse_dag_only(g, "estimate_sbn_parameters")) return 1;
   return estimate_sbn(g, nullptr, out_q);
 }
 int32_t mi_gp_estimate_sbn_parameters_hybrid(mi_gp* g, double* out_q) {
   if (!g) return fail("null object");
+  if (refuse_dag_only(g, "estimate_sbn_parameters_hybrid")) return 1;
   std::vector<double> hybrid(g->d.G);
   if (mi_gp_hybrid_marginals(g, hybrid.data(), nullptr)) return 1;
   return estimate_sbn(g, hybrid.data(), out_q);
@@ -809,6 +788,7 @@ int32_t mi_gp_hybrid_request_count(int32_t T, int32_t n, const int32_t* parent_i
 
 int32_t mi_gp_reserve_hybrid(mi_gp* g) {
   if (!g) return fail("null object");
+  if (refuse_dag_only(g, "reserve_hybrid")) return 1;
   if (g->hybrid_reserved) return 0;
   const HybridTables& t = g->ht;
   if (t.too_large) return refuse_too_large(t);
@@ -855,6 +835,7 @@ int32_t mi_gp_reserve_hybrid(mi_gp* g) {
 
 int32_t mi_gp_hybrid_marginals_device(mi_gp* g, void* stream, double* out_hybrid, double* out_summands) {
   if (!g) return fail("null object");
+  if (refuse_dag_only(g, "hybrid_marginals")) return 1;
   if (!out_hybrid) return fail("null output pointer");
   if (!g->hybrid_reserved)
     return fail("generalized pruning: mi_gp_hybrid_marginals_device before mi_gp_reserve_hybrid (the device form allocates nothing)");
@@ -870,6 +851,7 @@ int32_t mi_gp_hybrid_marginals_device(mi_gp* g, void* stream, double* out_hybrid
 
 int32_t mi_gp_hybrid_marginals(mi_gp* g, double* out_hybrid, double* out_summands) {
   if (!g) return fail("null object");
+  if (refuse_dag_only(g, "hybrid_marginals")) return 1;
   HIP_TRY(hipSetDevice(g->e->spec.device));
   if (mi_gp_reserve_hybrid(g)) return 1;
   if (fresh(g)) return 1;
@@ -887,6 +869,7 @@ int32_t mi_gp_hybrid_marginals(mi_gp* g, double* out_hybrid, double* out_summand
 int32_t mi_gp_optimize_branch_lengths(mi_gp* g, const mi_branch_opt_options* options, double* out_trace,
                                       int32_t* out_evaluations, int32_t* out_status) {
   if (!g) return fail("null object");
+  if (refuse_dag_only(g, "optimize_branch_lengths")) return 1;
   if (!out_status) return fail("null output pointer");
   mi_engine* e = g->e;
   mi_branch_opt_options o = options ? *options : kBranchOptDefaults;

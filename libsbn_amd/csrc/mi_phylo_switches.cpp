@@ -96,6 +96,7 @@ bool parse_switches(Switches& out, std::string& error) {
   s.split_hash_bits = (int)r.integer("MI_PHYLO_SPLIT_HASH_BITS", 0, 32, 32);
   s.sbn_trees_per_wave = r.listed("MI_PHYLO_SBN_TREES_PER_WAVE", "16|32|64", 16);
   s.gp_hybrid_z = (int)r.integer("MI_PHYLO_GP_HYBRID_Z", 0, 65535, 0);
+  s.gp_trees_global = r.choice("MI_PHYLO_GP_TREES_STORE", "lds|global", 0) == 1;
   s.aa_jacobi_seq = r.choice("MI_PHYLO_AA_JACOBI", "wave|seq", 0) == 1;
   s.aa_post_wave = r.choice("MI_PHYLO_AA_POST", "wg|wave", 0) == 1;
   s.aa_pre_wave = r.choice("MI_PHYLO_AA_PRE", "wg|wave", 0) == 1;

@@ -44,6 +44,7 @@ struct Switches {
   // subsplit Bayesian networks
   int sbn_trees_per_wave = 16;  // SBN_TREES_PER_WAVE: trees (lanes at work) per wave of the per-tree kernels, 16 | 32 | 64
   int gp_hybrid_z = 0;         // GP_HYBRID_Z: gridDim.z of the hybrid summand kernel (0: by the widest request, at most 16)
+  bool gp_trees_global = false;  // GP_TREES_STORE=global: the per-tree kernels of the DAG's trees keep their node words in the workspace even where they fit LDS
   // 20-state kernels
   bool aa_jacobi_seq = false;        // AA_JACOBI=seq
   bool aa_post_wave = false;         // AA_POST=wave

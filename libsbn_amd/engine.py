@@ -1740,6 +1740,53 @@ class Engine:
                                                   C.byref(h)))
         return GeneralizedPruning(self, h)
 
+    def gp_create_dag(self, parent_ids, branch_lengths=None):
+        """A DAG-only GeneralizedPruning on any engine (mi_engine_gp_create_dag): the
+        DAG, numbering, initial q and b of gp_create, no vectors.  It serves the structure, b / q and
+        tree calls (index, log q, training, sampling, enumeration) and refuses whatever needs vectors."""
+        pid = _np(parent_ids, np.int32)
+        if pid.ndim == 1:
+            pid = pid[None, :]
+        if pid.ndim != 2 or pid.shape[1] < 4 or pid.shape[1] % 2:
+            raise RuntimeError("gp_create_dag: parent_ids must be [T][2n-2]")
+        n = pid.shape[1] // 2 + 1
+        bl = None
+        if branch_lengths is not None:
+            bl = _np(branch_lengths, np.float64).reshape(-1, 2 * n - 1)
+            if bl.shape[0] != pid.shape[0]:
+                raise RuntimeError("gp_create_dag: branch_lengths must be [T][2n-1]")
+        h = C.c_void_p()
+        self._check(self._lib.mi_engine_gp_create_dag(self._h, pid.shape[0], n, _ptr(pid), _ptr(bl), C.byref(h)))
+        return GeneralizedPruning(self, h)
+
+    def deroot_trees(self, parent_ids, branch_lengths=None):
+        """Rooted trees parent_ids [T][2n-2] (root 2n-2), de-rooted as Node::Deroot does and renumbered
+        in the unrooted convention (mi_engine_deroot_trees): a DerootedTrees."""
+        pid = _np(parent_ids, np.int32)
+        if pid.ndim == 1:
+            pid = pid[None, :]
+        if pid.ndim != 2 or pid.shape[1] < 4 or pid.shape[1] % 2:
+            raise RuntimeError("deroot_trees: parent_ids must be [T][2n-2]")
+        T, n = pid.shape[0], pid.shape[1] // 2 + 1
+        bl = out_bl = None
+        if branch_lengths is not None:
+            bl = _np(branch_lengths, np.float64).reshape(-1, 2 * n - 1)
+            if bl.shape[0] != T:
+                raise RuntimeError("deroot_trees: branch_lengths must be [T][2n-1]")
+            out_bl = np.empty((T, 2 * n - 2))
+        out, edge = np.empty((T, 2 * n - 3), np.int32), np.empty(T, np.int32)
+        self._check(self._lib.mi_engine_deroot_trees(self._h, T, n, _ptr(pid), _ptr(bl), _ptr(out), _ptr(out_bl), _ptr(edge)))
+        return DerootedTrees(out, out_bl, edge)
+
+    def reserve_deroot(self, tree_count, taxon_count):
+        self._check(self._lib.mi_engine_reserve_deroot(self._h, tree_count, taxon_count))
+
+    def deroot_trees_device(self, stream, T, n, parent_ids, branch_lengths, out_parent_ids, out_branch_lengths,
+                            out_root_edge):
+        """mi_engine_deroot_trees_device: device pointers, enqueued on `stream`; needs reserve_deroot."""
+        self._check(self._lib.mi_engine_deroot_trees_device(self._h, stream, T, n, parent_ids, branch_lengths,
+                                                            out_parent_ids, out_branch_lengths, out_root_edge))
+
     def check_status(self, stream=None):
         self._check(self._lib.mi_engine_check_status(self._h, stream))
 
@@ -1974,6 +2021,31 @@ class GpOptimizeResult:
     status: int                  # MI_BRANCH_OPT_*: 0 converged, 1 iteration limit, 2 stalled
 
 
+@dataclass
+class GpTreeIndex:
+    """GeneralizedPruning.tree_index(): which entries and nodes of the DAG rooted trees use."""
+    entries: np.ndarray   # [T][2n-1] per tree node the entry into it (the root: its rootsplit entry); G: not in the DAG
+    nodes: np.ndarray     # [T][2n-1] the DAG node of every tree node; -1: not in the DAG
+
+
+@dataclass
+class GpTrees:
+    """GeneralizedPruning.sample_trees() / enumerate_trees(): rooted trees built from the DAG."""
+    parent_ids: np.ndarray       # [K][2n-2] leaves by taxon, post-order, children by largest leaf, root 2n-2
+    entries: np.ndarray          # [K][2n-1] as tree_index gives them
+    log_q: np.ndarray            # [K] as tree_log_prob gives it
+    branch_lengths: np.ndarray   # [K][2n-1] the GP lengths b[entries], 0 at the root
+    cdf: np.ndarray = None       # [G] the sampler's per-block running sums of q
+
+
+@dataclass
+class DerootedTrees:
+    """Engine.deroot_trees()."""
+    parent_ids: np.ndarray       # [T][2n-3]
+    branch_lengths: np.ndarray   # [T][2n-2] or None
+    root_edge: np.ndarray        # [T] the edge that carries the rooting
+
+
 def gp_hybrid_request_count(parent_ids, max_summands=0):
     """(fully formed quartet hybrid requests, summands S) of the subsplit DAG that Engine.gp_create
     would build from rooted topologies parent_ids [T][2n-2] (mi_gp_hybrid_request_count).  Host
@@ -2139,6 +2211,110 @@ class GeneralizedPruning:
         """mi_gp_hybrid_marginals_device: device pointers, enqueued on `stream`; reads the last
         populate; needs reserve_hybrid() first."""
         self._check(self._lib.mi_gp_hybrid_marginals_device(self._h, stream, out_hybrid, out_summands))
+
+    # ---- trees of the DAG (DESIGN.md 4.27) ----
+    def _trees(self, parent_ids):
+        pid = _np(parent_ids, np.int32)
+        if pid.ndim == 1:
+            pid = pid[None, :]
+        if pid.ndim != 2 or pid.shape[1] != 2 * self.taxon_count - 2:
+            raise RuntimeError("parent_ids must be [T][2n-2]")
+        return pid
+
+    def _entries(self, entries):
+        ent = _np(entries, np.int32)
+        if ent.ndim == 1:
+            ent = ent[None, :]
+        if ent.ndim != 2 or ent.shape[1] != 2 * self.taxon_count - 1:
+            raise RuntimeError("entries must be [T][2n-1]")
+        return ent
+
+    def reserve_trees(self, tree_capacity):
+        """mi_gp_reserve_trees: upload the tree calls' tables, allocate workspace for tree_capacity trees."""
+        self._check(self._lib.mi_gp_reserve_trees(self._h, int(tree_capacity)))
+
+    def topology_count(self):
+        """The DAG's topology count as an integer, saturated at 2^62 (mi_gp_topology_count)."""
+        out = C.c_uint64()
+        self._check(self._lib.mi_gp_topology_count(self._h, C.byref(out)))
+        return out.value
+
+    def tree_index(self, parent_ids):
+        """mi_gp_tree_index: a GpTreeIndex of rooted trees parent_ids [T][2n-2]."""
+        pid = self._trees(parent_ids)
+        N = 2 * self.taxon_count - 1
+        ent, nodes = np.empty((pid.shape[0], N), np.int32), np.empty((pid.shape[0], N), np.int32)
+        self._check(self._lib.mi_gp_tree_index(self._h, pid.shape[0], _ptr(pid), _ptr(ent), _ptr(nodes)))
+        return GpTreeIndex(ent, nodes)
+
+    def tree_index_device(self, stream, T, parent_ids, out_entries, out_nodes=None):
+        self._check(self._lib.mi_gp_tree_index_device(self._h, stream, T, parent_ids, out_entries, out_nodes))
+
+    def tree_log_prob(self, entries):
+        """mi_gp_tree_log_prob: log q [T] of indexed trees at the object's q (-inf at a sentinel)."""
+        ent = self._entries(entries)
+        out = np.empty(ent.shape[0])
+        self._check(self._lib.mi_gp_tree_log_prob(self._h, ent.shape[0], _ptr(ent), _ptr(out)))
+        return out
+
+    def tree_log_prob_device(self, stream, T, entries, out_log_q):
+        self._check(self._lib.mi_gp_tree_log_prob_device(self._h, stream, T, entries, out_log_q))
+
+    def tree_branch_lengths(self, entries, missing_length=0.0):
+        """mi_gp_tree_branch_lengths: [T][2n-1] the GP lengths of indexed trees."""
+        ent = self._entries(entries)
+        out = np.empty(ent.shape, np.float64)
+        self._check(self._lib.mi_gp_tree_branch_lengths(self._h, ent.shape[0], _ptr(ent), float(missing_length), _ptr(out)))
+        return out
+
+    def tree_branch_lengths_device(self, stream, T, entries, missing_length, out_branch_lengths):
+        self._check(self._lib.mi_gp_tree_branch_lengths_device(self._h, stream, T, entries, float(missing_length),
+                                                               out_branch_lengths))
+
+    def train_simple_average(self, entries, tree_weights=None):
+        """mi_gp_train_simple_average (the rooted TrainSimpleAverage): sets and returns q [G]."""
+        ent = self._entries(entries)
+        w = None
+        if tree_weights is not None:
+            w = _np(tree_weights, np.float64).reshape(-1)
+            if w.shape[0] != ent.shape[0]:
+                raise RuntimeError("tree_weights must be [T]")
+        out = np.empty(self.entry_count)
+        self._check(self._lib.mi_gp_train_simple_average(self._h, ent.shape[0], _ptr(ent), _ptr(w), _ptr(out)))
+        return out
+
+    def _built(self, K, cdf):
+        n = self.taxon_count
+        return GpTrees(np.empty((K, 2 * n - 2), np.int32), np.empty((K, 2 * n - 1), np.int32), np.empty(K),
+                       np.empty((K, 2 * n - 1)), np.empty(self.entry_count) if cdf else None)
+
+    def sample_trees(self, sample_count, seed, first_sample=0, cdf=False):
+        """mi_gp_sample_trees: a GpTrees of sample_count rooted trees drawn from q (Philox stream
+        (seed, first_sample + k))."""
+        t = self._built(int(sample_count), cdf)
+        self._check(self._lib.mi_gp_sample_trees(self._h, int(sample_count), int(seed), int(first_sample), _ptr(t.parent_ids),
+                                                 _ptr(t.entries), _ptr(t.log_q), _ptr(t.branch_lengths), _ptr(t.cdf)))
+        return t
+
+    def sample_trees_device(self, stream, K, seed, first_sample, out_parent_ids, out_entries, out_log_q,
+                            out_branch_lengths=None, out_cdf=None):
+        self._check(self._lib.mi_gp_sample_trees_device(self._h, stream, K, int(seed), int(first_sample), out_parent_ids,
+                                                        out_entries, out_log_q, out_branch_lengths, out_cdf))
+
+    def enumerate_trees(self, first=0, count=None):
+        """mi_gp_enumerate_trees: a GpTrees of trees first .. first + count - 1 of the DAG (count None:
+        all from `first` on)."""
+        if count is None:
+            count = self.topology_count() - int(first)
+        t = self._built(int(count), False)
+        self._check(self._lib.mi_gp_enumerate_trees(self._h, int(first), int(count), _ptr(t.parent_ids), _ptr(t.entries),
+                                                    _ptr(t.log_q), _ptr(t.branch_lengths)))
+        return t
+
+    def enumerate_trees_device(self, stream, first, count, out_parent_ids, out_entries, out_log_q,
+                               out_branch_lengths=None):
+        self._check(self._lib.mi_gp_enumerate_trees_device(self._h, stream, int(first), int(count), out_parent_ids,
+                                                           out_entries, out_log_q, out_branch_lengths))
 
     def optimize_branch_lengths(self, tolerance=1e-6, max_iterations=100, min_length=np.exp(-13.9),
                                 max_length=np.exp(1.1), check_interval=4):
