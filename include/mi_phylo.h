@@ -476,6 +476,77 @@ int32_t mi_engine_pattern_mixture(mi_engine* engine, int32_t tree_count, int32_t
                                   double* out_pattern_log_marginal /* [P] */,
                                   double* out_log_marginal /* [1] */);
 
+/* Replicate weights of a (multiscale) bootstrap, drawn on the device (an extension).
+ * Any engine serves: P is an argument.  pattern_weights [P] must be non-negative integer site
+ * counts with N = sum in [1, 2^31); `sites` = n in [1, 2^33] is the number of draws per replicate
+ * (n = N: the ordinary bootstrap; another n: a scaled replicate of the AU test).  The output
+ * W [B][P] (float64) is what mi_engine_rell, mi_engine_pairwise_distances and
+ * mi_engine_starting_trees_unrooted take as replicate_weights.
+ *
+ * The definition is part of the interface and integer-exact: a row's bits depend on (seed,
+ * replicate number, n, pattern_weights) alone.  For replicate number rho = first_replicate + b,
+ * Philox4x32-10 call j = 0 .. ceil(n/2) - 1 has key (seed lo, seed hi) and counter
+ * (j, 0x72656C6C, rho lo, rho hi) -- the fixed second word keeps the stream apart from
+ * mi_engine_sbn_sample's and mi_engine_branch_model_sample's -- and yields c0..c3: draw 2j is
+ * x = c0 2^32 + c1, draw 2j+1 is x = c2 2^32 + c3 (unused when n is odd).  The site of a draw is
+ * (x N) >> 64 (the high word of the 64 x 64 product), its pattern the p with cum[p] <= site <
+ * cum[p+1], cum the exclusive integer prefix sum of the weights; W[b][p] counts the draws that
+ * landed in p (a zero-weight pattern is never drawn).  A count of 2^32 or more wraps. */
+int32_t mi_engine_bootstrap_weights(mi_engine* engine, int32_t pattern_count,
+                                    const double* pattern_weights /* [P] */, int32_t replicate_count,
+                                    int64_t sites, uint64_t seed, int64_t first_replicate,
+                                    double* out_replicate_weights /* [B][P] */);
+
+/* The KH, SH and AU tests with BP and ELW for T trees from their per-pattern log-likelihoods
+ * s [T][P] and the pattern weights w [P] (an extension; any engine serves).
+ * K blocks (1 <= K <= MI_TOPOLOGY_MAX_SCALES) of replicates[k] >= 1 replicates with sites[k] draws
+ * each: sites[0] must equal N = sum w, the sites pairwise distinct.  Block k draws its weights as
+ * mi_engine_bootstrap_weights does, replicate numbers continuing from block to block
+ * (first_replicate + sum_{j<k} replicates[j]), forms C_k = W_k s^T and counts the replicates each
+ * tree wins, counts[k][t], exactly as mi_engine_rell does; one workspace sized by the largest
+ * block serves them in turn.  L = s w through the same product.  From block 0 (B, C):
+ *   bp, elw    as mi_engine_rell gives them
+ *   t1, t2     argmax_t L and the argmax over the others, the lowest index among equals
+ *   mean[t]    (sum_b C[b][t]) / B, one accumulator, b ascending;  Z[b][t] = C[b][t] - mean[t]
+ *   p_SH[t]    #{b : max_t' Z[b][t'] - Z[b][t] >= L[t1] - L[t]} / B
+ *   p_KH[t]    #{b : Z[b][ref] - Z[b][t] >= L[ref] - L[t]} / B, ref = t1 (t != t1), t2 (t = t1);
+ *              one tree: 1
+ * AU per tree over the usable blocks (0 < counts[k][t] < replicates[k]), in block order: with
+ * r = sites[k] / N, pi = counts[k][t] / replicates[k], z = -Phi^-1(pi), omega = replicates[k]
+ * phi(z)^2 / (pi (1 - pi)), the weighted least-squares fit z ~ d sqrt(r) + c / sqrt(r);
+ * p_AU = Phi(c - d), rss = sum omega (z - d sqrt(r) - c / sqrt(r))^2; fewer than two usable
+ * blocks: p_AU = bp, d = c = rss = NaN.
+ * out_table [T][MI_TOPOLOGY_COLUMNS], per tree: L | L[t1] - L | bp | elw | p_KH | p_SH | p_AU | d |
+ * c | rss | usable blocks.  Counts are integers (integer atomics, ordered sums); no float atomics. */
+#define MI_TOPOLOGY_MAX_SCALES 64
+#define MI_TOPOLOGY_COLUMNS 11
+int32_t mi_engine_topology_tests(mi_engine* engine, int32_t tree_count, int32_t pattern_count,
+                                 const double* pattern_log_likelihoods /* [T][P] */,
+                                 const double* pattern_weights /* [P] */, int32_t block_count,
+                                 const int64_t* sites /* [K], host */, const int32_t* replicates /* [K], host */,
+                                 uint64_t seed, int64_t first_replicate,
+                                 double* out_table /* [T][MI_TOPOLOGY_COLUMNS] */,
+                                 int32_t* out_counts /* [K][T] */, double* out_mean /* [T] or NULL */,
+                                 double* out_replicate_log_likelihoods /* [B_0][T] or NULL */,
+                                 int32_t* out_best_tree /* [B_0] or NULL */);
+
+/* From trees to the table in one host call: upload, mi_engine_pattern_log_likelihoods_unrooted,
+ * mi_engine_topology_tests with the engine's own pattern weights, one download.  Support as
+ * mi_engine_rell_bootstrap_unrooted: 4-state engines; a handle of more than one shard and a
+ * pattern-sharded handle are refused; engine weights that are no integer site counts are refused. */
+int32_t mi_engine_topology_tests_unrooted(mi_engine* engine, int32_t tree_count,
+                                          const int32_t* parent_ids,     /* [T][2n-3] */
+                                          const double* branch_lengths,  /* [T][2n-2] */
+                                          const double* params, int32_t rescaling, int32_t block_count,
+                                          const int64_t* sites /* [K] */, const int32_t* replicates /* [K] */,
+                                          uint64_t seed, int64_t first_replicate,
+                                          double* out_log_likelihoods /* [T] */,
+                                          double* out_pattern_log_likelihoods /* [T][P] or NULL */,
+                                          double* out_table /* [T][MI_TOPOLOGY_COLUMNS] */,
+                                          int32_t* out_counts /* [K][T] */, double* out_mean /* [T] or NULL */,
+                                          double* out_replicate_log_likelihoods /* [B_0][T] or NULL */,
+                                          int32_t* out_best_tree /* [B_0] or NULL */);
+
 /* Starting trees from the engine's alignment (an extension; 4-state engines):
  * pairwise maximum-likelihood distances for B sets of pattern weights, neighbour joining of B
  * distance matrices, and the two in one call.  With the replicate weights of a bootstrap
@@ -1266,6 +1337,28 @@ int32_t mi_engine_pattern_mixture_device(mi_engine* engine, void* stream, int32_
                                          int32_t pattern_count, const double* pattern_log_likelihoods,
                                          const double* tree_log_weights, const double* pattern_weights,
                                          double* out_pattern_log_marginal, double* out_log_marginal);
+
+/* The device forms of mi_engine_bootstrap_weights and mi_engine_topology_tests (sites and
+ * replicates stay host arrays: they fix the launch shapes and are read while the call enqueues):
+ * they only enqueue -- no allocation and no synchronisation after
+ * mi_engine_reserve_bootstrap_weights(B, P) / mi_engine_reserve_topology_tests(T, P, max_k
+ * replicates[k]) --, and can be captured in a hipGraph.  What the host forms refuse about the
+ * weights (no integer site counts, N outside [1, 2^31), sites[0] != N) goes to the status word
+ * (mi_engine_check_status); the replicate weights of such a call are zeros. */
+int32_t mi_engine_bootstrap_weights_device(mi_engine* engine, void* stream, int32_t pattern_count,
+                                           const double* pattern_weights, int32_t replicate_count,
+                                           int64_t sites, uint64_t seed, int64_t first_replicate,
+                                           double* out_replicate_weights);
+int32_t mi_engine_reserve_bootstrap_weights(mi_engine* engine, int32_t replicate_count, int32_t pattern_count);
+int32_t mi_engine_topology_tests_device(mi_engine* engine, void* stream, int32_t tree_count,
+                                        int32_t pattern_count, const double* pattern_log_likelihoods,
+                                        const double* pattern_weights, int32_t block_count,
+                                        const int64_t* sites, const int32_t* replicates, uint64_t seed,
+                                        int64_t first_replicate, double* out_table, int32_t* out_counts,
+                                        double* out_mean, double* out_replicate_log_likelihoods,
+                                        int32_t* out_best_tree);
+int32_t mi_engine_reserve_topology_tests(mi_engine* engine, int32_t tree_count, int32_t pattern_count,
+                                         int32_t max_replicate_count);
 
 /* The device form of mi_engine_optimize_branch_lengths_unrooted.  Unlike the other *_device
  * calls it SYNCHRONISES `stream` at its check points (it reads the number of active trees to

@@ -159,6 +159,20 @@ SYMBOLS = {
     "mi_engine_reserve_rell": (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32]),
     "mi_engine_rell_bootstrap_unrooted":
         (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_bootstrap_weights":
+        (C.c_int32, [_V, C.c_int32, _V, C.c_int32, C.c_int64, C.c_uint64, C.c_int64, _V]),
+    "mi_engine_bootstrap_weights_device":
+        (C.c_int32, [_V, _V, C.c_int32, _V, C.c_int32, C.c_int64, C.c_uint64, C.c_int64, _V]),
+    "mi_engine_reserve_bootstrap_weights": (C.c_int32, [_V, C.c_int32, C.c_int32]),
+    "mi_engine_topology_tests":
+        (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, C.c_int32, _V, _V, C.c_uint64, C.c_int64, _V, _V, _V, _V, _V]),
+    "mi_engine_topology_tests_device":
+        (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, C.c_int32, _V, _V, C.c_uint64, C.c_int64, _V, _V, _V, _V,
+                     _V]),
+    "mi_engine_reserve_topology_tests": (C.c_int32, [_V, C.c_int32, C.c_int32, C.c_int32]),
+    "mi_engine_topology_tests_unrooted":
+        (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32, _V, _V, C.c_uint64, C.c_int64, _V, _V, _V, _V,
+                     _V, _V, _V]),
     "mi_engine_pattern_mixture": (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),
     "mi_engine_pattern_mixture_device":
         (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),

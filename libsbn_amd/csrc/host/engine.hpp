@@ -12,6 +12,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <map>
 #include <string>
 #include <tuple>
@@ -72,6 +73,18 @@ struct RellBootstrapResult {
   std::vector<double> log_likelihoods_, pattern_log_likelihoods_, replicate_log_likelihoods_;
   std::vector<int32_t> best_tree_;
   std::vector<double> bootstrap_proportion_, expected_likelihood_weight_;
+};
+
+// Engine::TopologyTests (an extension, include/mi_phylo.h): the trees' log-likelihoods [T] and
+// per-pattern values [T][P], the table [T][MI_TOPOLOGY_COLUMNS] (per tree: L | L[best] - L | bp |
+// elw | p_KH | p_SH | p_AU | d | c | rss | usable scales), the replicates every tree won per block
+// [K][T], the column means of block 0 [T], and the blocks' sites and replicates [K]
+struct TopologyTestsResult {
+  std::vector<double> log_likelihoods_, pattern_log_likelihoods_, table_;
+  std::vector<int32_t> counts_;
+  std::vector<double> column_mean_;
+  std::vector<int64_t> sites_;
+  std::vector<int32_t> replicates_;
 };
 
 // Engine::PairwiseDistances (an extension, include/mi_phylo.h): distances_ [B][n][n] (symmetric,
@@ -792,6 +805,53 @@ class Engine {
         static_cast<int32_t>(B), replicate_weights.data(), out.log_likelihoods_.data(),
         out.pattern_log_likelihoods_.data(), out.replicate_log_likelihoods_.data(), out.best_tree_.data(),
         out.bootstrap_proportion_.data(), out.expected_likelihood_weight_.data()));
+    return out;
+  }
+
+  // `replicates` rows of bootstrap weights drawn on the device from the engine's pattern weights,
+  // `sites` draws each (0: the ordinary bootstrap, N = sum of the weights), [replicates][P] in the
+  // layout RellBootstrap, PairwiseDistances and StartingTrees take (an extension):
+  // mi_engine_bootstrap_weights.
+  std::vector<double> BootstrapWeights(const size_t replicates, const int64_t sites, const uint64_t seed,
+                                       const int64_t first_replicate) const {
+    const std::vector<double>& w = site_pattern_.GetWeights();
+    double total = 0.;
+    for (const double x : w) total += x;
+    std::vector<double> out(replicates * w.size());
+    Check(mi_engine_bootstrap_weights(handle_, static_cast<int32_t>(w.size()), w.data(),
+                                      static_cast<int32_t>(replicates), sites > 0 ? sites : static_cast<int64_t>(total),
+                                      seed, first_replicate, out.data()));
+    return out;
+  }
+
+  // The KH, SH and AU tests of the trees with BP and ELW, from trees to the table in one call (an
+  // extension; 4-state engines, one device): mi_engine_topology_tests_unrooted.  Block k draws
+  // replicates replicates of floor(scales[k] N + 0.5) sites; scales[0] must be 1.
+  TopologyTestsResult TopologyTests(const UnrootedTreeCollection& trees, const ParamMatrix& params,
+                                    const bool rescaling,
+                                    const std::vector<double>& scales = {1.0, 0.5, 0.6, 0.7, 0.8, 0.9, 1.1, 1.2, 1.3, 1.4},
+                                    const size_t replicates = 10000, const uint64_t seed = 0,
+                                    const int64_t first_replicate = 0) const {
+    const size_t T = trees.size(), P = site_pattern_.PatternCount(), K = scales.size();
+    std::vector<int32_t> parents;
+    std::vector<double> bl;
+    Flatten(trees, params, false, &parents, &bl);
+    TopologyTestsResult out;
+    if (trees.empty()) return out;
+    double total = 0.;
+    for (const double x : site_pattern_.GetWeights()) total += x;
+    out.replicates_.assign(K, static_cast<int32_t>(replicates));
+    for (const double scale : scales) out.sites_.push_back(static_cast<int64_t>(std::floor(scale * total + 0.5)));
+    out.log_likelihoods_.resize(T);
+    out.pattern_log_likelihoods_.resize(T * P);
+    out.table_.resize(T * MI_TOPOLOGY_COLUMNS);
+    out.counts_.resize(K * T);
+    out.column_mean_.resize(T);
+    Check(mi_engine_topology_tests_unrooted(
+        handle_, static_cast<int32_t>(T), parents.data(), bl.data(), params.data.data(), rescaling,
+        static_cast<int32_t>(K), out.sites_.data(), out.replicates_.data(), seed, first_replicate,
+        out.log_likelihoods_.data(), out.pattern_log_likelihoods_.data(), out.table_.data(), out.counts_.data(),
+        out.column_mean_.data(), nullptr, nullptr));
     return out;
   }
 

@@ -105,6 +105,9 @@ enum StatusCode : int32_t {
   kGpTreeBadParam = 23,       // (its second status word carries the entry)
   kGpTreeEmptyBlock = 24,     // (its second and fourth status words carry the sample and 2 node + clade, -1: the rootsplits)
   kGpTreeOutOfDag = 25,
+  kBootBadWeight = 26,      // (its second status word carries the pattern)
+  kBootBadTotal = 27,
+  kBootSitesNotTotal = 28,
 };
 
 }  // namespace miphylo

@@ -366,6 +366,8 @@ int check_status(mi_engine* e, hipStream_t s) {
     if (st[0] == kGpTreeEmptyBlock)
       return fail(std::string(status_message(st[0])) + " (sample " + std::to_string(st[1]) +
                   (st[3] < 0 ? ", the rootsplits)" : ", block of node " + std::to_string(st[3] >> 1) + ", clade " + std::to_string(st[3] & 1) + ")"));
+    if (st[0] == kBootBadWeight) return fail(std::string(status_message(st[0])) + " (pattern " + std::to_string(st[1]) + ")");
+    if (st[0] == kBootBadTotal || st[0] == kBootSitesNotTotal) return fail(status_message(st[0]));
     if (st[0] == kSbnBadParam) return fail(std::string(status_message(st[0])) + " (parameter " + std::to_string(st[1]) + ")");
     return fail(std::string(status_message(st[0])) + (st[0] == kBadDistance ? " (matrix " : " (tree ") +
                 std::to_string(st[1] + e->status_tree_offset) + ")");

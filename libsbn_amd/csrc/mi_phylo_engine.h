@@ -9,6 +9,7 @@
 //   mi_phylo_spr.cpp          mi_spr_neighbour (no device code)
 //   mi_phylo_search.cpp       NNI and SPR moves on the device, the two hill-climbing searches
 //   mi_phylo_rell.cpp         per-pattern log-likelihoods (device form), RELL re-summation, tree mixtures
+//   mi_phylo_topology_tests.cpp  bootstrap weights drawn on the device, the KH / SH / AU tests
 //   mi_phylo_start_trees.cpp  pairwise distances, neighbour joining, starting trees (device forms, reservation)
 //   mi_phylo_splits.cpp       split tables, Robinson-Foulds distances (device and host forms, reservation), mi_consensus_tree
 //   mi_phylo_sbn.cpp          subsplit Bayesian networks: support and slots, probabilities, normalisation, training
@@ -76,6 +77,9 @@ inline const char* status_message(int code) {
     case kGpTreeBadParam: return "generalized pruning: SBN parameters must be finite and not negative to be sampled from";
     case kGpTreeOutOfDag: return "generalized pruning: a training tree has a subsplit or an entry outside the DAG";
     case kGpTreeEmptyBlock: return "generalized pruning: a sample reached a block whose parameters are all 0";
+    case kBootBadWeight: return "bootstrap weights: pattern weights must be non-negative integer site counts";
+    case kBootBadTotal: return "bootstrap weights: the pattern weights must sum to N with 1 <= N < 2^31";
+    case kBootSitesNotTotal: return "topology tests: sites[0] must equal the sum of the pattern weights";
     default: return "unknown device status";
   }
 }
@@ -138,6 +142,9 @@ struct mi_engine {
   Buffer pattern_ll_out;  // [T] the call's log-likelihoods when the caller wants none (mi_engine_reserve)
   Buffer rell_ws;         // [B][T] product (when the caller wants none) | row maxima, 1 / denominators [B] each | counts [T] (mi_engine_reserve_rell)
   Buffer rell_s;          // the fused host call: [T][P] per-pattern values nobody downloads
+  // bootstrap weights and the KH / SH / AU tests (mi_engine_bootstrap_weights*, mi_engine_topology_tests*)
+  Buffer boot_ws;         // prefix sum [P+1] | N | the global form's histogram rows (mi_engine_reserve_bootstrap_weights)
+  Buffer topo_ws;         // a block's weights [B][P] and product [B][T] | row statistics [B] x 3 | per-tree rows (mi_engine_reserve_topology_tests)
   // starting trees (mi_engine_pairwise_distances*, mi_engine_neighbour_joining*, mi_engine_starting_trees_unrooted*)
   Buffer dist_codes;   // [n4][Pp] one-byte tip codes of the count kernel (once per engine: launch_distance_codes)
   Buffer dist_model;   // the call's one model instance

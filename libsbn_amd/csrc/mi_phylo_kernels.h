@@ -459,6 +459,59 @@ struct MixtureArgs {
   double* out_total;              // [1]
 };
 void launch_pattern_mixture(const MixtureArgs& a, hipStream_t s);
+// kernels_boot.hip: multiscale bootstrap weights drawn on the device and the KH, SH and AU tests on
+// the RELL matrices.  The sampler: a workgroup per replicate (grid-stride), its
+// draws dealt over the lanes, an int32 histogram of the replicate's P counts in LDS -- with the
+// prefix sum beside it, (2 P + 1) words -- up to kBootLdsPatterns patterns, else in a row of `hist`.
+constexpr int kBootThreads = 256;
+constexpr int kBootLdsPatterns = 6144;  // (2 P + 1) words <= 48 KiB + 4: three workgroups share a CU's 160 KiB
+constexpr int kBootLdsGrid = 2048;      // workgroups of the LDS form, at most
+constexpr int kBootGlobalRows = 1024;   // workgroups of the global form = histogram rows of the workspace, at most
+inline bool boot_hist_global(int P, bool forced) { return forced || P > kBootLdsPatterns; }
+inline int boot_hist_rows(int B, int P, bool forced) {  // rows of BootArgs::hist
+  return boot_hist_global(P, forced) ? (B < kBootGlobalRows ? B : kBootGlobalRows) : 0;
+}
+struct BootArgs {
+  int P, B;
+  int global_hist;           // 1: the histograms are rows of `hist` (boot_hist_global)
+  uint64_t sites;            // n: draws per replicate
+  uint64_t seed;
+  uint64_t first_replicate;  // replicate b of the launch is number first_replicate + b
+  int64_t expect_total;      // the prefix sum: N must equal it (kBootSitesNotTotal), or -1
+  const double* weights;     // [P] the prefix sum's input
+  uint32_t* cum;             // [P + 1] exclusive prefix sum of the weights, cum[P] = N
+  uint32_t* total;           // [1] N; 0 where the weights were refused: the sampler then writes zeros
+  int32_t* hist;             // [boot_hist_rows][P] or nullptr
+  int32_t* status;           // the engine's status word
+  double* out;               // [B][P]
+};
+void launch_boot_prefix(const BootArgs& a, hipStream_t s);  // checks, cum, total
+void launch_boot_sample(const BootArgs& a, hipStream_t s);
+void launch_boot_zero(int32_t* words, size_t count, hipStream_t s);  // a call's integer counters
+// The tests: what is made of block 0's product C [B][T] (column means, row maxima of the centred
+// matrix, the KH and SH counts), and the table from those, the observed log-likelihoods and every
+// block's counts.  The blocks' sizes travel by value: a captured call keeps no host pointer.
+constexpr int kTopoMaxScales = 64;  // MI_TOPOLOGY_MAX_SCALES
+constexpr int kTopoColumns = 11;    // MI_TOPOLOGY_COLUMNS
+struct TopoArgs {
+  int T, B, K;            // trees, replicates of block 0, blocks
+  const double* c;        // [B][T] block 0's product
+  const double* L;        // [T] observed log-likelihoods
+  const int32_t* counts;  // [K][T] replicates won per block
+  const double* bp;       // [T] block 0's bootstrap proportions
+  const double* elw;      // [T] ... and expected-likelihood weights
+  const uint32_t* total;  // [1] N
+  double* mean;           // [T]
+  double* zmax;           // [B] workspace: max_t (C[b][t] - mean[t])
+  int32_t* sel;           // [2] workspace: t1, t2 (-1: T = 1)
+  int32_t* sh;            // [T] workspace, zeroed: SH counts
+  int32_t* kh;            // [T] workspace, zeroed: KH counts
+  double* table;          // [T][kTopoColumns]
+  int64_t sites[kTopoMaxScales];
+  int32_t replicates[kTopoMaxScales];
+};
+void launch_topo_block0(const TopoArgs& a, hipStream_t s);  // best two, means, row maxima, counts
+void launch_topo_table(const TopoArgs& a, hipStream_t s);
 // Starting trees.  kernels_distance.hip: the substitution counts of all pairs of
 // taxa for B sets of pattern weights on the matrix cores, and each pair's maximum-likelihood
 // distance.  The tip codes [distance_code_rows(n)][distance_code_stride(P)] (a byte each: the

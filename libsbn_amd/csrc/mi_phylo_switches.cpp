@@ -93,6 +93,7 @@ bool parse_switches(Switches& out, std::string& error) {
   s.fused_debug_skip = (int)r.integer("MI_PHYLO_DEBUG_FUSED_SKIP", 0, INT_MAX, 0);
   s.plv_bytes = r.integer("MI_PHYLO_PLV_BYTES", 0, LLONG_MAX, -1);
   s.place_table_global = r.choice("MI_PHYLO_PLACE_TABLE", "lds|global", 0) == 1;
+  s.boot_hist_global = r.choice("MI_PHYLO_BOOT_HIST", "lds|global", 0) == 1;
   s.split_hash_bits = (int)r.integer("MI_PHYLO_SPLIT_HASH_BITS", 0, 32, 32);
   s.sbn_trees_per_wave = r.listed("MI_PHYLO_SBN_TREES_PER_WAVE", "16|32|64", 16);
   s.gp_hybrid_z = (int)r.integer("MI_PHYLO_GP_HYBRID_Z", 0, 65535, 0);

@@ -39,6 +39,8 @@ struct Switches {
   long long plv_bytes = -1;    // PLV_BYTES: the arena budget (-1: the engine's default)
   // placement
   bool place_table_global = false;  // PLACE_TABLE=global: the scoring gathers from memory even where the table fits LDS
+  // bootstrap weights
+  bool boot_hist_global = false;  // BOOT_HIST=global: the sampler's histograms are rows of the workspace even where a row fits LDS
   // split tables
   int split_hash_bits = 32;  // SPLIT_HASH_BITS: bits of the hash that choose the first slot (testing: 0 sends every split to slot 0)
   // subsplit Bayesian networks

@@ -118,6 +118,44 @@ class RellResult:
 
 
 @dataclass
+class TopologyTests:
+    """What Engine.topology_tests and Engine.topology_tests_matrix return, per tree [T]: the
+    observed log-likelihood L, L[best] - L, the bootstrap proportion and expected-likelihood
+    weight of block 0, the p-values of the KH, SH and AU tests, the AU fit's d, c and residual sum
+    of squares (NaN, and p_au = bp, where fewer than two scales were usable) and the usable-scale
+    count; counts [K][T] (int32) the replicates each tree won per block, column_mean [T] the means
+    of block 0's replicate log-likelihoods, sites and replicates [K] the blocks; `table` is the
+    [T][11] matrix the columns come from.  On request replicate_log_likelihood [B_0][T] and
+    best_tree [B_0] of block 0; the fused call adds tree_log_likelihood [T] (what log_likelihoods
+    returns) and pattern_log_likelihood [T][P]."""
+    table: np.ndarray
+    log_likelihood: np.ndarray
+    delta: np.ndarray
+    bootstrap_proportion: np.ndarray
+    expected_likelihood_weight: np.ndarray
+    p_kh: np.ndarray
+    p_sh: np.ndarray
+    p_au: np.ndarray
+    au_d: np.ndarray
+    au_c: np.ndarray
+    au_rss: np.ndarray
+    usable_scales: np.ndarray
+    counts: np.ndarray
+    column_mean: np.ndarray
+    sites: np.ndarray
+    replicates: np.ndarray
+    replicate_log_likelihood: np.ndarray = None
+    best_tree: np.ndarray = None
+    tree_log_likelihood: np.ndarray = None
+    pattern_log_likelihood: np.ndarray = None
+
+    @classmethod
+    def from_table(cls, table, counts, mean, sites, replicates, c=None, best=None):
+        cols = [np.ascontiguousarray(table[:, j]) for j in range(10)]
+        return cls(table, *cols, table[:, 10].astype(np.int32), counts, mean, sites, replicates, c, best)
+
+
+@dataclass
 class StartingTrees:
     """What Engine.starting_trees returns: per replicate the neighbour-joining tree of its
     maximum-likelihood distances -- parent ids [B][2n-3] and branch lengths [B][2n-2] in the form
@@ -855,6 +893,87 @@ class Engine:
             _ptr(out.expected_likelihood_weight)))
         return out
 
+    def bootstrap_weights(self, replicates, sites=None, seed=0, first_replicate=0, weights=None):
+        """Replicate weights of a bootstrap drawn on the device (mi_engine_bootstrap_weights):
+        `replicates` rows of `sites` draws each (default: N = sum of the weights, the ordinary
+        bootstrap; another count: a scaled replicate of the AU test) over the patterns of
+        `weights` (default: the engine's pattern weights; non-negative integer site counts).  A
+        row's bits depend on (seed, first_replicate + row, sites, weights) alone.  Returns float64
+        [replicates][P] in the layout rell, rell_bootstrap, pairwise_distances and starting_trees
+        take as replicate_weights: it can be handed over as it is."""
+        w = self._weights if weights is None else weights
+        if w is None:
+            raise RuntimeError("bootstrap_weights: this engine keeps no host copy of its pattern weights; "
+                               "pass weights")
+        w = _np(w, np.float64).reshape(-1)
+        B = int(replicates)
+        n = int(w.sum()) if sites is None else int(sites)
+        out = np.empty((B, w.size))
+        self._check(self._lib.mi_engine_bootstrap_weights(self._h, w.size, _ptr(w), B, n, int(seed),
+                                                          int(first_replicate), _ptr(out)))
+        return out
+
+    def topology_tests_matrix(self, pattern_log_likelihoods, weights, sites, replicates, seed=0,
+                              first_replicate=0, replicate_log_likelihoods=False):
+        """The KH, SH and AU tests with BP and ELW from per-pattern log-likelihoods s [T][P] and
+        pattern weights [P] (mi_engine_topology_tests; any engine serves): block k draws
+        replicates[k] replicates of sites[k] sites on the device (sites[0] = N).  Returns a
+        TopologyTests."""
+        s = _np(pattern_log_likelihoods, np.float64)
+        w = _np(weights, np.float64).reshape(-1)
+        if s.ndim != 2 or s.shape[1] != w.size:
+            raise RuntimeError("topology tests: pattern log-likelihoods [T][P] and pattern weights [P] "
+                               f"must share P; got {s.shape} and {w.shape}")
+        T, P = s.shape
+        si, reps = _np(sites, np.int64).reshape(-1), _np(replicates, np.int32).reshape(-1)
+        if si.size != reps.size or si.size < 1:
+            raise RuntimeError("topology tests: sites and replicates must have one entry per block")
+        K = si.size
+        B0 = max(int(reps[0]), 0)
+        table, counts, mean = np.empty((T, 11)), np.empty((K, T), np.int32), np.empty(T)
+        c = np.empty((B0, T)) if replicate_log_likelihoods else None
+        best = np.empty(B0, np.int32) if replicate_log_likelihoods else None
+        self._check(self._lib.mi_engine_topology_tests(
+            self._h, T, P, _ptr(s), _ptr(w), K, _ptr(si), _ptr(reps), int(seed), int(first_replicate),
+            _ptr(table), _ptr(counts), _ptr(mean), _ptr(c), _ptr(best)))
+        return TopologyTests.from_table(table, counts, mean, si, reps, c, best)
+
+    def topology_tests(self, parent_ids, branch_lengths, params=None, rescaling=False,
+                       scales=(1.0, 0.5, 0.6, 0.7, 0.8, 0.9, 1.1, 1.2, 1.3, 1.4), replicates=10000,
+                       seed=0, first_replicate=0, replicate_log_likelihoods=False):
+        """From trees to the table of p-values in one host call
+        (mi_engine_topology_tests_unrooted; single-device 4-state engines): the per-pattern
+        log-likelihoods, then the tests with the engine's own pattern weights, nothing returning
+        to the host in between.  scales[0] must be 1; block k draws `replicates` (one count, or
+        one per scale) replicates of floor(scales[k] N + 0.5) sites.  Returns a TopologyTests
+        (with the per-pattern log-likelihoods)."""
+        n, P = self.taxon_count, self.pattern_count
+        pid = _np(parent_ids, np.int32).reshape(-1, 2 * n - 3)
+        T = pid.shape[0]
+        if self._weights is None:
+            raise RuntimeError("topology_tests: this engine keeps no host copy of its pattern weights; use "
+                               "pattern_log_likelihoods and topology_tests_matrix")
+        N = int(np.rint(float(np.sum(self._weights))))
+        sc = np.asarray(scales, np.float64).reshape(-1)
+        si = np.floor(sc * N + 0.5).astype(np.int64)
+        reps = np.ascontiguousarray(np.broadcast_to(np.asarray(replicates, np.int32), sc.shape))
+        K = si.size
+        if K < 1:
+            raise RuntimeError("topology tests: at least one scale")
+        B0 = max(int(reps[0]), 0)
+        bl = _np(branch_lengths, np.float64).reshape(T, 2 * n - 2)
+        pr = self._params(params, T)
+        ll, s = np.empty(T), np.empty((T, P))
+        table, counts, mean = np.empty((T, 11)), np.empty((K, T), np.int32), np.empty(T)
+        c = np.empty((B0, T)) if replicate_log_likelihoods else None
+        best = np.empty(B0, np.int32) if replicate_log_likelihoods else None
+        self._check(self._lib.mi_engine_topology_tests_unrooted(
+            self._h, T, _ptr(pid), _ptr(bl), _ptr(pr), int(rescaling), K, _ptr(si), _ptr(reps), int(seed),
+            int(first_replicate), _ptr(ll), _ptr(s), _ptr(table), _ptr(counts), _ptr(mean), _ptr(c), _ptr(best)))
+        out = TopologyTests.from_table(table, counts, mean, si, reps, c, best)
+        out.tree_log_likelihood, out.pattern_log_likelihood = ll, s
+        return out
+
     def _replicates(self, replicate_weights):
         if replicate_weights is None:  # one replicate: the engine's pattern weights
             return None, 1
@@ -1527,6 +1646,32 @@ class Engine:
         """mi_engine_reserve_rell: workspace of a RELL call of that size."""
         self._check(self._lib.mi_engine_reserve_rell(self._h, int(replicate_count), int(tree_count),
                                                      int(pattern_count)))
+
+    def bootstrap_weights_device(self, stream, P, weights, B, sites, seed, first_replicate, out_weights):
+        """mi_engine_bootstrap_weights_device: device pointers, enqueued on `stream`."""
+        self._check(self._lib.mi_engine_bootstrap_weights_device(
+            self._h, stream, int(P), weights, int(B), int(sites), int(seed), int(first_replicate), out_weights))
+
+    def reserve_bootstrap_weights(self, replicate_count, pattern_count):
+        """mi_engine_reserve_bootstrap_weights: workspace of a sampler call of that size."""
+        self._check(self._lib.mi_engine_reserve_bootstrap_weights(self._h, int(replicate_count), int(pattern_count)))
+
+    def topology_tests_device(self, stream, T, P, pattern_ll, weights, sites, replicates, seed, first_replicate,
+                              out_table, out_counts, out_mean=None, out_replicate_ll=None, out_best=None):
+        """mi_engine_topology_tests_device: device pointers but sites and replicates (host
+        sequences), enqueued on `stream`."""
+        si, reps = _np(sites, np.int64).reshape(-1), _np(replicates, np.int32).reshape(-1)
+        if si.size != reps.size:
+            raise RuntimeError("topology tests: sites and replicates must have one entry per block")
+        self._check(self._lib.mi_engine_topology_tests_device(
+            self._h, stream, int(T), int(P), pattern_ll, weights, si.size, _ptr(si), _ptr(reps), int(seed),
+            int(first_replicate), out_table, out_counts, out_mean, out_replicate_ll, out_best))
+
+    def reserve_topology_tests(self, tree_count, pattern_count, max_replicate_count):
+        """mi_engine_reserve_topology_tests: workspace of the tests for that many trees, patterns
+        and replicates of the largest block (the *_device form then allocates nothing)."""
+        self._check(self._lib.mi_engine_reserve_topology_tests(self._h, int(tree_count), int(pattern_count),
+                                                               int(max_replicate_count)))
 
     def pairwise_distances_device(self, stream, B, replicate_weights, params, out_distances,
                                   out_pair_counts=None, out_pair_status=None, min_length=1e-8,
