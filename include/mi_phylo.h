@@ -1714,7 +1714,8 @@ int32_t mi_vi_set_state(mi_vi* fit, const double* log_params, const double* q_pa
                         const double* q_moments, const double* scalars, const int64_t* counters);
 /* The last step's particles: out_parent_ids [K][2n-3] is required, the others may be NULL:
  * out_branch_lengths [K][2n-2], and out_log_likelihoods, out_log_q_topology, out_log_q_branch,
- * out_log_prior [K] each.  Synchronises the engine's stream. */
+ * out_log_prior [K] each.  Synchronises the engine's stream.  A fit over a subsplit DAG
+ * (mi_gp_vi_create) has rooted particles: it is refused here and served by mi_gp_vi_particles. */
 int32_t mi_vi_particles(mi_vi* fit, int32_t* out_parent_ids, double* out_branch_lengths, double* out_log_likelihoods,
                         double* out_log_q_topology, double* out_log_q_branch, double* out_log_prior);
 
@@ -2009,6 +2010,138 @@ int32_t mi_engine_deroot_trees(mi_engine* engine, int32_t tree_count, int32_t ta
 int32_t mi_engine_deroot_trees_device(mi_engine* engine, void* stream, int32_t tree_count, int32_t taxon_count,
                                       const int32_t* parent_ids, const double* branch_lengths,
                                       int32_t* out_parent_ids, double* out_branch_lengths, int32_t* out_root_edge);
+
+/* ---- a variational fit over the rooted trees of the subsplit DAG (an extension) ----
+ *
+ * The rooted counterpart of mi_engine_vi_create: the variational family is the rooted SBN of a mi_gp
+ * (full or DAG-only, so any engine serves: 4 or 20 states, any number of rate categories) with one
+ * log-normal branch-length variable per entry, which is what generalized pruning keeps (b[G]).
+ * Notation: G entries, R rootsplits, N = 2n-1 nodes of a rooted tree (the root N-1), and blocks as
+ * mi_gp_structure gives them: the rootsplits [0, R), then one block per (node, clade).  The tables
+ * are log_params [G] (phi, unnormalised) and q_params [G][2] (mu, sigma of entry e); the object's
+ * own q and b are read by nothing here and changed by nothing here.
+ *
+ * mi_gp_log_normalize: per block with maximum m,
+ *   out_log_q[e] = (phi_e - m) - log(sum_{i in block} exp(phi_i - m)),  out_q[e] = exp(out_log_q[e])
+ * the sum in ascending entry order with one accumulator (a lane per block).  -inf is allowed (q = 0;
+ * a block that is all -inf gets log q = -inf and q = 0 throughout); NaN and +inf are an error that
+ * names the entry.  out_log_q may be NULL.
+ *
+ * The topology side of a step is mi_gp_sample_trees with that q in the object's place: the same
+ * Philox layout, entries, and log q = sum over v = 0 .. 2n-2 ascending of log q[entries[v]].
+ *
+ * mi_gp_branch_sample: branch lengths of tree_count rooted trees given by their entries [T][N].  Per
+ * tree t and node v = 0 .. 2n-3 the variable is e = entries[t][v]; the root's slot N-1 carries its
+ * rootsplit entry and no length.  A sentinel (anything outside [0, G)) is an error that names the
+ * tree and the node; so is sigma_e <= 0 or not finite, or a NaN mu_e.
+ *   eps = epsilon_in[t][v] if given, else the standard normal of mi_engine_branch_model_sample:
+ *   Philox key (seed lo, seed hi), counter (v, 1, s lo, s hi), s = first_sample + t, the same
+ *   Box-Muller form.  x = mu_e + sigma_e eps (a rounded product, a rounded sum), theta = exp(x).
+ *   out_branch_lengths [T][N]  theta; 0 in the root's slot: the layout mi_engine_deroot_trees takes
+ *   out_epsilon [T][N-1]
+ *   out_log_q [T]      -sum_v (((x + log sigma) + log(2 pi)/2) + 0.5 (eps eps)), ascending v < N-1,
+ *                      one accumulator from 0
+ *   out_log_prior [T]  (2n-2) log(prior_rate) - prior_rate sum_v theta, the sum in the same order:
+ *                      Exp(prior_rate) on every rooted edge
+ * Rows of rootsplit entries (j < R) are carried in q_params and never drawn from.
+ *
+ * mi_engine_deroot_trees_mapped: mi_engine_deroot_trees with one more output,
+ *   out_new_id [T][N]  the unrooted id under which every rooted node's edge lands: both root
+ *                      children map to out_root_edge, the root to -1 (a refused tree: all -1)
+ * so that out_branch_lengths[u] = sum over v with new_id[v] == u of branch_lengths[v], and the
+ * derivative of log L with respect to a rooted edge v is the unrooted gradient's entry new_id[v]
+ * (the two root edges share the merged edge's).
+ *
+ * mi_gp_branch_gradient: the reparametrisation gradient with respect to q_params and log_f.
+ * branch_lengths, epsilon, log_q_branch, log_prior: the sample call's outputs; new_id: the mapped
+ * de-rooting's; branch_gradient [T][N] and log_likelihoods [T]: mi_engine_gradients_unrooted's for
+ * the de-rooted trees (2n-1 = N entries per tree).  Per (t, v), v < N-1, with g =
+ * branch_gradient[t][new_id[t][v]], d = g - prior_rate, w = tree_weights[t] (1 if NULL):
+ *   c0 = w ((d theta) + 1)      c1 = w ((((d theta) eps) + eps) + (1 / sigma))
+ * every operation rounded once, in the order the parentheses give.
+ *   out_gradient [G][2]  row j: the sum of c0 resp. c1 over the positions (t, v), v < N-1, with
+ *       entries[t][v] == j, in ascending position t N + v, one accumulator per component from 0
+ *       (a run of more than 16 positions is a wave's: 64 side by side, added lane after lane: the same
+ *       additions in the same order).  An entry no position names, and every rootsplit row, gets 0.
+ *   out_log_f [T]  ((beta log_likelihoods[t] + log_prior[t]) - log_q_topology[t]) - log_q_branch[t]
+ *       (log_q_topology NULL: 0)
+ *
+ * mi_gp_topology_gradient: the gradient of the multi-sample objective with respect to log_params.
+ * The usage of a parameter by a tree is an indicator, so
+ *   G_j = sum over the trees t that use j (the root's slot included) of a_t, in ascending t with one
+ *         accumulator (the same runs of the same stable sort by entry as above)
+ *   out_gradient[j] = G_j - q_j sum_{i in block(j)} G_i, the block's sum in ascending entry order,
+ *         q the normalised table of mi_gp_log_normalize
+ * with the factors a_t from log_f by the formulas of mi_engine_sbn_topology_gradient
+ * (MI_SBN_FACTORS_PLAIN, _VIMCO, _GIVEN; out_factors [T] or NULL).  Sentinel entries are skipped.
+ *
+ * mi_gp_reserve_vi reserves what these calls need for tree_capacity trees (it includes
+ * mi_gp_reserve_trees); after it the *_device forms allocate nothing, synchronise nothing and can be
+ * captured; the host forms reserve on first use.  Device forms take device pointers.
+ *
+ * mi_gp_vi_create: a fit whose step is the chain
+ *   log-normalise, CDF and tree building (sampling), branch draw, mapped de-rooting,
+ *   mi_engine_gradients_unrooted_device for K trees with the one model row, the terms, the factors,
+ *   one sort and the two ordered sums, the update of mi_vi_update* with P = V = G
+ * on one stream.  Step t draws the samples first_sample + t K + k and its beta from the fit's state
+ * in device memory, as DESIGN.md 4.24 words it; every variable's sigma (rootsplit rows included)
+ * must stay positive, else the step fails as an unrooted fit's does; a non-finite gradient entry
+ * fails it too.  options->rows must be 1.  parameter_count and variable_count must both be G.
+ * Creation reserves (mi_gp_reserve_trees, mi_engine_reserve for K gradient evaluations,
+ * mi_engine_reserve_deroot), cuts one buffer and uploads; a step allocates nothing, synchronises
+ * nothing and reads nothing back.  mi_vi_destroy releases the fit's buffer; the three reservations belong
+ * to the object and the engine and stay grown, so mi_device_bytes_held is back where it was before
+ * mi_gp_vi_create only when an earlier fit (or the reserve calls) had made them already.  mi_vi_step_device, mi_vi_fit, mi_vi_trace, mi_vi_update[_device],
+ * mi_vi_get_state, mi_vi_set_state, mi_vi_sizes (rows 1, S = R, C = 0, V = P = G) and mi_vi_destroy
+ * serve it as they serve an unrooted fit; mi_vi_particles refuses it and mi_gp_vi_particles gives
+ * the last step's rooted particles: out_parent_ids [K][2n-2] (required), out_entries [K][N],
+ * out_branch_lengths [K][N], and out_log_likelihoods, out_log_q_topology, out_log_q_branch,
+ * out_log_prior [K] each (or NULL).  An object made on a handle of several shards is refused.  The
+ * object and its engine must outlive the fit, and reserving more trees on the object invalidates a
+ * captured step.  The bits of a fit depend on the options, the initial state, the DAG and the
+ * alignment alone.
+ * mi_engine_last_call_path: "gp_vi_fit n=<n> K=<K> G=<G> steps=<s> | <the gradient call's path>". */
+int32_t mi_gp_reserve_vi(mi_gp* gp, int32_t tree_capacity);
+int32_t mi_gp_log_normalize(mi_gp* gp, const double* log_params /* [G] */, double* out_log_q, double* out_q);
+int32_t mi_gp_log_normalize_device(mi_gp* gp, void* stream, const double* log_params, double* out_log_q, double* out_q);
+int32_t mi_gp_branch_sample(mi_gp* gp, int32_t tree_count, const int32_t* entries, const double* q_params /* [G][2] */,
+                            uint64_t seed, int64_t first_sample, double prior_rate,
+                            const double* epsilon_in /* [T][2n-2] or NULL */, double* out_branch_lengths,
+                            double* out_epsilon, double* out_log_q, double* out_log_prior);
+int32_t mi_gp_branch_sample_device(mi_gp* gp, void* stream, int32_t tree_count, const int32_t* entries,
+                                   const double* q_params, uint64_t seed, int64_t first_sample, double prior_rate,
+                                   const double* epsilon_in, double* out_branch_lengths, double* out_epsilon,
+                                   double* out_log_q, double* out_log_prior);
+int32_t mi_gp_branch_gradient(mi_gp* gp, int32_t tree_count, const int32_t* entries, const double* q_params,
+                              const double* branch_lengths, const double* epsilon, const double* log_q_branch,
+                              const double* log_prior, const int32_t* new_id, const double* branch_gradient,
+                              const double* log_likelihoods, const double* log_q_topology /* [T] or NULL */,
+                              const double* tree_weights /* [T] or NULL */, double beta, double prior_rate,
+                              double* out_gradient, double* out_log_f);
+int32_t mi_gp_branch_gradient_device(mi_gp* gp, void* stream, int32_t tree_count, const int32_t* entries,
+                                     const double* q_params, const double* branch_lengths, const double* epsilon,
+                                     const double* log_q_branch, const double* log_prior, const int32_t* new_id,
+                                     const double* branch_gradient, const double* log_likelihoods,
+                                     const double* log_q_topology, const double* tree_weights, double beta,
+                                     double prior_rate, double* out_gradient, double* out_log_f);
+int32_t mi_gp_topology_gradient(mi_gp* gp, int32_t tree_count, const int32_t* entries, const double* log_params,
+                                const double* log_f, int32_t estimator, double* out_gradient, double* out_factors);
+int32_t mi_gp_topology_gradient_device(mi_gp* gp, void* stream, int32_t tree_count, const int32_t* entries,
+                                       const double* log_params, const double* log_f, int32_t estimator,
+                                       double* out_gradient, double* out_factors);
+int32_t mi_engine_deroot_trees_mapped(mi_engine* engine, int32_t tree_count, int32_t taxon_count,
+                                      const int32_t* parent_ids, const double* branch_lengths,
+                                      int32_t* out_parent_ids, double* out_branch_lengths, int32_t* out_root_edge,
+                                      int32_t* out_new_id /* [T][2n-1] or NULL */);
+int32_t mi_engine_deroot_trees_mapped_device(mi_engine* engine, void* stream, int32_t tree_count, int32_t taxon_count,
+                                             const int32_t* parent_ids, const double* branch_lengths,
+                                             int32_t* out_parent_ids, double* out_branch_lengths,
+                                             int32_t* out_root_edge, int32_t* out_new_id);
+int32_t mi_gp_vi_create(mi_gp* gp, const double* model_params, int32_t parameter_count, const double* log_params,
+                        int32_t variable_count, const double* q_params, const mi_vi_options* options, mi_vi** out_fit);
+int32_t mi_gp_vi_particles(mi_vi* fit, int32_t* out_parent_ids, int32_t* out_entries, double* out_branch_lengths,
+                           double* out_log_likelihoods, double* out_log_q_topology, double* out_log_q_branch,
+                           double* out_log_prior);
 
 /* Synchronise `stream` and report the first per-tree error since the last check (the status
  * word is sticky and cleared when an error is reported: calls themselves never clear it). */

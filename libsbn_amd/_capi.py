@@ -305,6 +305,24 @@ SYMBOLS = {
     "mi_engine_reserve_deroot": (C.c_int32, [_V, C.c_int32, C.c_int32]),
     "mi_engine_deroot_trees": (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),
     "mi_engine_deroot_trees_device": (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V]),
+    "mi_gp_reserve_vi": (C.c_int32, [_V, C.c_int32]),
+    "mi_gp_log_normalize": (C.c_int32, [_V, _V, _V, _V]),
+    "mi_gp_log_normalize_device": (C.c_int32, [_V, _V, _V, _V, _V]),
+    "mi_gp_branch_sample":
+        (C.c_int32, [_V, C.c_int32, _V, _V, C.c_uint64, C.c_int64, C.c_double, _V, _V, _V, _V, _V]),
+    "mi_gp_branch_sample_device":
+        (C.c_int32, [_V, _V, C.c_int32, _V, _V, C.c_uint64, C.c_int64, C.c_double, _V, _V, _V, _V, _V]),
+    "mi_gp_branch_gradient":
+        (C.c_int32, [_V, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, C.c_double, C.c_double, _V, _V]),
+    "mi_gp_branch_gradient_device":
+        (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, C.c_double, C.c_double, _V, _V]),
+    "mi_gp_topology_gradient": (C.c_int32, [_V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V]),
+    "mi_gp_topology_gradient_device": (C.c_int32, [_V, _V, C.c_int32, _V, _V, _V, C.c_int32, _V, _V]),
+    "mi_engine_deroot_trees_mapped": (C.c_int32, [_V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V]),
+    "mi_engine_deroot_trees_mapped_device": (C.c_int32, [_V, _V, C.c_int32, C.c_int32, _V, _V, _V, _V, _V, _V]),
+    "mi_gp_vi_create":
+        (C.c_int32, [_V, _V, C.c_int32, _V, C.c_int32, _V, C.POINTER(ViOptions), C.POINTER(_V)]),
+    "mi_gp_vi_particles": (C.c_int32, [_V, _V, _V, _V, _V, _V, _V, _V]),
     "mi_consensus_tree":
         (C.c_int32, [C.c_int32, C.c_int32, _V, _V, C.c_double, C.c_double, I32P, _V, _V]),
     "mi_engine_check_status": (C.c_int32, [_V, _V]),

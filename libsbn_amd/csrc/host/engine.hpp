@@ -237,6 +237,12 @@ struct DerootedTrees {
   std::vector<double> branch_lengths_;  // [T][2n-2], empty without input lengths
   std::vector<int32_t> root_edge_;      // [T]
 };
+struct GpViParticles {  // GeneralizedPruning::ViParticles: the last step's rooted particles of a fit over the DAG
+  std::vector<int32_t> parent_ids_;     // [K][2n-2]
+  std::vector<int32_t> entries_;        // [K][2n-1]
+  std::vector<double> branch_lengths_;  // [K][2n-1], 0 at the root
+  std::vector<double> log_likelihoods_, log_q_topology_, log_q_branch_, log_prior_;  // [K] each
+};
 class GeneralizedPruning {
  public:
   GeneralizedPruning() = default;
@@ -372,6 +378,31 @@ class GeneralizedPruning {
     GpTreesResult out = Built(count);
     Try(mi_gp_enumerate_trees(handle_, first, static_cast<int32_t>(count), out.parent_ids_.data(), out.entries_.data(),
                               out.log_q_.data(), out.branch_lengths_.data()));
+    return out;
+  }
+
+  // A device-resident variational fit over the rooted trees of this DAG (mi_gp_vi_create):
+  // log_params [G], q_params [G][2], model_params the one parameter row (empty: the model takes none).
+  // options.rows must be 1.  Engine::ViFit, ViState and ViUpdate serve the fit; it must not outlive this object.
+  VariationalFit ViCreate(const std::vector<double>& log_params, const std::vector<double>& q_params,
+                          const mi_vi_options& options, const std::vector<double>& model_params = {}) const {
+    if (q_params.size() % 2) Failwith("ViCreate: q_params is [G][2].");
+    mi_vi* fit = nullptr;
+    Try(mi_gp_vi_create(handle_, model_params.empty() ? nullptr : model_params.data(), static_cast<int32_t>(log_params.size()),
+                        log_params.data(), static_cast<int32_t>(q_params.size() / 2), q_params.data(), &options, &fit));
+    return VariationalFit(fit);
+  }
+  // the last step's rooted particles (mi_gp_vi_particles)
+  GpViParticles ViParticles(const VariationalFit& fit) const {
+    const size_t K = static_cast<size_t>(fit.Sizes()[1]), N = NodesPerTree();
+    GpViParticles out;
+    out.parent_ids_.resize(K * (N - 1));
+    out.entries_.resize(K * N);
+    out.branch_lengths_.resize(K * N);
+    for (auto* v : {&out.log_likelihoods_, &out.log_q_topology_, &out.log_q_branch_, &out.log_prior_}) v->resize(K);
+    Try(mi_gp_vi_particles(fit.Handle(), out.parent_ids_.data(), out.entries_.data(), out.branch_lengths_.data(),
+                           out.log_likelihoods_.data(), out.log_q_topology_.data(), out.log_q_branch_.data(),
+                           out.log_prior_.data()));
     return out;
   }
 

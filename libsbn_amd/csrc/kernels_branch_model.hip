@@ -105,15 +105,7 @@ __device__ __forceinline__ bool edge_params(const int32_t* index, const double* 
   return good;
 }
 
-// the standard normal of edge v of sample s: counter (v, 1, s lo, s hi)
-__device__ __forceinline__ double philox_normal(uint64_t seed, uint64_t s, uint32_t v) {
-  uint32_t c[4] = {v, 1u, (uint32_t)s, (uint32_t)(s >> 32)};
-  philox4x32_10(c, seed);
-  const uint64_t b1 = ((uint64_t)c[0] << 32) | c[1], b2 = ((uint64_t)c[2] << 32) | c[3];
-  const double u1 = (double)((b1 >> 11) + 1) * 0x1.0p-53, u2 = (double)(b2 >> 11) * 0x1.0p-53;
-  return sqrt(-2.0 * log(u1)) * cos((2.0 * M_PI) * u2);
-}
-
+// (the standard normal of edge v of sample s: philox_normal, mi_phylo_philox_device.h)
 constexpr double kHalfLog2Pi = 0.91893853320467274178;  // log(2 pi) / 2
 
 __global__ __launch_bounds__(256) void branch_sample_kernel(BranchSampleArgs a) {

@@ -37,6 +37,7 @@
 #include "mi_phylo_device.h"
 #include "mi_phylo_device_utils.h"
 #include "mi_phylo_gp_trees.h"
+#include "mi_phylo_kernels.h"
 #include "mi_phylo_philox_device.h"
 
 namespace miphylo {
@@ -390,21 +391,25 @@ __device__ __forceinline__ void gp_tree_build(const GpTreesArgs& a, int sample, 
     for (int v = 0; v < N; v++) lengths[v] = gp_tree_length(a.b, a.G, ent[v], v, N, 0.0);
 }
 
+// vi: a fit's step: the first sample is the state's, `first` is not read
 __global__ __launch_bounds__(64) void gp_tree_build_kernel(GpTreesArgs a, int K, int sample, uint64_t seed, int64_t first,
-                                                           int32_t* out_parent_ids, int32_t* out_entries, double* out_log_q,
-                                                           double* out_lengths, int tpw, int in_lds) {
+                                                           const ViState* vi, int32_t* out_parent_ids, int32_t* out_entries,
+                                                           double* out_log_q, double* out_lengths, int tpw, int in_lds) {
   extern __shared__ __attribute__((aligned(16))) int32_t gp_trees_lds[];
   const int lane = threadIdx.x, k = blockIdx.x * tpw + lane, N = 2 * a.n - 1;
   if (lane >= tpw || k >= K) return;
   const Lane s = lane_store(gp_trees_lds, a.store, gp_tree_build_words(a.n), tpw, in_lds);
+  if (vi) first = vi_sample_base(*vi);
   gp_tree_build(a, sample, seed, (uint64_t)(first + (int64_t)k), k, out_parent_ids + (size_t)k * (N - 1), out_entries + (size_t)k * N,
                 out_log_q + k, out_lengths ? out_lengths + (size_t)k * N : nullptr, s);
 }
 
 // ---- de-rooting ----
+// out_new_id [T][2n-1] or null: the unrooted id under which every rooted node's edge lands (both root
+// children: the root edge; the root: -1)
 __global__ __launch_bounds__(64) void gp_tree_deroot_kernel(int T, int n, const int32_t* parent_ids, const double* lengths,
                                                             int32_t* out_parent_ids, double* out_lengths, int32_t* out_root_edge,
-                                                            int32_t* store, int32_t* status) {
+                                                            int32_t* out_new_id, int32_t* store, int32_t* status) {
   const int t = blockIdx.x * 64 + threadIdx.x, N = 2 * n - 1, m = n - 1, E = 2 * n - 3;
   if (t >= T) return;
   Lane s;
@@ -414,6 +419,7 @@ __global__ __launch_bounds__(64) void gp_tree_deroot_kernel(int T, int n, const 
   const int32_t* par = parent_ids + (size_t)t * (N - 1);
   int32_t* out = out_parent_ids + (size_t)t * E;
   double* bl = out_lengths ? out_lengths + (size_t)t * (E + 1) : nullptr;
+  int32_t* nid = out_new_id ? out_new_id + (size_t)t * N : nullptr;
   for (int i = 0; i < m; i++) s(K0 + i) = s(K1 + i) = -1;
   int code = kOk;
   for (int v = 0; v < N - 1; v++) {
@@ -435,6 +441,8 @@ __global__ __launch_bounds__(64) void gp_tree_deroot_kernel(int T, int n, const 
     for (int v = 0; v < E; v++) out[v] = -1;
     if (bl)
       for (int v = 0; v <= E; v++) bl[v] = NAN;
+    if (nid)
+      for (int v = 0; v < N; v++) nid[v] = -1;
     out_root_edge[t] = -1;
     return;
   }
@@ -454,6 +462,7 @@ __global__ __launch_bounds__(64) void gp_tree_deroot_kernel(int T, int n, const 
       const int kid = s((c ? K1 : K0) + i), ki = id(kid);
       out[ki] = me;
       if (bl) bl[ki] = in[kid];
+      if (nid) nid[kid] = ki;
     }
   }
   const int yi = id(y);
@@ -461,6 +470,11 @@ __global__ __launch_bounds__(64) void gp_tree_deroot_kernel(int T, int n, const 
   if (bl) {
     bl[yi] = in[y] + in[x];
     bl[E] = 0.0;
+  }
+  if (nid) {
+    nid[y] = yi;
+    nid[x] = yi;
+    nid[N - 1] = -1;
   }
   out_root_edge[t] = yi;
 }
@@ -563,20 +577,21 @@ void launch_gp_tree_cdf(const GpTreesArgs& a, double* out_cdf, hipStream_t s) {
   hipLaunchKernelGGL(gp_tree_cdf_kernel, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, s, a, out_cdf);
 }
 
-void launch_gp_tree_build(const GpTreesArgs& a, int K, int sample, uint64_t seed, int64_t first, int32_t* out_parent_ids,
-                          int32_t* out_entries, double* out_log_q, double* out_lengths, hipStream_t s) {
+void launch_gp_tree_build(const GpTreesArgs& a, int K, int sample, uint64_t seed, int64_t first, const ViState* vi,
+                          int32_t* out_parent_ids, int32_t* out_entries, double* out_log_q, double* out_lengths, hipStream_t s) {
   bool in_lds;
   const size_t words = gp_tree_build_words(a.n);
   const int tpw = gp_trees_per_wave(words, a.force_global != 0, in_lds);
   const size_t lds = in_lds ? words * 4 * tpw : 0;
-  hipLaunchKernelGGL(gp_tree_build_kernel, dim3((unsigned)((K + tpw - 1) / tpw)), dim3(64), lds, s, a, K, sample, seed, first,
+  hipLaunchKernelGGL(gp_tree_build_kernel, dim3((unsigned)((K + tpw - 1) / tpw)), dim3(64), lds, s, a, K, sample, seed, first, vi,
                      out_parent_ids, out_entries, out_log_q, out_lengths, tpw, in_lds ? 1 : 0);
 }
 
 void launch_gp_tree_deroot(int T, int n, const int32_t* parent_ids, const double* lengths, int32_t* out_parent_ids,
-                           double* out_lengths, int32_t* out_root_edge, int32_t* store, int32_t* status, hipStream_t s) {
+                           double* out_lengths, int32_t* out_root_edge, int32_t* out_new_id, int32_t* store, int32_t* status,
+                           hipStream_t s) {
   hipLaunchKernelGGL(gp_tree_deroot_kernel, dim3((unsigned)((T + 63) / 64)), dim3(64), 0, s, T, n, parent_ids, lengths,
-                     out_parent_ids, out_lengths, out_root_edge, store, status);
+                     out_parent_ids, out_lengths, out_root_edge, out_new_id, store, status);
 }
 
 }  // namespace miphylo

@@ -592,11 +592,16 @@ void launch_sbn_sample(const SbnSampleArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(sbn_sample_kernel, dim3((unsigned)sbn_wave_count(a.K, a.tpw)), dim3(64), lds, s, a, in_lds ? 1 : 0);
 }
 
+// the factors a_t alone: reads T, estimator, log_f and sums; writes out_factors
+void launch_sbn_factors(const SbnGradientArgs& a, hipStream_t s) {
+  if (a.estimator != MI_SBN_FACTORS_GIVEN) hipLaunchKernelGGL(sbn_factor_sums_kernel, dim3(1), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(sbn_factors_kernel, dim3((unsigned)(a.T + 255) / 256), dim3(256), 0, s, a);
+}
+
 int launch_sbn_gradient(const SbnGradientArgs& a, hipStream_t s) {
   const size_t Q = (size_t)a.T * (2 * a.n - 3) * 7;
   const unsigned blocks = (unsigned)((std::max<size_t>(Q, a.P) + 255) / 256);
-  if (a.estimator != MI_SBN_FACTORS_GIVEN) hipLaunchKernelGGL(sbn_factor_sums_kernel, dim3(1), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(sbn_factors_kernel, dim3((unsigned)(a.T + 255) / 256), dim3(256), 0, s, a);
+  launch_sbn_factors(a, s);
   hipLaunchKernelGGL(sbn_gradient_keys_kernel, dim3(blocks), dim3(256), 0, s, a);
   size_t sort_bytes = a.sort_tmp_bytes;
   if (rocprim::radix_sort_pairs(a.sort_tmp, sort_bytes, a.keys, a.keys2, a.vals, a.vals2, Q, 0,

@@ -57,6 +57,27 @@ struct Buffer {
   T* as() const { return static_cast<T*>(ptr); }
 };
 
+// One device block cut into arrays, each starting on a 256-byte boundary: sizes first (base null: every
+// pointer null, `at` the bytes needed), then the pointers.
+struct Cutter {
+  char* base;
+  size_t at = 0;
+  template <typename T>
+  void take(T*& p, size_t count) {
+    p = base ? reinterpret_cast<T*>(base + at) : nullptr;
+    at += (std::max<size_t>(count, 1) * sizeof(T) + 255) & ~(size_t)255;
+  }
+};
+// Synchronous copies of the creation and host-form paths; a null host pointer (an optional array) copies nothing.
+inline int upload(void* dst, const void* src, size_t bytes) {
+  if (src && bytes) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+inline int download(void* dst, const void* src, size_t bytes) {
+  if (dst && bytes) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // Pinned host staging for the host-pointer entry points: inputs are copied into it and
 // DMA'd from there, outputs are DMA'd into it and copied out after the call's one
 // synchronisation.  (hipMemcpyAsync on pageable memory is staged by the runtime, copy by

@@ -108,6 +108,7 @@ enum StatusCode : int32_t {
   kBootBadWeight = 26,      // (its second status word carries the pattern)
   kBootBadTotal = 27,
   kBootSitesNotTotal = 28,
+  kGpViBadEntry = 29,       // (its second and fourth status words carry the tree and the node)
 };
 
 }  // namespace miphylo

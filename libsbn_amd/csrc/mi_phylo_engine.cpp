@@ -362,6 +362,8 @@ int check_status(mi_engine* e, hipStream_t s) {
     if (st[0] == kBranchModelBadParam)
       return fail(std::string(status_message(st[0])) + " (tree " + std::to_string(st[1] + e->status_tree_offset) +
                   ", edge " + std::to_string(st[3]) + ")");
+    if (st[0] == kGpViBadEntry)
+      return fail(std::string(status_message(st[0])) + " (tree " + std::to_string(st[1]) + ", node " + std::to_string(st[3]) + ")");
     if (st[0] == kGpTreeBadParam) return fail(std::string(status_message(st[0])) + " (entry " + std::to_string(st[1]) + ")");
     if (st[0] == kGpTreeEmptyBlock)
       return fail(std::string(status_message(st[0])) + " (sample " + std::to_string(st[1]) +

@@ -80,6 +80,7 @@ inline const char* status_message(int code) {
     case kBootBadWeight: return "bootstrap weights: pattern weights must be non-negative integer site counts";
     case kBootBadTotal: return "bootstrap weights: the pattern weights must sum to N with 1 <= N < 2^31";
     case kBootSitesNotTotal: return "topology tests: sites[0] must equal the sum of the pattern weights";
+    case kGpViBadEntry: return "generalized pruning: a node of a tree names no entry of the DAG to take its branch length from";
     default: return "unknown device status";
   }
 }

@@ -272,16 +272,6 @@ void node_probabilities(const GpDag& d, const double* q, double* out) {
 
 namespace {
 
-struct Cutter {
-  char* base;
-  size_t at = 0;
-  template <typename T>
-  void take(T*& p, size_t count) {
-    p = base ? reinterpret_cast<T*>(base + at) : nullptr;
-    at += (std::max<size_t>(count, 1) * sizeof(T) + 255) & ~(size_t)255;
-  }
-};
-
 size_t cut(mi_gp* g, char* base) {
   const size_t G = g->d.G, I = g->I, Pp = g->Pp, nodes = g->d.nodes, n = g->d.n;
   GpArgs& a = g->a;
@@ -336,15 +326,6 @@ size_t cut(mi_gp* g, char* base) {
   c.take(g->d_hlevels, g->ht.levels.size());
   c.take(g->o_hybrid, G);
   return c.at;
-}
-
-int upload(void* dst, const void* src, size_t bytes) {
-  if (bytes) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-  return 0;
-}
-int download(void* dst, const void* src, size_t bytes) {
-  if (dst && bytes) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-  return 0;
 }
 
 // both sweeps at branch lengths `b` (a device pointer), on stream s; matrix: the [G][P] output or nullptr
@@ -409,6 +390,7 @@ static int gp_create(mi_engine* e, int32_t T, int32_t n, const int32_t* parent_i
   if (!e) return fail("null engine");
   if (!out) return fail("null output pointer");
   *out = nullptr;
+  const bool several_shards = e->shards.size() > 1;
   if (dag_only) {
     if (!e->shards.empty()) e = e->shards[0];  // (a handle of several shards: its first)
   } else {
@@ -428,6 +410,7 @@ static int gp_create(mi_engine* e, int32_t T, int32_t n, const int32_t* parent_i
   mi_gp* g = new mi_gp;
   g->e = e;
   g->dag_only = dag_only;
+  g->several_shards = several_shards;
   g->threshold = rescaling_threshold;
   std::vector<double> b;
   auto make = [&]() -> int {

@@ -47,6 +47,7 @@ struct mi_gp {
   mi_engine* e = nullptr;
   miphylo::GpDag d;
   bool dag_only = false;  // mi_engine_gp_create_dag: no model, no codes, no vectors
+  bool several_shards = false;  // made on a handle of several shards (e is its first): a variational fit refuses it
   int P = 0, Pp = 0, tiles = 0, I = 0;
   double threshold = miphylo::kGpDefaultThreshold;
   bool stale = true;  // the vectors are not those of the current b and q
@@ -82,4 +83,14 @@ struct mi_gp {
   double *s_log_q = nullptr, *s_lengths = nullptr;                        // [cap], [cap][2n-1]
   double *s_weights = nullptr, *s_cdf = nullptr;                          // [cap], [G]
   miphylo::GpTrainArgs train{};  // the rooted TrainSimpleAverage's workspace
+  // the by-value pieces of a variational step (mi_gp_reserve_vi): their workspace and the staging
+  // arrays of the host forms, for vi_capacity trees (the sort's arrays are `train`'s)
+  Buffer vi_ws;
+  int vi_capacity = 0;
+  struct ViWork {
+    double *log_q, *qn, *usage, *sums, *factors, *terms;                       // [G] x 3, [2], [cap], [cap][2n-2][2]
+    double *s_phi, *s_q_params, *s_eps_in, *s_eps, *s_lengths, *s_grad, *s_terms;  // staging: [G], [G][2], [cap][2n-2] x 2,
+    double *o_q_gradient, *o_gradient;                                         // [cap][2n-1] x 2, [7][cap]; [G][2], [G]
+    int32_t *s_entries, *s_new_id;                                             // [cap][2n-1] each
+  } vw{};
 };

@@ -12,25 +12,6 @@
 
 namespace {
 
-struct Cutter {
-  char* base;
-  size_t at = 0;
-  template <typename T>
-  void take(T*& p, size_t count) {
-    p = base ? reinterpret_cast<T*>(base + at) : nullptr;
-    at += (std::max<size_t>(count, 1) * sizeof(T) + 255) & ~(size_t)255;
-  }
-};
-
-int upload(void* dst, const void* src, size_t bytes) {
-  if (bytes) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-  return 0;
-}
-int download(void* dst, const void* src, size_t bytes) {
-  if (dst && bytes) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-  return 0;
-}
-
 uint64_t add_capped(uint64_t a, uint64_t b) { return std::min(a + b, kGpTreesCountCap); }  // (both at most 2^62)
 uint64_t mul_capped(uint64_t a, uint64_t b) {
   const unsigned __int128 p = (unsigned __int128)a * b;
@@ -221,7 +202,7 @@ int build_device(mi_gp* g, hipStream_t s, int K, int sample, uint64_t seed, int6
   if (!out_parent_ids || !out_entries || !out_log_q) return fail("null output pointer");
   HIP_TRY(hipSetDevice(g->e->spec.device));
   if (sample) launch_gp_tree_cdf(g->t, out_cdf, s);
-  launch_gp_tree_build(g->t, K, sample, seed, first, out_parent_ids, out_entries, out_log_q, out_lengths, s);
+  launch_gp_tree_build(g->t, K, sample, seed, first, nullptr, out_parent_ids, out_entries, out_log_q, out_lengths, s);
   HIP_TRY(hipGetLastError());
   note(g, "gp_tree_build_kernel", K, gp_tree_build_words(g->d.n));
   return 0;
@@ -409,8 +390,9 @@ int32_t mi_engine_reserve_deroot(mi_engine* e, int32_t T, int32_t n) {
   if (T < 1) return fail("tree_count must be positive");
   if (n < 3) return fail("de-rooting needs at least 3 taxa");
   const size_t N = 2 * (size_t)n - 1, waves = ((size_t)T + 63) / 64;
-  // node words | parent ids in | lengths in | parent ids out | lengths out | root edges
-  const size_t bytes = waves * 64 * gp_tree_deroot_words(n) * 4 + (size_t)T * ((N - 1) * 4 + N * 8 + (N - 2) * 4 + (N - 1) * 8 + 4) + 6 * 256;
+  // node words | parent ids in | lengths in | parent ids out | lengths out | root edges | new ids
+  const size_t bytes =
+      waves * 64 * gp_tree_deroot_words(n) * 4 + (size_t)T * ((N - 1) * 4 + N * 8 + (N - 2) * 4 + (N - 1) * 8 + 4 + N * 4) + 7 * 256;
   if (bytes > e->plv_budget)
     return fail("de-rooting " + std::to_string(T) + " trees of " + std::to_string(n) + " taxa takes " + std::to_string(bytes) +
                 " bytes of workspace, over the budget of " + std::to_string(e->plv_budget) + " bytes (MI_PHYLO_PLV_BYTES)");
@@ -420,9 +402,9 @@ int32_t mi_engine_reserve_deroot(mi_engine* e, int32_t T, int32_t n) {
   return e->deroot_ws.ensure(bytes);
 }
 
-int32_t mi_engine_deroot_trees_device(mi_engine* e, void* stream, int32_t T, int32_t n, const int32_t* parent_ids,
-                                      const double* branch_lengths, int32_t* out_parent_ids, double* out_branch_lengths,
-                                      int32_t* out_root_edge) {
+int32_t mi_engine_deroot_trees_mapped_device(mi_engine* e, void* stream, int32_t T, int32_t n, const int32_t* parent_ids,
+                                             const double* branch_lengths, int32_t* out_parent_ids, double* out_branch_lengths,
+                                             int32_t* out_root_edge, int32_t* out_new_id) {
   if (!e) return fail("null engine");
   if (!e->shards.empty()) e = e->shards[0];
   if (T < 1) return fail("tree_count must be positive");
@@ -434,16 +416,23 @@ int32_t mi_engine_deroot_trees_device(mi_engine* e, void* stream, int32_t T, int
     return fail("de-rooting " + std::to_string(T) + " trees of " + std::to_string(n) +
                 " taxa before mi_engine_reserve_deroot reserved them (the device form allocates nothing)");
   HIP_TRY(hipSetDevice(e->spec.device));
-  launch_gp_tree_deroot(T, n, parent_ids, branch_lengths, out_parent_ids, out_branch_lengths, out_root_edge,
+  launch_gp_tree_deroot(T, n, parent_ids, branch_lengths, out_parent_ids, out_branch_lengths, out_root_edge, out_new_id,
                         e->deroot_ws.as<int32_t>(), e->status.as<int32_t>(), pick_stream(e, stream));
   HIP_TRY(hipGetLastError());
   e->dominant = "gp_tree_deroot_kernel";
   e->last_path = "deroot n=" + std::to_string(n) + " T=" + std::to_string(T);
   return 0;
 }
+int32_t mi_engine_deroot_trees_device(mi_engine* e, void* stream, int32_t T, int32_t n, const int32_t* parent_ids,
+                                      const double* branch_lengths, int32_t* out_parent_ids, double* out_branch_lengths,
+                                      int32_t* out_root_edge) {
+  return mi_engine_deroot_trees_mapped_device(e, stream, T, n, parent_ids, branch_lengths, out_parent_ids, out_branch_lengths,
+                                              out_root_edge, nullptr);
+}
 
-int32_t mi_engine_deroot_trees(mi_engine* e, int32_t T, int32_t n, const int32_t* parent_ids, const double* branch_lengths,
-                               int32_t* out_parent_ids, double* out_branch_lengths, int32_t* out_root_edge) {
+int32_t mi_engine_deroot_trees_mapped(mi_engine* e, int32_t T, int32_t n, const int32_t* parent_ids, const double* branch_lengths,
+                                      int32_t* out_parent_ids, double* out_branch_lengths, int32_t* out_root_edge,
+                                      int32_t* out_new_id) {
   if (!e) return fail("null engine");
   if (!e->shards.empty()) e = e->shards[0];
   if (!parent_ids || !out_parent_ids || !out_root_edge) return fail("null tree arrays or output pointer");
@@ -451,21 +440,28 @@ int32_t mi_engine_deroot_trees(mi_engine* e, int32_t T, int32_t n, const int32_t
   if (mi_engine_reserve_deroot(e, T, n)) return 1;
   const size_t N = 2 * (size_t)n - 1, words = (((size_t)T + 63) / 64) * 64 * gp_tree_deroot_words(n);
   Cutter c{e->deroot_ws.as<char>() + words * 4};
-  int32_t *in_p, *out_p, *edge;
+  int32_t *in_p, *out_p, *edge, *new_id;
   double *in_b, *out_b;
   c.take(in_p, T * (N - 1));
   c.take(in_b, T * N);
   c.take(out_p, T * (N - 2));
   c.take(out_b, T * (N - 1));
   c.take(edge, (size_t)T);
+  c.take(new_id, T * N);
   if (upload(in_p, parent_ids, sizeof(int32_t) * T * (N - 1))) return 1;
   if (branch_lengths && upload(in_b, branch_lengths, sizeof(double) * T * N)) return 1;
-  if (mi_engine_deroot_trees_device(e, nullptr, T, n, in_p, branch_lengths ? in_b : nullptr, out_p, out_branch_lengths ? out_b : nullptr,
-                                    edge))
+  if (mi_engine_deroot_trees_mapped_device(e, nullptr, T, n, in_p, branch_lengths ? in_b : nullptr, out_p,
+                                           out_branch_lengths ? out_b : nullptr, edge, out_new_id ? new_id : nullptr))
     return 1;
   if (check_status(e, e->stream)) return 1;
   return download(out_parent_ids, out_p, sizeof(int32_t) * T * (N - 2)) ||
-         download(out_branch_lengths, out_b, sizeof(double) * T * (N - 1)) || download(out_root_edge, edge, sizeof(int32_t) * T);
+         download(out_branch_lengths, out_b, sizeof(double) * T * (N - 1)) || download(out_root_edge, edge, sizeof(int32_t) * T) ||
+         download(out_new_id, new_id, sizeof(int32_t) * T * N);
+}
+int32_t mi_engine_deroot_trees(mi_engine* e, int32_t T, int32_t n, const int32_t* parent_ids, const double* branch_lengths,
+                               int32_t* out_parent_ids, double* out_branch_lengths, int32_t* out_root_edge) {
+  return mi_engine_deroot_trees_mapped(e, T, n, parent_ids, branch_lengths, out_parent_ids, out_branch_lengths, out_root_edge,
+                                       nullptr);
 }
 
 }  // extern "C"

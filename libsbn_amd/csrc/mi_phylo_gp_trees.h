@@ -85,11 +85,15 @@ void launch_gp_tree_lengths(const GpTreesArgs& a, int T, const int32_t* entries,
 // out_cdf: a second copy, or null
 void launch_gp_tree_cdf(const GpTreesArgs& a, double* out_cdf, hipStream_t s);
 // sample != 0: draws (seed, first + k); else tree number first + k of the DAG.  out_lengths may be null.
-void launch_gp_tree_build(const GpTreesArgs& a, int K, int sample, uint64_t seed, int64_t first, int32_t* out_parent_ids,
-                          int32_t* out_entries, double* out_log_q, double* out_lengths, hipStream_t s);
+// vi (or null): a fit's state in device memory, whose sample base replaces `first`.
+struct ViState;
+void launch_gp_tree_build(const GpTreesArgs& a, int K, int sample, uint64_t seed, int64_t first, const ViState* vi,
+                          int32_t* out_parent_ids, int32_t* out_entries, double* out_log_q, double* out_lengths, hipStream_t s);
 // rooted [T][2n-2] (+ lengths [T][2n-1] or null) -> unrooted [T][2n-3] (+ [T][2n-2] or null), root edge [T];
-// store: gp_tree_deroot_words(n) words for every tree of ceil(T / 64) waves
+// store: gp_tree_deroot_words(n) words for every tree of ceil(T / 64) waves; out_new_id [T][2n-1] or null: the
+// unrooted id under which every rooted node's edge lands (both root children: the root edge; the root: -1)
 void launch_gp_tree_deroot(int T, int n, const int32_t* parent_ids, const double* lengths, int32_t* out_parent_ids,
-                           double* out_lengths, int32_t* out_root_edge, int32_t* store, int32_t* status, hipStream_t s);
+                           double* out_lengths, int32_t* out_root_edge, int32_t* out_new_id, int32_t* store, int32_t* status,
+                           hipStream_t s);
 
 }  // namespace miphylo

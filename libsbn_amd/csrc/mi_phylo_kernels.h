@@ -776,6 +776,7 @@ struct SbnGradientArgs {
   double* out_gradient;         // [P]
 };
 int launch_sbn_gradient(const SbnGradientArgs& a, hipStream_t s);  // (after the walk; nonzero: rocPRIM refused)
+void launch_sbn_factors(const SbnGradientArgs& a, hipStream_t s);  // (its first step alone: log_f -> out_factors, through sums)
 void sbn_vi_prepare(int n, int tpw);  // the large-LDS opt-in of the two per-tree kernels
 // kernels_branch_model.hip: PSP indexing and the log-normal branch-length models.
 // E = 2n-3 edges; an index array is [T][R][E], R = 1 (splits) or 3 (rootsplit, down PSP, up PSP);

@@ -29,5 +29,15 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint64_t key) {
   }
 }
 
+// the standard normal of edge v of sample s (mi_engine_branch_model_sample): counter (v, 1, s lo, s hi),
+// the Box-Muller form of the first two and the last two output words
+__device__ __forceinline__ double philox_normal(uint64_t seed, uint64_t s, uint32_t v) {
+  uint32_t c[4] = {v, 1u, (uint32_t)s, (uint32_t)(s >> 32)};
+  philox4x32_10(c, seed);
+  const uint64_t b1 = ((uint64_t)c[0] << 32) | c[1], b2 = ((uint64_t)c[2] << 32) | c[3];
+  const double u1 = (double)((b1 >> 11) + 1) * 0x1.0p-53, u2 = (double)(b2 >> 11) * 0x1.0p-53;
+  return sqrt(-2.0 * log(u1)) * cos((2.0 * M_PI) * u2);
+}
+
 }  // namespace dev
 }  // namespace miphylo

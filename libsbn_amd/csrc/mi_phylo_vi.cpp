@@ -8,37 +8,9 @@
 #include <vector>
 
 #include "mi_phylo_engine.h"
+#include "mi_phylo_vi_host.h"
 
-// Everything a fit holds on the device is one block (`pool`), cut at creation.
-struct mi_vi {
-  mi_engine* e = nullptr;
-  mi_vi_options o{};
-  int n = 0, E = 0, T0 = 0, K = 0, R = 0, S = 0, C = 0, parents = 0, P = 0, V = 0, pc = 0, blocks = 0;
-  Buffer pool;
-  std::string grad_path;
-  // the state
-  ViState* state = nullptr;
-  double *phi = nullptr, *q = nullptr, *m_sbn = nullptr, *v_sbn = nullptr, *m_q = nullptr, *v_q = nullptr;
-  // the support's tables
-  int32_t *d_range = nullptr, *d_desc = nullptr, *d_psp = nullptr;
-  double* params = nullptr;  // [K][param_count]
-  // a step's buffers: the support trees with the samples behind them, and what the calls hand on
-  int32_t *all_pid = nullptr, *root = nullptr, *slot = nullptr, *counts = nullptr, *clades = nullptr,
-          *prange = nullptr, *pparent = nullptr, *edge = nullptr, *sparams = nullptr, *index = nullptr;
-  uint32_t* bits = nullptr;
-  double *lp = nullptr, *bl = nullptr, *eps = nullptr, *lqb = nullptr, *lprior = nullptr, *ll = nullptr, *g = nullptr,
-         *rooting = nullptr, *lqt = nullptr, *qgrad = nullptr, *f = nullptr, *grad = nullptr, *factors = nullptr,
-         *glq = nullptr;
-  // the optimiser
-  int32_t* block_flags = nullptr;
-  double *trace = nullptr, *row = nullptr;
-  // staging of the host form of the optimiser call
-  double *u_grad = nullptr, *u_qgrad = nullptr, *u_terms = nullptr;
-};
-
-namespace {
-
-int check_options(const mi_vi_options& o) {
+int vi_check_options(const mi_vi_options& o) {
   if (o.particle_count < 1) return fail("variational fit: particle_count must be positive");
   if (o.rows != 1 && o.rows != 3) return fail("variational fit: rows must be 1 (splits) or 3 (rootsplit, down PSP, up PSP)");
   if (o.estimator != MI_SBN_FACTORS_PLAIN && o.estimator != MI_SBN_FACTORS_VIMCO)
@@ -60,16 +32,8 @@ int check_options(const mi_vi_options& o) {
   return 0;
 }
 
-// cut `bytes` off the block: sizes first (base null), then the pointers
-struct Cutter {
-  char* base;
-  size_t at = 0;
-  template <typename T>
-  void take(T*& p, size_t count) {
-    p = base ? reinterpret_cast<T*>(base + at) : nullptr;
-    at += (std::max<size_t>(count, 1) * sizeof(T) + 255) & ~(size_t)255;
-  }
-};
+namespace {
+
 
 size_t cut(mi_vi* v, char* base) {
   const size_t K = v->K, E = v->E, T = (size_t)v->T0 + K, P = v->P, V = v->V, W = ((size_t)v->n + 31) / 32;
@@ -144,22 +108,16 @@ int support_tables(mi_engine* e, int T0, const int32_t* parent_ids, SupportTable
   return 0;
 }
 
-int upload(void* dst, const void* src, size_t bytes) {
-  if (bytes) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-  return 0;
-}
-int download(void* dst, const void* src, size_t bytes) {
-  if (dst && bytes) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-  return 0;
-}
-
 std::string fit_path(const mi_vi* v, int steps) {
+  if (v->gp) return gp_vi_path(v, steps);
   return "vi_fit n=" + std::to_string(v->n) + " K=" + std::to_string(v->K) + " rows=" + std::to_string(v->R) +
          " steps=" + std::to_string(steps) + " | " + v->grad_path;
 }
 
-int enqueue_update(mi_vi* v, hipStream_t s, const double* g_sbn, const double* g_q, const double* ll,
-                   const double* lprior, const double* lqt, const double* lqb, double* out_row) {
+}  // namespace
+
+int vi_enqueue_update(mi_vi* v, hipStream_t s, const double* g_sbn, const double* g_q, const double* ll, const double* lprior,
+                      const double* lqt, const double* lqb, double* out_row) {
   if (!g_sbn || !g_q || !ll || !lprior || !lqt || !lqb) return fail("variational fit: null gradient or term array");
   ViUpdateArgs a{};
   a.P = v->P;
@@ -192,6 +150,8 @@ int enqueue_update(mi_vi* v, hipStream_t s, const double* g_sbn, const double* g
   return 0;
 }
 
+namespace {
+
 int enqueue_step(mi_vi* v, hipStream_t s) {
   mi_engine* e = v->e;
   const int n = v->n, K = v->K, T0 = v->T0, S = v->S, C = v->C, E = v->E;
@@ -220,15 +180,16 @@ int enqueue_step(mi_vi* v, hipStream_t s) {
   if (mi_engine_sbn_topology_gradient_device(e, s, K, n, samples, s_root, s_slot, S, C, v->parents, v->d_range, v->phi, 0,
                                              v->f, v->o.estimator, v->grad, v->factors, v->glq))
     return 1;
-  return enqueue_update(v, s, v->grad, v->qgrad, v->ll, v->lprior, v->lqt, v->lqb, nullptr);
+  return vi_enqueue_update(v, s, v->grad, v->qgrad, v->ll, v->lprior, v->lqt, v->lqb, nullptr);
 }
 
 int step(mi_vi* v, hipStream_t s) {
   mi_engine* e = v->e;
-  if (v->T0 < 1) return fail("variational fit: a fit without a support holds the tables only; it takes updates, no steps");
+  if (v->T0 < 1 && !v->gp)
+    return fail("variational fit: a fit without a support holds the tables only; it takes updates, no steps");
   HIP_TRY(hipSetDevice(e->spec.device));
   e->vi_state = v->state;
-  const int rc = enqueue_step(v, s);
+  const int rc = v->gp ? gp_vi_enqueue_step(v, s) : enqueue_step(v, s);
   e->vi_state = nullptr;
   if (rc) return 1;
   e->dominant = "vi_finish_kernel";
@@ -272,7 +233,7 @@ int32_t mi_engine_vi_create(mi_engine* e, int32_t T0, const int32_t* parent_ids,
   if (e->shards.size() == 1) e = e->shards[0];  // (a handle of one shard is its one engine)
   if (!e->shards.empty()) return fail(kShardedDeviceCall);
   if (!options) return fail("variational fit: null options");
-  if (check_options(*options)) return 1;
+  if (vi_check_options(*options)) return 1;
   if (T0 < 0) return fail("variational fit: support_tree_count must not be negative");
   if (P < 0 || V < 0 || (size_t)P + 2 * (size_t)V < 1 || (size_t)P + 2 * (size_t)V >= ((size_t)1 << 31))
     return fail("variational fit: bad parameter or variable count");
@@ -397,7 +358,7 @@ int32_t mi_vi_update_device(mi_vi* v, void* stream, const double* g_sbn, const d
                             const double* lprior, const double* lqt, const double* lqb, double* out_row) {
   if (!v) return fail("null fit");
   HIP_TRY(hipSetDevice(v->e->spec.device));
-  return enqueue_update(v, pick_stream(v->e, stream), g_sbn, g_q, ll, lprior, lqt, lqb, out_row);
+  return vi_enqueue_update(v, pick_stream(v->e, stream), g_sbn, g_q, ll, lprior, lqt, lqb, out_row);
 }
 
 int32_t mi_vi_update(mi_vi* v, const double* g_sbn, const double* g_q, const double* ll, const double* lprior,
@@ -412,7 +373,7 @@ int32_t mi_vi_update(mi_vi* v, const double* g_sbn, const double* g_q, const dou
   if (upload(v->u_grad, g_sbn, sizeof(double) * v->P) || upload(v->u_qgrad, g_q, sizeof(double) * 2 * v->V)) return 1;
   for (int j = 0; j < 4; j++)
     if (upload(v->u_terms + j * K, terms[j], sizeof(double) * K)) return 1;
-  if (enqueue_update(v, e->stream, v->u_grad, v->u_qgrad, v->u_terms, v->u_terms + K, v->u_terms + 2 * K,
+  if (vi_enqueue_update(v, e->stream, v->u_grad, v->u_qgrad, v->u_terms, v->u_terms + K, v->u_terms + 2 * K,
                      v->u_terms + 3 * K, v->row))
     return 1;
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -467,6 +428,8 @@ int32_t mi_vi_set_state(mi_vi* v, const double* phi, const double* q, const doub
 
 int32_t mi_vi_particles(mi_vi* v, int32_t* pid, double* bl, double* ll, double* lqt, double* lqb, double* lprior) {
   if (!v) return fail("null fit");
+  if (v->gp)
+    return fail("variational fit: a fit over a subsplit DAG has rooted particles; mi_gp_vi_particles gives them");
   if (!pid) return fail("null output pointer");
   HIP_TRY(hipSetDevice(v->e->spec.device));
   HIP_TRY(hipStreamSynchronize(v->e->stream));

@@ -1923,6 +1923,33 @@ class Engine:
         self._check(self._lib.mi_engine_deroot_trees(self._h, T, n, _ptr(pid), _ptr(bl), _ptr(out), _ptr(out_bl), _ptr(edge)))
         return DerootedTrees(out, out_bl, edge)
 
+    def deroot_trees_mapped(self, parent_ids, branch_lengths=None):
+        """deroot_trees plus new_id [T][2n-1] (mi_engine_deroot_trees_mapped): the unrooted id under which
+        every rooted node's edge lands (both root children: root_edge; the root: -1)."""
+        pid = _np(parent_ids, np.int32)
+        if pid.ndim == 1:
+            pid = pid[None, :]
+        if pid.ndim != 2 or pid.shape[1] < 4 or pid.shape[1] % 2:
+            raise RuntimeError("deroot_trees_mapped: parent_ids must be [T][2n-2]")
+        T, n = pid.shape[0], pid.shape[1] // 2 + 1
+        bl = out_bl = None
+        if branch_lengths is not None:
+            bl = _np(branch_lengths, np.float64).reshape(-1, 2 * n - 1)
+            if bl.shape[0] != T:
+                raise RuntimeError("deroot_trees_mapped: branch_lengths must be [T][2n-1]")
+            out_bl = np.empty((T, 2 * n - 2))
+        out, edge, new_id = np.empty((T, 2 * n - 3), np.int32), np.empty(T, np.int32), np.empty((T, 2 * n - 1), np.int32)
+        self._check(self._lib.mi_engine_deroot_trees_mapped(self._h, T, n, _ptr(pid), _ptr(bl), _ptr(out), _ptr(out_bl),
+                                                            _ptr(edge), _ptr(new_id)))
+        return DerootedTrees(out, out_bl, edge, new_id)
+
+    def deroot_trees_mapped_device(self, stream, T, n, parent_ids, branch_lengths, out_parent_ids, out_branch_lengths,
+                                   out_root_edge, out_new_id):
+        """mi_engine_deroot_trees_mapped_device: device pointers, enqueued on `stream`; needs reserve_deroot."""
+        self._check(self._lib.mi_engine_deroot_trees_mapped_device(self._h, stream, T, n, parent_ids, branch_lengths,
+                                                                   out_parent_ids, out_branch_lengths, out_root_edge,
+                                                                   out_new_id))
+
     def reserve_deroot(self, tree_count, taxon_count):
         self._check(self._lib.mi_engine_reserve_deroot(self._h, tree_count, taxon_count))
 
@@ -2189,6 +2216,16 @@ class DerootedTrees:
     parent_ids: np.ndarray       # [T][2n-3]
     branch_lengths: np.ndarray   # [T][2n-2] or None
     root_edge: np.ndarray        # [T] the edge that carries the rooting
+    new_id: np.ndarray = None    # [T][2n-1] deroot_trees_mapped: the unrooted edge of every rooted node's edge; the root: -1
+
+
+@dataclass
+class GpBranchDraw:
+    """GeneralizedPruning.branch_sample(): branch lengths of rooted trees drawn per entry."""
+    branch_lengths: np.ndarray   # [T][2n-1] theta; 0 in the root's slot
+    epsilon: np.ndarray          # [T][2n-2]
+    log_q: np.ndarray            # [T]
+    log_prior: np.ndarray        # [T]
 
 
 def gp_hybrid_request_count(parent_ids, max_summands=0):
@@ -2461,6 +2498,120 @@ class GeneralizedPruning:
         self._check(self._lib.mi_gp_enumerate_trees_device(self._h, stream, int(first), int(count), out_parent_ids,
                                                            out_entries, out_log_q, out_branch_lengths))
 
+    # ---- the variational fit over the DAG's rooted trees ----
+    def reserve_vi(self, tree_capacity):
+        """mi_gp_reserve_vi: the workspace of the calls below for tree_capacity trees (reserve_trees included)."""
+        self._check(self._lib.mi_gp_reserve_vi(self._h, int(tree_capacity)))
+
+    def log_normalize(self, log_params):
+        """mi_gp_log_normalize: (log q [G], q [G]) of unnormalised log parameters, normalised per block."""
+        phi = _np(log_params, np.float64).reshape(self.entry_count)
+        lq, q = np.empty(self.entry_count), np.empty(self.entry_count)
+        self._check(self._lib.mi_gp_log_normalize(self._h, _ptr(phi), _ptr(lq), _ptr(q)))
+        return lq, q
+
+    def log_normalize_device(self, stream, log_params, out_log_q, out_q):
+        self._check(self._lib.mi_gp_log_normalize_device(self._h, stream, log_params, out_log_q, out_q))
+
+    def branch_sample(self, entries, q_params, seed, first_sample=0, prior_rate=10.0, epsilon=None):
+        """mi_gp_branch_sample: a GpBranchDraw of the trees given by entries [T][2n-1], one log-normal
+        variable (mu, sigma) = q_params[e] per entry; epsilon [T][2n-2] replaces the Philox normals."""
+        ent = self._entries(entries)
+        T, N = ent.shape
+        q = _np(q_params, np.float64).reshape(self.entry_count, 2)
+        eps = None if epsilon is None else _np(epsilon, np.float64).reshape(T, N - 1)
+        d = GpBranchDraw(np.empty((T, N)), np.empty((T, N - 1)), np.empty(T), np.empty(T))
+        self._check(self._lib.mi_gp_branch_sample(self._h, T, _ptr(ent), _ptr(q), int(seed) & (2 ** 64 - 1), int(first_sample),
+                                                  float(prior_rate), _ptr(eps), _ptr(d.branch_lengths), _ptr(d.epsilon),
+                                                  _ptr(d.log_q), _ptr(d.log_prior)))
+        return d
+
+    def branch_sample_device(self, stream, T, entries, q_params, seed, first_sample, prior_rate, epsilon_in,
+                             out_branch_lengths, out_epsilon, out_log_q, out_log_prior):
+        self._check(self._lib.mi_gp_branch_sample_device(self._h, stream, T, entries, q_params, int(seed) & (2 ** 64 - 1),
+                                                         int(first_sample), float(prior_rate), epsilon_in, out_branch_lengths,
+                                                         out_epsilon, out_log_q, out_log_prior))
+
+    def branch_gradient(self, entries, q_params, draw, new_id, branch_gradient, log_likelihoods, log_q_topology=None,
+                        tree_weights=None, beta=1.0, prior_rate=10.0):
+        """mi_gp_branch_gradient: (gradient [G][2] with respect to q_params, log_f [T]) from a
+        GpBranchDraw, the mapped de-rooting's new_id [T][2n-1] and the unrooted gradient call's
+        branch gradient [T][2n-1] and log-likelihoods [T] of the de-rooted trees."""
+        ent = self._entries(entries)
+        T, N = ent.shape
+        q = _np(q_params, np.float64).reshape(self.entry_count, 2)
+        arrays = [_np(draw.branch_lengths, np.float64).reshape(T, N), _np(draw.epsilon, np.float64).reshape(T, N - 1),
+                  _np(draw.log_q, np.float64).reshape(T), _np(draw.log_prior, np.float64).reshape(T),
+                  _np(new_id, np.int32).reshape(T, N), _np(branch_gradient, np.float64).reshape(T, N),
+                  _np(log_likelihoods, np.float64).reshape(T)]
+        lqt = None if log_q_topology is None else _np(log_q_topology, np.float64).reshape(T)
+        w = None if tree_weights is None else _np(tree_weights, np.float64).reshape(T)
+        out, log_f = np.empty((self.entry_count, 2)), np.empty(T)
+        self._check(self._lib.mi_gp_branch_gradient(self._h, T, _ptr(ent), _ptr(q), *[_ptr(x) for x in arrays], _ptr(lqt),
+                                                    _ptr(w), float(beta), float(prior_rate), _ptr(out), _ptr(log_f)))
+        return out, log_f
+
+    def branch_gradient_device(self, stream, T, entries, q_params, branch_lengths, epsilon, log_q_branch, log_prior,
+                               new_id, branch_gradient, log_likelihoods, log_q_topology, tree_weights, beta, prior_rate,
+                               out_gradient, out_log_f):
+        self._check(self._lib.mi_gp_branch_gradient_device(self._h, stream, T, entries, q_params, branch_lengths, epsilon,
+                                                           log_q_branch, log_prior, new_id, branch_gradient,
+                                                           log_likelihoods, log_q_topology, tree_weights, float(beta),
+                                                           float(prior_rate), out_gradient, out_log_f))
+
+    def topology_gradient(self, entries, log_params, log_f, estimator="vimco"):
+        """mi_gp_topology_gradient: (gradient [G] with respect to log_params, factors [T])."""
+        ent = self._entries(entries)
+        T = ent.shape[0]
+        phi, f = _np(log_params, np.float64).reshape(self.entry_count), _np(log_f, np.float64).reshape(T)
+        out, factors = np.empty(self.entry_count), np.empty(T)
+        self._check(self._lib.mi_gp_topology_gradient(self._h, T, _ptr(ent), _ptr(phi), _ptr(f), _SBN_FACTORS[estimator],
+                                                      _ptr(out), _ptr(factors)))
+        return out, factors
+
+    def topology_gradient_device(self, stream, T, entries, log_params, log_f, estimator, out_gradient, out_factors=None):
+        self._check(self._lib.mi_gp_topology_gradient_device(self._h, stream, T, entries, log_params, log_f,
+                                                             _SBN_FACTORS[estimator], out_gradient, out_factors))
+
+    def default_q_params(self):
+        """The mode match of the object's b: sigma = -0.1 log clip(b, 1e-6, 1 - 1e-6), mu = sigma^2 +
+        log max(b, 1e-6); the rootsplit rows, which no edge draws from, are (0, 1)."""
+        b = self.get_branch_lengths()[:self.entry_count]
+        sigma = -0.1 * np.log(np.clip(b, 1e-6, 1.0 - 1e-6))
+        q = np.stack([sigma * sigma + np.log(np.maximum(b, 1e-6)), sigma], axis=1)
+        q[:self.rootsplit_count] = (0.0, 1.0)
+        return q
+
+    def vi_create(self, log_params=None, q_params=None, model_params=None, particle_count=10, estimator="vimco",
+                  anneal_steps=0, max_steps=1000, prior_rate=10.0, step_size=(0.001, 0.001), sbn_step_size=0.001,
+                  step_decay=0.99, adam_beta0=0.9, adam_beta1=0.999, adam_epsilon=1e-8, seed=0, first_sample=0, rows=1):
+        """A device-resident variational fit over the rooted trees of this DAG (mi_gp_vi_create;
+        DESIGN.md 4.29).  log_params [G] defaults to the log of the object's q, q_params [G][2] to
+        default_q_params(); model_params: the one parameter row every particle takes.  Returns a
+        RootedVariationalFit."""
+        if estimator not in ("plain", "vimco"):
+            raise RuntimeError(f"vi_create: estimator must be 'plain' or 'vimco', got {estimator!r}")
+        e = self.engine
+        if log_params is None:
+            with np.errstate(divide="ignore"):
+                log_params = np.log(self.get_sbn_parameters())
+        if q_params is None:
+            q_params = self.default_q_params()
+        phi, q = _np(log_params, np.float64).reshape(-1), _np(q_params, np.float64).reshape(-1, 2)
+        mp = None if model_params is None or e.param_count == 0 else _np(model_params, np.float64).reshape(e.param_count)
+        o = _capi.ViOptions()
+        self._check(self._lib.mi_vi_default_options(C.byref(o)))
+        o.particle_count, o.rows, o.estimator = int(particle_count), int(rows), _SBN_FACTORS[estimator]
+        o.anneal_steps, o.max_steps, o.prior_rate = int(anneal_steps), int(max_steps), float(prior_rate)
+        o.step_size[0], o.step_size[1] = (float(x) for x in np.broadcast_to(step_size, 2))
+        o.sbn_step_size, o.step_decay = float(sbn_step_size), float(step_decay)
+        o.adam_beta0, o.adam_beta1, o.adam_epsilon = float(adam_beta0), float(adam_beta1), float(adam_epsilon)
+        o.seed, o.first_sample = int(seed) & (2 ** 64 - 1), int(first_sample)
+        h = C.c_void_p()
+        self._check(self._lib.mi_gp_vi_create(self._h, _ptr(mp), phi.shape[0], _ptr(phi), q.shape[0], _ptr(q), C.byref(o),
+                                              C.byref(h)))
+        return RootedVariationalFit(self, h, mp, o)
+
     def optimize_branch_lengths(self, tolerance=1e-6, max_iterations=100, min_length=np.exp(-13.9),
                                 max_length=np.exp(1.1), check_interval=4):
         """Maximise log_marginal over all branch lengths (mi_gp_optimize_branch_lengths): a
@@ -2471,6 +2622,68 @@ class GeneralizedPruning:
         self._check(self._lib.mi_gp_optimize_branch_lengths(self._h, C.byref(o), _ptr(trace), C.byref(evals),
                                                             C.byref(status)))
         return GpOptimizeResult(self.get_branch_lengths(), trace[:evals.value].copy(), evals.value, status.value)
+
+
+class RootedVariationalFit(VariationalFit):
+    """A variational fit over the rooted trees of a subsplit DAG (mi_gp_vi_create),
+    made by GeneralizedPruning.vi_create.  step_device, fit, trace, update, state and set_state are
+    VariationalFit's.  The object and its engine must outlive it."""
+
+    def __init__(self, gp, handle, model_params, options):
+        super().__init__(gp.engine, handle, None, model_params, options)
+        self.gp = gp
+
+    def particles(self):
+        """The last step's rooted particles (mi_gp_vi_particles): (parent ids [K][2n-2], entries
+        [K][2n-1], branch lengths [K][2n-1], logL [K], log q of the topology [K], log q of the
+        lengths [K], log prior [K])."""
+        K, N = self.particle_count, 2 * self.taxon_count - 1
+        pid, ent, bl = np.empty((K, N - 1), np.int32), np.empty((K, N), np.int32), np.empty((K, N))
+        ll, lqt, lqb, lp = np.empty(K), np.empty(K), np.empty(K), np.empty(K)
+        self._check(self._lib.mi_gp_vi_particles(self._h, _ptr(pid), _ptr(ent), _ptr(bl), _ptr(ll), _ptr(lqt), _ptr(lqb),
+                                                 _ptr(lp)))
+        return pid, ent, bl, ll, lqt, lqb, lp
+
+    def export(self):
+        """(normalised q [G], exp(mu - sigma^2) [G]) of the current state, in plain Python: what
+        set_sbn_parameters and set_branch_lengths of the object take (the mode of every entry's
+        log-normal as its branch length)."""
+        st = self.state()
+        s = self.gp.structure()
+        blocks = [(0, s.rootsplit_count)] + [tuple(int(x) for x in s.block_range[v, c])
+                                             for v in range(s.taxon_count, s.node_count) for c in range(2)]
+        q = np.zeros(s.entry_count)
+        for lo, hi in blocks:
+            phi = st.log_params[lo:hi]
+            top = np.max(phi) if hi > lo else 0.0
+            if np.isfinite(top):
+                w = np.exp(phi - top)
+                q[lo:hi] = w / np.sum(w)
+        return q, np.exp(st.q_params[:, 0] - st.q_params[:, 1] ** 2)
+
+    def estimate(self, particle_count, seed, first_sample=0):
+        """(elbo, marginal likelihood estimate) of the current state on fresh particles, composed from
+        the by-value calls.  Unlike a step of the fit, which never touches the object, this draws
+        through sample_trees: the object's own q is set to the state's for the draw and put back
+        (set_sbn_parameters), which leaves a full object's vectors stale: populate() again before
+        its likelihood calls.  A DAG-only object has no vectors to go stale."""
+        g, e, K = self.gp, self.engine, int(particle_count)
+        st = self.state()
+        _, q = g.log_normalize(st.log_params)
+        kept = g.get_sbn_parameters()
+        g.set_sbn_parameters(q)
+        try:
+            trees = g.sample_trees(K, seed, first_sample=first_sample)
+        finally:
+            g.set_sbn_parameters(kept)
+        draw = g.branch_sample(trees.entries, st.q_params, seed, first_sample=first_sample,
+                               prior_rate=self.options.prior_rate)
+        un = e.deroot_trees(trees.parent_ids, draw.branch_lengths)
+        params = None if self.model_params is None else np.tile(self.model_params, (K, 1))
+        ll = e.log_likelihoods(un.parent_ids, un.branch_lengths, params)
+        f = ll + draw.log_prior - trees.log_q - draw.log_q
+        top = np.max(f)
+        return float(np.mean(f)), float(top + np.log(np.sum(np.exp(f - top))) - np.log(K))
 
 
 class DevicePatterns:
