@@ -1908,7 +1908,7 @@ int32_t mi_gp_optimize_branch_lengths(mi_gp* gp, const mi_branch_opt_options* op
  * to node (open addressing, keyed by a hash of the two clades' W words; a candidate is CONFIRMED by
  * comparing the clade words, so identification is exact), the rootsplit entry of every node and,
  * as uint64 saturated at 2^62, the number of topologies below every node -- and allocates the
- * workspace and staging for tree_capacity trees, counted by mi_device_bytes_held and refused with
+ * workspace for tree_capacity trees, counted by mi_device_bytes_held and refused with
  * the sizes in the message when over MI_PHYLO_PLV_BYTES (a batch is not chunked).  After it the
  * *_device forms of at most tree_capacity trees allocate nothing, synchronise nothing and can be
  * captured in a hipGraph; before it, or with more trees, they are refused.  Reserving MORE

@@ -178,7 +178,7 @@ struct mi_engine {
   // a variational fit (mi_vi, mi_phylo_vi.cpp): set while mi_vi_step_device enqueues, so that the
   // sampler, the branch-length draw and its gradient read first_sample and beta from the fit's state
   const ViState* vi_state = nullptr;
-  Buffer deroot_ws;    // de-rooting (mi_engine_reserve_deroot): per-tree node words | staging of the host form
+  Buffer deroot_ws;    // de-rooting (mi_engine_reserve_deroot): per-tree node words
   Buffer rf_ws;        // a batch's sorted lists: lengths [T][2n-3] | indices [T][2n-3] | counts [T]
   size_t plv_budget = (size_t)8 << 30;  // sw.plv_bytes if set; 20 states: reduced by aa_reserve's back-offs
   // kernel timing (bench.py)
@@ -391,6 +391,18 @@ struct HostCall {
   std::function<int(mi_engine* e, int T, const HostArray* in, const HostArray* out)> enqueue;
   bool retry = false;       // a one-launch time-out: run again through the four-launch sequence
   bool one_by_one = false;  // tree shards run shard after shard (the work synchronises its device)
+  bool deliver_on_error = false;  // an error of the status words: the outputs are handed over all the same
+};
+// A host form that takes NULL for an output its device form requires: the output is made all the same, into host
+// memory of the call's that nobody reads.
+struct Unwanted {
+  std::vector<std::vector<char>> blocks;
+  template <typename U>
+  U* operator()(U* wanted, size_t count) {
+    if (wanted) return wanted;
+    blocks.emplace_back(count * sizeof(U));
+    return reinterpret_cast<U*>(blocks.back().data());
+  }
 };
 int run_host_call(mi_engine* e, HostCall& c);   // on an engine, or dealt to the shards of a handle
 int run_on_engine(mi_engine* e, HostCall& c);   // on this engine

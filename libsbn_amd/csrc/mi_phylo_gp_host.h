@@ -72,25 +72,19 @@ struct mi_gp {
   Buffer hybrid;
   bool hybrid_reserved = false;
   GpHybridArgs h{};
-  // the tree side (mi_gp_reserve_trees): the tables the tree kernels read, the per-tree
-  // workspace and the staging arrays of the host forms, for tree_capacity trees
+  // the tree side (mi_gp_reserve_trees): the tables the tree kernels read and the per-tree
+  // workspace, for tree_capacity trees
   Buffer trees;
   int tree_capacity = 0;
   uint64_t topologies = 0;  // the DAG's topology count, saturated at 2^62 (once `counted`)
   bool counted = false;
   miphylo::GpTreesArgs t{};
-  int32_t *s_parents = nullptr, *s_entries = nullptr, *s_nodes = nullptr;  // staging [cap][2n-2], [cap][2n-1] twice
-  double *s_log_q = nullptr, *s_lengths = nullptr;                        // [cap], [cap][2n-1]
-  double *s_weights = nullptr, *s_cdf = nullptr;                          // [cap], [G]
   miphylo::GpTrainArgs train{};  // the rooted TrainSimpleAverage's workspace
-  // the by-value pieces of a variational step (mi_gp_reserve_vi): their workspace and the staging
-  // arrays of the host forms, for vi_capacity trees (the sort's arrays are `train`'s)
+  // the by-value pieces of a variational step (mi_gp_reserve_vi): their workspace, for
+  // vi_capacity trees (the sort's arrays are `train`'s)
   Buffer vi_ws;
   int vi_capacity = 0;
   struct ViWork {
-    double *log_q, *qn, *usage, *sums, *factors, *terms;                       // [G] x 3, [2], [cap], [cap][2n-2][2]
-    double *s_phi, *s_q_params, *s_eps_in, *s_eps, *s_lengths, *s_grad, *s_terms;  // staging: [G], [G][2], [cap][2n-2] x 2,
-    double *o_q_gradient, *o_gradient;                                         // [cap][2n-1] x 2, [7][cap]; [G][2], [G]
-    int32_t *s_entries, *s_new_id;                                             // [cap][2n-1] each
+    double *log_q, *qn, *usage, *sums, *factors, *terms;  // [G] x 3, [2], [cap], [cap][2n-2][2]
   } vw{};
 };

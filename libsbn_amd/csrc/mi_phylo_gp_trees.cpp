@@ -2,8 +2,8 @@
 // workspace (mi_gp_reserve_trees), the index of rooted trees into the DAG, log q and the GP branch
 // lengths of indexed trees, the rooted TrainSimpleAverage, the sampler, the enumerator, and
 // de-rooting on any engine.  The kernels are kernels_gp_trees.hip's.  A *_device form enqueues on
-// the caller's stream and allocates and synchronises nothing; a host form reserves on first use,
-// stages through the reservation and synchronises.
+// the caller's stream and allocates and synchronises nothing; a host form reserves on first use and
+// is one HostCall on the object's engine.
 #include <cmath>
 #include <vector>
 
@@ -57,15 +57,12 @@ struct TreeLayout {
   uint32_t* clades;
   int32_t *table, *root_entry;
   uint64_t *below, *options1;
-  double *cdf, *o_cdf;
+  double* cdf;
   int32_t* store;
   // the rooted TrainSimpleAverage
   uint32_t *keys, *keys2, *vals, *vals2;
   char* sort_tmp;
-  double *weights, *counts, *new_q;
-  // the staging arrays of the host forms
-  int32_t *s_parents, *s_entries, *s_nodes;
-  double *s_log_q, *s_lengths;
+  double *counts, *new_q;
   size_t sort_bytes, tables_end;
 };
 
@@ -86,21 +83,14 @@ size_t lay_trees(const mi_gp* g, size_t slots, int cap, char* base, TreeLayout& 
   c.take(l.below, (size_t)d.nodes);
   c.take(l.options1, (size_t)d.nodes);
   c.take(l.cdf, (size_t)d.G);
-  c.take(l.o_cdf, (size_t)d.G);
   c.take(l.counts, (size_t)d.G);
   c.take(l.new_q, (size_t)d.G);
   l.tables_end = c.at;
   c.take(l.store, store_words);
-  c.take(l.s_parents, cap * (N - 1));
-  c.take(l.s_entries, cap * N);
-  c.take(l.s_nodes, cap * N);
-  c.take(l.s_log_q, (size_t)cap);
-  c.take(l.s_lengths, cap * N);
   c.take(l.keys, cap * N);
   c.take(l.keys2, cap * N);
   c.take(l.vals, cap * N);
   c.take(l.vals2, cap * N);
-  c.take(l.weights, (size_t)cap);
   l.sort_bytes = gp_train_sort_tmp_bytes(cap * N);
   c.take(l.sort_tmp, l.sort_bytes);
   return c.at;
@@ -167,13 +157,6 @@ int reserve_trees(mi_gp* g, int cap) {
   tr.counts = l.counts;
   tr.out_q = l.new_q;
   tr.status = a.status;
-  g->s_parents = l.s_parents;
-  g->s_entries = l.s_entries;
-  g->s_nodes = l.s_nodes;
-  g->s_log_q = l.s_log_q;
-  g->s_lengths = l.s_lengths;
-  g->s_weights = l.weights;
-  g->s_cdf = l.o_cdf;
   g->topologies = tt.topologies;
   g->counted = true;
   g->tree_capacity = cap;
@@ -228,24 +211,23 @@ int check_enumeration(mi_gp* g, int64_t first, int32_t count) {
   return 0;
 }
 
-// the host side of sample / enumerate: build into the staging arrays, check, download
+// the host side of sample / enumerate
 int build_host(mi_gp* g, int K, int sample, uint64_t seed, int64_t first, int32_t* out_parent_ids, int32_t* out_entries,
                double* out_log_q, double* out_lengths, double* out_cdf) {
   if (K < 1) return fail("tree_count must be positive");
   if (!sample && check_enumeration(g, first, K)) return 1;  // (the range first: nothing is allocated for a refused one)
   if (reserve_trees(g, K)) return 1;
-  mi_engine* e = g->e;
   const size_t N = 2 * (size_t)g->d.n - 1;
-  if (build_device(g, e->stream, K, sample, seed, first, g->s_parents, g->s_entries, g->s_log_q, g->s_lengths,
-                   out_cdf ? g->s_cdf : nullptr))
-    return 1;
-  const int bad = check_status(e, e->stream);
-  // (the outputs are written for every sample, the refused one's as -1 and NaN)
-  if (download(out_parent_ids, g->s_parents, sizeof(int32_t) * K * (N - 1)) ||
-      download(out_entries, g->s_entries, sizeof(int32_t) * K * N) || download(out_log_q, g->s_log_q, sizeof(double) * K) ||
-      download(out_lengths, g->s_lengths, sizeof(double) * K * N) || download(out_cdf, g->s_cdf, sizeof(double) * g->d.G))
-    return 1;
-  return bad;
+  Unwanted spare;
+  HostCall c;
+  c.out = {fixed(spare(out_parent_ids, K * (N - 1)), K * (N - 1)), fixed(spare(out_entries, K * N), K * N),
+           fixed(spare(out_log_q, (size_t)K), (size_t)K), fixed(out_lengths, K * N), fixed(out_cdf, (size_t)g->d.G)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray*, const HostArray* out) {
+    return build_device(g, e->stream, K, sample, seed, first, out[0].at<int32_t>(), out[1].at<int32_t>(), out[2].at<double>(),
+                        out[3].at<double>(), out[4].at<double>());
+  };
+  c.deliver_on_error = true;  // (the outputs are written for every sample, the refused one's as -1 and NaN)
+  return run_on_engine(g->e, c);
 }
 
 }  // namespace
@@ -281,10 +263,13 @@ int32_t mi_gp_tree_index(mi_gp* g, int32_t T, const int32_t* parent_ids, int32_t
   if (T < 1) return fail("tree_count must be positive");
   if (reserve_trees(g, T)) return 1;
   const size_t N = 2 * (size_t)g->d.n - 1;
-  if (upload(g->s_parents, parent_ids, sizeof(int32_t) * T * (N - 1))) return 1;
-  if (mi_gp_tree_index_device(g, nullptr, T, g->s_parents, g->s_entries, out_nodes ? g->s_nodes : nullptr)) return 1;
-  if (check_status(g->e, g->e->stream)) return 1;
-  return download(out_entries, g->s_entries, sizeof(int32_t) * T * N) || download(out_nodes, g->s_nodes, sizeof(int32_t) * T * N);
+  HostCall c;
+  c.in = {fixed(parent_ids, T * (N - 1))};
+  c.out = {fixed(out_entries, T * N), fixed(out_nodes, T * N)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    return mi_gp_tree_index_device(g, e->stream, T, in[0].at<const int32_t>(), out[0].at<int32_t>(), out[1].at<int32_t>());
+  };
+  return run_on_engine(g->e, c);
 }
 
 int32_t mi_gp_tree_log_prob_device(mi_gp* g, void* stream, int32_t T, const int32_t* entries, double* out_log_q) {
@@ -303,10 +288,13 @@ int32_t mi_gp_tree_log_prob(mi_gp* g, int32_t T, const int32_t* entries, double*
   if (T < 1) return fail("tree_count must be positive");
   if (reserve_trees(g, T)) return 1;
   const size_t N = 2 * (size_t)g->d.n - 1;
-  if (upload(g->s_entries, entries, sizeof(int32_t) * T * N)) return 1;
-  if (mi_gp_tree_log_prob_device(g, nullptr, T, g->s_entries, g->s_log_q)) return 1;
-  HIP_TRY(hipStreamSynchronize(g->e->stream));
-  return download(out_log_q, g->s_log_q, sizeof(double) * T);
+  HostCall c;
+  c.in = {fixed(entries, T * N)};
+  c.out = {fixed(out_log_q, (size_t)T)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    return mi_gp_tree_log_prob_device(g, e->stream, T, in[0].at<const int32_t>(), out[0].at<double>());
+  };
+  return run_on_engine(g->e, c);
 }
 
 int32_t mi_gp_tree_branch_lengths_device(mi_gp* g, void* stream, int32_t T, const int32_t* entries, double missing_length,
@@ -326,10 +314,13 @@ int32_t mi_gp_tree_branch_lengths(mi_gp* g, int32_t T, const int32_t* entries, d
   if (T < 1) return fail("tree_count must be positive");
   if (reserve_trees(g, T)) return 1;
   const size_t N = 2 * (size_t)g->d.n - 1;
-  if (upload(g->s_entries, entries, sizeof(int32_t) * T * N)) return 1;
-  if (mi_gp_tree_branch_lengths_device(g, nullptr, T, g->s_entries, missing_length, g->s_lengths)) return 1;
-  HIP_TRY(hipStreamSynchronize(g->e->stream));
-  return download(out_branch_lengths, g->s_lengths, sizeof(double) * T * N);
+  HostCall c;
+  c.in = {fixed(entries, T * N)};
+  c.out = {fixed(out_branch_lengths, T * N)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    return mi_gp_tree_branch_lengths_device(g, e->stream, T, in[0].at<const int32_t>(), missing_length, out[0].at<double>());
+  };
+  return run_on_engine(g->e, c);
 }
 
 int32_t mi_gp_train_simple_average(mi_gp* g, int32_t T, const int32_t* entries, const double* tree_weights, double* out_q) {
@@ -337,21 +328,25 @@ int32_t mi_gp_train_simple_average(mi_gp* g, int32_t T, const int32_t* entries, 
   if (!entries) return fail("null input pointer");
   if (T < 1) return fail("tree_count must be positive");
   if (reserve_trees(g, T)) return 1;
-  mi_engine* e = g->e;
   const size_t N = 2 * (size_t)g->d.n - 1, G = g->d.G;
-  if (upload(g->s_entries, entries, sizeof(int32_t) * T * N)) return 1;
-  if (tree_weights && upload(g->s_weights, tree_weights, sizeof(double) * T)) return 1;
-  GpTrainArgs a = g->train;
-  a.T = T;
-  a.entries = g->s_entries;
-  a.weights = tree_weights ? g->s_weights : nullptr;
-  if (launch_gp_train(a, e->stream)) return fail("generalized pruning: the radix sort of the training entries failed");
-  HIP_TRY(hipGetLastError());
-  e->dominant = "gp_train_runs_kernel";
-  if (check_status(e, e->stream)) return 1;  // (a sentinel names its tree; q is left as it was)
-  HIP_TRY(hipMemcpy(g->q, a.out_q, sizeof(double) * G, hipMemcpyDeviceToDevice));
+  HostCall c;
+  c.in = {fixed(entries, T * N), fixed(tree_weights, (size_t)T)};
+  c.out = {fixed(out_q, G)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    GpTrainArgs a = g->train;
+    a.T = T;
+    a.entries = in[0].at<const int32_t>();
+    a.weights = in[1].at<const double>();
+    if (launch_gp_train(a, e->stream)) return fail("generalized pruning: the radix sort of the training entries failed");
+    HIP_TRY(hipGetLastError());
+    e->dominant = "gp_train_runs_kernel";
+    if (out[0].dev) HIP_TRY(hipMemcpyAsync(out[0].dev, a.out_q, sizeof(double) * G, hipMemcpyDeviceToDevice, e->stream));
+    return 0;
+  };
+  if (run_on_engine(g->e, c)) return 1;  // (a sentinel names its tree; q is left as it was)
+  HIP_TRY(hipMemcpy(g->q, g->train.out_q, sizeof(double) * G, hipMemcpyDeviceToDevice));
   g->stale = true;
-  return download(out_q, g->q, sizeof(double) * G);
+  return 0;
 }
 
 int32_t mi_gp_sample_trees_device(mi_gp* g, void* stream, int32_t K, uint64_t seed, int64_t first_sample, int32_t* out_parent_ids,
@@ -389,10 +384,7 @@ int32_t mi_engine_reserve_deroot(mi_engine* e, int32_t T, int32_t n) {
   if (!e->shards.empty()) e = e->shards[0];
   if (T < 1) return fail("tree_count must be positive");
   if (n < 3) return fail("de-rooting needs at least 3 taxa");
-  const size_t N = 2 * (size_t)n - 1, waves = ((size_t)T + 63) / 64;
-  // node words | parent ids in | lengths in | parent ids out | lengths out | root edges | new ids
-  const size_t bytes =
-      waves * 64 * gp_tree_deroot_words(n) * 4 + (size_t)T * ((N - 1) * 4 + N * 8 + (N - 2) * 4 + (N - 1) * 8 + 4 + N * 4) + 7 * 256;
+  const size_t bytes = (((size_t)T + 63) / 64) * 64 * gp_tree_deroot_words(n) * 4;  // (the node words: what the device form checks)
   if (bytes > e->plv_budget)
     return fail("de-rooting " + std::to_string(T) + " trees of " + std::to_string(n) + " taxa takes " + std::to_string(bytes) +
                 " bytes of workspace, over the budget of " + std::to_string(e->plv_budget) + " bytes (MI_PHYLO_PLV_BYTES)");
@@ -438,25 +430,17 @@ int32_t mi_engine_deroot_trees_mapped(mi_engine* e, int32_t T, int32_t n, const 
   if (!parent_ids || !out_parent_ids || !out_root_edge) return fail("null tree arrays or output pointer");
   if (out_branch_lengths && !branch_lengths) return fail("de-rooting: out_branch_lengths without branch_lengths");
   if (mi_engine_reserve_deroot(e, T, n)) return 1;
-  const size_t N = 2 * (size_t)n - 1, words = (((size_t)T + 63) / 64) * 64 * gp_tree_deroot_words(n);
-  Cutter c{e->deroot_ws.as<char>() + words * 4};
-  int32_t *in_p, *out_p, *edge, *new_id;
-  double *in_b, *out_b;
-  c.take(in_p, T * (N - 1));
-  c.take(in_b, T * N);
-  c.take(out_p, T * (N - 2));
-  c.take(out_b, T * (N - 1));
-  c.take(edge, (size_t)T);
-  c.take(new_id, T * N);
-  if (upload(in_p, parent_ids, sizeof(int32_t) * T * (N - 1))) return 1;
-  if (branch_lengths && upload(in_b, branch_lengths, sizeof(double) * T * N)) return 1;
-  if (mi_engine_deroot_trees_mapped_device(e, nullptr, T, n, in_p, branch_lengths ? in_b : nullptr, out_p,
-                                           out_branch_lengths ? out_b : nullptr, edge, out_new_id ? new_id : nullptr))
-    return 1;
-  if (check_status(e, e->stream)) return 1;
-  return download(out_parent_ids, out_p, sizeof(int32_t) * T * (N - 2)) ||
-         download(out_branch_lengths, out_b, sizeof(double) * T * (N - 1)) || download(out_root_edge, edge, sizeof(int32_t) * T) ||
-         download(out_new_id, new_id, sizeof(int32_t) * T * N);
+  const size_t N = 2 * (size_t)n - 1;
+  HostCall c;
+  c.in = {fixed(parent_ids, T * (N - 1)), fixed(branch_lengths, T * N)};
+  c.out = {fixed(out_parent_ids, T * (N - 2)), fixed(out_branch_lengths, T * (N - 1)), fixed(out_root_edge, (size_t)T),
+           fixed(out_new_id, T * N)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    return mi_engine_deroot_trees_mapped_device(e, e->stream, T, n, in[0].at<const int32_t>(), in[1].at<const double>(),
+                                                out[0].at<int32_t>(), out[1].at<double>(), out[2].at<int32_t>(),
+                                                out[3].at<int32_t>());
+  };
+  return run_on_engine(e, c);
 }
 int32_t mi_engine_deroot_trees(mi_engine* e, int32_t T, int32_t n, const int32_t* parent_ids, const double* branch_lengths,
                                int32_t* out_parent_ids, double* out_branch_lengths, int32_t* out_root_edge) {

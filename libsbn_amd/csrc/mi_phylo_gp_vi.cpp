@@ -4,8 +4,8 @@
 // chain of launches and its rooted particles (mi_gp_vi_particles).  The kernels are kernels_gp_vi.hip's,
 // the tree-building and de-rooting kernels kernels_gp_trees.hip's, the factors kernels_sbn_vi.hip's,
 // the optimiser kernels_vi_fit.hip's.  A *_device form enqueues on the caller's stream and allocates and
-// synchronises nothing; a host form reserves on first use, stages through the reservation and
-// synchronises.  Every mi_vi_* call serves the fit made here (mi_phylo_vi.cpp).
+// synchronises nothing; a host form reserves on first use and is one HostCall on the object's engine
+// (DESIGN.md 4.14).  Every mi_vi_* call serves the fit made here (mi_phylo_vi.cpp).
 #include <cmath>
 #include <vector>
 
@@ -94,17 +94,6 @@ size_t lay_vi(const mi_gp* g, int cap, char* base, mi_gp::ViWork& w) {
   c.take(w.sums, 2);
   c.take(w.factors, T);
   c.take(w.terms, T * (N - 1) * 2);
-  c.take(w.s_phi, G);
-  c.take(w.s_q_params, 2 * G);
-  c.take(w.s_eps_in, T * (N - 1));
-  c.take(w.s_eps, T * (N - 1));
-  c.take(w.s_lengths, T * N);
-  c.take(w.s_grad, T * N);
-  c.take(w.s_terms, 7 * T);
-  c.take(w.o_q_gradient, 2 * G);
-  c.take(w.o_gradient, G);
-  c.take(w.s_entries, T * N);
-  c.take(w.s_new_id, T * N);
   return c.at;
 }
 
@@ -193,10 +182,6 @@ size_t cut_fit(mi_vi* v, char* base) {
   c.take(v->grad, G);
   c.take(v->block_flags, (size_t)v->blocks);
   c.take(v->trace, 6 * (size_t)v->o.max_steps);
-  c.take(v->row, 6);
-  c.take(v->u_grad, G);
-  c.take(v->u_qgrad, 2 * G);
-  c.take(v->u_terms, 4 * K);
   return c.at;
 }
 
@@ -288,11 +273,14 @@ int32_t mi_gp_log_normalize(mi_gp* g, const double* log_params, double* out_log_
   if (!log_params) return fail("null input pointer");
   if (g->vi_capacity < 1 && reserve_vi(g, 1)) return 1;
   const size_t G = g->d.G;
-  const mi_gp::ViWork& w = g->vw;
-  if (upload(w.s_phi, log_params, sizeof(double) * G)) return 1;
-  if (mi_gp_log_normalize_device(g, nullptr, w.s_phi, w.log_q, w.qn)) return 1;
-  if (check_status(g->e, g->e->stream)) return 1;
-  return download(out_log_q, w.log_q, sizeof(double) * G) || download(out_q, w.qn, sizeof(double) * G);
+  Unwanted spare;
+  HostCall c;
+  c.in = {fixed(log_params, G)};
+  c.out = {fixed(out_log_q, G), fixed(spare(out_q, G), G)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    return mi_gp_log_normalize_device(g, e->stream, in[0].at<const double>(), out[0].at<double>(), out[1].at<double>());
+  };
+  return run_on_engine(g->e, c);
 }
 
 int32_t mi_gp_branch_sample_device(mi_gp* g, void* stream, int32_t T, const int32_t* entries, const double* q_params, uint64_t seed,
@@ -332,17 +320,18 @@ int32_t mi_gp_branch_sample(mi_gp* g, int32_t T, const int32_t* entries, const d
   if (!entries || !q_params) return fail("null input pointer");
   if (T < 1) return fail("tree_count must be positive");
   if (reserve_vi(g, T)) return 1;
-  const size_t N = 2 * (size_t)g->d.n - 1, G = g->d.G, d = sizeof(double);
-  const mi_gp::ViWork& w = g->vw;
-  if (upload(w.s_entries, entries, sizeof(int32_t) * T * N) || upload(w.s_q_params, q_params, d * 2 * G) ||
-      upload(w.s_eps_in, epsilon_in, d * T * (N - 1)))
-    return 1;
-  if (mi_gp_branch_sample_device(g, nullptr, T, w.s_entries, w.s_q_params, seed, first_sample, prior_rate,
-                                 epsilon_in ? w.s_eps_in : nullptr, w.s_lengths, w.s_eps, w.s_terms, w.s_terms + T))
-    return 1;
-  if (check_status(g->e, g->e->stream)) return 1;
-  return download(out_lengths, w.s_lengths, d * T * N) || download(out_epsilon, w.s_eps, d * T * (N - 1)) ||
-         download(out_log_q, w.s_terms, d * T) || download(out_log_prior, w.s_terms + T, d * T);
+  const size_t N = 2 * (size_t)g->d.n - 1, G = g->d.G, K = (size_t)T;
+  Unwanted spare;
+  HostCall c;
+  c.in = {fixed(entries, K * N), fixed(q_params, 2 * G), fixed(epsilon_in, K * (N - 1))};
+  c.out = {fixed(spare(out_lengths, K * N), K * N), fixed(spare(out_epsilon, K * (N - 1)), K * (N - 1)),
+           fixed(spare(out_log_q, K), K), fixed(spare(out_log_prior, K), K)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    return mi_gp_branch_sample_device(g, e->stream, T, in[0].at<const int32_t>(), in[1].at<const double>(), seed, first_sample,
+                                      prior_rate, in[2].at<const double>(), out[0].at<double>(), out[1].at<double>(),
+                                      out[2].at<double>(), out[3].at<double>());
+  };
+  return run_on_engine(g->e, c);
 }
 
 int32_t mi_gp_branch_gradient_device(mi_gp* g, void* stream, int32_t T, const int32_t* entries, const double* q_params,
@@ -396,21 +385,21 @@ int32_t mi_gp_branch_gradient(mi_gp* g, int32_t T, const int32_t* entries, const
     return fail("null input pointer");
   if (T < 1) return fail("tree_count must be positive");
   if (reserve_vi(g, T)) return 1;
-  const size_t N = 2 * (size_t)g->d.n - 1, G = g->d.G, d = sizeof(double);
-  const mi_gp::ViWork& w = g->vw;
-  double* t = w.s_terms;  // logL | log prior | log q branch | log q topology | weights | log_f
-  if (upload(w.s_entries, entries, sizeof(int32_t) * T * N) || upload(w.s_q_params, q_params, d * 2 * G) ||
-      upload(w.s_lengths, lengths, d * T * N) || upload(w.s_eps, epsilon, d * T * (N - 1)) ||
-      upload(w.s_new_id, new_id, sizeof(int32_t) * T * N) || upload(w.s_grad, branch_gradient, d * T * N) ||
-      upload(t, log_likelihoods, d * T) || upload(t + T, log_prior, d * T) || upload(t + 2 * T, log_q_branch, d * T) ||
-      upload(t + 3 * T, log_q_topology, d * T) || upload(t + 4 * T, tree_weights, d * T))
-    return 1;
-  if (mi_gp_branch_gradient_device(g, nullptr, T, w.s_entries, w.s_q_params, w.s_lengths, w.s_eps, t + 2 * T, t + T, w.s_new_id,
-                                   w.s_grad, t, log_q_topology ? t + 3 * T : nullptr, tree_weights ? t + 4 * T : nullptr, beta,
-                                   prior_rate, w.o_q_gradient, t + 5 * T))
-    return 1;
-  if (check_status(g->e, g->e->stream)) return 1;
-  return download(out_gradient, w.o_q_gradient, d * 2 * G) || download(out_log_f, t + 5 * T, d * T);
+  const size_t N = 2 * (size_t)g->d.n - 1, G = g->d.G, K = (size_t)T;
+  Unwanted spare;
+  HostCall c;
+  c.in = {fixed(entries, K * N),         fixed(q_params, 2 * G),  fixed(lengths, K * N),   fixed(epsilon, K * (N - 1)),
+          fixed(log_q_branch, K),        fixed(log_prior, K),     fixed(new_id, K * N),    fixed(branch_gradient, K * N),
+          fixed(log_likelihoods, K),     fixed(log_q_topology, K), fixed(tree_weights, K)};
+  c.out = {fixed(spare(out_gradient, 2 * G), 2 * G), fixed(spare(out_log_f, K), K)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    return mi_gp_branch_gradient_device(g, e->stream, T, in[0].at<const int32_t>(), in[1].at<const double>(),
+                                        in[2].at<const double>(), in[3].at<const double>(), in[4].at<const double>(),
+                                        in[5].at<const double>(), in[6].at<const int32_t>(), in[7].at<const double>(),
+                                        in[8].at<const double>(), in[9].at<const double>(), in[10].at<const double>(), beta,
+                                        prior_rate, out[0].at<double>(), out[1].at<double>());
+  };
+  return run_on_engine(g->e, c);
 }
 
 int32_t mi_gp_topology_gradient_device(mi_gp* g, void* stream, int32_t T, const int32_t* entries, const double* log_params,
@@ -438,14 +427,16 @@ int32_t mi_gp_topology_gradient(mi_gp* g, int32_t T, const int32_t* entries, con
   if (T < 1) return fail("tree_count must be positive");
   if (check_estimator(estimator, T)) return 1;
   if (reserve_vi(g, T)) return 1;
-  const size_t N = 2 * (size_t)g->d.n - 1, G = g->d.G, d = sizeof(double);
-  const mi_gp::ViWork& w = g->vw;
-  if (upload(w.s_entries, entries, sizeof(int32_t) * T * N) || upload(w.s_phi, log_params, d * G) ||
-      upload(w.s_terms, log_f, d * T))
-    return 1;
-  if (mi_gp_topology_gradient_device(g, nullptr, T, w.s_entries, w.s_phi, w.s_terms, estimator, w.o_gradient, w.factors)) return 1;
-  if (check_status(g->e, g->e->stream)) return 1;
-  return download(out_gradient, w.o_gradient, d * G) || download(out_factors, w.factors, d * T);
+  const size_t N = 2 * (size_t)g->d.n - 1, G = g->d.G, K = (size_t)T;
+  Unwanted spare;
+  HostCall c;
+  c.in = {fixed(entries, K * N), fixed(log_params, G), fixed(log_f, K)};
+  c.out = {fixed(spare(out_gradient, G), G), fixed(out_factors, K)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    return mi_gp_topology_gradient_device(g, e->stream, T, in[0].at<const int32_t>(), in[1].at<const double>(),
+                                          in[2].at<const double>(), estimator, out[0].at<double>(), out[1].at<double>());
+  };
+  return run_on_engine(g->e, c);
 }
 
 int32_t mi_gp_vi_create(mi_gp* g, const double* model_params, int32_t P, const double* log_params, int32_t V,

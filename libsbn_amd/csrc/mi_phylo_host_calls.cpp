@@ -84,7 +84,10 @@ int finish_host(mi_engine* e, HostCall& c) {
     if (rc == 0) rc = check_status(e, e->stream);
   }
   e->fused_timed_out = false;
-  if (rc == 0) e->pinned.flush();
+  // (deliver_on_error: the call marks what it refused inside its outputs, and the caller gets them with the
+  // error.  The stream idle again says that the error is check_status's, read after its synchronisation: the
+  // staged bytes are the call's.  After a HIP error they are not, and nothing is delivered.)
+  if (rc == 0 || (c.deliver_on_error && hipStreamQuery(e->stream) == hipSuccess)) e->pinned.flush();
   e->pinned.reset();
   return rc;
 }

@@ -76,10 +76,6 @@ size_t cut(mi_vi* v, char* base) {
   c.take(v->glq, K);
   c.take(v->block_flags, (size_t)v->blocks);
   c.take(v->trace, 6 * (size_t)v->o.max_steps);
-  c.take(v->row, 6);
-  c.take(v->u_grad, P);
-  c.take(v->u_qgrad, 2 * V);
-  c.take(v->u_terms, 4 * K);
   return c.at;
 }
 
@@ -365,19 +361,15 @@ int32_t mi_vi_update(mi_vi* v, const double* g_sbn, const double* g_q, const dou
                      const double* lqt, const double* lqb, double* out_row) {
   if (!v) return fail("null fit");
   if (!g_sbn || !g_q || !ll || !lprior || !lqt || !lqb) return fail("variational fit: null gradient or term array");
-  mi_engine* e = v->e;
-  HIP_TRY(hipSetDevice(e->spec.device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
   const size_t K = v->K;
-  const double* terms[4] = {ll, lprior, lqt, lqb};
-  if (upload(v->u_grad, g_sbn, sizeof(double) * v->P) || upload(v->u_qgrad, g_q, sizeof(double) * 2 * v->V)) return 1;
-  for (int j = 0; j < 4; j++)
-    if (upload(v->u_terms + j * K, terms[j], sizeof(double) * K)) return 1;
-  if (vi_enqueue_update(v, e->stream, v->u_grad, v->u_qgrad, v->u_terms, v->u_terms + K, v->u_terms + 2 * K,
-                     v->u_terms + 3 * K, v->row))
-    return 1;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return download(out_row, v->row, sizeof(double) * 6);
+  HostCall c;
+  c.in = {fixed(g_sbn, (size_t)v->P), fixed(g_q, 2 * (size_t)v->V), fixed(ll, K), fixed(lprior, K), fixed(lqt, K), fixed(lqb, K)};
+  c.out = {fixed(out_row, 6)};
+  c.enqueue = [=](mi_engine* e, int, const HostArray* in, const HostArray* out) {
+    return vi_enqueue_update(v, e->stream, in[0].at<const double>(), in[1].at<const double>(), in[2].at<const double>(),
+                             in[3].at<const double>(), in[4].at<const double>(), in[5].at<const double>(), out[0].at<double>());
+  };
+  return run_on_engine(v->e, c);
 }
 
 int32_t mi_vi_get_state(mi_vi* v, double* phi, double* q, double* sbn_moments, double* q_moments, double* scalars,

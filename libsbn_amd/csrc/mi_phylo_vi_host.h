@@ -30,9 +30,7 @@ struct mi_vi {
          *glq = nullptr;
   // the optimiser
   int32_t* block_flags = nullptr;
-  double *trace = nullptr, *row = nullptr;
-  // staging of the host form of the optimiser call
-  double *u_grad = nullptr, *u_qgrad = nullptr, *u_terms = nullptr;
+  double* trace = nullptr;
   // A fit over the rooted trees of a subsplit DAG (mi_gp_vi_create): `gp` is set, T0 is 0,
   // P = V = G, and of the arrays above a step uses all_pid, edge, bl, eps, lqb, lprior, ll, g, lqt, qgrad, f,
   // grad and factors for the de-rooted particles.  What it adds: the rooted particles, the normalised table,

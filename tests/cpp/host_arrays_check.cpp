@@ -86,8 +86,41 @@ std::vector<Kind> kinds() {
 }
 // (not per tree throughout: these go to one engine whole, so only their packing is checked)
 std::vector<Kind> unsharded_kinds(size_t T) {
-  const size_t B = 7;
+  const size_t B = 7, G = 23, V = 5;  // replicates; DAG entries; a fit's branch-length variables
+  int32_t* const NO_I32 = nullptr;
   return {
+      // the trees of the subsplit DAG, de-rooting, the pieces of a rooted variational step, the optimiser call
+      {"gp_tree_index", {fixed(I32, T * (N - 1))}, {fixed(I32, T * N), fixed(I32, T * N)}},
+      {"gp_tree_index, no nodes", {fixed(I32, T * (N - 1))}, {fixed(I32, T * N), fixed(NO_I32, T * N)}},
+      {"gp_tree_log_prob", {fixed(I32, T * N)}, {fixed(F64, T)}},
+      {"gp_tree_branch_lengths", {fixed(I32, T * N)}, {fixed(F64, T * N)}},
+      {"gp_train_simple_average", {fixed(I32, T * N), fixed(F64, T)}, {fixed(F64, G)}},
+      {"gp_train_simple_average, no weights, no q", {fixed(I32, T * N), fixed(NO_F64, T)}, {fixed(NO_F64, G)}},
+      {"gp_sample_trees", {}, {fixed(I32, T * (N - 1)), fixed(I32, T * N), fixed(F64, T), fixed(F64, T * N), fixed(F64, G)}},
+      {"gp_enumerate_trees, no lengths", {}, {fixed(I32, T * (N - 1)), fixed(I32, T * N), fixed(F64, T), fixed(NO_F64, T * N), fixed(NO_F64, G)}},
+      {"deroot_trees_mapped", {fixed(I32, T * (N - 1)), fixed(F64, T * N)},
+       {fixed(I32, T * (N - 2)), fixed(F64, T * (N - 1)), fixed(I32, T), fixed(I32, T * N)}},
+      {"deroot_trees, no lengths", {fixed(I32, T * (N - 1)), fixed(NO_F64, T * N)},
+       {fixed(I32, T * (N - 2)), fixed(NO_F64, T * (N - 1)), fixed(I32, T), fixed(NO_I32, T * N)}},
+      {"gp_log_normalize", {fixed(F64, G)}, {fixed(F64, G), fixed(F64, G)}},
+      {"gp_log_normalize, no log q", {fixed(F64, G)}, {fixed(NO_F64, G), fixed(F64, G)}},
+      {"gp_branch_sample", {fixed(I32, T * N), fixed(F64, 2 * G), fixed(F64, T * (N - 1))},
+       {fixed(F64, T * N), fixed(F64, T * (N - 1)), fixed(F64, T), fixed(F64, T)}},
+      {"gp_branch_sample, no epsilon given", {fixed(I32, T * N), fixed(F64, 2 * G), fixed(NO_F64, T * (N - 1))},
+       {fixed(F64, T * N), fixed(F64, T * (N - 1)), fixed(F64, T), fixed(F64, T)}},
+      {"gp_branch_gradient",
+       {fixed(I32, T * N), fixed(F64, 2 * G), fixed(F64, T * N), fixed(F64, T * (N - 1)), fixed(F64, T), fixed(F64, T), fixed(I32, T * N),
+        fixed(F64, T * N), fixed(F64, T), fixed(F64, T), fixed(F64, T)},
+       {fixed(F64, 2 * G), fixed(F64, T)}},
+      {"gp_branch_gradient, no log q of the topology, no weights",
+       {fixed(I32, T * N), fixed(F64, 2 * G), fixed(F64, T * N), fixed(F64, T * (N - 1)), fixed(F64, T), fixed(F64, T), fixed(I32, T * N),
+        fixed(F64, T * N), fixed(F64, T), fixed(NO_F64, T), fixed(NO_F64, T)},
+       {fixed(F64, 2 * G), fixed(F64, T)}},
+      {"gp_topology_gradient", {fixed(I32, T * N), fixed(F64, G), fixed(F64, T)}, {fixed(F64, G), fixed(F64, T)}},
+      {"gp_topology_gradient, no factors", {fixed(I32, T * N), fixed(F64, G), fixed(F64, T)}, {fixed(F64, G), fixed(NO_F64, T)}},
+      {"vi_update", {fixed(F64, G), fixed(F64, 2 * V), fixed(F64, T), fixed(F64, T), fixed(F64, T), fixed(F64, T)}, {fixed(F64, 6)}},
+      {"vi_update, the tables' one element, no row", {fixed(F64, 1), fixed(F64, 0), fixed(F64, T), fixed(F64, T), fixed(F64, T), fixed(F64, T)},
+       {fixed(NO_F64, 6)}},
       {"rell", {fixed(F64, T * P), fixed(F64, B * P)}, {fixed(F64, B * T), fixed(I32, B), fixed(F64, T), fixed(NO_F64, T)}},
       {"rell_bootstrap", plus(tree_inputs(), {fixed(F64, B * P)}),
        {per_tree(F64, 1), per_tree(NO_F64, P), fixed(F64, B * T), fixed(I32, B), per_tree(F64, 1), per_tree(F64, 1)}},

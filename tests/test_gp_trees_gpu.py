@@ -403,6 +403,12 @@ def test_dag_only_object(kind):
     full_eng, row = _model_engine(tips, w, "JC69")
     full_eng.gp_create(pids, params=row).close()   # (whatever an engine reserves at a first creation is the engine's)
     other = _plain_engine(d.n, "JC69", "weibull+4") if kind == "four_categories" else _plain_engine(d.n, "WAG")
+    near = np.concatenate([pids, TR.nni_neighbours(pids[0])])
+    for eng in (full_eng, other):   # (... and so are the staging blocks of its host calls: the calls below, on a throw-away object)
+        prime = eng.gp_create_dag(pids)
+        prime.tree_index(near)
+        prime.train_simple_average(prime.sample_trees(65, seed=1, cdf=True).entries)
+        prime.close()
     held = L._capi.load().mi_device_bytes_held()
     full = full_eng.gp_create(pids, params=row)
     with_full = L._capi.load().mi_device_bytes_held()
@@ -413,7 +419,6 @@ def test_dag_only_object(kind):
     assert gp.strings() == full.strings()
     assert gp.get_sbn_parameters().tobytes() == full.get_sbn_parameters().tobytes()
     assert gp.get_branch_lengths().tobytes() == full.get_branch_lengths().tobytes()
-    near = np.concatenate([pids, TR.nni_neighbours(pids[0])])
     a, b = gp.tree_index(near), full.tree_index(near)
     assert a.entries.tobytes() == b.entries.tobytes() and a.nodes.tobytes() == b.nodes.tobytes()
     x, y = gp.sample_trees(65, seed=1, cdf=True), full.sample_trees(65, seed=1, cdf=True)
